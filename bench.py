@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """bench.py - env-steps/s of NightmareV3Env.step() on MI355X (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--envs-per-gpu 4096]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--envs-per-gpu 4096] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line. --full adds the secondary legs after the timed steps
+(roofline, contact regime, sustained clock, physics-only, closed loop, MLP, rollout, PPO, fp64 kernel, CPU baseline, live counters).
+--dump-outputs DIR writes what the last timed step() returned (obs, rewards, dones, time_outs, episode sums, per-env returns) as
+float32 .npy files; actions and env seeds are fixed, so two runs with the same arguments get the same inputs. The per-env arrays are
+bit-identical from run to run; the episode sums add over all envs in the order the waves finish and may differ in the last bits.
 
 One "step" = one step() call over all envs of a rank = `decimation` (2) physics substeps of 8 ms + the env
 epilogue (obs / rewards / termination / reset), random actions already resident in HBM. N>1: one rank per GPU, either started by
@@ -44,6 +50,23 @@ def host_cores():
     return (max(1, min(n, 16)) if n > 64 else n), vis
 
 
+def dump_outputs(d, suffix, arrays, limit=64 << 20):
+    """Writes each device tensor of `arrays` as d/<name><suffix>.npy (float32; None entries are skipped). Above `limit` bytes in all,
+    the per-env arrays (first dimension = the env count of `obs`) keep a fixed, seeded sample of env rows, listed in env_ids.npy."""
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items() if v is not None}
+    n = arrays["obs"].shape[0]
+    per_env = [k for k, v in arrays.items() if v.ndim and v.shape[0] == n]
+    if sum(v.nbytes for v in arrays.values()) > limit:
+        budget = limit - sum(v.nbytes for k, v in arrays.items() if k not in per_env)
+        row_bytes = sum(arrays[k][:1].nbytes for k in per_env) + 8          # + its float64 entry in env_ids
+        rows = np.sort(np.random.default_rng(0).choice(n, budget // row_bytes, replace=False))
+        arrays = {k: v[rows] if k in per_env else v for k, v in arrays.items()}
+        arrays["env_ids"] = rows.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, f"{k}{suffix}.npy"), v)
+
+
 def _time_oracle(n, threads, seconds, physics_only=False):
     from oracle import oracle as orc
     env = orc.OracleEnv(n, seed=0, num_threads=threads)
@@ -77,7 +100,7 @@ def live_pmc(E):
         lanes_ctrs = ["SQ_THREAD_CYCLES_VALU", "SQ_ACTIVE_INST_VALU", "SQ_INSTS_VALU_ADD_F32", "SQ_INSTS_VALU_MUL_F32", "SQ_INSTS_VALU_FMA_F32", "SQ_INSTS_VALU_TRANS_F32"]
         def one_pass(k, ctrs, script, pat, prefix=""):
             d = os.path.join(out, f"p{k}")
-            r = subprocess.run([exe, "--kernel-trace", "--output-format", "csv", "--pmc", *ctrs, "-d", d, "-o", "run", "--", "python3", os.path.join(ROOT, "scripts", script), "4096"],
+            r = subprocess.run([exe, "--kernel-trace", "--output-format", "csv", "--pmc", *ctrs, "-d", d, "-o", "run", "--", sys.executable, os.path.join(ROOT, "scripts", script), "4096"],
                                cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=90)
             if r.returncode != 0:
                 raise RuntimeError("rocprofv3 pass failed")
@@ -135,8 +158,11 @@ def main():
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--envs-per-gpu", type=int, default=4096)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-live-pmc", action="store_true", help="do not start the rocprofv3 --pmc child passes (roofline.traffic / valu then come from profiles/)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the secondary legs (roofline, contact regime, sustained "
+                    "clock, physics-only, closed loop, MLP, rollout, PPO, fp64 kernel, CPU baseline, live counters); default: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step() returned as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline (and the live counter passes)")
+    ap.add_argument("--no-live-pmc", action="store_true", help="with --full: do not start the rocprofv3 --pmc child passes (roofline.traffic / valu then come from profiles/)")
     args = ap.parse_args()
     if args.gpus is None:
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
@@ -195,10 +221,11 @@ def main():
     mism = torch.zeros((), dtype=torch.int64, device=dev)      # gathered[rank*E:(rank+1)*E] != what this rank contributed (device-side count)
 
     env.accumulate_rewards_into(returns)     # returns[env] += reward inside the step kernel (nm_set_return_accumulator), not a launch of its own
+    result = None                            # what the last step() returned (--dump-outputs)
 
     def one_step(i, last=False):
-        nonlocal returns, gathered, ncoll, mism
-        env.step(acts[i % pool])
+        nonlocal returns, gathered, ncoll, mism, result
+        result = env.step(acts[i % pool])
         # PPO-update boundary: one all-gather of per-env returns over xGMI, every `horizon` steps and at the end of the run (so a
         # short timed region still contains the collective)
         if ((i + 1) % horizon == 0 or last) and world > 1:
@@ -237,6 +264,12 @@ def main():
     sync()
     dt = time.perf_counter() - t0
     env.accumulate_rewards_into(None)
+    if args.dump_outputs:
+        obs, _, rew, done, extras = result
+        dump_outputs(args.dump_outputs, "" if world == 1 else f"_rank{rank}", {
+            "obs": obs, "rewards": rew, "dones": done, "time_outs": extras.get("time_outs"),
+            "returns": returns if world == 1 else gathered[rank * E:(rank + 1) * E],     # N > 1: the last timed step gathered and zeroed them
+            "episode_sums": torch.stack(list(extras["episode"].values()))})
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -246,7 +279,19 @@ def main():
 
     out = None
     if rank == 0:
-        value = world * E * args.steps / dt
+        out = {
+            "metric": "env-steps/sec at N parallel Nightmare-v3 envs, 1/2/4/8 MI355X",
+            "value": world * E * args.steps / dt, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": dt / args.steps * 1e3, "settle_steps": settle, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+            "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{E} Nightmare-v3 envs per GPU, random-action rollout U(-1,1)^18, full step(): 2 x 8 ms substeps "
+                                   "(18-DoF dynamics + floor contact, PGS x3 + noslip x4) + obs/reward/termination/reset",
+                       "envs_per_gpu": E, "decimation": 2,
+                       "sharding": f"dp{world} by env id, all-gather of returns every {horizon} steps and on the last timed step"},
+            "collectives_timed": ncoll, "gather_order_mismatches": int(mism.item()),
+            "counters": env.counters(),
+        }
+    if rank == 0 and args.full:
         # roofline leg: HIP events around the dominant (step) kernel on its launch stream, separate pass
         # (a) ONE event pair on the launch stream around n back-to-back launches: span / n is the average launch duration including the
         #     ~1 us between two launches, i.e. an upper bound of what rocprofv3 --kernel-trace reports per launch - the roofline uses it;
@@ -482,16 +527,7 @@ def main():
         torch.cuda.synchronize(dev)
         f64 = E * 40 / (time.perf_counter() - t1)
         env64.close()
-        out = {
-            "metric": "env-steps/sec at N parallel Nightmare-v3 envs, 1/2/4/8 MI355X",
-            "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": dt / args.steps * 1e3, "settle_steps": settle, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{E} Nightmare-v3 envs per GPU, random-action rollout U(-1,1)^18, full step(): 2 x 8 ms substeps "
-                                   "(18-DoF dynamics + floor contact, PGS x3 + noslip x4) + obs/reward/termination/reset",
-                       "envs_per_gpu": E, "decimation": 2,
-                       "sharding": f"dp{world} by env id, all-gather of returns every {horizon} steps and on the last timed step"},
-            "collectives_timed": ncoll, "gather_order_mismatches": int(mism.item()),
+        out.update({
             "same_region_at_sustained_clock": sustained,
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "traffic": traffic, "traffic_source": pmc_file and f"{pmc_file} (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE, separate passes; not measured in this run)",
@@ -506,8 +542,8 @@ def main():
             "mlp_2x256": mlp,
             "policy_rollout_one_launch_env_steps_per_s": roll, "rollout_roofline": roll_roof, "ppo_end_to_end_env_steps_per_s": ppo_e2e,
             "fp64_verification_kernel_env_steps_per_s": f64,
-            "counters": env.counters(),
-        }
+            "counters": env.counters(),      # over every step of the run, the secondary legs' included
+        })
         if not args.no_cpu_baseline and world == 1:      # reported baseline: rank 0 at N=1 only
             out["cpu_baseline"] = cpu_baseline(E)
         if not args.no_cpu_baseline and not args.no_live_pmc and world == 1 and E == 4096:
@@ -527,7 +563,10 @@ def main():
                                                 "active_lanes_per_valu_instruction": lp["active_lanes_per_valu_instruction"],
                                                 "source": "measured in this run: (add + mul + 2 fma + trans f32 wave-instructions) x active lanes per VALU instruction "
                                                           "(SQ_THREAD_CYCLES_VALU / SQ_ACTIVE_INST_VALU), rocprofv3 --pmc child pass; over this run's kernel time"}
-    if world > 1:
+    if world > 1 and not args.full:
+        dist.barrier()
+        dist.destroy_process_group()
+    if world > 1 and args.full:
         # BASELINE config 5 at N > 1: the full PPO loop, `E` envs per rank, data-parallel update (one RCCL all-reduce of
         # gradient | KL per mini-batch, inside the update's graph), whole-job env-steps/s. Runs LAST and under a deadline: the headline
         # numbers above are complete, and if this leg should hang on some node (it is the one part of this file that only a multi-GPU

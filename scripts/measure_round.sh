@@ -8,8 +8,8 @@ OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd $ROOT
 if [ "$PART" != "b" ]; then
-echo "== bench"; python bench.py > $OUT/${TAG}_bench.json.log 2>&1; tail -c 600 $OUT/${TAG}_bench.json.log; echo
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/${TAG}_bench_driverargs.json.log 2>&1
+echo "== bench"; python bench.py --full > $OUT/${TAG}_bench.json.log 2>&1; tail -c 600 $OUT/${TAG}_bench.json.log; echo
+python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline > $OUT/${TAG}_bench_driverargs.json.log 2>&1
 echo "== train 40 iterations + play"; rm -rf logs; python train.py -e 4096 --iters 40 > $OUT/${TAG}_train40.log 2>&1; grep -E "^it +(1|20|39)/" $OUT/${TAG}_train40.log
 python scripts/play.py --log-root logs/nightmare_v3 -e 64 --steps 400 > $OUT/${TAG}_play.log 2>&1; tail -4 $OUT/${TAG}_play.log
 echo "== curves (HIP side; the CPU side of the same size: profiles/r05_curve_cpu_runs.json (round-5 tables: see DESIGN 6.3), tests/tools/curve_vs_cpu.py --kinds cpu in the build container)"
@@ -17,7 +17,7 @@ python tests/tools/curve_vs_cpu.py --kinds hip --envs 4096 --iters 150 --seeds 3
 echo "== one-launch rollout"; python scripts/rolloutbench.py 4096 80 > $OUT/${TAG}_rolloutbench.txt 2>&1; grep -v amdgpu $OUT/${TAG}_rolloutbench.txt
 python scripts/rolloutwaves.py 4096 80 > $OUT/${TAG}_rolloutwaves.txt 2>&1; grep -v amdgpu $OUT/${TAG}_rolloutwaves.txt
 cd /tmp && export TMPDIR=/tmp
-echo "== rocprof kernel stats: bench"; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_bench -o run -- python3 $ROOT/bench.py --steps 200 --warmup 50 --no-cpu-baseline > $OUT/${TAG}_prof_bench.log 2>&1
+echo "== rocprof kernel stats: bench"; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_bench -o run -- python3 $ROOT/bench.py --steps 200 --warmup 50 --full --no-cpu-baseline > $OUT/${TAG}_prof_bench.log 2>&1
 echo "== rocprof kernel stats: train"; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_train -o run -- python3 $ROOT/train.py -e 4096 --iters 12 > $OUT/${TAG}_prof_train.log 2>&1
 echo "== rocprof kernel trace: train down the MULTI-RANK path on one rank (NM_FORCE_DATA_PARALLEL=1: RCCL all-reduce per mini-batch inside the update graph, pipelined logging with its all-reduce)"
 NM_FORCE_DATA_PARALLEL=1 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_prof_train_dp -o run -- python3 $ROOT/train.py -e 4096 --iters 12 > $OUT/${TAG}_prof_train_dp.log 2>&1
