@@ -138,12 +138,28 @@ int nm_profile(nm_env* env, int32_t enable, double* sum_ms, int64_t* count);
 /* Stage-skipping measurement switches are NOT part of this ABI: they exist only in the -DNM_MEASURE build
  * (libnightmare_hip_measure.so, include/nightmare_hip_measure.h). */
 
-/* ---- ActorCritic MLP forward on the matrix cores (rsl_rl v1.0.2 ActorCritic: Linear -> ELU x n_hidden -> Linear; reference call
+/* ---- Hidden-layer activation of the networks below (rsl_rl v1.0.2 ActorCritic's get_activation; the user's choice is the reference
+ * config's `activation = 'elu' # can be elu, relu, selu, crelu, lrelu, tanh, sigmoid`, envs/nightmare_v3_config.py:109; crelu is a plain
+ * ReLU upstream). SELU uses torch's constants, LRELU torch's default slope 0.01. Every entry point without an activation argument means
+ * NM_ACT_ELU. An unknown code is refused before any device call (nm_last_error names it). */
+typedef enum {
+  NM_ACT_ELU = 0,
+  NM_ACT_SELU = 1,
+  NM_ACT_RELU = 2,
+  NM_ACT_LRELU = 3,
+  NM_ACT_TANH = 4,
+  NM_ACT_SIGMOID = 5
+} nm_activation;
+#define NM_NUM_ACTIVATIONS 6
+
+/* ---- ActorCritic MLP forward on the matrix cores (rsl_rl v1.0.2 ActorCritic: Linear -> activation x n_hidden -> Linear; reference call
  * sites play.py:122 `nn.act(obs)`, train.py:40), batched over envs, exact-f32 MFMA, all layers in one launch.
  * One handle = one network: it owns a packed copy of the parameters, so nothing is shared between networks, streams or devices.
- * dims = {n_in, h1, ..., n_out}, n_layers = len(dims) - 1. Networks of <= 4 layers and <= 256 units run fused; others per layer. */
+ * dims = {n_in, h1, ..., n_out}, n_layers = len(dims) - 1. Networks of <= 4 layers and <= 256 units run fused; others per layer.
+ * nm_policy_create: ELU hidden layers; nm_policy_create_act: any NM_ACT_* code (reference envs/nightmare_v3_config.py:109). */
 typedef struct nm_policy nm_policy;
 int nm_policy_create(const int32_t* dims, int32_t n_layers, int32_t device, nm_policy** out);
+int nm_policy_create_act(const int32_t* dims, int32_t n_layers, int32_t activation, int32_t device, nm_policy** out);
 int nm_policy_destroy(nm_policy* h);
 /* Copy + repack the parameters (device f32, torch.nn.Linear layout: weights[l] is [out_l, in_l] row-major, bias[l] is [out_l]).
  * Stream-ordered; call again after every optimiser step / load_state_dict - the handle never reads the caller's tensors later. */
@@ -180,10 +196,12 @@ int nm_ppo_record(const float* rew_dev, const int64_t* done_dev, const float* ti
  * adaptive-KL learning rate, gradient-norm clipping, Adam; caller reference train.py:54; hyper-parameters envs/nightmare_v3_config.py:111-128)
  * as two launches per mini-batch (forward/backward; then partial-gradient reduction, gradient-norm clip, KL-adaptive learning rate, Adam and
  * the repacking of the weights in one launch with one grid barrier) with no host synchronisation. actor_dims / critic_dims = {n_obs, h1, ..., n_out} (same depth, same
- * observation, critic output 1, ELU). The parameters live in ONE caller-owned flat device vector in the order
+ * observation, critic output 1, hidden activation ELU - or any NM_ACT_* code with nm_ppo_create_act, reference envs/nightmare_v3_config.py:109).
+ * The parameters live in ONE caller-owned flat device vector in the order
  * actor W0 b0 W1 b1 ..., critic W0 b0 ..., std[A] (W row-major [out, in] as torch.nn.Linear); Adam's moments in two more such vectors. */
 typedef struct nm_ppo nm_ppo;
 int nm_ppo_create(const int32_t* actor_dims, const int32_t* critic_dims, int32_t n_layers, int32_t device, nm_ppo** out);
+int nm_ppo_create_act(const int32_t* actor_dims, const int32_t* critic_dims, int32_t n_layers, int32_t activation, int32_t device, nm_ppo** out);
 int nm_ppo_destroy(nm_ppo* h);
 int32_t nm_ppo_num_params(const nm_ppo* h);
 /* (re)read the flat parameters (after load_state_dict or a step taken elsewhere) and set the learning rate / Adam step count */
@@ -219,7 +237,7 @@ int nm_ppo_debug_break_barrier(nm_ppo* h, void* stream);
  * out_dev[i] (int32) = image of i under a pseudo-random permutation of 0..n-1 keyed by (seed, counter) - a cycle-walked Feistel network,
  * one launch, no sort. */
 int nm_ppo_permutation(int32_t* out_dev, int32_t n, uint64_t seed, uint64_t counter, void* stream);
-/* 1 if the network runs on the compiled register-resident kernels (the reference's 66 -> 54 -> 42 -> 30 -> 18 | 1 shape), else 0 */
+/* 1 if the network runs on the compiled register-resident kernels (the reference's 66 -> 54 -> 42 -> 30 -> 18 | 1 shape, any activation), else 0 */
 int32_t nm_ppo_has_fast_path(const nm_ppo* h);
 /* rsl_rl v1.0.2 PPO.act (caller reference train.py:54) in ONE launch, fast-path networks only: merged actor+critic forward from the
  * update's packed weights (always current: no repack between update and collection), then exactly what nm_ppo_sample does */
@@ -276,12 +294,22 @@ typedef struct {
   float* last_values_dev;              /* [N] or NULL: the critic's value of the observation after the last step - rsl_rl PPO.compute_returns'
                                           `last_values = actor_critic.evaluate(last_critic_obs)` - evaluated by the env's wave at the end of the launch */
 } nm_rollout_args;
-/* 1 if nm_rollout / nm_rollout_act are compiled for these networks (dims = {n_obs, h1, h2, h3, n_out}, HOST arrays) */
+/* 1 if nm_rollout / nm_rollout_act are compiled for these networks (dims = {n_obs, h1, h2, h3, n_out}, HOST arrays); ELU hidden layers */
 int nm_rollout_supported(const int32_t* actor_dims, const int32_t* critic_dims, int32_t n_layers);
+/* the same for hidden layers of activation `activation` (reference envs/nightmare_v3_config.py:109): 0 for an unknown code. Host only. */
+int nm_rollout_supported_act(const int32_t* actor_dims, const int32_t* critic_dims, int32_t n_layers, int32_t activation);
 int nm_rollout(nm_env* env, const nm_rollout_args* args, void* stream);
+/* nm_rollout for networks with hidden activation `activation` (NM_ACT_*; reference envs/nightmare_v3_config.py:109, collection loop train.py:54).
+ * nm_rollout = nm_rollout_ex(..., NM_ACT_ELU, ...). */
+int nm_rollout_ex(nm_env* env, const nm_rollout_args* args, int32_t activation, void* stream);
 /* PPO.act alone, on the code the rollout's waves run (one wave = two envs): the per-step counterpart of nm_rollout. Arguments as nm_ppo_act. */
 int nm_rollout_act(nm_env* env, const float* params_flat_dev, const float* obs_dev, uint64_t seed, const int64_t* iter_dev, int32_t step,
                    float* actions_dev, float* logp_dev, float* values_dev, float* mu_dev, float* sigma_dev, float* obs_store_dev, void* stream);
+/* nm_rollout_act with hidden activation `activation` (the per-step counterpart of nm_rollout_ex; reference envs/nightmare_v3_config.py:109,
+ * PPO.act caller train.py:54). nm_rollout_act = nm_rollout_act_ex(..., NM_ACT_ELU, ...). */
+int nm_rollout_act_ex(nm_env* env, const float* params_flat_dev, const float* obs_dev, uint64_t seed, const int64_t* iter_dev, int32_t step,
+                      float* actions_dev, float* logp_dev, float* values_dev, float* mu_dev, float* sigma_dev, float* obs_store_dev, int32_t activation,
+                      void* stream);
 
 /* ---- scripted gait / IK engine (reference nikengine/engine.py; caller custom_play.py:49-76), batched over envs ----
  * One handle = num_envs independent EngineNode objects (engine.py:660-677), all in IdleState. */

@@ -7,10 +7,23 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("NM_HIP_LIB") or os.path.join(HERE, "csrc", "libnightmare_hip.so")   # NM_HIP_LIB: measurement builds
 NUM_OBS, NUM_ACTIONS, NUM_REWARDS = 66, 18, 16
 DTYPE_F32, DTYPE_F64 = 0, 1
+# hidden-layer activation names (rsl_rl v1.0.2 get_activation; ActorCritic's `activation`) -> NM_ACT_* of include/nightmare_hip.h.
+# crelu is a plain ReLU in rsl_rl v1.0.2's published code, so it shares the ReLU kernels.
+ACTIVATIONS = {"elu": 0, "selu": 1, "relu": 2, "crelu": 2, "lrelu": 3, "tanh": 4, "sigmoid": 5}
+
+
+def activation_code(name):
+    """NM_ACT_* code of an activation name; ValueError for a name the kernels do not implement."""
+    try:
+        return ACTIVATIONS[name]
+    except (KeyError, TypeError):
+        raise ValueError(f"activation {name!r} has no kernel (known: {sorted(ACTIVATIONS)})") from None
+
 
 EXPORTS = ["nm_default_config", "nm_reward_name", "nm_last_error", "nm_create", "nm_destroy", "nm_num_envs", "nm_dtype", "nm_reset",
            "nm_step", "nm_step_physics", "nm_get_state", "nm_set_state", "nm_get_buffers", "nm_set_buffers",
            "nm_set_command_uniforms", "nm_get_feet_state", "nm_set_feet_state", "nm_get_counters", "nm_set_debug_buffer", "nm_set_return_accumulator", "nm_invalidate_time_outs", "nm_rollout", "nm_rollout_act", "nm_rollout_supported", "nm_policy_create", "nm_policy_destroy", "nm_policy_load", "nm_policy_forward", "nm_profile", "nm_gae", "nm_gae_advantages", "nm_ppo_sample", "nm_ppo_record", "nm_ppo_create", "nm_ppo_destroy", "nm_ppo_num_params", "nm_ppo_sync_params", "nm_ppo_minibatch", "nm_ppo_minibatch_rows", "nm_ppo_set_storage_rows", "nm_ppo_step_is_fused", "nm_ppo_debug_break_barrier", "nm_ppo_permutation", "nm_ppo_copy_grad", "nm_ppo_set_grad_buffer", "nm_ppo_get_state", "nm_ppo_snapshot_state", "nm_ppo_has_fast_path", "nm_ppo_act", "nm_ppo_record_act",
+           "nm_policy_create_act", "nm_ppo_create_act", "nm_rollout_supported_act", "nm_rollout_ex", "nm_rollout_act_ex",
            "nm_set_observation_noise", "nm_set_noise_uniforms", "nm_set_state_record", "nm_get_state_record",
            "nm_nik_create", "nm_nik_destroy", "nm_nik_reset", "nm_nik_set_gait", "nm_nik_update", "nm_nik_get_state"]
 
@@ -109,6 +122,9 @@ def _bind(L, full):
         L.nm_rollout.argtypes = [vp, C.POINTER(NmRolloutArgs), vp]
         L.nm_rollout_act.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
         L.nm_rollout_supported.argtypes = [vp, vp, C.c_int32]
+        L.nm_rollout_supported_act.argtypes = [vp, vp, C.c_int32, C.c_int32]
+        L.nm_rollout_ex.argtypes = [vp, C.POINTER(NmRolloutArgs), C.c_int32, vp]
+        L.nm_rollout_act_ex.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32, vp]
     L.nm_profile.argtypes = [vp, C.c_int32, vp, vp]
     L.nm_set_observation_noise.argtypes = [vp, vp]
     L.nm_set_noise_uniforms.argtypes = [vp, vp]
@@ -121,6 +137,7 @@ def _bind(L, full):
     L.nm_ppo_sample.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
     L.nm_ppo_record.argtypes = [vp, vp, vp, vp, C.c_float, C.c_int32, vp, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp]
     L.nm_ppo_create.argtypes = [vp, vp, C.c_int32, C.c_int32, C.POINTER(vp)]
+    L.nm_ppo_create_act.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
     L.nm_ppo_destroy.argtypes = [vp]
     L.nm_ppo_num_params.argtypes = [vp]
     L.nm_ppo_sync_params.argtypes = [vp, vp, C.c_float, C.c_int64, vp]
@@ -142,6 +159,7 @@ def _bind(L, full):
     L.nm_ppo_debug_break_barrier.argtypes = [vp, vp]
     L.nm_ppo_snapshot_state.argtypes = [vp, vp, C.c_int32, vp]
     L.nm_policy_create.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(vp)]
+    L.nm_policy_create_act.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]
     L.nm_policy_destroy.argtypes = [vp]
     L.nm_policy_load.argtypes = [vp, vp, vp, vp]
     L.nm_policy_forward.argtypes = [vp, vp, C.c_int32, vp, vp]

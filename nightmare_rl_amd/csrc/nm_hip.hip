@@ -244,8 +244,8 @@ struct nm_env {
   virtual void set_dbg(void* p) = 0;
   virtual void set_ret_acc(float* p) = 0;
   virtual int invalidate_time_outs(hipStream_t s) = 0;
-  virtual int rollout(const nm_rollout_args* r, hipStream_t s) = 0;
-  virtual int rollout_act(const float* flat, const float* obs, uint64_t seed, const int64_t* iter_dev, int step, float* actions, float* logp, float* values,
+  virtual int rollout(const nm_rollout_args* r, int act, hipStream_t s) = 0;
+  virtual int rollout_act(const float* flat, const float* obs, uint64_t seed, const int64_t* iter_dev, int step, int act, float* actions, float* logp, float* values,
                           float* mu, float* sigma, float* obs_store, hipStream_t s) = 0;
   virtual int profiling(int on, double* sum_ms, int64_t* count) = 0;
   virtual void set_ablate(int m) = 0;
@@ -534,16 +534,16 @@ template <class real> struct Env : nm_env {
     if (nmr::launch_pack(flat, roll_wp, roll_bp, s)) return fail("nm_rollout: packing the policy failed to launch");
     return 0;
   }
-  int rollout_act(const float* flat, const float* obs, uint64_t seed, const int64_t* iter_dev, int step, float* actions, float* logp, float* values,
+  int rollout_act(const float* flat, const float* obs, uint64_t seed, const int64_t* iter_dev, int step, int act, float* actions, float* logp, float* values,
                   float* mu, float* sigma, float* obs_store, hipStream_t s) override {
     HIPCHK(hipSetDevice(device));
     if (!flat || !obs || !iter_dev || !actions || !logp || !values || !mu || !sigma) return fail("nm_rollout_act: NULL pointer");
     if (roll_pack(flat, s)) return 1;
     nmr::ActOut o{actions, logp, values, mu, sigma, obs_store};
-    if (nmr::launch_act(roll_wp, roll_bp, flat + RS::stdoff(), obs, N, seed, iter_dev, step, o, s)) return fail("nm_rollout_act: launch failed");
+    if (nmr::launch_act(roll_wp, roll_bp, flat + RS::stdoff(), obs, N, seed, iter_dev, step, o, act, s)) return fail("nm_rollout_act: launch failed");
     return 0;
   }
-  int rollout(const nm_rollout_args* r, hipStream_t s) override {
+  int rollout(const nm_rollout_args* r, int act, hipStream_t s) override {
     HIPCHK(hipSetDevice(device));
     if constexpr (sizeof(real) == 8 || NM_ENVS_PER_WAVE != 2) {
       return fail("nm_rollout: the fused rollout runs on the fp32 kernel (two envs per wave) only");
@@ -585,7 +585,7 @@ template <class real> struct Env : nm_env {
       R.wave_clock = A.dbg ? reinterpret_cast<unsigned long long*>(A.dbg) : nullptr;   // measurement: the debug buffer ([N,256] reals) takes the waves' clocks instead
       nmr::TailArgs ta{N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, r->bootstrap_time_outs ? r->gamma : -1.0f, r->s_values, r->s_rewards,
                        r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
-      if (nmr::launch_rollout(M_dev, a, R, ta, s)) return fail("nm_rollout: launch failed");
+      if (nmr::launch_rollout(M_dev, a, R, ta, act, s)) return fail("nm_rollout: launch failed");
       return 0;
     }
   }
@@ -702,17 +702,35 @@ int nm_set_debug_buffer(nm_env* env, void* dbg) { NEED(env); env->set_dbg(dbg); 
 int nm_set_return_accumulator(nm_env* env, float* acc) { NEED(env); env->set_ret_acc(acc); return 0; }
 int nm_invalidate_time_outs(nm_env* env, void* stream) { NEED(env); return env->invalidate_time_outs((hipStream_t)stream); }
 int nm_rollout_supported(const int32_t* actor_dims, const int32_t* critic_dims, int32_t n_layers) {
+  return nm_rollout_supported_act(actor_dims, critic_dims, n_layers, NM_ACT_ELU);
+}
+int nm_rollout_supported_act(const int32_t* actor_dims, const int32_t* critic_dims, int32_t n_layers, int32_t activation) {
   typedef nmr::RefShape RS;
+  if (!nmact::valid(activation)) return 0;
   if (!actor_dims || !critic_dims || n_layers != RS::NL) return 0;
   if (actor_dims[0] != RS::I || critic_dims[0] != RS::I) return 0;
   for (int l = 0; l < RS::NL; l++)
     if (actor_dims[l + 1] != RS::aout(l) || critic_dims[l + 1] != RS::cout(l)) return 0;
   return 1;
 }
-int nm_rollout(nm_env* env, const nm_rollout_args* args, void* stream) { NEED(env); return env->rollout(args, (hipStream_t)stream); }
+static int bad_activation(const char* who, int32_t act) {
+  return fail(std::string(who) + ": unknown activation code " + std::to_string(act) + " (NM_ACT_*: 0.." + std::to_string(NM_NUM_ACTIVATIONS - 1) + ")");
+}
+int nm_rollout(nm_env* env, const nm_rollout_args* args, void* stream) { return nm_rollout_ex(env, args, NM_ACT_ELU, stream); }
+int nm_rollout_ex(nm_env* env, const nm_rollout_args* args, int32_t activation, void* stream) {
+  NEED(env);
+  if (!nmact::valid(activation)) return bad_activation("nm_rollout", activation);
+  return env->rollout(args, activation, (hipStream_t)stream);
+}
 int nm_rollout_act(nm_env* env, const float* flat, const float* obs, uint64_t seed, const int64_t* iter_dev, int32_t step, float* actions, float* logp,
                    float* values, float* mu, float* sigma, float* obs_store, void* stream) {
-  NEED(env); return env->rollout_act(flat, obs, seed, iter_dev, step, actions, logp, values, mu, sigma, obs_store, (hipStream_t)stream);
+  return nm_rollout_act_ex(env, flat, obs, seed, iter_dev, step, actions, logp, values, mu, sigma, obs_store, NM_ACT_ELU, stream);
+}
+int nm_rollout_act_ex(nm_env* env, const float* flat, const float* obs, uint64_t seed, const int64_t* iter_dev, int32_t step, float* actions, float* logp,
+                      float* values, float* mu, float* sigma, float* obs_store, int32_t activation, void* stream) {
+  NEED(env);
+  if (!nmact::valid(activation)) return bad_activation("nm_rollout_act", activation);
+  return env->rollout_act(flat, obs, seed, iter_dev, step, activation, actions, logp, values, mu, sigma, obs_store, (hipStream_t)stream);
 }
 #ifdef NM_MEASURE   // include/nightmare_hip_measure.h: not part of the shipped ABI
 int nm_set_ablation(nm_env* env, int32_t mask) { NEED(env); env->set_ablate(mask); return 0; }

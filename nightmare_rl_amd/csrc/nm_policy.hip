@@ -1,6 +1,7 @@
-// nm_policy.hip - ActorCritic MLP forward (rsl_rl v1.0.2 ActorCritic: Linear -> ELU ... -> Linear; reference call sites
-// play.py:122, train.py:40) as a batched GEMM chain on the matrix cores: exact-f32 MFMA (v_mfma_f32_16x16x4_f32), bias + ELU fused
-// into the accumulator epilogue, all layers in ONE launch.
+// nm_policy.hip - ActorCritic MLP forward (rsl_rl v1.0.2 ActorCritic: Linear -> activation ... -> Linear; reference call sites
+// play.py:122, train.py:40) as a batched GEMM chain on the matrix cores: exact-f32 MFMA (v_mfma_f32_16x16x4_f32), bias + activation
+// fused into the accumulator epilogue, all layers in ONE launch. The activation (nm_act.h) is a template argument of k_mlp_fused - one
+// instantiation per NM_ACT_* code - and a wave-uniform argument of the per-layer fallback.
 //
 // Shape of the problem: M = num_envs rows (4096), K, N <= 256: 0.7 GFLOP for 66->256->256->18 - a small GEMM chain whose floor is
 // the matrix pipe (16 rows per CU on 256 CUs: 1360 MFMAs per CU = 10.9k cycles). Design:
@@ -19,6 +20,7 @@
 #include <vector>
 
 #include "../../include/nightmare_hip.h"
+#include "nm_act.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -130,6 +132,7 @@ extern "C" int nm_mlp_read_stamps(unsigned long long* out16) {
 #define MLP_STEP(l, k)
 #endif
 
+template <int ACT>
 __global__ void __launch_bounds__(kMlpThreads) k_mlp_fused(const float* __restrict__ obs, float* __restrict__ out, MlpArgs a) {
   __shared__ __attribute__((aligned(16))) float act[2][kTileRows * kActLd];
   __shared__ __attribute__((aligned(16))) float red[kMlpWaves][8][64];     // split-K partial accumulators of narrow layers
@@ -281,7 +284,7 @@ __global__ void __launch_bounds__(kMlpThreads) k_mlp_fused(const float* __restri
     // next layer's k-steps wants (see the fused last layer below), and 16 contiguous bytes of the output row.
     if (fuse) {
       // ---- the last layer from registers: Y2' = W2 Y1'. Lane (r, q) holds, for each of its two feature tiles t, the features
-      // 16 t + 4 q + reg of batch row r after bias + ELU - as a B operand that is k-step `reg` of k-group t in the packing of wt_last.
+      // 16 t + 4 q + reg of batch row r after bias + activation - as a B operand that is k-step `reg` of k-group t in the packing of wt_last.
       // A wave contributes the partial sums over ITS features; the eight waves' partials are added through LDS (split-k by wave).
       const int OL = a.dims[a.n_layers], ntoL = (OL + 15) >> 4;
       f32x4 a2[2] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
@@ -294,8 +297,8 @@ __global__ void __launch_bounds__(kMlpThreads) k_mlp_fused(const float* __restri
             for (int reg = 0; reg < 4; reg++) {
               const int f = 16 * tile + 4 * q + reg;
               float v = (half ? acc1[reg] : acc0[reg]) + (half ? bias1[reg] : bias0[reg]);
-              v = v > 0.0f ? v : __expf(v) - 1.0f;
-              v = f < O ? v : 0.0f;
+              v = nmact::f<ACT>(v);
+              v = f < O ? v : 0.0f;                   // padding features (sigmoid(0) = 0.5): explicit zeros
               a2[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wl[0][half][reg], v, a2[0], 0, 0, 0);
               a2[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(wl[1][half][reg], v, a2[1], 0, 0, 0);
             }
@@ -328,8 +331,8 @@ __global__ void __launch_bounds__(kMlpThreads) k_mlp_fused(const float* __restri
             const int f = 16 * tile + 4 * q + reg;
             float v = (half ? acc1[reg] : acc0[reg]) + (half ? bias1[reg] : bias0[reg]);
             if (!last) {
-              v = v > 0.0f ? v : __expf(v) - 1.0f;   // ELU; v_exp_f32 (1 ulp) - 1: absolute error < 1.2e-7, no libm call in the epilogue
-              y[r * kActLd + reg * kQStride + (4 * tile + q)] = f < O ? v : 0.0f;   // = act_pos(f); features up to the next multiple of 16 feed zero weights: keep them finite
+              v = nmact::f<ACT>(v);   // ELU: v_exp_f32 (1 ulp) - 1, absolute error < 1.2e-7, no libm call in the epilogue (nm_act.h: the others)
+              y[r * kActLd + reg * kQStride + (4 * tile + q)] = f < O ? v : 0.0f;   // = act_pos(f); features up to the next multiple of 16 feed zero weights: explicit zeros (finite, and act(0) may be != 0)
             } else if (f < O && row0 + r < a.N) {
               out[(size_t)(row0 + r) * O + f] = v;
             }
@@ -343,8 +346,9 @@ __global__ void __launch_bounds__(kMlpThreads) k_mlp_fused(const float* __restri
 }
 
 // y[N,O] = act(x[N,K] W[O,K]^T + b[O]);  grid = (ceil(N/32), ceil(O/32)), block = 64   (fallback for layers wider than 256)
+// act: an NM_ACT_* code or nmact::kLinear (the last layer); ELU keeps its expm1f form
 __global__ void __launch_bounds__(64) k_linear_mfma(const float* __restrict__ x, const float* __restrict__ W, const float* __restrict__ b,
-                                                    float* __restrict__ y, int N, int K, int O, int elu) {
+                                                    float* __restrict__ y, int N, int K, int O, int act) {
   const int lane = threadIdx.x, r = lane & 31, h = lane >> 5;
   const int row0 = blockIdx.x * 32, col0 = blockIdx.y * 32;
   const int ar = row0 + r, bc = col0 + r;
@@ -366,7 +370,8 @@ __global__ void __launch_bounds__(64) k_linear_mfma(const float* __restrict__ x,
       int row = row0 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
       if (row < N) {
         float v = acc[reg] + bias;
-        if (elu) v = v > 0.0f ? v : expm1f(v);
+        if (act == NM_ACT_ELU) v = v > 0.0f ? v : expm1f(v);
+        else if (act != nmact::kLinear) v = nmact::f_rt(act, v);
         y[(size_t)row * O + col] = v;
       }
     }
@@ -376,6 +381,7 @@ __global__ void __launch_bounds__(64) k_linear_mfma(const float* __restrict__ x,
 // ------------------------------------------------------------------------------------------------ handle
 struct nm_policy {
   int device = 0, n_layers = 0;
+  int act = NM_ACT_ELU;               // hidden-layer activation (NM_ACT_*)
   std::vector<int> dims;
   bool fused = false, loaded = false;
   f32x4* packed = nullptr;            // fused path: packed weights of all layers
@@ -396,8 +402,16 @@ static bool mlp_fits(const int32_t* dims, int32_t n_layers) {
 }
 
 extern "C" int nm_policy_create(const int32_t* dims, int32_t n_layers, int32_t device, nm_policy** out) {
+  return nm_policy_create_act(dims, n_layers, NM_ACT_ELU, device, out);
+}
+
+// the network with hidden activation `activation` (NM_ACT_*; reference envs/nightmare_v3_config.py:109, call sites play.py:122, train.py:40)
+extern "C" int nm_policy_create_act(const int32_t* dims, int32_t n_layers, int32_t activation, int32_t device, nm_policy** out) {
   if (!out) return nm_policy_set_error("nm_policy_create: out is NULL");
   *out = nullptr;
+  if (!nmact::valid(activation))
+    return nm_policy_set_error(("nm_policy_create: unknown activation code " + std::to_string(activation) + " (NM_ACT_*: 0.." +
+                                std::to_string(NM_NUM_ACTIVATIONS - 1) + ")").c_str());
   if (!dims || n_layers <= 0) return nm_policy_set_error("nm_policy_create: bad argument");
   for (int l = 0; l <= n_layers; l++)
     if (dims[l] <= 0) return nm_policy_set_error("nm_policy_create: layer sizes must be positive");
@@ -405,7 +419,7 @@ extern "C" int nm_policy_create(const int32_t* dims, int32_t n_layers, int32_t d
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return nm_policy_set_error("nm_policy_create: no such HIP device");
   if (hipSetDevice(device) != hipSuccess) return nm_policy_set_error("nm_policy_create: hipSetDevice failed");
   nm_policy* h = new nm_policy();
-  h->device = device; h->n_layers = n_layers;
+  h->device = device; h->n_layers = n_layers; h->act = activation;
   h->dims.assign(dims, dims + n_layers + 1);
   h->fused = mlp_fits(dims, n_layers);
   size_t wtot = 0, btot = 0, ptot = 0;
@@ -486,7 +500,9 @@ extern "C" int nm_policy_forward(nm_policy* h, const float* obs, int32_t N, floa
   if (h->fused) {
     MlpArgs a = h->args;
     a.N = N;
-    hipLaunchKernelGGL(k_mlp_fused, dim3((N + kTileRows - 1) / kTileRows), dim3(kMlpThreads), 0, s, obs, out, a);
+    nmact::dispatch(h->act, [&](auto ACT) {
+      hipLaunchKernelGGL(k_mlp_fused<decltype(ACT)::value>, dim3((N + kTileRows - 1) / kTileRows), dim3(kMlpThreads), 0, s, obs, out, a);
+    });
     if (hipGetLastError() != hipSuccess) return nm_policy_set_error("nm_policy_forward: launch failed");
     return 0;
   }
@@ -507,7 +523,7 @@ extern "C" int nm_policy_forward(nm_policy* h, const float* obs, int32_t N, floa
     float* o = last ? out : h->scratch[l & 1];
     dim3 grid((N + 31) / 32, (h->dims[l + 1] + 31) / 32);
     hipLaunchKernelGGL(k_linear_mfma, grid, dim3(64), 0, s, in, h->wcopy + h->w_off[l], h->bias + h->b_off[l], o, N, h->dims[l], h->dims[l + 1],
-                       last ? 0 : 1);
+                       last ? nmact::kLinear : h->act);
     if (hipGetLastError() != hipSuccess) return nm_policy_set_error("nm_policy_forward: launch failed");
     in = o;
   }

@@ -3,11 +3,14 @@
 // clipping, the KL-adaptive learning rate and Adam - TWO launches per mini-batch (k_ppo_fwdbwd / k_ppo_fwdbwd_split, k_ppo_step), no host synchronisation, instead of ~60 framework
 // launches (elementwise chains on [81920 x 54] activations + library GEMMs with K = 82 k).
 //
-// The two MLPs (reference envs/nightmare_v3_config.py:107-109: 66 -> 54 -> 42 -> 30 -> 18 and -> 1, ELU) run as ONE merged network:
+// The two MLPs (reference envs/nightmare_v3_config.py:107-109: 66 -> 54 -> 42 -> 30 -> 18 and -> 1, ELU - or any activation of :109,
+// written as act below: nm_act.h) run as ONE merged network:
 // actor and critic side by side, block-diagonal hidden layers, the bias of a layer stored as one more weight column fed by a constant
 // 1 - so forward, dX and dW are three plain GEMM shapes per layer, all on exact-f32 MFMA (v_mfma_f32_16x16x4_f32):
-//     forward   a_l  = ELU(a_{l-1} Wm_l')              A = activations [16 rows x K],  B = packed Wm_l   (k-major per lane)
-//     dX        d_{l-1} = (d_l Wm_l) * ELU'(a_{l-1})   A = deltas      [16 rows x O],  B = packed Wm_l'  (o-major per lane)
+//     forward   a_l  = act(a_{l-1} Wm_l')              A = activations [16 rows x K],  B = packed Wm_l   (k-major per lane)
+//     dX        d_{l-1} = (d_l Wm_l) * act'(a_{l-1})   A = deltas      [16 rows x O],  B = packed Wm_l'  (o-major per lane)
+// (act' written from the output a = act(z): nmact::dfy; only post-activation values are kept.) The generic kernel takes the activation as
+// a uniform argument (PpoNet::act), the register-resident fast-path kernels are instantiated per activation.
 //     dW        G_l += d_l' a_{l-1}                    A = deltas^T, B = activations, reduction over the 16 rows of the tile
 // k_ppo_fwdbwd: a workgroup of 8 waves walks its share of the mini-batch in tiles of 16 rows; activations and deltas live in LDS
 //   ([row][k mod 4][k div 4]: the A operand of 4 k-steps is one ds_read_b128); the dW accumulators stay in registers for the whole
@@ -22,10 +25,12 @@
 
 #include <cmath>
 #include <cstdlib>
+#include <string>
 #include <utility>
 #include <vector>
 
 #include "../../include/nightmare_hip.h"
+#include "nm_act.h"
 
 extern "C" int nm_policy_set_error(const char* m);
 
@@ -57,6 +62,7 @@ struct PpoNet {
   int nparam_flat;
   const f32x4* sf[2];                  // split kernel: per net (actor, critic), forward fragments in consumption order
   const f32x4* sb[2];                  // ... and the dX fragments
+  int act;                             // hidden-layer activation, NM_ACT_* (read by the generic kernel; the fast-path kernels are instantiated per code)
 };
 struct PpoBatch {
   const float *obs, *actions, *old_mu, *old_sigma, *old_logp, *adv, *ret, *tval, *std;
@@ -127,7 +133,10 @@ __global__ void __launch_bounds__(kThreads) k_ppo_fwdbwd(PpoNet net, PpoBatch bt
         for (int reg = 0; reg < 4; reg++) {
           const int rr = q * 4 + reg;
           float v = acc[reg];
-          if (!last) v = col < Or ? (v > 0.0f ? v : __expf(v) - 1.0f) : (col == Or ? 1.0f : 0.0f);   // ELU | bias carrier | padding
+          if (!last) {     // activation | bias carrier | padding (the carrier and the padding never pass through the activation)
+            if (col < Or) v = net.act == NM_ACT_ELU ? (v > 0.0f ? v : __expf(v) - 1.0f) : nmact::f_rt(net.act, v);
+            else v = col == Or ? 1.0f : 0.0f;
+          }
           y[rr * kLD + pos(col)] = v;
         }
       }
@@ -217,7 +226,7 @@ __global__ void __launch_bounds__(kThreads) k_ppo_fwdbwd(PpoNet net, PpoBatch bt
             gw[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(dp[4 * st * kLD], ap[4 * st * kLD], gw[s], 0, 0, 0);
         }
       }
-      // d_{l-1} = (D Wm_l) * ELU'(a_{l-1})
+      // d_{l-1} = (D Wm_l) * act'(a_{l-1})
       if (l > 0) {
         const int ngrp = net.Op[l] >> 4, ntile = net.Kp[l] >> 4, Kr = net.Kr[l];
         const float* x = D + r * kLD + q * kQS;
@@ -235,7 +244,8 @@ __global__ void __launch_bounds__(kThreads) k_ppo_fwdbwd(PpoNet net, PpoBatch bt
           for (int reg = 0; reg < 4; reg++) {
             const int rr = q * 4 + reg;
             const float a = act[l][rr * kLD + pos(col)];
-            Dn[rr * kLD + pos(col)] = col < Kr ? acc[reg] * (a > 0.0f ? 1.0f : a + 1.0f) : 0.0f;   // ELU'(z) from ELU(z); no gradient into the 1-column
+            const float da = net.act == NM_ACT_ELU ? (a > 0.0f ? 1.0f : a + 1.0f) : nmact::dfy_rt(net.act, a);   // act'(z) from act(z)
+            Dn[rr * kLD + pos(col)] = col < Kr ? acc[reg] * da : 0.0f;   // no gradient into the 1-column / padding
           }
         }
       }
@@ -426,7 +436,7 @@ constexpr int kSplitWaves = 4, kSplitSlots = 16;
 // request keeps each request at its place in the MFMA stream.
 #define NM_PPO_PIN() __builtin_amdgcn_sched_barrier(0)
 
-template <class S>
+template <class S, int ACT>
 __global__ void __launch_bounds__(64 * kSplitWaves, 2) k_ppo_fwdbwd_split(PpoNet net, PpoBatch bt, float* __restrict__ partial) {
   typedef Split<S> X;
   constexpr int NL = S::NL, NG = X::NG, MT = X::maxT(), PO = X::P(NL) / 16, AO = S::aout(NL - 1), I = X::in(0), T0 = X::nkt(0);
@@ -571,15 +581,21 @@ __global__ void __launch_bounds__(64 * kSplitWaves, 2) k_ppo_fwdbwd_split(PpoNet
 #if NM_PPO_ABL & 16     // measurement only: no ELU
               const float y = v;
 #else
-              // ELU(v) = v > 0 ? v : e with e = exp(v) - 1 >= v for every v: the median of (v, e, 0) - one v_med3_f32 instead of compare + select
-              const float e = __expf(v) - 1.0f, y = __builtin_amdgcn_fmed3f(v, e, 0.0f);
+              float y;
+              if constexpr (ACT == NM_ACT_ELU) {
+                // ELU(v) = v > 0 ? v : e with e = exp(v) - 1 >= v for every v: the median of (v, e, 0) - one v_med3_f32 instead of compare + select
+                const float e = __expf(v) - 1.0f;
+                y = __builtin_amdgcn_fmed3f(v, e, 0.0f);
+              } else {
+                y = nmact::f<ACT>(v);
+              }
 #endif
               if constexpr (16 * to + 16 <= NO) {
                 a[l + 1][to][reg] = y;
               } else {
                 const int col = 16 * to + 4 * q + reg;
                 const float pad = col == NO ? 1.0f : 0.0f;
-                a[l + 1][to][reg] = col < NO ? y : pad;   // ELU | bias carrier | padding
+                a[l + 1][to][reg] = col < NO ? y : pad;   // activation | bias carrier | padding
               }
             }
           }
@@ -694,7 +710,7 @@ __global__ void __launch_bounds__(64 * kSplitWaves, 2) k_ppo_fwdbwd_split(PpoNet
         for (int reg = 0; reg < 4; reg++) xb[((abase + t) * NG + g) * kTileF + (4 * q + reg) * kXT + prow] = a[l][t][reg];
       });
       }
-      // d_{l-1} = (W' d_l) * ELU'(a_l): registers only
+      // d_{l-1} = (W' d_l) * act'(a_l): registers only
       if constexpr (l > 0) {
         sfor<(nkt + 1) / 2>([&](auto PP) {
           constexpr int tk0 = 2 * PP, tk1 = tk0 + 1;
@@ -726,7 +742,7 @@ __global__ void __launch_bounds__(64 * kSplitWaves, 2) k_ppo_fwdbwd_split(PpoNet
 #if NM_PPO_ABL & 16
               const float gr = acc[reg] + av;
 #else
-              const float gr = acc[reg] * fminf(av + 1.0f, 1.0f);                                // ELU'(z) from ELU(z): 1 if ELU > 0, else ELU + 1 (<= 1)
+              const float gr = acc[reg] * nmact::dfy<ACT>(av);                                   // act'(z) from act(z); ELU: min(ELU + 1, 1)
 #endif
               if constexpr (16 * tk + 16 <= X::in(l)) d[nxt][tk][reg] = gr;
               else d[nxt][tk][reg] = 16 * tk + 4 * q + reg < X::in(l) ? gr : 0.0f;              // no gradient into the 1-column / padding
@@ -845,7 +861,7 @@ struct PpoRecord {
   float *cur_ret, *cur_len, *fin3;
   const float* ep_stats; const int* ep_idx; int n_ep; float* ep_acc;
 };
-template <class S>
+template <class S, int ACT>
 __global__ void __launch_bounds__(64) k_ppo_act_fast(PpoNet net, const float* __restrict__ obs, const float* __restrict__ std, int N, uint64_t seed,
                                                      const int64_t* __restrict__ iter_dev, int step, float* __restrict__ actions, float* __restrict__ logp,
                                                      float* __restrict__ values, float* __restrict__ mu, float* __restrict__ sigma, float* __restrict__ obs_store,
@@ -930,7 +946,7 @@ __global__ void __launch_bounds__(64) k_ppo_act_fast(PpoNet net, const float* __
           for (int reg = 0; reg < 4; reg++) {
             const int col = 16 * to + 4 * q + reg;
             const float v = acc[reg];
-            a[l + 1][to][reg] = col < S::Or(l) ? (v > 0.0f ? v : __expf(v) - 1.0f) : (col == S::Or(l) ? 1.0f : 0.0f);
+            a[l + 1][to][reg] = col < S::Or(l) ? nmact::f<ACT>(v) : (col == S::Or(l) ? 1.0f : 0.0f);   // activation | bias carrier | padding
           }
         }
       };
@@ -1294,8 +1310,16 @@ extern "C" int nm_ppo_destroy(nm_ppo* h) {
 // actor_dims / critic_dims: {n_obs, h1, ..., n_out} with the same number of layers and the same input; critic output 1.
 // Flat parameter order: actor W0 b0 W1 b1 ..., critic W0 b0 ..., std[A] (W row-major [out, in] as torch.nn.Linear).
 extern "C" int nm_ppo_create(const int32_t* actor_dims, const int32_t* critic_dims, int32_t n_layers, int32_t device, nm_ppo** out) {
+  return nm_ppo_create_act(actor_dims, critic_dims, n_layers, NM_ACT_ELU, device, out);
+}
+// the same networks with hidden activation `activation` (NM_ACT_*; reference envs/nightmare_v3_config.py:109, PPO.update caller train.py:54).
+// The reference shape keeps its fast path with every activation (k_ppo_fwdbwd_split / k_ppo_act_fast are instantiated per code).
+extern "C" int nm_ppo_create_act(const int32_t* actor_dims, const int32_t* critic_dims, int32_t n_layers, int32_t activation, int32_t device, nm_ppo** out) {
   if (!out) return nm_policy_set_error("nm_ppo_create: out is NULL");
   *out = nullptr;
+  if (!nmact::valid(activation))
+    return nm_policy_set_error(("nm_ppo_create: unknown activation code " + std::to_string(activation) + " (NM_ACT_*: 0.." +
+                                std::to_string(NM_NUM_ACTIVATIONS - 1) + ")").c_str());
   if (!actor_dims || !critic_dims || n_layers < 1 || n_layers > kL) return nm_policy_set_error("nm_ppo_create: 1..4 layers");
   if (actor_dims[0] != critic_dims[0] || critic_dims[n_layers] != 1 || actor_dims[n_layers] > kMaxA || actor_dims[n_layers] < 1)
     return nm_policy_set_error("nm_ppo_create: actor and critic must share the observation, critic output 1, at most 32 actions");
@@ -1305,7 +1329,7 @@ extern "C" int nm_ppo_create(const int32_t* actor_dims, const int32_t* critic_di
   nm_ppo* h = new nm_ppo();
   h->device = device; h->n_layers = n_layers; h->A = actor_dims[n_layers];
   PpoNet& n = h->net;
-  n.n_layers = n_layers; n.A = h->A;
+  n.n_layers = n_layers; n.A = h->A; n.act = activation;
   int goff = 0;
   for (int l = 0; l < n_layers; l++) {
     n.Kr[l] = l == 0 ? actor_dims[0] : actor_dims[l] + critic_dims[l];
@@ -1529,7 +1553,9 @@ extern "C" int nm_ppo_minibatch_rows(nm_ppo* h, float* flat_dev, float* exp_avg_
     // the reductions add the `grid` rows this launch writes and no others (the rows beyond used to be cleared by a 28 MB memset per
     // mini-batch; inside the update's captured graph that memset node corrupted the loss sums of small batches: grid < number of CUs)
     h->nrows = grid;
-    if (h->fast) hipLaunchKernelGGL(k_ppo_fwdbwd_split<RefShape>, dim3(2 * grid), dim3(64 * kSplitWaves), 0, s, h->net, bt, h->partial);      // two blocks (actor, critic) per partial row
+    if (h->fast) nmact::dispatch(h->net.act, [&](auto ACT) {      // two blocks (actor, critic) per partial row
+      hipLaunchKernelGGL((k_ppo_fwdbwd_split<RefShape, decltype(ACT)::value>), dim3(2 * grid), dim3(64 * kSplitWaves), 0, s, h->net, bt, h->partial);
+    });
     else hipLaunchKernelGGL(k_ppo_fwdbwd, dim3(grid), dim3(kThreads), 0, s, h->net, bt, h->partial);
     if (phase == 1 || !h->fused_step)
       hipLaunchKernelGGL(k_ppo_reduce, dim3(nbr), dim3(kRedParams * kRedWaves), 0, s, h->partial, h->nrows, stride, h->map, h->nparam, h->net.gtotal, flat_dev, entropy_coef, 1.0f / (float)B, ppo_grad(h), h->fast ? 1 : 0);
@@ -1562,8 +1588,10 @@ extern "C" int nm_ppo_act(nm_ppo* h, const float* flat_dev, const float* obs, in
   if (!h || !flat_dev || !obs || !iter_dev || !actions || !logp || !values || !mu || !sigma || N <= 0) return nm_policy_set_error("nm_ppo_act: bad argument");
   if (!h->fast) return nm_policy_set_error("nm_ppo_act: this network shape has no compiled fast path (use nm_policy_forward + nm_ppo_sample)");
   PPO_CHK(hipSetDevice(h->device));
-  hipLaunchKernelGGL(k_ppo_act_fast<RefShape>, dim3((N + 15) / 16), dim3(64), 0, (hipStream_t)stream, h->net, obs, flat_dev + (h->nparam - h->A), N, seed, iter_dev,
-                     step, actions, logp, values, mu, sigma, obs_store, PpoRecord{});
+  nmact::dispatch(h->net.act, [&](auto ACT) {
+    hipLaunchKernelGGL((k_ppo_act_fast<RefShape, decltype(ACT)::value>), dim3((N + 15) / 16), dim3(64), 0, (hipStream_t)stream, h->net, obs, flat_dev + (h->nparam - h->A),
+                       N, seed, iter_dev, step, actions, logp, values, mu, sigma, obs_store, PpoRecord{});
+  });
   if (hipGetLastError() != hipSuccess) return nm_policy_set_error("nm_ppo_act: launch failed");
   return 0;
 }
@@ -1580,8 +1608,10 @@ extern "C" int nm_ppo_record_act(nm_ppo* h, const float* rew, const int64_t* don
   if (!h->fast) return nm_policy_set_error("nm_ppo_record_act: this network shape has no compiled fast path");
   PPO_CHK(hipSetDevice(h->device));
   PpoRecord rec{rew, done, time_outs, prev_values, gamma, rewards_store, dones_store, cur_ret, cur_len, fin3, ep_stats, ep_idx, n_ep, ep_acc};
-  hipLaunchKernelGGL(k_ppo_act_fast<RefShape>, dim3((N + 15) / 16), dim3(64), 0, (hipStream_t)stream, h->net, obs, flat_dev + (h->nparam - h->A), N, seed, iter_dev,
-                     step, actions, logp, values, mu, sigma, obs_store, rec);
+  nmact::dispatch(h->net.act, [&](auto ACT) {
+    hipLaunchKernelGGL((k_ppo_act_fast<RefShape, decltype(ACT)::value>), dim3((N + 15) / 16), dim3(64), 0, (hipStream_t)stream, h->net, obs, flat_dev + (h->nparam - h->A),
+                       N, seed, iter_dev, step, actions, logp, values, mu, sigma, obs_store, rec);
+  });
   if (hipGetLastError() != hipSuccess) return nm_policy_set_error("nm_ppo_record_act: launch failed");
   return 0;
 }

@@ -12,8 +12,9 @@
 // a 16x16x4 tile with two live columns. Weights stream from L2 in consumption order through a register ring (one 16-byte load per lane
 // = the A operands of 4 k steps), activations go from layer to layer through 2 KB of the wave's LDS.
 //
-// Arithmetic: exact f32 FMA chains in k order, bias as the accumulator's initial value, ELU with the hardware exponential - the same
-// network as nm_ppo_act (16x16x4 tiles), rounded in another order (agreement ~1e-6; tests/test_gpu_rollout.py states the tolerance).
+// Arithmetic: exact f32 FMA chains in k order, bias as the accumulator's initial value, the hidden activation of nm_act.h (a template
+// argument: ELU by default, with the hardware exponential) - the same network as nm_ppo_act (16x16x4 tiles), rounded in another order
+// (agreement ~1e-6; tests/test_gpu_rollout.py states the tolerance).
 // The action noise uses the generator and keys of nm_ppo_sample / nm_ppo_act (seed, iteration, step, env, action pair): the same z.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,6 +22,8 @@
 
 #include <type_traits>
 #include <utility>
+
+#include "nm_act.h"
 
 namespace nmr {
 
@@ -122,7 +125,7 @@ struct ActOut {
 // PPO.act for the wave's two envs (env = 2 wave + column). xb: kXFloats floats of the wave's LDS. obs: [N, I] device memory that this wave
 // may have written itself a moment ago (the caller has waited for those stores). `env_id0` = global id of env 0 (noise key).
 // VALUE_ONLY: the same forward, but nothing is sampled or filed except the critic's value into o.values[env] (the last observation of a rollout).
-template <class S, bool VALUE_ONLY = false>
+template <class S, int ACT, bool VALUE_ONLY = false>
 __device__ __forceinline__ void policy_wave(float* xb, const f32x4* __restrict__ wp, const float* __restrict__ bp, const float* __restrict__ stdv,
                                             const float* obs, int N, int wave, uint64_t seed, uint64_t ctr, const ActOut& o) {
   constexpr int NL = S::NL, NF = S::nfrag(), I = S::I, AO = S::AO;
@@ -190,7 +193,9 @@ __device__ __forceinline__ void policy_wave(float* xb, const f32x4* __restrict__
         const int b = 16 * g + blk, o0 = 4 * b;
         f32x4 v = acc[g];
 #pragma unroll
-        for (int i = 0; i < 4; i++) v[i] = v[i] > 0.0f ? v[i] : __expf(v[i]) - 1.0f;     // ELU; padding neurons: bias 0, weights 0 -> 0
+        for (int i = 0; i < 4; i++) v[i] = nmact::f<ACT>(v[i]);
+        // padding neurons (bias 0, weights 0) hold act(0) - 0.5 for sigmoid - but every packed weight that reads them is 0 (k_roll_pack:
+        // widx = -1 for k >= ka / kc), so a finite act(0) adds exactly 0; the next layer's k range ends at the padded width
         if (col < 2 && b < nb) *reinterpret_cast<f32x4*>(xout + (o0 < oa4 ? o0 : 64 + o0 - oa4)) = v;
       });
       roll_sync();
@@ -265,7 +270,22 @@ struct TailArgs {
 namespace nm { template <class real> struct Model; template <class real> struct Args; }
 namespace nmr {
 int launch_pack(const float* flat, float* wp, float* bp, hipStream_t s);
-int launch_act(const float* wp, const float* bp, const float* stdv, const float* obs, int N, uint64_t seed, const int64_t* iter_dev, int step, const ActOut& o, hipStream_t s);
-int launch_rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, const TailArgs& t, hipStream_t s);
+// the launches of k_roll_act / k_env_rollout for one hidden activation (NM_ACT_*): defined in nm_rollout_kernels.h, instantiated once per
+// code by nm_rollout_<activation>.hip
+template <int ACT> struct RollKernels {
+  static int act(const float* wp, const float* bp, const float* stdv, const float* obs, int N, uint64_t seed, const int64_t* iter_dev, int step,
+                 const ActOut& o, hipStream_t s);
+  static int rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, hipStream_t s);
+};
+extern template struct RollKernels<NM_ACT_ELU>;
+extern template struct RollKernels<NM_ACT_SELU>;
+extern template struct RollKernels<NM_ACT_RELU>;
+extern template struct RollKernels<NM_ACT_LRELU>;
+extern template struct RollKernels<NM_ACT_TANH>;
+extern template struct RollKernels<NM_ACT_SIGMOID>;
+// act: the hidden activation (NM_ACT_*); a code this build has no instantiation for (the measurement build: ELU only) fails the launch
+int launch_act(const float* wp, const float* bp, const float* stdv, const float* obs, int N, uint64_t seed, const int64_t* iter_dev, int step, const ActOut& o,
+               int act, hipStream_t s);
+int launch_rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, const TailArgs& t, int act, hipStream_t s);
 
 }  // namespace nmr

@@ -1,0 +1,4 @@
+// nm_rollout_relu.hip - the rollout kernels (k_env_rollout, k_roll_act) for hidden activation NM_ACT_RELU, a translation unit of
+// their own (why: nm_rollout_kernels.h).
+#define NM_ROLLOUT_ACT NM_ACT_RELU
+#include "nm_rollout_kernels.h"

@@ -1,0 +1,4 @@
+// nm_rollout_sigmoid.hip - the rollout kernels (k_env_rollout, k_roll_act) for hidden activation NM_ACT_SIGMOID, a translation unit of
+// their own (why: nm_rollout_kernels.h).
+#define NM_ROLLOUT_ACT NM_ACT_SIGMOID
+#include "nm_rollout_kernels.h"

@@ -215,14 +215,15 @@ class NightmareV3Env:
         return self.obs_buf, None, self.rew_buf, self.reset_buf, self.extras
 
     # ------------------------------------------------------------------ K steps per launch with the policy in the env's wave
-    def policy_rollout(self, steps, params_flat, seed, iter_dev, storage, gamma, cur_ret, cur_len, fin, ep=None, last_values=None):
+    def policy_rollout(self, steps, params_flat, seed, iter_dev, storage, gamma, cur_ret, cur_len, fin, ep=None, last_values=None, activation="elu"):
         """`steps` iterations of rsl_rl's collection loop `act -> env.step -> process_env_step` (OnPolicyRunner.learn; reference
         train.py:54) as ONE launch (nm_rollout): starts from the current observation, files every transition into `storage` (a
         RolloutStorage with `steps` rows: observations, actions, values, log-probabilities, mu, sigma, rewards incl. the time-out bootstrap,
         dones), updates the runner's bookkeeping tensors (cur_ret / cur_len [N], fin [3], and ep = (ep_idx int32, ep_acc) for the running
         sum of extras['episode']) and leaves the env as `steps` calls of step() would: obs_buf / rew_buf / reset_buf / extras of the last step.
         params_flat: the flat parameter vector of FusedUpdate (actor W0 b0 ..., critic ..., std). last_values ([N] float32 on the device,
-        optional) receives the critic's value of the last observation - what PPO.compute_returns evaluates next."""
+        optional) receives the critic's value of the last observation - what PPO.compute_returns evaluates next. activation: the networks'
+        hidden activation (a name of _lib.ACTIVATIONS, as ActorCritic takes it)."""
         if self.cfg.viewer.record_states:
             raise ValueError("policy_rollout: cfg.viewer.record_states needs one launch per step")
         T = int(steps)
@@ -250,7 +251,7 @@ class NightmareV3Env:
         a.cur_ret, a.cur_len, a.fin3 = cur_ret.data_ptr(), cur_len.data_ptr(), fin.data_ptr()
         a.ep_idx_dev, a.n_ep, a.ep_acc_dev = (ep_idx.data_ptr(), int(ep_idx.numel()), ep_acc.data_ptr()) if ep_idx is not None else (None, 0, None)
         a.last_values_dev = last_values.data_ptr() if last_values is not None else None
-        self._ck(self._L.nm_rollout(self._h, C.byref(a), self._stream()))
+        self._ck(self._L.nm_rollout_ex(self._h, C.byref(a), _lib.activation_code(activation), self._stream()))
         self._keep_rollout = (params_flat, iter_dev, storage, cur_ret, cur_len, fin, ep_idx, ep_acc, last_values)
         self.common_step_counter += T
         storage.step = T
@@ -258,12 +259,12 @@ class NightmareV3Env:
             self._fill_extras()
         return self.obs_buf
 
-    def policy_act(self, params_flat, obs, seed, iter_dev, step, storage):
-        """PPO.act as one launch of the rollout's wave code (nm_rollout_act): the per-step counterpart of policy_rollout."""
+    def policy_act(self, params_flat, obs, seed, iter_dev, step, storage, activation="elu"):
+        """PPO.act as one launch of the rollout's wave code (nm_rollout_act_ex): the per-step counterpart of policy_rollout."""
         s = int(step)
-        self._ck(self._L.nm_rollout_act(self._h, params_flat.data_ptr(), obs.data_ptr(), int(seed), iter_dev.data_ptr(), s, storage.actions[s].data_ptr(),
-                                        storage.actions_log_prob[s].data_ptr(), storage.values[s].data_ptr(), storage.mu[s].data_ptr(),
-                                        storage.sigma[s].data_ptr(), storage.observations[s].data_ptr(), self._stream()))
+        self._ck(self._L.nm_rollout_act_ex(self._h, params_flat.data_ptr(), obs.data_ptr(), int(seed), iter_dev.data_ptr(), s, storage.actions[s].data_ptr(),
+                                           storage.actions_log_prob[s].data_ptr(), storage.values[s].data_ptr(), storage.mu[s].data_ptr(),
+                                           storage.sigma[s].data_ptr(), storage.observations[s].data_ptr(), _lib.activation_code(activation), self._stream()))
         return storage.actions[s]
 
     def actions_from_joint_targets(self, targets):

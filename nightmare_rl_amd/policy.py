@@ -1,5 +1,5 @@
-"""MLP forward on the MFMA units (nm_policy_*): the inference half of rsl_rl's ActorCritic (Linear -> ELU ... -> Linear),
-torch.nn.Linear weight layout so state_dicts load unchanged.
+"""MLP forward on the MFMA units (nm_policy_*): the inference half of rsl_rl's ActorCritic (Linear -> activation ... -> Linear; any
+hidden activation of rsl_rl's get_activation, ELU by default), torch.nn.Linear weight layout so state_dicts load unchanged.
 
 Each network owns ONE library handle with a packed copy of its parameters. The copy is refreshed by `repack()`: explicitly (after
 an optimiser step, `load_state_dict`, or any write through `.data`) or, in `forward`, whenever the parameters' generation changed -
@@ -15,16 +15,18 @@ from . import _lib
 class PackedMLP:
     """Handle of one packed network on one device (no torch module semantics): load(weights, biases) then forward(obs)."""
 
-    def __init__(self, dims, device):
+    def __init__(self, dims, device, activation="elu"):
         self.dims = [int(d) for d in dims]
         self.device = torch.device(device)
+        self.activation = activation
+        code = _lib.activation_code(activation)
         if self.device.type != "cuda":
             raise _lib.NightmareHipError("the MLP kernels need a HIP device (no CPU path)")
         self._L = _lib.load()
         h = C.c_void_p()
         arr = (C.c_int32 * len(self.dims))(*self.dims)
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-        _lib.check(self._L.nm_policy_create(arr, len(self.dims) - 1, idx, C.byref(h)))
+        _lib.check(self._L.nm_policy_create_act(arr, len(self.dims) - 1, code, idx, C.byref(h)))
         self._h = h
         self._out = None
 
@@ -65,10 +67,18 @@ class PackedMLP:
             pass
 
 
+_TORCH_ACT = {"elu": torch.nn.functional.elu, "selu": torch.nn.functional.selu, "relu": torch.relu, "crelu": torch.relu,
+              "lrelu": torch.nn.functional.leaky_relu, "tanh": torch.tanh, "sigmoid": torch.sigmoid}
+
+
 class ActorMLP(torch.nn.Module):
-    def __init__(self, dims=(66, 256, 256, 18)):
+    """activation: the hidden layers' (a name of rsl_rl's get_activation, as ActorCritic takes it). A checkpoint does not record it."""
+
+    def __init__(self, dims=(66, 256, 256, 18), activation="elu"):
         super().__init__()
+        _lib.activation_code(activation)
         self.dims = list(dims)
+        self.activation = activation
         self.layers = torch.nn.ModuleList(torch.nn.Linear(dims[i], dims[i + 1]) for i in range(len(dims) - 1))
         self._packed = None
         self._generation = None
@@ -78,7 +88,7 @@ class ActorMLP(torch.nn.Module):
         for i, l in enumerate(self.layers):
             x = l(x)
             if i < len(self.layers) - 1:
-                x = torch.nn.functional.elu(x)
+                x = _TORCH_ACT[self.activation](x)
         return x
 
     def _fingerprint(self):
@@ -91,7 +101,7 @@ class ActorMLP(torch.nn.Module):
     def repack(self):
         dev = self.layers[0].weight.device
         if self._packed is None or self._packed.device != dev:
-            self._packed = PackedMLP(self.dims, dev)
+            self._packed = PackedMLP(self.dims, dev, self.activation)
         self._packed.load([l.weight for l in self.layers], [l.bias for l in self.layers])
         self._generation = self._fingerprint()
         self._dirty = False

@@ -6,7 +6,9 @@ import torch
 import torch.nn as nn
 from torch.distributions import Normal
 
-_ACTIVATIONS = {"elu": nn.ELU, "selu": nn.SELU, "relu": nn.ReLU, "lrelu": nn.LeakyReLU, "tanh": nn.Tanh, "sigmoid": nn.Sigmoid}
+# rsl_rl v1.0.2 get_activation: the names the reference config lists (envs/nightmare_v3_config.py:109). "crelu" is a plain nn.ReLU() in
+# rsl_rl v1.0.2's published code (not a concatenated ReLU), and so it is here.
+_ACTIVATIONS = {"elu": nn.ELU, "selu": nn.SELU, "relu": nn.ReLU, "crelu": nn.ReLU, "lrelu": nn.LeakyReLU, "tanh": nn.Tanh, "sigmoid": nn.Sigmoid}
 
 
 class _SplitKLinearFn(torch.autograd.Function):

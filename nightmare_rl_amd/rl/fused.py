@@ -9,8 +9,8 @@ train.py:54), writing straight into the rollout storage:
     the two MLPs side by side, block-diagonal hidden layers), `nm_ppo_sample`, `nm_ppo_record`; the packed copy of the parameters is
     refreshed once per iteration by `refresh()`, outside any captured graph.
 
-Used by PPO when the networks qualify (`FusedCollector.supported`); otherwise PPO keeps its torch path (host tests, other
-activations)."""
+Used by PPO when the networks qualify (`FusedCollector.supported`: any activation of `_lib.ACTIVATIONS`); otherwise PPO keeps its
+torch path (host tests, deeper or wider networks)."""
 import ctypes as C
 
 import torch
@@ -23,7 +23,7 @@ from ..policy import PackedMLP
 class FusedCollector:
     @staticmethod
     def supported(ac, device):
-        if torch.device(device).type != "cuda" or getattr(ac, "activation_name", None) != "elu":
+        if torch.device(device).type != "cuda" or getattr(ac, "activation_name", None) not in _lib.ACTIVATIONS:
             return False
         a = [m for m in ac.actor if isinstance(m, nn.Linear)]
         c = [m for m in ac.critic if isinstance(m, nn.Linear)]
@@ -36,12 +36,14 @@ class FusedCollector:
         """update: the FusedUpdate of the same networks, if there is one. When its handle has the compiled fast path, `act` is ONE
         launch (nm_ppo_act: forward from the update's own packed weights + sampling) and `refresh` has nothing to repack."""
         self.ac, self.device, self.N = ac, torch.device(device), int(num_envs)
+        self.activation = ac.activation_name
+        self.act_code = _lib.activation_code(self.activation)
         self.update = update if (update is not None and update.has_fast_path) else None
         self.a_lin = [m for m in ac.actor if isinstance(m, nn.Linear)]
         self.c_lin = [m for m in ac.critic if isinstance(m, nn.Linear)]
         self.A = self.a_lin[-1].out_features
         dims = [self.a_lin[0].in_features] + [x.out_features + y.out_features for x, y in zip(self.a_lin, self.c_lin)]
-        self.net = PackedMLP(dims, self.device)
+        self.net = PackedMLP(dims, self.device, self.activation)
         self.out = torch.empty(self.N, self.A + 1, device=self.device)
         self.iter_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
         self.seed = int(seed)
@@ -127,7 +129,7 @@ class FusedCollector:
             return False
         a = (C.c_int32 * (len(self.a_lin) + 1))(self.a_lin[0].in_features, *[m.out_features for m in self.a_lin])
         c = (C.c_int32 * (len(self.c_lin) + 1))(self.c_lin[0].in_features, *[m.out_features for m in self.c_lin])
-        return bool(self._L.nm_rollout_supported(a, c, len(self.a_lin)))
+        return bool(self._L.nm_rollout_supported_act(a, c, len(self.a_lin), self.act_code))
 
     def rollout(self, env, storage, steps, gamma, cur_ret, cur_len, fin, ep=None):
         """`steps` x (PPO.act, env.step, PPO.process_env_step + the runner's bookkeeping) as one launch; returns the last observation.
@@ -136,7 +138,8 @@ class FusedCollector:
         storage.clear()
         if getattr(self, "_last_values", None) is None or self._last_values.numel() != env.num_envs:
             self._last_values = torch.zeros(env.num_envs, device=self.device)
-        o = env.policy_rollout(steps, self.update.flat, self.seed, self.iter_dev, storage, gamma, cur_ret, cur_len, fin, ep=ep, last_values=self._last_values)
+        o = env.policy_rollout(steps, self.update.flat, self.seed, self.iter_dev, storage, gamma, cur_ret, cur_len, fin, ep=ep, last_values=self._last_values,
+                               activation=self.activation)
         self.last_values = self._last_values      # the value of the observation after the last step: PPO.compute_returns takes it (once)
         return o
 
@@ -170,6 +173,7 @@ class FusedUpdate:
 
     def __init__(self, ac, optimizer, device, lr):
         self.ac, self.opt, self.device = ac, optimizer, torch.device(device)
+        self.activation = ac.activation_name
         self._L = _lib.load()
         a = [m for m in ac.actor if isinstance(m, nn.Linear)]
         c = [m for m in ac.critic if isinstance(m, nn.Linear)]
@@ -202,7 +206,7 @@ class FusedUpdate:
         if shared:
             os.environ["NM_PPO_UNFUSED_STEP"] = "1"
         try:
-            _lib.check(self._L.nm_ppo_create(adims, cdims, len(a), idx, C.byref(h)))
+            _lib.check(self._L.nm_ppo_create_act(adims, cdims, len(a), _lib.activation_code(self.activation), idx, C.byref(h)))
         finally:
             if shared:
                 if prev is None:

@@ -6,6 +6,10 @@ Here: the checkpoint's actor runs on the matrix cores (nm_policy_* handle), the 
 once, no viewer. Like upstream the actions are SAMPLED (`nn.act`, not `act_inference`) unless --deterministic.
 
   python scripts/play.py [checkpoint.pt | --log-root logs/nightmare_v3] [-e 64] [--steps 1300] [--decimation 2] [--cmd 0.3 0.0 0.2]
+                         [--activation elu]
+
+A checkpoint does not record the hidden activation of its networks (rsl_rl saves the state_dict only): --activation names it, by default
+the training config's (NightmareV3ConfigPPO.policy.activation).
 """
 import argparse
 import os
@@ -17,17 +21,19 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from nightmare_rl_amd.envs.helpers import get_load_path  # noqa: E402
-from nightmare_rl_amd.envs.nightmare_v3_config import NightmareV3Config  # noqa: E402
+from nightmare_rl_amd.envs.nightmare_v3_config import NightmareV3Config, NightmareV3ConfigPPO  # noqa: E402
 from nightmare_rl_amd.envs.nightmare_v3_env import NightmareV3Env  # noqa: E402
 from nightmare_rl_amd.policy import ActorMLP  # noqa: E402
 
 
-def actor_from_checkpoint(path, device):
-    """ActorMLP with the weights of `actor.<2i>.weight/bias` (rsl_rl ActorCritic layout) + the learned action std."""
+def actor_from_checkpoint(path, device, activation=None):
+    """ActorMLP with the weights of `actor.<2i>.weight/bias` (rsl_rl ActorCritic layout) + the learned action std. activation: the
+    networks' hidden activation (None: the training config's, NightmareV3ConfigPPO.policy.activation)."""
+    activation = activation or NightmareV3ConfigPPO.policy.activation
     sd = torch.load(path, map_location="cpu")["model_state_dict"]
     idx = sorted({int(k.split(".")[1]) for k in sd if k.startswith("actor.") and k.endswith(".weight")})
     dims = [sd[f"actor.{idx[0]}.weight"].shape[1]] + [sd[f"actor.{i}.weight"].shape[0] for i in idx]
-    net = ActorMLP(dims)
+    net = ActorMLP(dims, activation=activation)
     for layer, i in zip(net.layers, idx):
         layer.weight.data.copy_(sd[f"actor.{i}.weight"])
         layer.bias.data.copy_(sd[f"actor.{i}.bias"])
@@ -46,10 +52,12 @@ def main():
     ap.add_argument("--deterministic", action="store_true", help="act_inference (mean action) instead of upstream's sampled nn.act")
     ap.add_argument("--cmd", type=float, nargs=3, default=None, metavar=("VX", "VY", "YAW"), help="fixed velocity command (default: the env's own resampling)")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--activation", default=NightmareV3ConfigPPO.policy.activation,
+                    help="hidden activation the checkpoint was trained with (not stored in it; default: the training config's)")
     a = ap.parse_args()
     path = a.checkpoint or get_load_path(a.log_root)
     dev = torch.device("cuda", 0)
-    net, std = actor_from_checkpoint(path, dev)
+    net, std = actor_from_checkpoint(path, dev, a.activation)
     cfg = NightmareV3Config()
     cfg.env.num_envs = a.envs
     if a.decimation is not None:
