@@ -130,6 +130,14 @@ int nm_set_noise_uniforms(nm_env* env, const double* u_host);
  * the number of MuJoCo bad-state resets inside that step (data.time restarts there). Synchronous. */
 int nm_set_state_record(nm_env* env, int32_t env_index);
 int nm_get_state_record(nm_env* env, double* qpos, double* qvel, int32_t* bad_state_resets);
+/* The same log inside a K-step launch (nm_rollout*, nm_play): with recording on, the launch keeps one row [qpos 25 | qvel 24 | bad-state
+ * resets 1] per step for the chosen env (envs/nightmare_v3_env.py:261-272 appends one record per step; reader open_custom_play.py:50-66),
+ * and nm_get_state_record returns the launch's last step. nm_get_state_log copies rows first_step .. first_step + count - 1 of the LAST
+ * K-step launch to HOST rows_host[count, 50] (doubles). Synchronous. */
+int nm_get_state_log(nm_env* env, int32_t first_step, int32_t count, double* rows_host);
+/* The logged env's reset flag (reset_buf[0] at envs/nightmare_v3_env.py:263: the step at which the reader starts a new file) for the same
+ * steps of the last nm_play launch, HOST dones_host[count] uint8. After nm_rollout* the flags are column env_index of its dones rows. Synchronous. */
+int nm_get_state_log_dones(nm_env* env, int32_t first_step, int32_t count, unsigned char* dones_host);
 
 /* Measurement hook (no reference counterpart): when enabled, every nm_step / nm_step_physics brackets its step
  * kernel with HIP events on the launch stream. Each call synchronises, returns the summed kernel time and the
@@ -310,6 +318,36 @@ int nm_rollout_act(nm_env* env, const float* params_flat_dev, const float* obs_d
 int nm_rollout_act_ex(nm_env* env, const float* params_flat_dev, const float* obs_dev, uint64_t seed, const int64_t* iter_dev, int32_t step,
                       float* actions_dev, float* logp_dev, float* values_dev, float* mu_dev, float* sigma_dev, float* obs_store_dev, int32_t activation,
                       void* stream);
+
+/* ---- Playing a policy (the loop of reference play.py:118-132: `actions = nn.act(obs)`, scale / clip, servo command, mj_step x decimation)
+ * as ONE launch of `steps` steps with nothing collected for PPO: every wavefront keeps its two envs, evaluates the actor on the observation
+ * its previous step left and steps the env. fp32 env, networks nm_play_supported accepts. Per step the results are those of nm_rollout_act_ex
+ * (its `mu` row when deterministic, its `actions` row otherwise; noise key step = step0 + t) followed by nm_step, bit for bit; extras
+ * (time_outs, ep_stats), counters and episode lengths afterwards are what the last of `steps` nm_step calls would have left. `steps` may
+ * exceed the episode length (an env may time out several times per launch). All pointers are device memory. */
+typedef struct {
+  int32_t steps;                       /* K in 1..4096; longer runs are consecutive launches (step0 continues the noise keys) */
+  int32_t deterministic;               /* != 0: action = actor mean (rsl_rl act_inference); 0: mean + std * N(0,1) (nn.act, reference play.py:122) */
+  const float* params_flat_dev;        /* actor W0 b0 W1 b1 ..., critic W0 b0 ..., std[18]: the flat vector nm_rollout reads (the critic's shape is the reference's) */
+  uint64_t seed;                       /* action noise: (seed, *iter_dev * 4096 + step0 + t, env, action pair), the keys of nm_rollout_act_ex */
+  const int64_t* iter_dev;
+  uint64_t step0;
+  const float* obs0_dev;               /* [N,66] the observation the first act sees */
+  float* obs_dev;                      /* [N,66] every step files its observation here; holds the last one afterwards (may alias obs0_dev) */
+  float* actions_dev;                  /* [N,18] the actions of the step under way; holds the last step's afterwards */
+  int64_t* episode_length_dev;         /* [N] episode_length_buf, in/out */
+  float* rew_dev; int64_t* done_dev;   /* [N] reward / reset buffers: the last step's values afterwards */
+  float* time_outs_dev;                /* [N] extras['time_outs'] in/out or NULL */
+  float* ep_stats_dev;                 /* [NM_NUM_REWARDS] extras['episode'] in/out or NULL */
+  float *cur_ret, *cur_len, *fin3;     /* [N] [N] [3] or NULL: running return / length per env, finished episodes (sum of returns, of lengths, count) as nm_ppo_record */
+  float *ret_sum, *ret_cnt;            /* [N] [N] or NULL: per env the sum and the number of the returns of the episodes it finished (no atomics) */
+  const int32_t* ep_idx_dev; int32_t n_ep; float* ep_acc_dev;   /* ep_acc[i] += extras['episode'][ep_idx[i]] after every step, as nm_rollout */
+} nm_play_args;
+/* 1 if nm_play is compiled for this actor (dims = {n_obs, h1, h2, h3, n_actions}, HOST array; reference play.py:118-132 plays the network of
+ * envs/nightmare_v3_config.py:105-109) with hidden activation `activation`; the shapes nm_rollout_supported_act accepts. Host only. */
+int nm_play_supported(const int32_t* actor_dims, int32_t n_layers, int32_t activation);
+/* reference play.py:118-132, `steps` iterations per launch; stream-ordered, no host synchronisation */
+int nm_play(nm_env* env, const nm_play_args* args, int32_t activation, void* stream);
 
 /* ---- scripted gait / IK engine (reference nikengine/engine.py; caller custom_play.py:49-76), batched over envs ----
  * One handle = num_envs independent EngineNode objects (engine.py:660-677), all in IdleState. */

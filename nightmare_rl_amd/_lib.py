@@ -25,6 +25,7 @@ EXPORTS = ["nm_default_config", "nm_reward_name", "nm_last_error", "nm_create", 
            "nm_set_command_uniforms", "nm_get_feet_state", "nm_set_feet_state", "nm_get_counters", "nm_set_debug_buffer", "nm_set_return_accumulator", "nm_invalidate_time_outs", "nm_rollout", "nm_rollout_act", "nm_rollout_supported", "nm_policy_create", "nm_policy_destroy", "nm_policy_load", "nm_policy_forward", "nm_profile", "nm_gae", "nm_gae_advantages", "nm_ppo_sample", "nm_ppo_record", "nm_ppo_create", "nm_ppo_destroy", "nm_ppo_num_params", "nm_ppo_sync_params", "nm_ppo_minibatch", "nm_ppo_minibatch_rows", "nm_ppo_set_storage_rows", "nm_ppo_step_is_fused", "nm_ppo_debug_break_barrier", "nm_ppo_permutation", "nm_ppo_copy_grad", "nm_ppo_set_grad_buffer", "nm_ppo_get_state", "nm_ppo_snapshot_state", "nm_ppo_has_fast_path", "nm_ppo_act", "nm_ppo_record_act",
            "nm_policy_create_act", "nm_ppo_create_act", "nm_rollout_supported_act", "nm_rollout_ex", "nm_rollout_act_ex",
            "nm_set_observation_noise", "nm_set_noise_uniforms", "nm_set_state_record", "nm_get_state_record",
+           "nm_get_state_log", "nm_get_state_log_dones", "nm_play", "nm_play_supported",
            "nm_nik_create", "nm_nik_destroy", "nm_nik_reset", "nm_nik_set_gait", "nm_nik_update", "nm_nik_get_state"]
 
 
@@ -46,6 +47,14 @@ class NmRolloutArgs(C.Structure):     # nm_rollout_args of include/nightmare_hip
                 ("s_sigma", C.c_void_p), ("s_rewards", C.c_void_p), ("s_dones", C.c_void_p), ("gamma", C.c_float),
                 ("cur_ret", C.c_void_p), ("cur_len", C.c_void_p), ("fin3", C.c_void_p),
                 ("ep_idx_dev", C.c_void_p), ("n_ep", C.c_int32), ("ep_acc_dev", C.c_void_p), ("last_values_dev", C.c_void_p)]
+
+
+class NmPlayArgs(C.Structure):        # nm_play_args of include/nightmare_hip.h
+    _fields_ = [("steps", C.c_int32), ("deterministic", C.c_int32), ("params_flat_dev", C.c_void_p), ("seed", C.c_uint64), ("iter_dev", C.c_void_p),
+                ("step0", C.c_uint64), ("obs0_dev", C.c_void_p), ("obs_dev", C.c_void_p), ("actions_dev", C.c_void_p), ("episode_length_dev", C.c_void_p),
+                ("rew_dev", C.c_void_p), ("done_dev", C.c_void_p), ("time_outs_dev", C.c_void_p), ("ep_stats_dev", C.c_void_p),
+                ("cur_ret", C.c_void_p), ("cur_len", C.c_void_p), ("fin3", C.c_void_p), ("ret_sum", C.c_void_p), ("ret_cnt", C.c_void_p),
+                ("ep_idx_dev", C.c_void_p), ("n_ep", C.c_int32), ("ep_acc_dev", C.c_void_p)]
 
 
 class NightmareHipError(RuntimeError):
@@ -130,6 +139,11 @@ def _bind(L, full):
     L.nm_set_noise_uniforms.argtypes = [vp, vp]
     L.nm_set_state_record.argtypes = [vp, C.c_int32]
     L.nm_get_state_record.argtypes = [vp, vp, vp, vp]
+    if hasattr(L, "nm_play"):
+        L.nm_get_state_log.argtypes = [vp, C.c_int32, C.c_int32, vp]
+        L.nm_get_state_log_dones.argtypes = [vp, C.c_int32, C.c_int32, vp]
+        L.nm_play.argtypes = [vp, C.POINTER(NmPlayArgs), C.c_int32, vp]
+        L.nm_play_supported.argtypes = [vp, C.c_int32, C.c_int32]
     if not full:        # the measurement build holds the env entry points only
         return L
     L.nm_gae.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_float, vp, vp]

@@ -253,6 +253,9 @@ struct nm_env {
   virtual int set_noise_u(const double* u) = 0;
   virtual int set_record(int idx) = 0;
   virtual int get_record(double* qpos, double* qvel, int32_t* nbad) = 0;
+  virtual int play(const nm_play_args* r, int act, hipStream_t s) = 0;
+  virtual int get_log(int first, int count, double* rows) = 0;
+  virtual int get_log_dones(int first, int count, unsigned char* dones) = 0;
 };
 
 template <class real> struct Env : nm_env {
@@ -272,6 +275,12 @@ template <class real> struct Env : nm_env {
   uint64_t noise_step = 0;
   real* rec_dev = nullptr;
   int rec_env = -1;
+  // the state log of a K-step launch (nm_rollout / nm_play): one row [qpos 25 | qvel 24 | bad-state resets] per step
+  real* rec_log = nullptr;
+  int rec_log_cap = 0, rec_log_rows = 0;
+  unsigned char* rec_done = nullptr;   // [rec_log_cap]: the logged env's reset flag per step of the last nm_play
+  bool rec_done_valid = false;
+  const real* rec_last = nullptr;      // where the last step's record is: rec_dev after nm_step, the last row of rec_log after a K-step launch
   bool prof_on = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;
   size_t prof_used = 0;
@@ -387,6 +396,7 @@ template <class real> struct Env : nm_env {
       a.noise_step = noise_step++;
       a.rec = rec_env >= 0 ? rec_dev : nullptr;
       a.rec_env = rec_env;
+      if (rec_env >= 0) rec_last = rec_dev;
     }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (prof_on) {  // HIP events on the launch stream around the dominant kernel only (bench.py's roofline leg)
@@ -509,20 +519,65 @@ template <class real> struct Env : nm_env {
     if (idx >= N) return fail("nm_set_state_record: env index out of range");
     if (idx >= 0 && !rec_dev && dalloc(&rec_dev, 64)) return 1;
     rec_env = idx < 0 ? -1 : idx;
+    rec_last = nullptr; rec_log_rows = 0; rec_done_valid = false;
     return 0;
   }
   int get_record(double* qpos, double* qvel, int32_t* nbad) override {
     HIPCHK(hipSetDevice(device));
     if (rec_env < 0) return fail("nm_get_state_record: recording is off (nm_set_state_record)");
+    if (!rec_last) return fail("nm_get_state_record: no step has been recorded yet");
     HIPCHK(hipDeviceSynchronize());
     double tmp[50];
-    if (d2h(rec_dev, tmp, 50)) return 1;
+    if (d2h(rec_last, tmp, 50)) return 1;
     if (qpos) for (int i = 0; i < 25; i++) qpos[i] = tmp[i];
     if (qvel) for (int i = 0; i < 24; i++) qvel[i] = tmp[25 + i];
     if (nbad) *nbad = (int32_t)tmp[49];
     return 0;
   }
 
+  int get_log(int first, int count, double* rows) override {
+    HIPCHK(hipSetDevice(device));
+    if (rec_env < 0) return fail("nm_get_state_log: recording is off (nm_set_state_record)");
+    if (first < 0 || count < 0 || first + count > rec_log_rows) return fail("nm_get_state_log: rows outside the last K-step launch");
+    if (count == 0) return 0;
+    if (!rows) return fail("nm_get_state_log: rows_host is NULL");
+    HIPCHK(hipDeviceSynchronize());
+    return d2h(rec_log + (size_t)first * nmr::kRecRow, rows, (size_t)count * nmr::kRecRow);
+  }
+  int get_log_dones(int first, int count, unsigned char* dones) override {
+    HIPCHK(hipSetDevice(device));
+    if (rec_env < 0) return fail("nm_get_state_log_dones: recording is off (nm_set_state_record)");
+    if (!rec_done_valid) return fail("nm_get_state_log_dones: the last K-step launch was not nm_play (nm_rollout files the flags in its dones rows)");
+    if (first < 0 || count < 0 || first + count > rec_log_rows) return fail("nm_get_state_log_dones: steps outside the last K-step launch");
+    if (count == 0) return 0;
+    if (!dones) return fail("nm_get_state_log_dones: dones_host is NULL");
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(dones, rec_done + first, (size_t)count, hipMemcpyDeviceToHost));
+    return 0;
+  }
+  // the log rows of a launch of K steps (null: recording is off); sized with the per-step accumulators (roll_cap)
+  int log_rows(int K, real** out) {
+    *out = nullptr;
+    if (rec_env < 0) return 0;
+    if (K > rec_log_cap) {
+      if (dalloc(&rec_log, (size_t)roll_cap * nmr::kRecRow) || dalloc(&rec_done, (size_t)roll_cap)) return 1;
+      rec_log_cap = roll_cap;
+    }
+    rec_log_rows = K;
+    rec_done_valid = false;
+    rec_last = rec_log + (size_t)(K - 1) * nmr::kRecRow;
+    *out = rec_log;
+    return 0;
+  }
+  int roll_reserve(int K) {   // per-step accumulators (zero: the slab and hipMalloc'ed blocks are cleared, k_rollout_clear keeps them so)
+    if (K > roll_cap) {
+      const int cap = (K + 127) & ~127;
+      if (dalloc(&roll_sum, (size_t)cap * nm::kNREW) || dalloc(&roll_cnt, (size_t)cap * 4)) return 1;
+      if (!roll_to && dalloc(&roll_to, (size_t)N)) return 1;
+      roll_cap = cap;
+    }
+    return 0;
+  }
   // ---- K-step rollout with the policy in the wave (nm_rollout; fp32 two-env waves and the reference's network shape only)
   float *roll_wp = nullptr, *roll_bp = nullptr;
   real* roll_sum = nullptr;
@@ -556,13 +611,8 @@ template <class real> struct Env : nm_env {
           !r->s_actions || !r->s_logp || !r->s_values || !r->s_mu || !r->s_sigma || !r->s_rewards || !r->s_dones || !r->cur_ret || !r->cur_len || !r->fin3)
         return fail("nm_rollout: NULL pointer");
       if (r->n_ep < 0 || r->n_ep > nm::kNREW || (r->n_ep > 0 && (!r->ep_idx_dev || !r->ep_acc_dev || !r->ep_stats_dev))) return fail("nm_rollout: bad episode-statistics arguments");
-      if (rec_env >= 0) return fail("nm_rollout: the state log (nm_set_state_record) needs one launch per step");
-      if (K > roll_cap) {   // per-step accumulators (zero: the slab and hipMalloc'ed blocks are cleared, k_rollout_clear keeps them so)
-        const int cap = (K + 127) & ~127;
-        if (dalloc(&roll_sum, (size_t)cap * nm::kNREW) || dalloc(&roll_cnt, (size_t)cap * 4)) return 1;
-        if (!roll_to && dalloc(&roll_to, (size_t)N)) return 1;
-        roll_cap = cap;
-      }
+      real* log = nullptr;
+      if (roll_reserve(K) || log_rows(K, &log)) return 1;
       if (roll_pack(r->params_flat_dev, s)) return 1;
       nm::Args<real> a = A;
       a.actions = nullptr; a.eplen = r->episode_length_dev; a.obs = r->obs_final_dev; a.rew = r->rew_dev; a.done = r->done_dev; a.timeout_now = timeout_now;
@@ -574,7 +624,7 @@ template <class real> struct Env : nm_env {
       a.noise_u = noise_on && noise_u_on ? noise_u_dev : nullptr;
       a.noise_step = noise_step;
       noise_step += (uint64_t)K;
-      a.rec = nullptr; a.rec_env = -1; a.dbg = nullptr; a.ret_acc = nullptr;
+      a.rec = log; a.rec_env = log ? rec_env : -1; a.dbg = nullptr; a.ret_acc = nullptr;    // (rec: row t, set by the kernel before every step)
       nmr::RollArgs R;
       R.K = K; R.wp = (const nmr::f32x4*)roll_wp; R.bp = roll_bp; R.stdv = r->params_flat_dev + RS::stdoff();
       R.seed = r->seed; R.iter_dev = r->iter_dev; R.obs0 = r->obs0_dev; R.obs_final = r->obs_final_dev;
@@ -582,10 +632,59 @@ template <class real> struct Env : nm_env {
       R.s_rewards = r->s_rewards; R.s_dones = r->s_dones; R.cur_ret = r->cur_ret; R.cur_len = r->cur_len; R.fin3 = r->fin3;
       R.st_sum = roll_sum; R.st_cnt = roll_cnt; R.to_step = roll_to;
       R.last_values = r->last_values_dev;
+      R.rec_log = log;
       R.wave_clock = A.dbg ? reinterpret_cast<unsigned long long*>(A.dbg) : nullptr;   // measurement: the debug buffer ([N,256] reals) takes the waves' clocks instead
       nmr::TailArgs ta{N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, r->bootstrap_time_outs ? r->gamma : -1.0f, r->s_values, r->s_rewards,
                        r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
       if (nmr::launch_rollout(M_dev, a, R, ta, act, s)) return fail("nm_rollout: launch failed");
+      return 0;
+    }
+  }
+  // ---- K x [policy, step] per launch with nothing collected (nm_play; reference play.py:118-132)
+  float* play_scratch = nullptr;       // [4 N + 4]: stand-ins for the bookkeeping tensors the caller does not want
+  int play(const nm_play_args* r, int act, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if constexpr (sizeof(real) == 8 || NM_ENVS_PER_WAVE != 2) {
+      return fail("nm_play: the play kernel runs on the fp32 kernel (two envs per wave) only");
+    } else {
+      if (!r) return fail("nm_play: args is NULL");
+      const int K = r->steps;
+      if (K < 1 || K > 4096) return fail("nm_play: steps must be in 1..4096 (longer runs: consecutive launches)");
+      if (!r->params_flat_dev || !r->iter_dev || !r->obs0_dev || !r->obs_dev || !r->actions_dev || !r->episode_length_dev || !r->rew_dev || !r->done_dev)
+        return fail("nm_play: NULL pointer");
+      if (r->n_ep < 0 || r->n_ep > nm::kNREW || (r->n_ep > 0 && (!r->ep_idx_dev || !r->ep_acc_dev || !r->ep_stats_dev))) return fail("nm_play: bad episode-statistics arguments");
+      if ((r->cur_ret == nullptr) != (r->cur_len == nullptr) || (r->ret_sum == nullptr) != (r->ret_cnt == nullptr))
+        return fail("nm_play: cur_ret / cur_len and ret_sum / ret_cnt come in pairs");
+      real* log = nullptr;
+      if (roll_reserve(K) || log_rows(K, &log)) return 1;
+      if (!play_scratch && dalloc(&play_scratch, (size_t)N * 4 + 4)) return 1;
+      if (roll_pack(r->params_flat_dev, s)) return 1;
+      nm::Args<real> a = A;
+      a.actions = r->actions_dev; a.eplen = r->episode_length_dev; a.obs = r->obs_dev; a.rew = r->rew_dev; a.done = r->done_dev; a.timeout_now = timeout_now;
+      a.cmd_u = cmd_u_on ? cmd_u_dev : nullptr;
+      a.physics_only = 0;
+      a.ep_stats = nullptr; a.time_outs = nullptr; a.counters = counters_dev;     // extras are closed by k_rollout_tail
+      a.to_list = nullptr;
+      a.noise_vec = noise_on ? noise_vec_dev : nullptr;
+      a.noise_u = noise_on && noise_u_on ? noise_u_dev : nullptr;
+      a.noise_step = noise_step;
+      noise_step += (uint64_t)K;
+      a.rec = log; a.rec_env = log ? rec_env : -1; a.dbg = nullptr; a.ret_acc = nullptr;
+      nmr::PlayArgs P;
+      P.K = K; P.deterministic = r->deterministic != 0;
+      P.wp = (const nmr::f32x4*)roll_wp; P.bp = roll_bp; P.stdv = r->params_flat_dev + RS::stdoff();
+      P.seed = r->seed; P.iter_dev = r->iter_dev; P.step0 = r->step0;
+      P.obs0 = r->obs0_dev; P.obs = r->obs_dev; P.actions = r->actions_dev;
+      const size_t n_ = (size_t)N;
+      P.cur_ret = r->cur_ret ? r->cur_ret : play_scratch; P.cur_len = r->cur_len ? r->cur_len : play_scratch + n_;
+      P.ret_sum = r->ret_sum ? r->ret_sum : play_scratch + 2 * n_; P.ret_cnt = r->ret_cnt ? r->ret_cnt : play_scratch + 3 * n_;
+      P.fin3 = r->fin3 ? r->fin3 : play_scratch + 4 * n_;
+      P.st_sum = roll_sum; P.st_cnt = roll_cnt; P.to_step = roll_to;
+      P.rec_log = log; P.rec_done = log ? rec_done : nullptr; P.rec_env = rec_env;
+      rec_done_valid = log != nullptr;
+      nmr::TailArgs ta{N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, -1.0f, nullptr, nullptr,
+                       r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
+      if (nmr::launch_play(M_dev, a, P, ta, act, s)) return fail("nm_play: launch failed");
       return 0;
     }
   }
@@ -739,6 +838,20 @@ int nm_set_observation_noise(nm_env* env, const double* vec) { NEED(env); return
 int nm_set_noise_uniforms(nm_env* env, const double* u) { NEED(env); return env->set_noise_u(u); }
 int nm_set_state_record(nm_env* env, int32_t idx) { NEED(env); return env->set_record(idx); }
 int nm_get_state_record(nm_env* env, double* qpos, double* qvel, int32_t* nbad) { NEED(env); return env->get_record(qpos, qvel, nbad); }
+int nm_get_state_log(nm_env* env, int32_t first_step, int32_t count, double* rows_host) { NEED(env); return env->get_log(first_step, count, rows_host); }
+int nm_get_state_log_dones(nm_env* env, int32_t first_step, int32_t count, unsigned char* dones_host) { NEED(env); return env->get_log_dones(first_step, count, dones_host); }
+int nm_play_supported(const int32_t* actor_dims, int32_t n_layers, int32_t activation) {
+  typedef nmr::RefShape RS;
+  if (!nmact::valid(activation) || !actor_dims || n_layers != RS::NL || actor_dims[0] != RS::I) return 0;
+  for (int l = 0; l < RS::NL; l++)
+    if (actor_dims[l + 1] != RS::aout(l)) return 0;
+  return 1;
+}
+int nm_play(nm_env* env, const nm_play_args* args, int32_t activation, void* stream) {
+  NEED(env);
+  if (!nmact::valid(activation)) return bad_activation("nm_play", activation);
+  return env->play(args, activation, (hipStream_t)stream);
+}
 #ifdef NM_STAMPS
 int nm_read_stamps(unsigned long long* out16, int reset) {   // measurement builds only
   (void)hipDeviceSynchronize();

@@ -124,10 +124,14 @@ struct ActOut {
 
 // PPO.act for the wave's two envs (env = 2 wave + column). xb: kXFloats floats of the wave's LDS. obs: [N, I] device memory that this wave
 // may have written itself a moment ago (the caller has waited for those stores). `env_id0` = global id of env 0 (noise key).
-// VALUE_ONLY: the same forward, but nothing is sampled or filed except the critic's value into o.values[env] (the last observation of a rollout).
-template <class S, int ACT, bool VALUE_ONLY = false>
+// MODE kPolicyValueOnly: the same forward, but nothing is sampled or filed except the critic's value into o.values[env] (the last observation of a rollout).
+// MODE kPolicyPlay (k_env_play, reference play.py:118-132): the same forward and the same draw, but only o.actions is filed - the mean itself when
+// `deterministic` (act_inference), mean + std * z otherwise (nn.act); no log-probability, value, mu or sigma.
+constexpr int kPolicyFull = 0, kPolicyValueOnly = 1, kPolicyPlay = 2;
+template <class S, int ACT, int MODE = kPolicyFull>
 __device__ __forceinline__ void policy_wave(float* xb, const f32x4* __restrict__ wp, const float* __restrict__ bp, const float* __restrict__ stdv,
-                                            const float* obs, int N, int wave, uint64_t seed, uint64_t ctr, const ActOut& o) {
+                                            const float* obs, int N, int wave, uint64_t seed, uint64_t ctr, const ActOut& o, bool deterministic = false) {
+  constexpr bool VALUE_ONLY = MODE == kPolicyValueOnly;
   constexpr int NL = S::NL, NF = S::nfrag(), I = S::I, AO = S::AO;
   // Inside the rollout kernel the pointers come out of an LDS copy of the launch arguments: the compiler no longer knows that they are
   // global memory and would emit flat_load / flat_store - which count on vmcnt AND lgkmcnt, out of order against LDS traffic, so every
@@ -208,6 +212,36 @@ __device__ __forceinline__ void policy_wave(float* xb, const f32x4* __restrict__
     if (blk == nab && live) ((gwp)o.values)[env] = out[0];
     return;
   }
+  if constexpr (MODE == kPolicyPlay) {
+    if (blk < nab) {
+#pragma unroll
+      for (int pr = 0; pr < 2; pr++) {
+        const int f0 = 4 * blk + 2 * pr;
+        if (f0 < AO) {
+          float z[2] = {0.0f, 0.0f};
+          if (!deterministic) {                        // the draw of the sampling head below: same keys, same arithmetic
+            const float u1 = u24(seed, (uint64_t)env * 64 + f0, ctr), u2 = u24(seed, (uint64_t)env * 64 + f0 + 1, ctr);
+            const float rad = sqrtf(-2.0f * __logf(u1));
+            float sn, cs;
+            __sincosf(6.283185307179586f * u2, &sn, &cs);
+            z[0] = rad * cs; z[1] = rad * sn;
+          }
+          f32x2u a2;
+#pragma unroll
+          for (int hh = 0; hh < 2; hh++) {
+            const float m = out[2 * pr + hh], sd = sg[f0 + hh];
+            const float a = m + sd * z[hh];
+            a2[hh] = deterministic ? m : a;
+          }
+          if (live) {
+            typedef __attribute__((address_space(1))) f32x2u* g2p;
+            *(g2p)((gwp)o.actions + (size_t)env * AO + f0) = a2;
+          }
+        }
+      }
+    }
+    return;
+  }
   if (blk < nab) {
 #pragma unroll
     for (int pr = 0; pr < 2; pr++) {
@@ -254,6 +288,22 @@ struct RollArgs {
   int* to_step;                                                // [N]: the step at which the env timed out in this rollout, or -1
   float* last_values;                                          // [N] or null: the critic's value of the observation after the last step (PPO.compute_returns)
   unsigned long long* wave_clock;                              // measurement (nm_set_debug_buffer on): [waves][2] s_memtime at the wave's start / end, else null
+  float* rec_log;                                              // [K,kRecRow] or null: the state log (Args::rec of step t = row t; env.py:261-272)
+};
+constexpr int kRecRow = 50;            // qpos 25 | qvel 24 | bad-state resets of the step (what wave_step files through Args::rec)
+// k_env_play (nm_play_kernels.h): K x [policy on the observation the previous step left, env.step], nothing collected - reference play.py:118-132
+struct PlayArgs {
+  int K, deterministic;
+  const f32x4* wp; const float* bp; const float* stdv;       // packed policy (k_roll_pack), std[AO]
+  uint64_t seed; const int64_t* iter_dev; uint64_t step0;      // action-noise key of step t: (seed, *iter_dev * 4096 + step0 + t, env, action pair) = nm_rollout_act's
+  const float* obs0; float* obs;                               // [N,66]: what the first act sees / where every step files its observation (this wave's rows: read back by its next act)
+  float* actions;                                              // [N,18]: the step's actions
+  float *cur_ret, *cur_len, *fin3;                             // episode bookkeeping as nm_ppo_record keeps it
+  float *ret_sum, *ret_cnt;                                    // [N], [N]: sum and number of the returns of the episodes this env finished
+  float* st_sum; int* st_cnt;                                  // [K,kNREW], [K,4]: per-step accumulators, closed by k_rollout_tail
+  int* to_step;                                                // [N]: the LATEST step at which the env timed out in this launch, or -1
+  float* rec_log;                                              // [K,kRecRow] or null
+  unsigned char* rec_done; int rec_env;                        // [K] or null: the logged env's reset flag per step (the log's reader dumps a file there)
 };
 struct TailArgs {
   int N, K;
@@ -277,6 +327,16 @@ template <int ACT> struct RollKernels {
                  const ActOut& o, hipStream_t s);
   static int rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, hipStream_t s);
 };
+// the launch of k_env_play for one hidden activation: defined in nm_play_kernels.h, instantiated once per code by nm_play_<activation>.hip
+template <int ACT> struct PlayKernels {
+  static int play(const nm::Model<float>* M_dev, const nm::Args<float>& a, const PlayArgs& P, hipStream_t s);
+};
+extern template struct PlayKernels<NM_ACT_ELU>;
+extern template struct PlayKernels<NM_ACT_SELU>;
+extern template struct PlayKernels<NM_ACT_RELU>;
+extern template struct PlayKernels<NM_ACT_LRELU>;
+extern template struct PlayKernels<NM_ACT_TANH>;
+extern template struct PlayKernels<NM_ACT_SIGMOID>;
 extern template struct RollKernels<NM_ACT_ELU>;
 extern template struct RollKernels<NM_ACT_SELU>;
 extern template struct RollKernels<NM_ACT_RELU>;
@@ -287,5 +347,7 @@ extern template struct RollKernels<NM_ACT_SIGMOID>;
 int launch_act(const float* wp, const float* bp, const float* stdv, const float* obs, int N, uint64_t seed, const int64_t* iter_dev, int step, const ActOut& o,
                int act, hipStream_t s);
 int launch_rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, const TailArgs& t, int act, hipStream_t s);
+// k_env_play + the rollout's closing launches (k_rollout_tail without the time-out bootstrap, k_rollout_clear)
+int launch_play(const nm::Model<float>* M_dev, const nm::Args<float>& a, const PlayArgs& P, const TailArgs& t, int act, hipStream_t s);
 
 }  // namespace nmr

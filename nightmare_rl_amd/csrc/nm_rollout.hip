@@ -109,5 +109,15 @@ int launch_rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, cons
   hipLaunchKernelGGL(k_rollout_clear, dim3((t.K * nm::kNREW + 255) / 256), dim3(256), 0, s, t.K, t.st_sum, t.st_cnt);
   return hipGetLastError() != hipSuccess;
 }
+// nm_play: the same closing launches. Without the bootstrap (t.gamma < 0) k_rollout_tail needs each env's LATEST time-out step only: the
+// time-out buffer is refreshed by the last step in which some env reset, and an env's flag there is "it timed out in that very step".
+int launch_play(const nm::Model<float>* M_dev, const nm::Args<float>& a, const PlayArgs& P, const TailArgs& t, int act, hipStream_t s) {
+  const int N = a.N;
+  if (with_act(act, [&](auto ACT) { return PlayKernels<decltype(ACT)::value>::play(M_dev, a, P, s); })) return 1;
+  hipLaunchKernelGGL(k_rollout_tail, dim3(min((N + 255) / 256, 64)), dim3(256), 0, s, t);
+  if (hipGetLastError() != hipSuccess) return 1;
+  hipLaunchKernelGGL(k_rollout_clear, dim3((t.K * nm::kNREW + 255) / 256), dim3(256), 0, s, t.K, t.st_sum, t.st_cnt);
+  return hipGetLastError() != hipSuccess;
+}
 
 }  // namespace nmr

@@ -62,6 +62,7 @@ __device__ __noinline__ void policy_step(float* xb, const RollArgs* Rs, nm::Args
     As->stat_sum = Rs->st_sum + (size_t)t * nm::kNREW;
     As->stat_cnt = Rs->st_cnt + (size_t)t * 4;
     As->noise_step = noise0 + (uint64_t)t;
+    As->rec = Rs->rec_log ? Rs->rec_log + (size_t)t * kRecRow : nullptr;           // the state log's row of this step (env.py:261-272)
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the actions are in L2 before the load stage asks for them (other lanes of this wave)
   nm::wave_sync();
@@ -79,7 +80,7 @@ template <class S, int ACT>
 __device__ __noinline__ void value_last(float* xb, const RollArgs* Rs, const nm::Args<float>* As, int wave) {
   ActOut o{nullptr, nullptr, Rs->last_values, nullptr, nullptr, nullptr};
   nm::wave_sync();
-  policy_wave<S, ACT, true>(xb, Rs->wp, Rs->bp, Rs->stdv, Rs->obs_final, As->N, wave, 0, 0, o);
+  policy_wave<S, ACT, kPolicyValueOnly>(xb, Rs->wp, Rs->bp, Rs->stdv, Rs->obs_final, As->N, wave, 0, 0, o);
 }
 
 template <class S, int ACT>

@@ -9,21 +9,18 @@ Differences a caller can observe (all documented in DESIGN.md):
     rewards / dones / time_outs are valid until the next step()
   * commands come from a counter-based generator keyed by (seed, global env id) instead of numpy's global RNG (:327-330)
   * no viewer (`cfg.viewer.render` must be False); `cfg.viewer.record_states` writes the reference's pickle log (:261-272)
-    at the price of one device sync per step
+    at the price of one device sync per step() - or one per K-step launch (policy_rollout, policy_play), which keep the log on the device
   * observation noise (`cfg.noise.add_noise`, :304-305) draws from the same counter generator; `cfg.noise.layout`
     chooses between the reference's noise_scale_vec (written for a 12-dof robot, :113-119) and the 18-dof one
 """
 import ctypes as C
-import os
-import pickle
-import time
-
 import numpy as np
 import torch
 
 from .. import _lib
 from .helpers import class_to_dict
 from .nightmare_v3_config import NightmareV3Config
+from .state_log import ROW as _LOG_ROW, StateLog
 
 
 class NightmareV3Env:
@@ -124,10 +121,28 @@ class NightmareV3Env:
         if self.add_noise:
             self._ck(L.nm_set_observation_noise(h, self.noise_scale_vec.ctypes.data_as(C.c_void_p)))
         # state log of env 0 (reference :261-272; reader open_custom_play.py:50-66)
-        self.recorded_states = []
-        self._rec_time = 0.0
+        self.state_log = None
+        self._rec_env = 0
+        self._fixed_cmd = None
+        self._play_step = 0
         if cfg.viewer.record_states:
+            self.state_log = StateLog(log_dir, self.dt)
             self._ck(L.nm_set_state_record(h, 0))
+
+    @property
+    def recorded_states(self):
+        """Upstream's self.recorded_states (:261-272): what has been logged since the last dump."""
+        return self.state_log.records if self.state_log is not None else []
+
+    def set_state_record(self, env_index):
+        """Which env the state log follows (nm_set_state_record; upstream logs data[0], :267). Needs cfg.viewer.record_states."""
+        if self.state_log is None:
+            raise ValueError("set_state_record: cfg.viewer.record_states is off")
+        i = int(env_index)
+        if not 0 <= i < self.num_envs:
+            raise ValueError("set_state_record: env index out of range")
+        self._ck(self._L.nm_set_state_record(self._h, i))
+        self._rec_env = i
 
     def _noise_scale_vec(self, cfg):
         ns, lvl, osc = cfg.noise.noise_scales, cfg.noise.noise_level, self.obs_scales
@@ -154,16 +169,22 @@ class NightmareV3Env:
     def _record_state(self):
         # reference :261-272: when env 0 resets, dump what was logged so far, then log (time, qpos, qvel, act) of env 0
         # as it is after the physics and before reset_idx. This model has no actuator state: act is empty.
+        # The order, the clock and the files are StateLog's.
         qpos, qvel, nbad = np.empty(25), np.empty(24), C.c_int32(0)
         self._ck(self._L.nm_get_state_record(self._h, qpos.ctypes.data_as(C.c_void_p), qvel.ctypes.data_as(C.c_void_p), C.byref(nbad)))
-        if bool(self.reset_buf[0].item()):
-            os.makedirs(self.log_dir, exist_ok=True)
-            with open(f"{self.log_dir}/{int(time.time())}.pkl", "wb") as f:
-                pickle.dump(self.recorded_states, f)
-            self.recorded_states = []
-        sim_dt = 0.008 * self.cfg.control.decimation
-        self._rec_time = sim_dt if nbad.value else self._rec_time + sim_dt   # mj_resetData restarts data.time
-        self.recorded_states.append((self._rec_time, qpos, qvel, np.zeros(0)))
+        self.state_log.add(qpos, qvel, nbad.value, bool(self.reset_buf[self._rec_env].item()))
+
+    def _record_launch(self, K, dones=None):
+        """The K log rows of the K-step launch just enqueued -> StateLog. dones: the logged env's K reset flags as a device tensor
+        (policy_rollout: a column of the storage), None: kept by the launch itself (nm_play). One host synchronisation."""
+        if dones is not None:
+            d = dones.reshape(-1).to("cpu").numpy()          # waits for the launch
+        rows = np.empty((K, _LOG_ROW))
+        self._ck(self._L.nm_get_state_log(self._h, 0, K, rows.ctypes.data_as(C.c_void_p)))
+        if dones is None:
+            d = np.empty(K, np.uint8)
+            self._ck(self._L.nm_get_state_log_dones(self._h, 0, K, d.ctypes.data_as(C.c_void_p)))
+        self.state_log.add_rows(rows, d)
 
     def _ck(self, rc):
         _lib.check(rc, self._L)
@@ -208,7 +229,7 @@ class NightmareV3Env:
                                    self.reset_buf.data_ptr(), self.time_out_buf.data_ptr(), self._ep_stats.data_ptr(), self._stream()))
         self._last_actions = a  # keep the input alive until the kernel has read it
         self.common_step_counter += 1
-        if self.cfg.viewer.record_states:
+        if self.state_log is not None:
             self._record_state()
         if "episode" not in self.extras:
             self._fill_extras()
@@ -223,9 +244,8 @@ class NightmareV3Env:
         sum of extras['episode']) and leaves the env as `steps` calls of step() would: obs_buf / rew_buf / reset_buf / extras of the last step.
         params_flat: the flat parameter vector of FusedUpdate (actor W0 b0 ..., critic ..., std). last_values ([N] float32 on the device,
         optional) receives the critic's value of the last observation - what PPO.compute_returns evaluates next. activation: the networks'
-        hidden activation (a name of _lib.ACTIVATIONS, as ActorCritic takes it)."""
-        if self.cfg.viewer.record_states:
-            raise ValueError("policy_rollout: cfg.viewer.record_states needs one launch per step")
+        hidden activation (a name of _lib.ACTIVATIONS, as ActorCritic takes it). With cfg.viewer.record_states the launch keeps the state log's
+        K rows on the device and they are read - one host synchronisation - after it has been enqueued."""
         T = int(steps)
         if storage.num_transitions_per_env < T or storage.num_envs != self.num_envs or storage.privileged_observations is not None:
             raise ValueError("policy_rollout: storage must hold `steps` rows of this env's transitions (no privileged observations)")
@@ -257,7 +277,97 @@ class NightmareV3Env:
         storage.step = T
         if "episode" not in self.extras:
             self._fill_extras()
+        if self.state_log is not None:
+            self._record_launch(T, storage.dones[:T, self._rec_env])
         return self.obs_buf
+
+    def policy_play(self, steps, params_flat, *, deterministic=False, seed=0, iter_dev=None, activation="elu", stats=None, step0=None):
+        """`steps` iterations of the reference's play loop (play.py:118-132: `actions = nn.act(obs)`, scale / clip, servo command, mj_step x
+        decimation) in launches of up to 4096 steps each (nm_play), nothing collected for PPO. Starts from the current observation; returns
+        the last one and leaves obs_buf / rew_buf / reset_buf / extras / episode_length_buf / common_step_counter as `steps` calls of step()
+        would. `steps` may exceed the episode length.
+        params_flat: the flat `actor ..., critic ..., std` vector policy_rollout reads (flat_params_from_state_dict builds it from a
+        checkpoint). deterministic: the actor's mean (rsl_rl act_inference) instead of upstream's sampled nn.act. Noise keys: (seed,
+        iter_dev[0] * 4096 + step, env, action pair) as policy_act's, where step continues over consecutive calls (step0=None) or
+        starts at step0. stats (all optional, float32 device tensors owned by the caller): 'cur_ret', 'cur_len' [N] and 'fin' [3] as the
+        runner keeps them, 'ret_sum', 'ret_cnt' [N] = per env the sum and the number of the returns of the episodes it finished,
+        'ep' = (ep_idx int32, ep_acc) for the running sum of extras['episode']. With cfg.viewer.record_states every launch's log rows are read
+        after it has been enqueued (one host synchronisation per launch)."""
+        T = int(steps)
+        if T < 1:
+            raise ValueError("policy_play: steps must be at least 1")
+        st = dict(stats or {})
+        unknown = set(st) - {"cur_ret", "cur_len", "fin", "ret_sum", "ret_cnt", "ep"}
+        if unknown:
+            raise ValueError(f"policy_play: unknown stats {sorted(unknown)}")
+        N, dev = self.num_envs, self.device
+        for k in ("cur_ret", "cur_len", "ret_sum", "ret_cnt", "fin"):
+            t = st.get(k)
+            if t is not None and (t.dtype != torch.float32 or t.numel() != (3 if k == "fin" else N) or not t.is_contiguous() or t.device != dev):
+                raise ValueError(f"policy_play: stats[{k!r}] must be a contiguous float32 tensor of {3 if k == 'fin' else N} entries on the env's device")
+        if (st.get("cur_ret") is None) != (st.get("cur_len") is None) or (st.get("ret_sum") is None) != (st.get("ret_cnt") is None):
+            raise ValueError("policy_play: stats 'cur_ret' / 'cur_len' and 'ret_sum' / 'ret_cnt' come in pairs")
+        if self.time_out_buf is not self._to_bound:
+            self._ck(self._L.nm_invalidate_time_outs(self._h, self._stream()))
+            self._to_bound = self.time_out_buf
+        if iter_dev is None:
+            if getattr(self, "_play_iter", None) is None:
+                self._play_iter = torch.zeros(1, dtype=torch.int64, device=dev)
+            iter_dev = self._play_iter
+        if getattr(self, "_play_actions", None) is None:
+            self._play_actions = torch.zeros((N, self.num_actions), dtype=torch.float32, device=dev)
+        if step0 is not None:
+            self._play_step = int(step0)
+        ep_idx, ep_acc = st["ep"] if st.get("ep") is not None else (None, None)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        a = _lib.NmPlayArgs()
+        a.deterministic, a.params_flat_dev, a.seed, a.iter_dev = int(bool(deterministic)), params_flat.data_ptr(), int(seed), iter_dev.data_ptr()
+        a.obs0_dev = self.obs_buf.data_ptr()
+        self._obs_idx ^= 1
+        self.obs_buf = self._obs_pair[self._obs_idx]           # the tensor handed out before the launch stays what it was
+        a.obs_dev, a.actions_dev = self.obs_buf.data_ptr(), self._play_actions.data_ptr()
+        a.episode_length_dev = self._eplen().data_ptr()
+        a.rew_dev, a.done_dev = self.rew_buf.data_ptr(), self.reset_buf.data_ptr()
+        a.time_outs_dev, a.ep_stats_dev = self.time_out_buf.data_ptr(), self._ep_stats.data_ptr()
+        a.cur_ret, a.cur_len, a.fin3, a.ret_sum, a.ret_cnt = (ptr(st.get(k)) for k in ("cur_ret", "cur_len", "fin", "ret_sum", "ret_cnt"))
+        a.ep_idx_dev, a.n_ep, a.ep_acc_dev = (ep_idx.data_ptr(), int(ep_idx.numel()), ep_acc.data_ptr()) if ep_idx is not None else (None, 0, None)
+        self._keep_play = (params_flat, iter_dev, st)
+        code = _lib.activation_code(activation)
+        done = 0
+        while done < T:
+            k = min(T - done, 4096)
+            a.steps, a.step0 = k, self._play_step
+            self._ck(self._L.nm_play(self._h, C.byref(a), code, self._stream()))
+            a.obs0_dev = a.obs_dev                            # the next launch goes on from what this one left
+            self._play_step += k
+            self.common_step_counter += k
+            done += k
+            if self.state_log is not None:
+                self._record_launch(k)
+        if "episode" not in self.extras:
+            self._fill_extras()
+        return self.obs_buf
+
+    def set_fixed_commands(self, cmd):
+        """Hold the velocity command (vx, yaw) for ALL envs across the periodic resample (:235) and the resample at a reset (:356):
+        the uniforms that map onto it are injected at every resample (nm_set_command_uniforms) and `commands` is written once, now.
+        None: back to the env's own resampling (the commands then change at each env's next resample). A command outside
+        cfg.commands.ranges (max_lin_vel_x, max_ang_vel) is a ValueError. Upstream's zeroing of small commands still applies: a command
+        whose linear part has norm <= 0.02 is held as (0, yaw) (:333, `commands[:, :2] *= norm > 0.02`). The resample computes
+        u * 2 * max - max in the env's precision, so the held value is the requested one to one ulp."""
+        if cmd is None:
+            self._fixed_cmd = None
+            self.set_command_uniforms(None)
+            return
+        vx, yaw = (float(x) for x in cmd)
+        mx, ma = float(self.command_ranges.max_lin_vel_x), float(self.command_ranges.max_ang_vel)
+        if not (abs(vx) <= mx and abs(yaw) <= ma) or mx <= 0 or ma <= 0:
+            raise ValueError(f"set_fixed_commands: ({vx}, {yaw}) is outside the command ranges (|vx| <= {mx}, |yaw| <= {ma})")
+        ux, uy = (vx + mx) / (2 * mx), (yaw + ma) / (2 * ma)
+        self.set_command_uniforms(np.tile(np.array([ux, uy, ux, uy]), (self.num_envs, 1)))
+        keep = 1.0 if abs(vx) > 0.02 else 0.0
+        self.set_buffers(commands=np.tile(np.array([vx * keep, 0.0, yaw]), (self.num_envs, 1)))
+        self._fixed_cmd = (vx, yaw)
 
     def policy_act(self, params_flat, obs, seed, iter_dev, step, storage, activation="elu"):
         """PPO.act as one launch of the rollout's wave code (nm_rollout_act_ex): the per-step counterpart of policy_rollout."""

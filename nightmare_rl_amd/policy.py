@@ -117,3 +117,23 @@ class ActorMLP(torch.nn.Module):
         if self._dirty or self._packed is None or self._generation != self._fingerprint() or self._packed.device != obs.device:
             self.repack()
         return self._packed.forward(obs)
+
+
+def flat_params_from_state_dict(sd, device):
+    """The flat parameter vector the wave policy reads (nm_rollout, nm_play: `actor W0 b0 W1 b1 ..., critic W0 b0 ..., std`) from an
+    rsl_rl ActorCritic state_dict (`actor.<2i>.weight/bias`, `critic.<2i>.weight/bias`, `std`; what reference play.py:60-72 loads from
+    `model_<it>.pt['model_state_dict']`): a checkpoint is played without a FusedUpdate or an optimizer. Returns (flat float32 device
+    tensor, actor dims [n_obs, h1, ..., n_actions])."""
+    parts, dims = [], None
+    for net in ("actor", "critic"):
+        idx = sorted({int(k.split(".")[1]) for k in sd if k.startswith(net + ".") and k.endswith(".weight")})
+        if not idx:
+            raise KeyError(f"state_dict has no {net}.<i>.weight entries")
+        if net == "actor":
+            dims = [int(sd[f"actor.{idx[0]}.weight"].shape[1])] + [int(sd[f"actor.{i}.weight"].shape[0]) for i in idx]
+        for i in idx:
+            parts += [sd[f"{net}.{i}.weight"].reshape(-1), sd[f"{net}.{i}.bias"].reshape(-1)]
+    parts.append(sd["std"].reshape(-1))
+    flat = torch.cat([p.detach().to(dtype=torch.float32, device="cpu") for p in parts]).to(device).contiguous()
+    return flat, dims
+

@@ -122,10 +122,11 @@ class FusedCollector:
 
     def can_rollout(self, env):
         """Can the whole rollout run as ONE launch inside the env's own waves (nm_rollout)? Needs this repo's fp32 env on the same device,
-        networks of the compiled shape next to a FusedUpdate (its flat parameter vector is what the kernel reads), no privileged observations."""
+        networks of the compiled shape next to a FusedUpdate (its flat parameter vector is what the kernel reads), no privileged observations.
+        The env's state log (cfg.viewer.record_states) is kept inside the launch and is no reason to leave it."""
         if self.update is None or not hasattr(env, "policy_rollout") or getattr(env, "_dtype", None) != _lib.DTYPE_F32:
             return False
-        if env.num_envs != self.N or torch.device(env.device) != self.device or env.cfg.viewer.record_states or env.get_privileged_observations() is not None:
+        if env.num_envs != self.N or torch.device(env.device) != self.device or env.get_privileged_observations() is not None:
             return False
         a = (C.c_int32 * (len(self.a_lin) + 1))(self.a_lin[0].in_features, *[m.out_features for m in self.a_lin])
         c = (C.c_int32 * (len(self.c_lin) + 1))(self.c_lin[0].in_features, *[m.out_features for m in self.c_lin])

@@ -6,7 +6,13 @@ Here: the checkpoint's actor runs on the matrix cores (nm_policy_* handle), the 
 once, no viewer. Like upstream the actions are SAMPLED (`nn.act`, not `act_inference`) unless --deterministic.
 
   python scripts/play.py [checkpoint.pt | --log-root logs/nightmare_v3] [-e 64] [--steps 1300] [--decimation 2] [--cmd 0.3 0.0 0.2]
-                         [--activation elu]
+                         [--activation elu] [--one-launch [--launch-steps K]] [--record-states DIR]
+
+--one-launch runs the same loop inside the env's own wavefronts (NightmareV3Env.policy_play -> nm_play: policy and step, K steps per
+launch, no host round trip per step) and prints the same summary from the device bookkeeping; the actions are then drawn by the
+rollout's counter generator, not torch's. --record-states DIR writes upstream's state log of env 0 (envs/nightmare_v3_env.py:261-272),
+the files open_custom_play.py:50-66 replays. With --one-launch, --cmd holds (VX, YAW) through set_fixed_commands (VY must be 0: the
+env never commands a lateral velocity, :330).
 
 A checkpoint does not record the hidden activation of its networks (rsl_rl saves the state_dict only): --activation names it, by default
 the training config's (NightmareV3ConfigPPO.policy.activation).
@@ -23,7 +29,7 @@ sys.path.insert(0, ROOT)
 from nightmare_rl_amd.envs.helpers import get_load_path  # noqa: E402
 from nightmare_rl_amd.envs.nightmare_v3_config import NightmareV3Config, NightmareV3ConfigPPO  # noqa: E402
 from nightmare_rl_amd.envs.nightmare_v3_env import NightmareV3Env  # noqa: E402
-from nightmare_rl_amd.policy import ActorMLP  # noqa: E402
+from nightmare_rl_amd.policy import ActorMLP, flat_params_from_state_dict  # noqa: E402
 
 
 def actor_from_checkpoint(path, device, activation=None):
@@ -42,6 +48,44 @@ def actor_from_checkpoint(path, device, activation=None):
     return net, sd["std"].to(device)
 
 
+def play_one_launch(a, path, env, cfg, dev):
+    """The loop of main() as launches of --launch-steps steps (NightmareV3Env.policy_play); the summary comes from the tensors the kernel
+    keeps: running returns, per-env sum / number of finished returns. The sum of all rewards up to a step is (finished returns + running
+    returns), so a launch boundary 200 steps before the end gives the 'last 200 steps' figure without a per-step read."""
+    from nightmare_rl_amd import _lib
+    flat, dims = flat_params_from_state_dict(torch.load(path, map_location="cpu")["model_state_dict"], dev)
+    if not _lib.load().nm_play_supported((_lib.C.c_int32 * len(dims))(*dims), len(dims) - 1, _lib.activation_code(a.activation)):
+        raise SystemExit(f"--one-launch: no play kernel for an actor of shape {dims} (use the per-step path)")
+    if a.cmd is not None:
+        if a.cmd[1] != 0.0:
+            raise SystemExit("--one-launch --cmd: VY must be 0 (the env commands no lateral velocity)")
+        env.set_fixed_commands((a.cmd[0], a.cmd[2]))
+    env.reset()
+    N = a.envs
+    z = lambda n: torch.zeros(n, device=dev)
+    stats = dict(cur_ret=z(N), cur_len=z(N), fin=z(3), ret_sum=z(N), ret_cnt=z(N))
+    chunk = a.launch_steps or int(env.max_episode_length)
+    if chunk < 1:
+        raise SystemExit("--launch-steps must be at least 1")
+    total = lambda: float(stats["ret_sum"].double().sum() + stats["cur_ret"].double().sum())
+    tail0, before_tail, done = max(a.steps - 200, 0), 0.0, 0
+    while done < a.steps:
+        k = min(chunk, a.steps - done, tail0 - done if done < tail0 else a.steps)
+        env.policy_play(k, flat, deterministic=a.deterministic, seed=a.seed, activation=a.activation, stats=stats)
+        done += k
+        if done == tail0:
+            before_tail = total()
+    tot = total()
+    ndone, ret_sum = int(stats["ret_cnt"].sum()), float(stats["ret_sum"].double().sum())
+    print(f"checkpoint {path}: {a.envs} robots x {a.steps} steps, decimation {cfg.control.decimation}, "
+          f"{'mean' if a.deterministic else 'sampled'} actions")
+    print(f"  mean reward per step {tot / (N * a.steps):.4f} (last 200 steps {(tot - before_tail) / (N * (a.steps - tail0)):.4f}); episodes finished {ndone}"
+          + (f", mean return {ret_sum / ndone:.2f}" if ndone else ""))
+    if "episode" in env.extras:
+        print("  last episode statistics:", {k: round(float(v), 4) for k, v in env.extras["episode"].items()})
+    print("  env counters:", env.counters())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("checkpoint", nargs="?", default=None)
@@ -54,15 +98,22 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--activation", default=NightmareV3ConfigPPO.policy.activation,
                     help="hidden activation the checkpoint was trained with (not stored in it; default: the training config's)")
+    ap.add_argument("--one-launch", action="store_true", help="policy and env step inside one kernel, --launch-steps steps per launch (nm_play)")
+    ap.add_argument("--launch-steps", type=int, default=None, help="steps per launch with --one-launch (default: one episode)")
+    ap.add_argument("--record-states", default=None, metavar="DIR", help="write upstream's state log of env 0 (pickle files) into DIR")
     a = ap.parse_args()
     path = a.checkpoint or get_load_path(a.log_root)
     dev = torch.device("cuda", 0)
-    net, std = actor_from_checkpoint(path, dev, a.activation)
     cfg = NightmareV3Config()
     cfg.env.num_envs = a.envs
     if a.decimation is not None:
         cfg.control.decimation = a.decimation
-    env = NightmareV3Env(cfg, device=dev, seed=a.seed)
+    if a.record_states is not None:
+        cfg.viewer.record_states = True
+    env = NightmareV3Env(cfg, device=dev, seed=a.seed, **({"log_dir": a.record_states} if a.record_states is not None else {}))
+    if a.one_launch:
+        return play_one_launch(a, path, env, cfg, dev)
+    net, std = actor_from_checkpoint(path, dev, a.activation)
     torch.manual_seed(a.seed)
     obs, _ = env.reset()
     ret = torch.zeros(a.envs, device=dev)

@@ -25,6 +25,8 @@ def main():
     ap.add_argument("-p", "--resume_path", type=str, default=None, dest="resume_path")
     ap.add_argument("--iters", type=int, default=None, help="learning iterations (default: cfg.runner.max_iterations)")
     ap.add_argument("--seed", type=int, default=None)
+    ap.add_argument("--record-states", action="store_true", default=False, dest="record_states",
+                    help="upstream's viewer.record_states: pickle env 0's states into the run's log directory whenever it resets (envs/nightmare_v3_env.py:261-272)")
     ap.add_argument("--gpus", type=int, default=None, help="ranks (one per GPU); without torch.distributed.run, train.py starts them itself")
     args = ap.parse_args()
 
@@ -56,6 +58,7 @@ def main():
     log_dir = f"logs/nightmare_v3/{datetime.datetime.now()}/"
     cfg, train_cfg = NightmareV3Config(), NightmareV3ConfigPPO()
     cfg.viewer.render = args.render
+    cfg.viewer.record_states = bool(args.record_states) and rank == 0        # one log: rank 0's env 0
     lo, hi = shard_range(args.num_envs, rank, world)
     cfg.env.num_envs = hi - lo
     train_cfg.runner.resume = args.resume
