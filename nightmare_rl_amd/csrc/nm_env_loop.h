@@ -1,0 +1,117 @@
+// nm_env_loop.h - what the K-step launches k_env_rollout (nm_rollout_kernels.h) and k_env_play (nm_play_kernels.h) share: the wave
+// index, the launch prologue, the episode books of the wave's two envs and the per-step update of the env step's launch arguments.
+// X below is the launch's own argument struct, RollArgs or PlayArgs (nm_rollout.h): the helpers read the fields both carry (cur_ret,
+// cur_len, fin3, to_step, st_sum, st_cnt, rec_log) and `if constexpr` on X decides what only one of them files.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <type_traits>
+
+#include "nm_core.h"
+#include "nm_rollout.h"
+
+namespace nmr {
+
+// XCD-aware block -> wave mapping: the dispatcher deals workgroups round-robin over the 8 XCDs (block b runs on XCD b % 8), each with
+// its own L2. Consecutive envs share cache lines (rows of 100 / 96 / 72 bytes), so each XCD takes a CONTIGUOUS eighth of the waves:
+// a line's bytes are then written through one L2 instead of being merged in memory from two.
+__device__ __forceinline__ int wave_index(int nxcd) {
+  int wave = blockIdx.x;
+#ifndef NM_NO_XCD_MAP
+  {
+    const int nwx = (int)gridDim.x >> 3;          // workgroups per XCD (the remainder, if any, keeps the identity mapping)
+    if (nxcd == 8 && wave < (nwx << 3)) wave = (wave & 7) * nwx + (wave >> 3);   // other partition modes (CPX, DPX): identity
+  }
+#endif
+  return wave;
+}
+
+// The first lines of a K-step launch: the wave's index, the launch arguments and the model constants into the workgroup's LDS (once for
+// all K steps), "no time-out yet" for the wave's envs. false: the wave has no env and leaves.
+template <class X>
+__device__ __forceinline__ bool loop_begin(const nm::Model<float>* __restrict__ Mp, const nm::Args<float>& A, const X& R, nm::Model<float>& Ms,
+                                           nm::Args<float>& As, X& Rs, int& wave) {
+  wave = wave_index(A.nxcd);
+  if (wave * 2 >= A.N) return false;
+  As = A;
+  Rs = R;
+  __syncthreads();
+  {  // the model constants: L2 -> LDS
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(Mp);
+    uint32_t* dst = reinterpret_cast<uint32_t*>(&Ms);
+    constexpr int kWords = (int)(sizeof(nm::Model<float>) / 4);
+    for (int i = threadIdx.x; i < kWords; i += 64) dst[i] = src[i];
+    __syncthreads();
+  }
+  if ((int)threadIdx.x < 2 && wave * 2 + (int)threadIdx.x < A.N) R.to_step[wave * 2 + threadIdx.x] = -1;
+  return true;
+}
+
+// PPO.process_env_step + the runner's bookkeeping for this wave's envs (k_ppo_record's arithmetic), in two halves so that its loads travel
+// with the next policy step's observation loads (one L2 round trip instead of two): `load` right after the step's stores have landed,
+// `file` whenever the values are needed.
+//   rollout: the transition's reward and done go into the storage rows of step t. The time-out bootstrap needs the step's
+//            extras['time_outs'], a cross-wave quantity: k_rollout_tail adds it. An env times out at most once per launch.
+//   play   : nothing is stored; per env the sum and the number of the returns of the episodes it finished (the wave owns the env: plain
+//            load / add / store in step order, no atomics), the logged env's reset flag, and a later time-out of the same env overwrites
+//            the earlier one's step.
+struct BookRegs { float rw, to, cr, cl, rs, rc; long long d; };
+template <class X>
+__device__ __forceinline__ void books_load(BookRegs& r, const X* Xs, const nm::Args<float>* As, int wave) {
+  const int lane = threadIdx.x, e = min(wave * 2 + (lane & 1), As->N - 1);
+  // (global-memory accessors of simt.h: the pointers come out of LDS copies of the arguments - plain dereferences would be flat_load)
+  r.rw = simt::gld1(As->rew, e); r.d = simt::gld1(As->done, e); r.to = simt::gld1(As->timeout_now, e);
+  r.cr = simt::gld1((const float*)Xs->cur_ret, e); r.cl = simt::gld1((const float*)Xs->cur_len, e);
+  if constexpr (std::is_same_v<X, PlayArgs>) { r.rs = simt::gld1((const float*)Xs->ret_sum, e); r.rc = simt::gld1((const float*)Xs->ret_cnt, e); }
+}
+template <class X>
+__device__ __forceinline__ void books_file(const BookRegs& r, const X* Xs, const nm::Args<float>* As, int t, int wave) {
+  constexpr bool PLAY = std::is_same_v<X, PlayArgs>;
+  const int lane = threadIdx.x, N = As->N, e = wave * 2 + lane;
+  if (lane < 2 && e < N) {
+    // (with the compiler this was written for, the place of this compare decides the order the scheduler gives the books' loads: each
+    // launch keeps the place it had when the two were written apart, and with it its instruction stream. C++ promises nothing of the
+    // kind: after a compiler upgrade the two places may mean nothing - then write the compare once, first)
+    bool d;
+    if constexpr (!PLAY) d = r.d > 0;
+    float cr = r.cr + r.rw, cl = r.cl + 1.0f;
+    if constexpr (PLAY) d = r.d > 0;
+    if constexpr (!PLAY) {
+      const size_t so = (size_t)t * N;
+      simt::gst1(Xs->s_rewards, so + e, r.rw);
+      simt::gst1(Xs->s_dones, so + e, (unsigned char)(d ? 1 : 0));
+    }
+    if (d) {
+      atomicAdd(Xs->fin3, cr); atomicAdd(Xs->fin3 + 1, cl); atomicAdd(Xs->fin3 + 2, 1.0f);
+      if constexpr (PLAY) { simt::gst1(Xs->ret_sum, (size_t)e, r.rs + cr); simt::gst1(Xs->ret_cnt, (size_t)e, r.rc + 1.0f); }
+      cr = 0.f; cl = 0.f;
+    }
+    simt::gst1(Xs->cur_ret, (size_t)e, cr); simt::gst1(Xs->cur_len, (size_t)e, cl);
+    if (r.to != 0.f) simt::gst1(Xs->to_step, (size_t)e, t);
+    if constexpr (PLAY)
+      if (Xs->rec_done && e == Xs->rec_env) simt::gst1(Xs->rec_done, (size_t)t, (unsigned char)(d ? 1 : 0));
+  }
+}
+// the books of the launch's last step (no policy step follows it)
+template <class X>
+__device__ __noinline__ void books_last(const X* Xs, const nm::Args<float>* As, int t, int wave) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  BookRegs rec;
+  books_load(rec, Xs, As, wave);
+  books_file(rec, Xs, As, t, wave);
+}
+
+// The launch arguments of env step t that every K-step launch sets (lane 0, after the policy of step t), and what closes the policy step.
+template <class X>
+__device__ __forceinline__ void step_args(nm::Args<float>* As, const X* Xs, int t, uint64_t noise0) {
+  As->stat_sum = Xs->st_sum + (size_t)t * nm::kNREW;
+  As->stat_cnt = Xs->st_cnt + (size_t)t * 4;
+  As->noise_step = noise0 + (uint64_t)t;
+  As->rec = Xs->rec_log ? Xs->rec_log + (size_t)t * kRecRow : nullptr;           // the state log's row of this step (env.py:261-272)
+}
+__device__ __forceinline__ void step_close() {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the actions are in L2 before the load stage asks for them (other lanes of this wave)
+  nm::wave_sync();
+}
+
+}  // namespace nmr

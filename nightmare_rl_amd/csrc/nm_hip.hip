@@ -9,6 +9,7 @@
 
 #include "../../include/nightmare_hip.h"
 #include "nm_host_model.h"
+#include "nm_env_loop.h"
 #include "nm_rollout.h"
 
 static thread_local std::string g_err;
@@ -92,16 +93,7 @@ __global__ void __launch_bounds__(64 * (sizeof(real) == 8 ? 1 : kWG), NM_WAVES_P
   __shared__ nm::Model<real> Ms;   // this workgroup's copy of the model constants
   __shared__ nm::Args<real> As;    // ... and of the launch arguments: ~30 pointers would otherwise pin 60 SGPRs for the whole kernel
   nm::ShW<real, G>& sh = shs[kWG == 1 ? 0 : (int)(threadIdx.x >> 6)];
-  // XCD-aware block -> wave mapping: the dispatcher deals workgroups round-robin over the 8 XCDs (block b runs on XCD b % 8), each with
-  // its own L2. Consecutive envs share cache lines (rows of 100 / 96 / 72 bytes), so each XCD takes a CONTIGUOUS eighth of the waves:
-  // a line's bytes are then written through one L2 instead of being merged in memory from two.
-  int wave = blockIdx.x;
-#ifndef NM_NO_XCD_MAP
-  {
-    const int nwx = (int)gridDim.x >> 3;          // workgroups per XCD (the remainder, if any, keeps the identity mapping)
-    if (A.nxcd == 8 && wave < (nwx << 3)) wave = (wave & 7) * nwx + (wave >> 3);   // other partition modes (CPX, DPX): identity
-  }
-#endif
+  int wave = nmr::wave_index(A.nxcd);      // XCD-aware block -> wave mapping (nm_env_loop.h)
   if (kWG > 1) wave = wave * kWG + (int)(threadIdx.x >> 6);
 #ifdef NM_MEASURE
   if (A.ablate & 512) return;      // measurement only: the empty launch
@@ -598,6 +590,28 @@ template <class real> struct Env : nm_env {
     if (nmr::launch_act(roll_wp, roll_bp, flat + RS::stdoff(), obs, N, seed, iter_dev, step, o, act, s)) return fail("nm_rollout_act: launch failed");
     return 0;
   }
+  // what nm_rollout and nm_play check alike: the range of `steps` and the episode-statistics arguments (`who`: the entry point's name)
+  int kstep_check(const char* who, int K, const char* hint, int n_ep, const int* ep_idx, const float* ep_acc, const float* ep_stats) {
+    if (K < 1 || K > 4096) return fail(std::string(who) + ": steps must be in 1..4096" + hint);
+    if (n_ep < 0 || n_ep > nm::kNREW || (n_ep > 0 && (!ep_idx || !ep_acc || !ep_stats))) return fail(std::string(who) + ": bad episode-statistics arguments");
+    return 0;
+  }
+  // the nm::Args of a K-step launch (the kernel sets stat_sum / stat_cnt / noise_step / rec per step; extras are closed by k_rollout_tail);
+  // advances noise_step by K
+  nm::Args<real> kstep_args(int K, const float* actions, int64_t* eplen, float* obs, float* rew, int64_t* done, real* log) {
+    nm::Args<real> a = A;
+    a.actions = actions; a.eplen = eplen; a.obs = obs; a.rew = rew; a.done = done; a.timeout_now = timeout_now;
+    a.cmd_u = cmd_u_on ? cmd_u_dev : nullptr;
+    a.physics_only = 0;
+    a.ep_stats = nullptr; a.time_outs = nullptr; a.counters = counters_dev;
+    a.to_list = nullptr;
+    a.noise_vec = noise_on ? noise_vec_dev : nullptr;
+    a.noise_u = noise_on && noise_u_on ? noise_u_dev : nullptr;
+    a.noise_step = noise_step;
+    noise_step += (uint64_t)K;
+    a.rec = log; a.rec_env = log ? rec_env : -1; a.dbg = nullptr; a.ret_acc = nullptr;    // (rec: row t, set by the kernel before every step)
+    return a;
+  }
   int rollout(const nm_rollout_args* r, int act, hipStream_t s) override {
     HIPCHK(hipSetDevice(device));
     if constexpr (sizeof(real) == 8 || NM_ENVS_PER_WAVE != 2) {
@@ -605,26 +619,15 @@ template <class real> struct Env : nm_env {
     } else {
       if (!r) return fail("nm_rollout: args is NULL");
       const int K = r->steps;
-      if (K < 1 || K > 4096) return fail("nm_rollout: steps must be in 1..4096");
+      if (kstep_check("nm_rollout", K, "", r->n_ep, r->ep_idx_dev, r->ep_acc_dev, r->ep_stats_dev)) return 1;
       if ((double)K > (double)M.max_ep_len) return fail("nm_rollout: more steps than an episode has (an env may time out once per rollout)");
       if (!r->params_flat_dev || !r->iter_dev || !r->obs0_dev || !r->obs_final_dev || !r->episode_length_dev || !r->rew_dev || !r->done_dev || !r->s_obs ||
           !r->s_actions || !r->s_logp || !r->s_values || !r->s_mu || !r->s_sigma || !r->s_rewards || !r->s_dones || !r->cur_ret || !r->cur_len || !r->fin3)
         return fail("nm_rollout: NULL pointer");
-      if (r->n_ep < 0 || r->n_ep > nm::kNREW || (r->n_ep > 0 && (!r->ep_idx_dev || !r->ep_acc_dev || !r->ep_stats_dev))) return fail("nm_rollout: bad episode-statistics arguments");
       real* log = nullptr;
       if (roll_reserve(K) || log_rows(K, &log)) return 1;
       if (roll_pack(r->params_flat_dev, s)) return 1;
-      nm::Args<real> a = A;
-      a.actions = nullptr; a.eplen = r->episode_length_dev; a.obs = r->obs_final_dev; a.rew = r->rew_dev; a.done = r->done_dev; a.timeout_now = timeout_now;
-      a.cmd_u = cmd_u_on ? cmd_u_dev : nullptr;
-      a.physics_only = 0;
-      a.ep_stats = nullptr; a.time_outs = nullptr; a.counters = counters_dev;     // extras are closed by k_rollout_tail
-      a.to_list = nullptr;
-      a.noise_vec = noise_on ? noise_vec_dev : nullptr;
-      a.noise_u = noise_on && noise_u_on ? noise_u_dev : nullptr;
-      a.noise_step = noise_step;
-      noise_step += (uint64_t)K;
-      a.rec = log; a.rec_env = log ? rec_env : -1; a.dbg = nullptr; a.ret_acc = nullptr;    // (rec: row t, set by the kernel before every step)
+      const nm::Args<real> a = kstep_args(K, nullptr, r->episode_length_dev, r->obs_final_dev, r->rew_dev, r->done_dev, log);
       nmr::RollArgs R;
       R.K = K; R.wp = (const nmr::f32x4*)roll_wp; R.bp = roll_bp; R.stdv = r->params_flat_dev + RS::stdoff();
       R.seed = r->seed; R.iter_dev = r->iter_dev; R.obs0 = r->obs0_dev; R.obs_final = r->obs_final_dev;
@@ -649,27 +652,16 @@ template <class real> struct Env : nm_env {
     } else {
       if (!r) return fail("nm_play: args is NULL");
       const int K = r->steps;
-      if (K < 1 || K > 4096) return fail("nm_play: steps must be in 1..4096 (longer runs: consecutive launches)");
+      if (kstep_check("nm_play", K, " (longer runs: consecutive launches)", r->n_ep, r->ep_idx_dev, r->ep_acc_dev, r->ep_stats_dev)) return 1;
       if (!r->params_flat_dev || !r->iter_dev || !r->obs0_dev || !r->obs_dev || !r->actions_dev || !r->episode_length_dev || !r->rew_dev || !r->done_dev)
         return fail("nm_play: NULL pointer");
-      if (r->n_ep < 0 || r->n_ep > nm::kNREW || (r->n_ep > 0 && (!r->ep_idx_dev || !r->ep_acc_dev || !r->ep_stats_dev))) return fail("nm_play: bad episode-statistics arguments");
       if ((r->cur_ret == nullptr) != (r->cur_len == nullptr) || (r->ret_sum == nullptr) != (r->ret_cnt == nullptr))
         return fail("nm_play: cur_ret / cur_len and ret_sum / ret_cnt come in pairs");
       real* log = nullptr;
       if (roll_reserve(K) || log_rows(K, &log)) return 1;
       if (!play_scratch && dalloc(&play_scratch, (size_t)N * 4 + 4)) return 1;
       if (roll_pack(r->params_flat_dev, s)) return 1;
-      nm::Args<real> a = A;
-      a.actions = r->actions_dev; a.eplen = r->episode_length_dev; a.obs = r->obs_dev; a.rew = r->rew_dev; a.done = r->done_dev; a.timeout_now = timeout_now;
-      a.cmd_u = cmd_u_on ? cmd_u_dev : nullptr;
-      a.physics_only = 0;
-      a.ep_stats = nullptr; a.time_outs = nullptr; a.counters = counters_dev;     // extras are closed by k_rollout_tail
-      a.to_list = nullptr;
-      a.noise_vec = noise_on ? noise_vec_dev : nullptr;
-      a.noise_u = noise_on && noise_u_on ? noise_u_dev : nullptr;
-      a.noise_step = noise_step;
-      noise_step += (uint64_t)K;
-      a.rec = log; a.rec_env = log ? rec_env : -1; a.dbg = nullptr; a.ret_acc = nullptr;
+      const nm::Args<real> a = kstep_args(K, r->actions_dev, r->episode_length_dev, r->obs_dev, r->rew_dev, r->done_dev, log);
       nmr::PlayArgs P;
       P.K = K; P.deterministic = r->deterministic != 0;
       P.wp = (const nmr::f32x4*)roll_wp; P.bp = roll_bp; P.stdv = r->params_flat_dev + RS::stdoff();

@@ -31,6 +31,8 @@
 
 #include "../../include/nightmare_hip.h"
 #include "nm_act.h"
+#include "nm_sample.h"
+#include "nm_sfor.h"
 
 extern "C" int nm_policy_set_error(const char* m);
 
@@ -296,8 +298,6 @@ __global__ void __launch_bounds__(kThreads) k_ppo_fwdbwd(PpoNet net, PpoBatch bt
 // the vector-memory queue (a workgroup-scope release has to assume global memory): at the layer-1 barrier that is the next pass's rows
 // (an HBM gather) and at every barrier the weight fragments prefetched across it - the ring would be waited for, not run under.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-template <int N, class F, int... Is> __device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }
-template <int N, class F> __device__ __forceinline__ void sfor(F&& f) { sfor_impl<N>(f, std::make_integer_sequence<int, N>{}); }
 
 template <int I_, int A1, int A2, int A3, int AO, int C1, int C2, int C3>
 struct Shape4 {
@@ -844,15 +844,8 @@ __global__ void __launch_bounds__(64 * kSplitWaves, 2) k_ppo_fwdbwd_split(PpoNet
 // PPO.act for the reference-shaped network in ONE launch: the register-resident forward of the merged network (one wave = 16 rows,
 // weights from the update's own packed copy - no separate repack for the collector), then the sampling head on the output registers:
 // lane (row r, q) holds outputs 16 t + 4 q + reg, i.e. whole action pairs, so Box-Muller pairs, log-probability partials and the
-// storage writes need no exchange; the log-probability crosses the four q lanes with two shuffles. Same counter generator and keys
-// as nm_ppo_sample (seed, iteration, step, env, action pair).
-__device__ __forceinline__ float ppo_u24(uint64_t seed, uint64_t a, uint64_t b) {   // = u24 of nm_rl.hip
-  uint64_t x = seed + 0x9E3779B97F4A7C15ull * (a + 1) + 0xD1B54A32D192ED03ull * b;
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return ((float)(uint32_t)(x >> 40) + 1.0f) * (1.0f / 16777216.0f);
-}
+// storage writes need no exchange; the log-probability crosses the four q lanes with two shuffles. The draw and its keys (seed,
+// iteration, step, env, action pair) are nm_sample.h's, as in nm_ppo_sample.
 // the bookkeeping of the PREVIOUS step (what nm_ppo_record does), done at the head of the next PPO.act launch: rew == nullptr = nothing to do
 struct PpoRecord {
   const float* rew; const int64_t* done; const float* time_outs; const float* values;
@@ -963,11 +956,8 @@ __global__ void __launch_bounds__(64) k_ppo_act_fast(PpoNet net, const float* __
     for (int pr = 0; pr < 2; pr++) {
       const int f0 = 16 * t + 4 * q + 2 * pr;            // even action index: the pair (f0, f0 + 1) shares one Box-Muller draw
       if (f0 < AO) {
-        const float u1 = ppo_u24(seed, (uint64_t)lrow * 64 + f0, ctr), u2 = ppo_u24(seed, (uint64_t)lrow * 64 + f0 + 1, ctr);
-        const float rad = sqrtf(-2.0f * __logf(u1));
-        float sn, cs;
-        __sincosf(6.283185307179586f * u2, &sn, &cs);
-        const float z[2] = {rad * cs, rad * sn};
+        float z[2];
+        nms::normal_pair(seed, (uint64_t)lrow * 64 + f0, ctr, z);
 #pragma unroll
         for (int hh = 0; hh < 2; hh++) {
           const float m = out[t][2 * pr + hh], sd = std[f0 + hh];
@@ -976,7 +966,7 @@ __global__ void __launch_bounds__(64) k_ppo_act_fast(PpoNet net, const float* __
             mu[lrow * AO + f0 + hh] = m;
             sigma[lrow * AO + f0 + hh] = sd;
           }
-          lp += -0.5f * z[hh] * z[hh] - __logf(sd) - 0.9189385332046727f;
+          lp += nms::logp_term(z[hh], sd);
         }
       } else if (f0 == AO && live) {
         values[lrow] = out[t][2 * pr];

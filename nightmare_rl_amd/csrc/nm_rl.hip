@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/nightmare_hip.h"
+#include "nm_sample.h"
 
 extern "C" int nm_policy_set_error(const char* m);
 
@@ -97,13 +98,6 @@ extern "C" int nm_gae_advantages(const float* rewards, const float* values, cons
 // after the fused actor+critic forward (nm_policy_forward on the merged network: out[N, A+1] = action means | value):
 // one pass per env row that draws the action, evaluates its log-probability and files everything the update needs directly into
 // step s of the rollout storage - instead of ~25 elementwise launches per step.
-__device__ __forceinline__ float u24(uint64_t seed, uint64_t a, uint64_t b) {   // counter-based uniform in (0,1], 24 bits
-  uint64_t x = seed + 0x9E3779B97F4A7C15ull * (a + 1) + 0xD1B54A32D192ED03ull * b;
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return ((float)(uint32_t)(x >> 40) + 1.0f) * (1.0f / 16777216.0f);
-}
 // 16 lanes per env: lane j < ceil(A/2) draws the action pair (2j, 2j+1) (Box-Muller: two normals per pair of uniforms), the
 // log-probability is summed over the 16 lanes, and the block copies its 16 envs' observations as one contiguous run.
 constexpr int kSampleEnvs = 16;    // envs per 256-thread block
@@ -121,17 +115,16 @@ __global__ void __launch_bounds__(256) k_ppo_sample(const float* __restrict__ ne
   if (e < N && j < A) {
     const uint64_t ctr = (uint64_t)iter_dev[0] * 4096ull + (uint64_t)step;
     const float* o = net_out + (size_t)e * (A + 1);
-    const float u1 = u24(seed, (uint64_t)e * 64 + j, ctr), u2 = u24(seed, (uint64_t)e * 64 + j + 1, ctr);
-    const float rad = sqrtf(-2.0f * __logf(u1));
-    float sn, cs;
-    __sincosf(6.283185307179586f * u2, &sn, &cs);
-    const float z[2] = {rad * cs, rad * sn};
+    // nms::normal_pair(seed, e * 64 + j, ctr, z) written out: called as such, this kernel's key arithmetic compiles to other (equivalent)
+    // integer instructions than it did before the draw moved into nm_sample.h
+    float z[2];
+    nms::box_muller(nms::u24(seed, (uint64_t)e * 64 + j, ctr), nms::u24(seed, (uint64_t)e * 64 + j + 1, ctr), z);
     for (int h = 0; h < 2 && j + h < A; h++) {
       const float m = o[j + h], sd = std[j + h];
       actions[(size_t)e * A + j + h] = m + sd * z[h];
       mu[(size_t)e * A + j + h] = m;
       sigma[(size_t)e * A + j + h] = sd;
-      lp += -0.5f * z[h] * z[h] - __logf(sd) - 0.9189385332046727f;   // Normal.log_prob: -(a-m)^2/(2 sd^2) - log sd - log sqrt(2 pi)
+      lp += nms::logp_term(z[h], sd);
     }
     if (j == 0) values[e] = o[A];
   }

@@ -15,24 +15,22 @@
 // Arithmetic: exact f32 FMA chains in k order, bias as the accumulator's initial value, the hidden activation of nm_act.h (a template
 // argument: ELU by default, with the hardware exponential) - the same network as nm_ppo_act (16x16x4 tiles), rounded in another order
 // (agreement ~1e-6; tests/test_gpu_rollout.py states the tolerance).
-// The action noise uses the generator and keys of nm_ppo_sample / nm_ppo_act (seed, iteration, step, env, action pair): the same z.
+// The action noise is nm_sample.h's, with the keys of nm_ppo_sample / nm_ppo_act (seed, iteration, step, env, action pair): the same z.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <type_traits>
-#include <utility>
 
 #include "nm_act.h"
+#include "nm_sample.h"
+#include "nm_sfor.h"
 
 namespace nmr {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
-
-template <int N, class F, int... Is> __device__ __forceinline__ void sfor_impl(F&& f, std::integer_sequence<int, Is...>) { (f(std::integral_constant<int, Is>{}), ...); }
-template <int N, class F> __device__ __forceinline__ void sfor(F&& f) { sfor_impl<N>(f, std::make_integer_sequence<int, N>{}); }
 
 // Network shape, compile time: observation I, three hidden layers of the actor (A1..A3) and of the critic (C1..C3), AO actions, value 1.
 // Layer l of the merged network: inputs ka(l) | kc(l) (layer 0: both read the observation), outputs padded to whole 4-neuron blocks:
@@ -103,13 +101,6 @@ template <class S> __global__ void k_roll_pack(const float* __restrict__ flat, f
   }
 }
 
-__device__ __forceinline__ float u24(uint64_t seed, uint64_t a, uint64_t b) {   // = u24 of nm_rl.hip / ppo_u24 of nm_ppo.hip
-  uint64_t x = seed + 0x9E3779B97F4A7C15ull * (a + 1) + 0xD1B54A32D192ED03ull * b;
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  return ((float)(uint32_t)(x >> 40) + 1.0f) * (1.0f / 16777216.0f);
-}
 __device__ __forceinline__ void roll_sync() {     // LDS traffic of one wave is executed in issue order: keep the compiler's order, nothing else
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -207,39 +198,10 @@ __device__ __forceinline__ void policy_wave(float* xb, const f32x4* __restrict__
   });
   // ---- sampling head on the output tile: lane (block b, column j) holds action means 4 b .. 4 b + 3 of env j (b < oa4 / 4) or the value (first critic block)
   constexpr int nab = S::oa4(NL - 1) / 4;
+  constexpr bool PLAY = MODE == kPolicyPlay;
   float lp = 0.0f;
   if constexpr (VALUE_ONLY) {
     if (blk == nab && live) ((gwp)o.values)[env] = out[0];
-    return;
-  }
-  if constexpr (MODE == kPolicyPlay) {
-    if (blk < nab) {
-#pragma unroll
-      for (int pr = 0; pr < 2; pr++) {
-        const int f0 = 4 * blk + 2 * pr;
-        if (f0 < AO) {
-          float z[2] = {0.0f, 0.0f};
-          if (!deterministic) {                        // the draw of the sampling head below: same keys, same arithmetic
-            const float u1 = u24(seed, (uint64_t)env * 64 + f0, ctr), u2 = u24(seed, (uint64_t)env * 64 + f0 + 1, ctr);
-            const float rad = sqrtf(-2.0f * __logf(u1));
-            float sn, cs;
-            __sincosf(6.283185307179586f * u2, &sn, &cs);
-            z[0] = rad * cs; z[1] = rad * sn;
-          }
-          f32x2u a2;
-#pragma unroll
-          for (int hh = 0; hh < 2; hh++) {
-            const float m = out[2 * pr + hh], sd = sg[f0 + hh];
-            const float a = m + sd * z[hh];
-            a2[hh] = deterministic ? m : a;
-          }
-          if (live) {
-            typedef __attribute__((address_space(1))) f32x2u* g2p;
-            *(g2p)((gwp)o.actions + (size_t)env * AO + f0) = a2;
-          }
-        }
-      }
-    }
     return;
   }
   if (blk < nab) {
@@ -247,31 +209,34 @@ __device__ __forceinline__ void policy_wave(float* xb, const f32x4* __restrict__
     for (int pr = 0; pr < 2; pr++) {
       const int f0 = 4 * blk + 2 * pr;                 // even action index: (f0, f0 + 1) share one Box-Muller draw, keyed like nm_ppo_sample
       if (f0 < AO) {
-        const float u1 = u24(seed, (uint64_t)env * 64 + f0, ctr), u2 = u24(seed, (uint64_t)env * 64 + f0 + 1, ctr);
-        const float rad = sqrtf(-2.0f * __logf(u1));
-        float sn, cs;
-        __sincosf(6.283185307179586f * u2, &sn, &cs);
-        const float z[2] = {rad * cs, rad * sn};
+        float z[2] = {0.0f, 0.0f};
+        if (!(PLAY && deterministic)) nms::normal_pair(seed, (uint64_t)env * 64 + f0, ctr, z);
         f32x2u a2, m2, s2;
 #pragma unroll
         for (int hh = 0; hh < 2; hh++) {
           const float m = out[2 * pr + hh], sd = sg[f0 + hh];
-          a2[hh] = m + sd * z[hh]; m2[hh] = m; s2[hh] = sd;
-          lp += -0.5f * z[hh] * z[hh] - __logf(sd) - 0.9189385332046727f;
+          const float a = m + sd * z[hh];
+          a2[hh] = PLAY && deterministic ? m : a;
+          m2[hh] = m; s2[hh] = sd;
+          if constexpr (!PLAY) lp += nms::logp_term(z[hh], sd);
         }
         if (live) {
           typedef __attribute__((address_space(1))) f32x2u* g2p;
           *(g2p)((gwp)o.actions + (size_t)env * AO + f0) = a2;
-          *(g2p)((gwp)o.mu + (size_t)env * AO + f0) = m2;
-          *(g2p)((gwp)o.sigma + (size_t)env * AO + f0) = s2;
+          if constexpr (!PLAY) {
+            *(g2p)((gwp)o.mu + (size_t)env * AO + f0) = m2;
+            *(g2p)((gwp)o.sigma + (size_t)env * AO + f0) = s2;
+          }
         }
       }
     }
-  } else if (blk == nab && live) {
+  } else if (!PLAY && blk == nab && live) {
     ((gwp)o.values)[env] = out[0];
   }
-  lp += __shfl_xor(lp, 4); lp += __shfl_xor(lp, 8); lp += __shfl_xor(lp, 16);     // over the action blocks (lane bits 2..4; blocks >= nab hold 0)
-  if (blk == 0 && live) ((gwp)o.logp)[env] = lp;
+  if constexpr (!PLAY) {
+    lp += __shfl_xor(lp, 4); lp += __shfl_xor(lp, 8); lp += __shfl_xor(lp, 16);     // over the action blocks (lane bits 2..4; blocks >= nab hold 0)
+    if (blk == 0 && live) ((gwp)o.logp)[env] = lp;
+  }
 }
 
 // ---- the K-step launch (kernels in nm_rollout.hip - a translation unit of its own, so that the code generation of k_env_step in

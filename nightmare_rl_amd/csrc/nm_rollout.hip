@@ -101,23 +101,22 @@ int launch_act(const float* wp, const float* bp, const float* stdv, const float*
                int act, hipStream_t s) {
   return with_act(act, [&](auto ACT) { return RollKernels<decltype(ACT)::value>::act(wp, bp, stdv, obs, N, seed, iter_dev, step, o, s); });
 }
-int launch_rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, const TailArgs& t, int act, hipStream_t s) {
-  const int N = a.N;
-  if (with_act(act, [&](auto ACT) { return RollKernels<decltype(ACT)::value>::rollout(M_dev, a, R, s); })) return 1;
-  hipLaunchKernelGGL(k_rollout_tail, dim3(min((N + 255) / 256, 64)), dim3(256), 0, s, t);
+// the closing launches of a K-step launch: k_rollout_tail, then k_rollout_clear
+static int launch_tail(const TailArgs& t, hipStream_t s) {
+  hipLaunchKernelGGL(k_rollout_tail, dim3(min((t.N + 255) / 256, 64)), dim3(256), 0, s, t);
   if (hipGetLastError() != hipSuccess) return 1;
   hipLaunchKernelGGL(k_rollout_clear, dim3((t.K * nm::kNREW + 255) / 256), dim3(256), 0, s, t.K, t.st_sum, t.st_cnt);
   return hipGetLastError() != hipSuccess;
 }
+int launch_rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, const TailArgs& t, int act, hipStream_t s) {
+  if (with_act(act, [&](auto ACT) { return RollKernels<decltype(ACT)::value>::rollout(M_dev, a, R, s); })) return 1;
+  return launch_tail(t, s);
+}
 // nm_play: the same closing launches. Without the bootstrap (t.gamma < 0) k_rollout_tail needs each env's LATEST time-out step only: the
 // time-out buffer is refreshed by the last step in which some env reset, and an env's flag there is "it timed out in that very step".
 int launch_play(const nm::Model<float>* M_dev, const nm::Args<float>& a, const PlayArgs& P, const TailArgs& t, int act, hipStream_t s) {
-  const int N = a.N;
   if (with_act(act, [&](auto ACT) { return PlayKernels<decltype(ACT)::value>::play(M_dev, a, P, s); })) return 1;
-  hipLaunchKernelGGL(k_rollout_tail, dim3(min((N + 255) / 256, 64)), dim3(256), 0, s, t);
-  if (hipGetLastError() != hipSuccess) return 1;
-  hipLaunchKernelGGL(k_rollout_clear, dim3((t.K * nm::kNREW + 255) / 256), dim3(256), 0, s, t.K, t.st_sum, t.st_cnt);
-  return hipGetLastError() != hipSuccess;
+  return launch_tail(t, s);
 }
 
 }  // namespace nmr

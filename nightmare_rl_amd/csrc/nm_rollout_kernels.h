@@ -8,8 +8,7 @@
 // the host launchers that pick the activation's instantiation) is nm_rollout.hip.
 #include <hip/hip_runtime.h>
 
-#include "nm_core.h"
-#include "nm_rollout.h"
+#include "nm_env_loop.h"
 
 #ifndef NM_ROLLOUT_ACT
 #error "define NM_ROLLOUT_ACT (an NM_ACT_* code) before including nm_rollout_kernels.h"
@@ -20,62 +19,29 @@
 
 namespace nmr {
 
-// PPO.process_env_step + the runner's bookkeeping for this wave's envs (k_ppo_record's arithmetic), in two halves so that its loads travel
-// with the next policy step's observation loads (one L2 round trip instead of two): `load` right after the step's stores have landed,
-// `file` whenever the values are needed. The time-out bootstrap needs the step's extras['time_outs'], a cross-wave quantity: k_rollout_tail adds it.
-struct RecordRegs { float rw, to, cr, cl; long long d; };
-__device__ __forceinline__ void record_load(RecordRegs& r, const RollArgs* Rs, const nm::Args<float>* As, int wave) {
-  const int lane = threadIdx.x, e = min(wave * 2 + (lane & 1), As->N - 1);
-  // (global-memory accessors of simt.h: the pointers come out of LDS copies of the arguments - plain dereferences would be flat_load)
-  r.rw = simt::gld1(As->rew, e); r.d = simt::gld1(As->done, e); r.to = simt::gld1(As->timeout_now, e);
-  r.cr = simt::gld1((const float*)Rs->cur_ret, e); r.cl = simt::gld1((const float*)Rs->cur_len, e);
-}
-__device__ __forceinline__ void record_file(const RecordRegs& r, const RollArgs* Rs, const nm::Args<float>* As, int t, int wave) {
-  const int lane = threadIdx.x, N = As->N, e = wave * 2 + lane;
-  if (lane < 2 && e < N) {
-    const size_t so = (size_t)t * N;
-    const bool d = r.d > 0;
-    float cr = r.cr + r.rw, cl = r.cl + 1.0f;
-    simt::gst1(Rs->s_rewards, so + e, r.rw);
-    simt::gst1(Rs->s_dones, so + e, (unsigned char)(d ? 1 : 0));
-    if (d) { atomicAdd(Rs->fin3, cr); atomicAdd(Rs->fin3 + 1, cl); atomicAdd(Rs->fin3 + 2, 1.0f); cr = 0.f; cl = 0.f; }
-    simt::gst1(Rs->cur_ret, (size_t)e, cr); simt::gst1(Rs->cur_len, (size_t)e, cl);
-    if (r.to != 0.f) simt::gst1(Rs->to_step, (size_t)e, t);
-  }
-}
-// The record of step t - 1 (t > 0) and PPO.act of step t for the wave's envs + the launch arguments of the env step that follows.
+// The record of step t - 1 (t > 0; the episode books of nm_env_loop.h) and PPO.act of step t for the wave's envs + the launch arguments
+// of the env step that follows.
 // Out of line: its registers (weight ring, accumulators) are not live across the physics, and the physics' are not live here.
 template <class S, int ACT>
 __device__ __noinline__ void policy_step(float* xb, const RollArgs* Rs, nm::Args<float>* As, int t, int wave, uint64_t noise0) {
   const int N = As->N;
   const size_t so = (size_t)t * N;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // state rows, observation, reward / done / time-out of the previous step: stored
-  RecordRegs rec;
-  if (t > 0) record_load(rec, Rs, As, wave);         // issued before the observation loads below: they return together
+  BookRegs rec;
+  if (t > 0) books_load(rec, Rs, As, wave);          // issued before the observation loads below: they return together
   ActOut o{Rs->s_actions + so * nm::kNU, Rs->s_logp + so, Rs->s_values + so, Rs->s_mu + so * nm::kNU, Rs->s_sigma + so * nm::kNU, t == 0 ? Rs->s_obs : nullptr};
   // the observation is the one this wave's previous step wrote into the storage row of step t
   policy_wave<S, ACT>(xb, Rs->wp, Rs->bp, Rs->stdv, t == 0 ? Rs->obs0 : Rs->s_obs + so * nm::kNOBS, N, wave, Rs->seed, (uint64_t)simt::gld1(Rs->iter_dev, 0) * 4096ull + (uint64_t)t, o);
-  if (t > 0) record_file(rec, Rs, As, t - 1, wave);
+  if (t > 0) books_file(rec, Rs, As, t - 1, wave);
   if (threadIdx.x == 0) {
     As->actions = o.actions;
     As->obs = t + 1 < Rs->K ? Rs->s_obs + (so + N) * nm::kNOBS : Rs->obs_final;     // the step files its observation where the next act reads it
-    As->stat_sum = Rs->st_sum + (size_t)t * nm::kNREW;
-    As->stat_cnt = Rs->st_cnt + (size_t)t * 4;
-    As->noise_step = noise0 + (uint64_t)t;
-    As->rec = Rs->rec_log ? Rs->rec_log + (size_t)t * kRecRow : nullptr;           // the state log's row of this step (env.py:261-272)
+    step_args(As, Rs, t, noise0);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the actions are in L2 before the load stage asks for them (other lanes of this wave)
-  nm::wave_sync();
-}
-// the record of the rollout's last step (no policy step follows it)
-__device__ __noinline__ void record_last(const RollArgs* Rs, const nm::Args<float>* As, int t, int wave) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  RecordRegs rec;
-  record_load(rec, Rs, As, wave);
-  record_file(rec, Rs, As, t, wave);
+  step_close();
 }
 // PPO.compute_returns' `last_values = actor_critic.evaluate(last_critic_obs)` for the wave's envs: the forward once more, on the observation the
-// last step left in obs_final (this wave's own stores: waited for by record_last), value head only - instead of nine framework launches
+// last step left in obs_final (this wave's own stores: waited for by books_last), value head only - instead of nine framework launches
 template <class S, int ACT>
 __device__ __noinline__ void value_last(float* xb, const RollArgs* Rs, const nm::Args<float>* As, int wave) {
   ActOut o{nullptr, nullptr, Rs->last_values, nullptr, nullptr, nullptr};
@@ -90,26 +56,9 @@ __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_rollout(const nm:
   __shared__ nm::Args<float> As;
   __shared__ RollArgs Rs;
   static_assert(sizeof(sh) >= kXFloats * sizeof(float), "the policy's activation rows alias the env images");
-  int wave = blockIdx.x;
-#ifndef NM_NO_XCD_MAP
-  {
-    const int nwx = (int)gridDim.x >> 3;
-    if (A.nxcd == 8 && wave < (nwx << 3)) wave = (wave & 7) * nwx + (wave >> 3);
-  }
-#endif
-  if (wave * 2 >= A.N) return;
-  As = A;
-  Rs = R;
-  __syncthreads();
-  {  // the model constants: L2 -> LDS, once for the whole rollout
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(Mp);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(&Ms);
-    constexpr int kWords = (int)(sizeof(nm::Model<float>) / 4);
-    for (int i = threadIdx.x; i < kWords; i += 64) dst[i] = src[i];
-    __syncthreads();
-  }
+  int wave;
+  if (!loop_begin(Mp, A, R, Ms, As, Rs, wave)) return;
   float* xb = reinterpret_cast<float*>(&sh);          // between two steps the env images hold nothing that is needed (env_load2 rewrites them)
-  if ((int)threadIdx.x < 2 && wave * 2 + (int)threadIdx.x < A.N) R.to_step[wave * 2 + threadIdx.x] = -1;
   const uint64_t noise0 = A.noise_step;
   const int K = R.K;
   if (R.wave_clock && threadIdx.x == 0) R.wave_clock[2 * wave] = __builtin_amdgcn_s_memtime();
@@ -117,7 +66,7 @@ __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_rollout(const nm:
     policy_step<S, ACT>(xb, &Rs, &As, t, wave, noise0);    // (+ the record of step t - 1)
     nm::wave_step<float, 2>(sh, Ms, As, wave);        // env.step: load, decimation x mj_step, epilogue - the code of k_env_step
   }
-  record_last(&Rs, &As, K - 1, wave);
+  books_last(&Rs, &As, K - 1, wave);
   if (Rs.last_values) value_last<S, ACT>(xb, &Rs, &As, wave);
   if (Rs.wave_clock && threadIdx.x == 0) Rs.wave_clock[2 * wave + 1] = __builtin_amdgcn_s_memtime();
 }

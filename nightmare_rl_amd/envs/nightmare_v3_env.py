@@ -236,6 +236,25 @@ class NightmareV3Env:
         return self.obs_buf, None, self.rew_buf, self.reset_buf, self.extras
 
     # ------------------------------------------------------------------ K steps per launch with the policy in the env's wave
+    def _kstep_launch_args(self, a, obs_field, params_flat, seed, iter_dev, ep):
+        """What policy_rollout and policy_play fill alike in their argument struct `a`: a stale time-out tensor is invalidated, the
+        observation pair is swapped (a.obs0_dev = the current observation, a.<obs_field> = the buffer the launch leaves its last one in)
+        and the env's own buffers and ep = (ep_idx, ep_acc) or None are bound. Returns (ep_idx, ep_acc)."""
+        if self.time_out_buf is not self._to_bound:
+            self._ck(self._L.nm_invalidate_time_outs(self._h, self._stream()))
+            self._to_bound = self.time_out_buf
+        a.params_flat_dev, a.seed, a.iter_dev = params_flat.data_ptr(), int(seed), iter_dev.data_ptr()
+        a.obs0_dev = self.obs_buf.data_ptr()
+        self._obs_idx ^= 1
+        self.obs_buf = self._obs_pair[self._obs_idx]           # the tensor handed out before the launch stays what it was
+        setattr(a, obs_field, self.obs_buf.data_ptr())
+        a.episode_length_dev = self._eplen().data_ptr()
+        a.rew_dev, a.done_dev = self.rew_buf.data_ptr(), self.reset_buf.data_ptr()
+        a.time_outs_dev, a.ep_stats_dev = self.time_out_buf.data_ptr(), self._ep_stats.data_ptr()
+        ep_idx, ep_acc = ep if ep is not None else (None, None)
+        a.ep_idx_dev, a.n_ep, a.ep_acc_dev = (ep_idx.data_ptr(), int(ep_idx.numel()), ep_acc.data_ptr()) if ep_idx is not None else (None, 0, None)
+        return ep_idx, ep_acc
+
     def policy_rollout(self, steps, params_flat, seed, iter_dev, storage, gamma, cur_ret, cur_len, fin, ep=None, last_values=None, activation="elu"):
         """`steps` iterations of rsl_rl's collection loop `act -> env.step -> process_env_step` (OnPolicyRunner.learn; reference
         train.py:54) as ONE launch (nm_rollout): starts from the current observation, files every transition into `storage` (a
@@ -249,27 +268,15 @@ class NightmareV3Env:
         T = int(steps)
         if storage.num_transitions_per_env < T or storage.num_envs != self.num_envs or storage.privileged_observations is not None:
             raise ValueError("policy_rollout: storage must hold `steps` rows of this env's transitions (no privileged observations)")
-        if self.time_out_buf is not self._to_bound:
-            self._ck(self._L.nm_invalidate_time_outs(self._h, self._stream()))
-            self._to_bound = self.time_out_buf
-        ep_idx, ep_acc = ep if ep is not None else (None, None)
         a = _lib.NmRolloutArgs()
-        a.steps, a.params_flat_dev, a.seed, a.iter_dev = T, params_flat.data_ptr(), int(seed), iter_dev.data_ptr()
-        a.obs0_dev = self.obs_buf.data_ptr()
-        self._obs_idx ^= 1
-        self.obs_buf = self._obs_pair[self._obs_idx]           # the tensor handed out before the rollout stays what it was
-        a.obs_final_dev = self.obs_buf.data_ptr()
-        a.episode_length_dev = self._eplen().data_ptr()
-        a.rew_dev, a.done_dev = self.rew_buf.data_ptr(), self.reset_buf.data_ptr()
-        a.time_outs_dev = self.time_out_buf.data_ptr()
+        a.steps = T
+        ep_idx, ep_acc = self._kstep_launch_args(a, "obs_final_dev", params_flat, seed, iter_dev, ep)
         a.bootstrap_time_outs = 1 if self.cfg.env.send_timeouts else 0
-        a.ep_stats_dev = self._ep_stats.data_ptr()
         a.s_obs, a.s_actions, a.s_logp, a.s_values = (storage.observations.data_ptr(), storage.actions.data_ptr(), storage.actions_log_prob.data_ptr(),
                                                        storage.values.data_ptr())
         a.s_mu, a.s_sigma, a.s_rewards, a.s_dones = storage.mu.data_ptr(), storage.sigma.data_ptr(), storage.rewards.data_ptr(), storage.dones.data_ptr()
         a.gamma = float(gamma)
         a.cur_ret, a.cur_len, a.fin3 = cur_ret.data_ptr(), cur_len.data_ptr(), fin.data_ptr()
-        a.ep_idx_dev, a.n_ep, a.ep_acc_dev = (ep_idx.data_ptr(), int(ep_idx.numel()), ep_acc.data_ptr()) if ep_idx is not None else (None, 0, None)
         a.last_values_dev = last_values.data_ptr() if last_values is not None else None
         self._ck(self._L.nm_rollout_ex(self._h, C.byref(a), _lib.activation_code(activation), self._stream()))
         self._keep_rollout = (params_flat, iter_dev, storage, cur_ret, cur_len, fin, ep_idx, ep_acc, last_values)
@@ -307,9 +314,6 @@ class NightmareV3Env:
                 raise ValueError(f"policy_play: stats[{k!r}] must be a contiguous float32 tensor of {3 if k == 'fin' else N} entries on the env's device")
         if (st.get("cur_ret") is None) != (st.get("cur_len") is None) or (st.get("ret_sum") is None) != (st.get("ret_cnt") is None):
             raise ValueError("policy_play: stats 'cur_ret' / 'cur_len' and 'ret_sum' / 'ret_cnt' come in pairs")
-        if self.time_out_buf is not self._to_bound:
-            self._ck(self._L.nm_invalidate_time_outs(self._h, self._stream()))
-            self._to_bound = self.time_out_buf
         if iter_dev is None:
             if getattr(self, "_play_iter", None) is None:
                 self._play_iter = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -318,19 +322,11 @@ class NightmareV3Env:
             self._play_actions = torch.zeros((N, self.num_actions), dtype=torch.float32, device=dev)
         if step0 is not None:
             self._play_step = int(step0)
-        ep_idx, ep_acc = st["ep"] if st.get("ep") is not None else (None, None)
         ptr = lambda t: None if t is None else t.data_ptr()
         a = _lib.NmPlayArgs()
-        a.deterministic, a.params_flat_dev, a.seed, a.iter_dev = int(bool(deterministic)), params_flat.data_ptr(), int(seed), iter_dev.data_ptr()
-        a.obs0_dev = self.obs_buf.data_ptr()
-        self._obs_idx ^= 1
-        self.obs_buf = self._obs_pair[self._obs_idx]           # the tensor handed out before the launch stays what it was
-        a.obs_dev, a.actions_dev = self.obs_buf.data_ptr(), self._play_actions.data_ptr()
-        a.episode_length_dev = self._eplen().data_ptr()
-        a.rew_dev, a.done_dev = self.rew_buf.data_ptr(), self.reset_buf.data_ptr()
-        a.time_outs_dev, a.ep_stats_dev = self.time_out_buf.data_ptr(), self._ep_stats.data_ptr()
+        a.deterministic, a.actions_dev = int(bool(deterministic)), self._play_actions.data_ptr()
+        self._kstep_launch_args(a, "obs_dev", params_flat, seed, iter_dev, st.get("ep"))
         a.cur_ret, a.cur_len, a.fin3, a.ret_sum, a.ret_cnt = (ptr(st.get(k)) for k in ("cur_ret", "cur_len", "fin", "ret_sum", "ret_cnt"))
-        a.ep_idx_dev, a.n_ep, a.ep_acc_dev = (ep_idx.data_ptr(), int(ep_idx.numel()), ep_acc.data_ptr()) if ep_idx is not None else (None, 0, None)
         self._keep_play = (params_flat, iter_dev, st)
         code = _lib.activation_code(activation)
         done = 0
