@@ -349,6 +349,27 @@ int nm_play_supported(const int32_t* actor_dims, int32_t n_layers, int32_t activ
 /* reference play.py:118-132, `steps` iterations per launch; stream-ordered, no host synchronisation */
 int nm_play(nm_env* env, const nm_play_args* args, int32_t activation, void* stream);
 
+/* ---- Stepping from an action tape: K x env.step(actions[t]) (reference envs/nightmare_v3_env.py:145-311, the joint-target hook at :186;
+ * the loop of custom_play.py:66-76 and of every caller that already has its actions) as ONE launch. No policy, no sampling: before step t the
+ * env's wavefront takes row t of the tape as its actions. fp32 env only. Afterwards every buffer, extra (time_outs, ep_stats), counter and
+ * episode length is what the last of `steps` nm_step calls with those actions would have left, bit for bit; sums that go through float
+ * atomics (fin3, ep_acc, ep_stats) agree to rounding, as for nm_play. `steps` may exceed the episode length. Observation noise and the
+ * state log (nm_set_state_record, nm_get_state_log, nm_get_state_log_dones) work as in nm_play. All pointers are device memory. */
+typedef struct {
+  int32_t steps;                      /* K in 1..4096 */
+  const float* actions_dev;           /* [K,N,18] the tape; row t is what nm_step would be given at step t */
+  float* obs_dev;                     /* [N,66] holds the last step's observation afterwards */
+  int64_t* episode_length_dev; float* rew_dev; int64_t* done_dev;   /* as nm_play_args */
+  float* time_outs_dev; float* ep_stats_dev;                         /* or NULL */
+  float *cur_ret, *cur_len, *fin3, *ret_sum, *ret_cnt;               /* or NULL, pairs as nm_play_args */
+  const int32_t* ep_idx_dev; int32_t n_ep; float* ep_acc_dev;
+  float* rec_obs_dev;                 /* [K,N,66] or NULL: the observation every step returned (obs_dev then receives a copy of the last row) */
+  float* rec_rew_dev;                 /* [K,N]    or NULL */
+  unsigned char* rec_done_dev;        /* [K,N]    or NULL */
+} nm_tape_args;
+/* reference custom_play.py:66-76 / envs/nightmare_v3_env.py:145-311, `steps` iterations per launch; stream-ordered, no host synchronisation */
+int nm_step_tape(nm_env* env, const nm_tape_args* args, void* stream);
+
 /* ---- scripted gait / IK engine (reference nikengine/engine.py; caller custom_play.py:49-76), batched over envs ----
  * One handle = num_envs independent EngineNode objects (engine.py:660-677), all in IdleState. */
 typedef struct nm_nik nm_nik;
@@ -369,6 +390,29 @@ int nm_nik_set_gait(nm_nik* h, const int32_t* ids_host, int32_t n, int32_t gait,
 int nm_nik_update(nm_nik* h, const double* lin_dev, const double* ang_dev, const unsigned char* awake_dev,
                   const unsigned char* walk_dev, double now_s, double engine_fps, float* angles_f32_dev,
                   double* angles_f64_dev, void* stream);
+/* K ticks of EngineNode.update in ONE launch (the engine is open loop: reference custom_play.py:66-76 feeds it commands and the clock,
+ * never the env), the FSM state in registers. Tick t runs at now = (double)(tick0 + t) * dt (one IEEE multiply) and writes row t of a
+ * [K,N,18] tape of set_hardware_pose's joint targets, bit for bit what K nm_nik_update calls with those clocks write; afterwards the
+ * handle's state (fsm, gait step, gait, t0, gait_step_state, pose, start, last) is theirs.
+ * Optional servo stage (servo_targets_dev and actions_dev both non-NULL, or both NULL): custom_play.py:72's rate limit and the inverse of
+ * the env's action -> joint target mapping (envs/nightmare_v3_env.py:152-156,183-188, hook :186) in fp32, every operation rounded on its
+ * own: q += clamp(float(goal) - q, -action_rate, +action_rate); a = (q + default_pos[j % 3]) * inv_action_scale. The mapping MULTIPLIES by
+ * inv_action_scale = float32(1.0 / action_scale), computed by the host (the library has no correctly rounded fp32 division). */
+typedef struct {
+  int32_t steps;                      /* K >= 1 */
+  const double *lin_dev, *ang_dev;    /* [N] commands, held for the K ticks */
+  const unsigned char *awake_dev, *walk_dev;   /* [N] or NULL = 1 */
+  int64_t tick0; double dt;           /* engine clock of tick t: now = (double)(tick0 + t) * dt  (one IEEE multiply) */
+  double engine_fps;
+  double* angles_f64_dev;             /* [K,N,18] or NULL: set_hardware_pose's joint targets per tick */
+  float*  angles_f32_dev;             /* [K,N,18] or NULL: the same, rounded once */
+  /* optional servo stage (all or none): custom_play.py:72 rate limit + the inverse of env.py:152-156,183-188 */
+  float*  servo_targets_dev;          /* [N,18] in/out: the rate limiter's memory */
+  float   action_rate;                /* q += clamp(float(goal) - q, -action_rate, +action_rate) */
+  float   default_pos[3]; float inv_action_scale;   /* a = (q + default_pos[j % 3]) * inv_action_scale */
+  float*  actions_dev;                /* [K,N,18]: what nm_step_tape reads */
+} nm_nik_tape_args;
+int nm_nik_tape(nm_nik* h, const nm_nik_tape_args* args, void* stream);
 /* FSM inspection for tests: HOST pose [N,18] (foot positions in the body frame), fsm id [N]
  * (0 idle 1 adjust-get-up 2 get-up 3 sit 4 adjust-sit 5 stand 6 walk), gait_step_state [N]. NULL = skip. Synchronous. */
 int nm_nik_get_state(nm_nik* h, double* pose_host, int32_t* fsm_host, double* gait_step_state_host);

@@ -26,7 +26,8 @@ EXPORTS = ["nm_default_config", "nm_reward_name", "nm_last_error", "nm_create", 
            "nm_policy_create_act", "nm_ppo_create_act", "nm_rollout_supported_act", "nm_rollout_ex", "nm_rollout_act_ex",
            "nm_set_observation_noise", "nm_set_noise_uniforms", "nm_set_state_record", "nm_get_state_record",
            "nm_get_state_log", "nm_get_state_log_dones", "nm_play", "nm_play_supported",
-           "nm_nik_create", "nm_nik_destroy", "nm_nik_reset", "nm_nik_set_gait", "nm_nik_update", "nm_nik_get_state"]
+           "nm_nik_create", "nm_nik_destroy", "nm_nik_reset", "nm_nik_set_gait", "nm_nik_update", "nm_nik_get_state",
+           "nm_step_tape", "nm_nik_tape"]
 
 
 class NmConfig(C.Structure):
@@ -55,6 +56,22 @@ class NmPlayArgs(C.Structure):        # nm_play_args of include/nightmare_hip.h
                 ("rew_dev", C.c_void_p), ("done_dev", C.c_void_p), ("time_outs_dev", C.c_void_p), ("ep_stats_dev", C.c_void_p),
                 ("cur_ret", C.c_void_p), ("cur_len", C.c_void_p), ("fin3", C.c_void_p), ("ret_sum", C.c_void_p), ("ret_cnt", C.c_void_p),
                 ("ep_idx_dev", C.c_void_p), ("n_ep", C.c_int32), ("ep_acc_dev", C.c_void_p)]
+
+
+class NmTapeArgs(C.Structure):        # nm_tape_args of include/nightmare_hip.h
+    _fields_ = [("steps", C.c_int32), ("actions_dev", C.c_void_p), ("obs_dev", C.c_void_p), ("episode_length_dev", C.c_void_p),
+                ("rew_dev", C.c_void_p), ("done_dev", C.c_void_p), ("time_outs_dev", C.c_void_p), ("ep_stats_dev", C.c_void_p),
+                ("cur_ret", C.c_void_p), ("cur_len", C.c_void_p), ("fin3", C.c_void_p), ("ret_sum", C.c_void_p), ("ret_cnt", C.c_void_p),
+                ("ep_idx_dev", C.c_void_p), ("n_ep", C.c_int32), ("ep_acc_dev", C.c_void_p),
+                ("rec_obs_dev", C.c_void_p), ("rec_rew_dev", C.c_void_p), ("rec_done_dev", C.c_void_p)]
+
+
+class NmNikTapeArgs(C.Structure):     # nm_nik_tape_args of include/nightmare_hip.h
+    _fields_ = [("steps", C.c_int32), ("lin_dev", C.c_void_p), ("ang_dev", C.c_void_p), ("awake_dev", C.c_void_p), ("walk_dev", C.c_void_p),
+                ("tick0", C.c_int64), ("dt", C.c_double), ("engine_fps", C.c_double),
+                ("angles_f64_dev", C.c_void_p), ("angles_f32_dev", C.c_void_p),
+                ("servo_targets_dev", C.c_void_p), ("action_rate", C.c_float), ("default_pos", C.c_float * 3), ("inv_action_scale", C.c_float),
+                ("actions_dev", C.c_void_p)]
 
 
 class NightmareHipError(RuntimeError):
@@ -144,6 +161,8 @@ def _bind(L, full):
         L.nm_get_state_log_dones.argtypes = [vp, C.c_int32, C.c_int32, vp]
         L.nm_play.argtypes = [vp, C.POINTER(NmPlayArgs), C.c_int32, vp]
         L.nm_play_supported.argtypes = [vp, C.c_int32, C.c_int32]
+    if hasattr(L, "nm_step_tape"):
+        L.nm_step_tape.argtypes = [vp, C.POINTER(NmTapeArgs), vp]
     if not full:        # the measurement build holds the env entry points only
         return L
     L.nm_gae.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_float, vp, vp]
@@ -185,6 +204,7 @@ def _bind(L, full):
     L.nm_nik_set_gait.argtypes = [vp, vp, C.c_int32, C.c_int32, vp]
     L.nm_nik_update.argtypes = [vp, vp, vp, vp, vp, C.c_double, C.c_double, vp, vp, vp]
     L.nm_nik_get_state.argtypes = [vp, vp, vp, vp]
+    L.nm_nik_tape.argtypes = [vp, C.POINTER(NmNikTapeArgs), vp]
     return L
 
 

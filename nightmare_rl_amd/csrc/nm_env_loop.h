@@ -1,7 +1,8 @@
-// nm_env_loop.h - what the K-step launches k_env_rollout (nm_rollout_kernels.h) and k_env_play (nm_play_kernels.h) share: the wave
-// index, the launch prologue, the episode books of the wave's two envs and the per-step update of the env step's launch arguments.
-// X below is the launch's own argument struct, RollArgs or PlayArgs (nm_rollout.h): the helpers read the fields both carry (cur_ret,
-// cur_len, fin3, to_step, st_sum, st_cnt, rec_log) and `if constexpr` on X decides what only one of them files.
+// nm_env_loop.h - what the K-step launches k_env_rollout (nm_rollout_kernels.h), k_env_play (nm_play_kernels.h) and k_env_tape
+// (nm_tape_kernels.h) share: the wave index, the launch prologue, the episode books of the wave's two envs and the per-step update of the
+// env step's launch arguments. X below is the launch's own argument struct, RollArgs, PlayArgs or TapeArgs (nm_rollout.h): the helpers read
+// the fields all carry (cur_ret, cur_len, fin3, to_step, st_sum, st_cnt, rec_log) and `if constexpr` on the struct's traits (kPlayBooks,
+// kStepRecord) decides what only some of them file.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -52,9 +53,9 @@ __device__ __forceinline__ bool loop_begin(const nm::Model<float>* __restrict__ 
 // `file` whenever the values are needed.
 //   rollout: the transition's reward and done go into the storage rows of step t. The time-out bootstrap needs the step's
 //            extras['time_outs'], a cross-wave quantity: k_rollout_tail adds it. An env times out at most once per launch.
-//   play   : nothing is stored; per env the sum and the number of the returns of the episodes it finished (the wave owns the env: plain
-//            load / add / store in step order, no atomics), the logged env's reset flag, and a later time-out of the same env overwrites
-//            the earlier one's step.
+//   play, tape: nothing is stored; per env the sum and the number of the returns of the episodes it finished (the wave owns the env:
+//            plain load / add / store in step order, no atomics), the logged env's reset flag, and a later time-out of the same env
+//            overwrites the earlier one's step. tape: the step's reward and reset flag also go into the caller's [K,N] record rows, if any.
 struct BookRegs { float rw, to, cr, cl, rs, rc; long long d; };
 template <class X>
 __device__ __forceinline__ void books_load(BookRegs& r, const X* Xs, const nm::Args<float>* As, int wave) {
@@ -62,11 +63,11 @@ __device__ __forceinline__ void books_load(BookRegs& r, const X* Xs, const nm::A
   // (global-memory accessors of simt.h: the pointers come out of LDS copies of the arguments - plain dereferences would be flat_load)
   r.rw = simt::gld1(As->rew, e); r.d = simt::gld1(As->done, e); r.to = simt::gld1(As->timeout_now, e);
   r.cr = simt::gld1((const float*)Xs->cur_ret, e); r.cl = simt::gld1((const float*)Xs->cur_len, e);
-  if constexpr (std::is_same_v<X, PlayArgs>) { r.rs = simt::gld1((const float*)Xs->ret_sum, e); r.rc = simt::gld1((const float*)Xs->ret_cnt, e); }
+  if constexpr (X::kPlayBooks) { r.rs = simt::gld1((const float*)Xs->ret_sum, e); r.rc = simt::gld1((const float*)Xs->ret_cnt, e); }
 }
 template <class X>
 __device__ __forceinline__ void books_file(const BookRegs& r, const X* Xs, const nm::Args<float>* As, int t, int wave) {
-  constexpr bool PLAY = std::is_same_v<X, PlayArgs>;
+  constexpr bool PLAY = X::kPlayBooks;
   const int lane = threadIdx.x, N = As->N, e = wave * 2 + lane;
   if (lane < 2 && e < N) {
     // (with the compiler this was written for, the place of this compare decides the order the scheduler gives the books' loads: each
@@ -80,6 +81,11 @@ __device__ __forceinline__ void books_file(const BookRegs& r, const X* Xs, const
       const size_t so = (size_t)t * N;
       simt::gst1(Xs->s_rewards, so + e, r.rw);
       simt::gst1(Xs->s_dones, so + e, (unsigned char)(d ? 1 : 0));
+    }
+    if constexpr (X::kStepRecord) {
+      const size_t so = (size_t)t * N;
+      if (Xs->rec_rew) simt::gst1(Xs->rec_rew, so + e, r.rw);
+      if (Xs->rec_dones) simt::gst1(Xs->rec_dones, so + e, (unsigned char)(d ? 1 : 0));
     }
     if (d) {
       atomicAdd(Xs->fin3, cr); atomicAdd(Xs->fin3 + 1, cl); atomicAdd(Xs->fin3 + 2, 1.0f);

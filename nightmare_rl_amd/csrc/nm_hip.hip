@@ -246,6 +246,7 @@ struct nm_env {
   virtual int set_record(int idx) = 0;
   virtual int get_record(double* qpos, double* qvel, int32_t* nbad) = 0;
   virtual int play(const nm_play_args* r, int act, hipStream_t s) = 0;
+  virtual int tape(const nm_tape_args* r, hipStream_t s) = 0;
   virtual int get_log(int first, int count, double* rows) = 0;
   virtual int get_log_dones(int first, int count, unsigned char* dones) = 0;
 };
@@ -680,6 +681,41 @@ template <class real> struct Env : nm_env {
       return 0;
     }
   }
+  // ---- K x step from an action tape (nm_step_tape; reference custom_play.py:66-76 around envs/nightmare_v3_env.py:145-311)
+  int tape(const nm_tape_args* r, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if constexpr (sizeof(real) == 8 || NM_ENVS_PER_WAVE != 2) {
+      return fail("nm_step_tape: the tape kernel runs on the fp32 kernel (two envs per wave) only");
+    } else {
+      if (!r) return fail("nm_step_tape: args is NULL");
+      const int K = r->steps;
+      if (kstep_check("nm_step_tape", K, " (longer tapes: consecutive launches)", r->n_ep, r->ep_idx_dev, r->ep_acc_dev, r->ep_stats_dev)) return 1;
+      if (!r->actions_dev || !r->obs_dev || !r->episode_length_dev || !r->rew_dev || !r->done_dev) return fail("nm_step_tape: NULL pointer");
+      if ((r->cur_ret == nullptr) != (r->cur_len == nullptr) || (r->ret_sum == nullptr) != (r->ret_cnt == nullptr))
+        return fail("nm_step_tape: cur_ret / cur_len and ret_sum / ret_cnt come in pairs");
+      real* log = nullptr;
+      if (roll_reserve(K) || log_rows(K, &log)) return 1;
+      if (!play_scratch && dalloc(&play_scratch, (size_t)N * 4 + 4)) return 1;
+      const nm::Args<real> a = kstep_args(K, r->actions_dev, r->episode_length_dev, r->obs_dev, r->rew_dev, r->done_dev, log);
+      nmr::TapeArgs T;
+      T.K = K; T.tape = r->actions_dev;
+      T.rec_obs = r->rec_obs_dev; T.rec_rew = r->rec_rew_dev; T.rec_dones = r->rec_done_dev;
+      const size_t n_ = (size_t)N;
+      T.cur_ret = r->cur_ret ? r->cur_ret : play_scratch; T.cur_len = r->cur_len ? r->cur_len : play_scratch + n_;
+      T.ret_sum = r->ret_sum ? r->ret_sum : play_scratch + 2 * n_; T.ret_cnt = r->ret_cnt ? r->ret_cnt : play_scratch + 3 * n_;
+      T.fin3 = r->fin3 ? r->fin3 : play_scratch + 4 * n_;
+      T.st_sum = roll_sum; T.st_cnt = roll_cnt; T.to_step = roll_to;
+      T.rec_log = log; T.rec_done = log ? rec_done : nullptr; T.rec_env = rec_env;
+      rec_done_valid = log != nullptr;
+      nmr::TailArgs ta{N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, -1.0f, nullptr, nullptr,
+                       r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
+      if (nmr::launch_tape(M_dev, a, T, ta, s)) return fail("nm_step_tape: launch failed");
+      // with an observation record every step filed its observation in its row: the env's own buffer receives the last one
+      if (r->rec_obs_dev)
+        HIPCHK(hipMemcpyAsync(r->obs_dev, r->rec_obs_dev + (size_t)(K - 1) * n_ * nm::kNOBS, n_ * nm::kNOBS * sizeof(float), hipMemcpyDeviceToDevice, s));
+      return 0;
+    }
+  }
   void set_dbg(void* p) override { A.dbg = (real*)p; }
   void set_ret_acc(float* p) override { A.ret_acc = p; }
   int invalidate_time_outs(hipStream_t s) override {
@@ -843,6 +879,11 @@ int nm_play(nm_env* env, const nm_play_args* args, int32_t activation, void* str
   NEED(env);
   if (!nmact::valid(activation)) return bad_activation("nm_play", activation);
   return env->play(args, activation, (hipStream_t)stream);
+}
+int nm_step_tape(nm_env* env, const nm_tape_args* args, void* stream) {
+  if (!env) return fail("nm_step_tape: env is NULL");
+  if (!args) return fail("nm_step_tape: args is NULL");
+  return env->tape(args, (hipStream_t)stream);
 }
 #ifdef NM_STAMPS
 int nm_read_stamps(unsigned long long* out16, int reset) {   // measurement builds only

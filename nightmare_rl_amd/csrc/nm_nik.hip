@@ -3,7 +3,7 @@
 //
 // 16 lanes own one env (4 envs per wavefront): lanes 0..14 are the 15 unordered leg pairs of the keep-out line search
 // (the reference scans the 30 ordered pairs, the distance is symmetric), lanes 0..5 are the legs for the pose update
-// and the IK. Everything is f64 like the reference's numpy: the search compares a distance with a threshold and a
+// and the IK. One tick is ONE device function (nik_tick) that k_nik_update calls once and k_nik_tape K times with the state in registers. Everything is f64 like the reference's numpy: the search compares a distance with a threshold and a
 // rounding flip there moves a foot target by a tenth of a step. State per env lives in HBM as rows of 18 doubles.
 #include <hip/hip_runtime.h>
 
@@ -115,21 +115,36 @@ __device__ inline void relative_ik(double x, double y, double z, double* out) {
   out[0] = alpha; out[1] = beta - kPi / 2; out[2] = gamma - 1.5 * kPi;
 }
 
-__global__ void __launch_bounds__(64) k_nik_update(NikArgs a) {
-  const int gid = blockIdx.x * 4 + (threadIdx.x >> 4), s = threadIdx.x & 15;
-  const bool live = gid < a.N;
-  const int e = live ? gid : a.N - 1;                     // idle groups shadow the last env and store nothing
+// One engine's state between two ticks, as a lane of its 16-lane group holds it: the scalars are the same in all 16 lanes, P / S / L are
+// the rows (RobotState.pose = the FSM's previous output, StandState's start pose, WalkState's pose at the last step boundary) of THIS
+// lane's leg (lanes 6..15 mirror leg 5 and store nothing).
+struct NikLane {
+  int fsm, step, gcur;
+  double t0, gss;
+  double P[3], S[3], L[3];
+};
+// what a tick reads besides the state: EngineNode.update's arguments, the clock, config.ENGINE_FPS and state.cmd.gait
+struct NikIn {
+  double lin, ang, now, fps;
+  bool awake, walk;
+  int gcmd;
+};
+
+// EngineNode.update (engine.py:700-715) for one env, once: the FSM state's tick, the state entry, set_hardware_pose. s: the lane within the
+// env's group; pix..pjy: the xy poses (before this tick) of the two legs this lane probes in the keep-out line search; q: the three joint
+// targets of this lane's leg. Every lane of the wavefront calls it (the 16-lane exchanges inside stay convergent).
+// OUT OF LINE on purpose: k_nik_update and k_nik_tape call the very same machine code, so K ticks of the tape are K single ticks bit for
+// bit - inlined, the two call sites could contract their multiply-adds differently.
+__device__ __noinline__ void nik_tick(NikLane& st, const NikIn& in, int s, double pix, double piy, double pjx, double pjy, double* q) {
   const int leg = s < 6 ? s : 5;
-  const bool isleg = live && s < 6;
-  const int fsm = a.fsm[e], step = a.step[e];
-  const int gcur = a.gait_cur[e], gcmd = a.gait_cmd[e];
+  const int fsm = st.fsm, step = st.step;
+  const int gcur = st.gcur, gcmd = in.gcmd;
   const int kNGait = c_gait_len[gcur];
   const unsigned swingm = c_gait_mask[gcur][step];
-  const double t0 = a.t0[e], gss = a.gss[e];
-  const double lin = a.lin[e], ang = a.ang[e];
-  const bool awake = a.awake ? a.awake[e] != 0 : true, walk = a.walk ? a.walk[e] != 0 : true;
-  const double* prow = a.pose + (size_t)e * 18;
-  const double P[3] = {prow[3 * leg], prow[3 * leg + 1], prow[3 * leg + 2]};   // the FSM's previous output
+  const double t0 = st.t0, gss = st.gss;
+  const double lin = in.lin, ang = in.ang;
+  const bool awake = in.awake, walk = in.walk;
+  const double P[3] = {st.P[0], st.P[1], st.P[2]};          // the FSM's previous output
   const double D[3] = {c_default_xy[leg][0], c_default_xy[leg][1], -kStandH};
   const double S[3] = {D[0], D[1], kSitH};
   double out[3] = {P[0], P[1], P[2]};
@@ -137,7 +152,7 @@ __global__ void __launch_bounds__(64) k_nik_update(NikArgs a) {
   double ngss = gss;
   int nstep = step, ngait = gcur;
   bool set_last = false;
-  const double adv_t = a.now - t0;
+  const double adv_t = in.now - t0;
   if (fsm == IDLE) {                                       // :414-431 (RobotState.pose is the default pose, never updated)
     for (int k = 0; k < 3; k++) out[k] = D[k];
     if (awake) nfsm = ADJ_GETUP;
@@ -168,8 +183,7 @@ __global__ void __launch_bounds__(64) k_nik_update(NikArgs a) {
     }
   } else if (fsm == STAND) {                               // :523-540 body commands are zero through EngineNode.update
     if (awake && !walk) {
-      const double* srow = a.start + (size_t)e * 18;
-      for (int k = 0; k < 3; k++) out[k] = srow[3 * leg + k];
+      for (int k = 0; k < 3; k++) out[k] = st.S[k];
     } else {
       nfsm = awake ? WALK : ADJ_SIT;
     }
@@ -183,7 +197,6 @@ __global__ void __launch_bounds__(64) k_nik_update(NikArgs a) {
   // only by walking envs.
   {
     const int pi = c_pair[s][0], pj = c_pair[s][1];
-    const double pix = prow[3 * pi], piy = prow[3 * pi + 1], pjx = prow[3 * pj], pjy = prow[3 * pj + 1];
     const bool wi = (swingm >> pi) & 1, wj = (swingm >> pj) & 1;
     double red = 1.0;
     bool done = !walking;
@@ -204,49 +217,140 @@ __global__ void __launch_bounds__(64) k_nik_update(NikArgs a) {
     if (walking) {
       const bool swing = (swingm >> leg) & 1;
       if (!swing) {
-        const double m = red * (1.0 / a.fps) * 2 * kNGait;
+        const double m = red * (1.0 / in.fps) * 2 * kNGait;
         out[0] = P[0]; out[1] = P[1] - lin * m; out[2] = P[2];
         rotz(out[0], out[1], -ang * m);
       } else {
         const double f = red * kStepTime;
         double T[3] = {D[0], D[1] + lin * f, D[2]};
         rotz(T[0], T[1], ang * f);
-        const double* lrow = a.last + (size_t)e * 18;
         const double t = gss, u = 1 - gss;
         for (int k = 0; k < 3; k++) {                      // modules/bezier.py:49-66 (de Casteljau on 4 points)
           const double up = k == 2 ? kStepHeight : 0.0;
-          const double b0 = lrow[3 * leg + k], b1 = b0 + up, b2 = T[k] + up, b3 = T[k];
+          const double b0 = st.L[k], b1 = b0 + up, b2 = T[k] + up, b3 = T[k];
           const double c0 = u * b0 + t * b1, c1 = u * b1 + t * b2, c2 = u * b2 + t * b3;
           const double d0 = u * c0 + t * c1, d1 = u * c1 + t * c2;
           out[k] = u * d0 + t * d1;
         }
       }
-      ngss = gss + kNGait / (kStepTime * a.fps);
+      ngss = gss + kNGait / (kStepTime * in.fps);
       if (ngss > 1) { ngait = gcmd; ngss = 0; nstep = (step + 1) % c_gait_len[ngait]; set_last = true; }   // engine.py:626-629
     }
   }
   // ---- state entry (constructors of the FSM states)
   if (nfsm != fsm) {
-    if (isleg && nfsm == STAND) { double* srow = a.start + (size_t)e * 18; for (int k = 0; k < 3; k++) srow[3 * leg + k] = P[k]; }
+    if (nfsm == STAND) for (int k = 0; k < 3; k++) st.S[k] = P[k];
     if (nfsm == WALK) { ngss = 0; nstep = 0; ngait = gcmd; set_last = true; }   // WalkState.__init__ (:539-543)
-    if (live && s == 0) { a.fsm[e] = nfsm; a.t0[e] = a.now; }
+    st.fsm = nfsm; st.t0 = in.now;
   }
-  if (isleg && set_last) { double* lrow = a.last + (size_t)e * 18; for (int k = 0; k < 3; k++) lrow[3 * leg + k] = P[k]; }
-  if (live && s == 0) { a.gss[e] = ngss; a.step[e] = nstep; a.gait_cur[e] = ngait; }
+  if (set_last) for (int k = 0; k < 3; k++) st.L[k] = P[k];
+  st.gss = ngss; st.step = nstep; st.gcur = ngait;
+  for (int k = 0; k < 3; k++) st.P[k] = out[k];
+  // EngineNode.set_hardware_pose (:700-708)
+  const double sgn = leg < 3 ? 1.0 : -1.0;
+  relative_ik((out[0] - c_offset_xy[leg][0]) * sgn, (out[1] - c_offset_xy[leg][1]) * sgn, out[2], q);
+  q[0] += c_servo[leg];
+  for (int k = 0; k < 3; k++) q[k] = q[k] + c_urdf[k];
+}
+
+// the state of env e <-> the lane (leg: the lane's leg). The scalars are stored by the group's lane 0, the rows by the leg lanes.
+__device__ inline void nik_load(const NikArgs& a, int e, int leg, NikLane& st, NikIn& in) {
+  st.fsm = a.fsm[e]; st.step = a.step[e]; st.gcur = a.gait_cur[e];
+  st.t0 = a.t0[e]; st.gss = a.gss[e];
+  const size_t r = (size_t)e * 18 + 3 * leg;
+  for (int k = 0; k < 3; k++) { st.P[k] = a.pose[r + k]; st.S[k] = a.start[r + k]; st.L[k] = a.last[r + k]; }
+  in.lin = a.lin[e]; in.ang = a.ang[e];
+  in.awake = a.awake ? a.awake[e] != 0 : true; in.walk = a.walk ? a.walk[e] != 0 : true;
+  in.gcmd = a.gait_cmd[e];
+  in.now = a.now; in.fps = a.fps;
+}
+__device__ inline void nik_store(const NikArgs& a, int e, int leg, bool lane0, bool isleg, const NikLane& st) {
+  if (lane0) { a.fsm[e] = st.fsm; a.t0[e] = st.t0; a.gss[e] = st.gss; a.step[e] = st.step; a.gait_cur[e] = st.gcur; }
   if (isleg) {
-    double* wrow = a.pose + (size_t)e * 18;
-    for (int k = 0; k < 3; k++) wrow[3 * leg + k] = out[k];
-    // EngineNode.set_hardware_pose (:700-708)
-    const double sgn = leg < 3 ? 1.0 : -1.0;
-    double q[3];
-    relative_ik((out[0] - c_offset_xy[leg][0]) * sgn, (out[1] - c_offset_xy[leg][1]) * sgn, out[2], q);
-    q[0] += c_servo[leg];
+    const size_t r = (size_t)e * 18 + 3 * leg;
+    for (int k = 0; k < 3; k++) { a.pose[r + k] = st.P[k]; a.start[r + k] = st.S[k]; a.last[r + k] = st.L[k]; }
+  }
+}
+
+__global__ void __launch_bounds__(64) k_nik_update(NikArgs a) {
+  const int gid = blockIdx.x * 4 + (threadIdx.x >> 4), s = threadIdx.x & 15;
+  const bool live = gid < a.N;
+  const int e = live ? gid : a.N - 1;                     // idle groups shadow the last env and store nothing
+  const int leg = s < 6 ? s : 5;
+  const bool isleg = live && s < 6;
+  NikLane st;
+  NikIn in;
+  nik_load(a, e, leg, st, in);
+  const double* prow = a.pose + (size_t)e * 18;
+  const int pi = c_pair[s][0], pj = c_pair[s][1];
+  double q[3];
+  nik_tick(st, in, s, prow[3 * pi], prow[3 * pi + 1], prow[3 * pj], prow[3 * pj + 1], q);
+  nik_store(a, e, leg, live && s == 0, isleg, st);
+  if (isleg) {
     for (int k = 0; k < 3; k++) {
-      const double v = q[k] + c_urdf[k];
-      if (a.out64) a.out64[(size_t)e * 18 + 3 * leg + k] = v;
-      if (a.out32) a.out32[(size_t)e * 18 + 3 * leg + k] = (float)v;
+      if (a.out64) a.out64[(size_t)e * 18 + 3 * leg + k] = q[k];
+      if (a.out32) a.out32[(size_t)e * 18 + 3 * leg + k] = (float)q[k];
     }
   }
+}
+
+// ---- K ticks per launch (nm_nik_tape)
+struct NikTape {
+  int K;
+  long long tick0; double dt;
+  double* out64; float* out32;          // [K,N,18] or null
+  float* servo; float* actions;         // [N,18] in/out, [K,N,18]: the servo stage, both or neither
+  float rate, dp[3], inv_scale;
+};
+// custom_play.py:72 `targets += clip(goal - targets, -rate, rate)` and the inverse of env.py:152-156,183-188 `(q + default_pos) / action_scale`
+// (as a multiplication by the host's float32(1 / action_scale)), fp32, every operation rounded on its own
+__device__ inline float servo_step(float goal, float& q, float rate, float dp, float inv) {
+#pragma clang fp contract(off)      // HIP's __fadd_rn / __fmul_rn are plain operators: without this the last pair becomes one fma
+  const float d = __fsub_rn(goal, q);
+  q = __fadd_rn(q, fminf(fmaxf(d, -rate), rate));
+  const float qd = __fadd_rn(q, dp);
+  return __fmul_rn(qd, inv);
+}
+// the 18 values of an env's row, three per leg lane, stored coalesced: lane s of the group writes elements s and s + 16
+template <class T> __device__ inline void row_store(T* row, const T* v, int s, bool live) {
+#pragma unroll
+  for (int part = 0; part < 2; part++) {
+    const int j = s + 16 * part, jj = j < 18 ? j : 17, src = jj / 3, kk = jj % 3;
+    const T x0 = __shfl(v[0], src, 16), x1 = __shfl(v[1], src, 16), x2 = __shfl(v[2], src, 16);
+    if (live && j < 18) row[j] = kk == 0 ? x0 : kk == 1 ? x1 : x2;
+  }
+}
+// K x k_nik_update with the state in registers: loaded once, stored once. Between two ticks the lanes of a group hand each other the
+// poses the line search probes by lane shuffles (leg l lives in lane l); tick t runs at now = (tick0 + t) * dt and writes row t.
+__global__ void __launch_bounds__(64) k_nik_tape(NikArgs a, NikTape tp) {
+  const int gid = blockIdx.x * 4 + (threadIdx.x >> 4), s = threadIdx.x & 15;
+  const bool live = gid < a.N;
+  const int e = live ? gid : a.N - 1;
+  const int leg = s < 6 ? s : 5;
+  const bool isleg = live && s < 6;
+  NikLane st;
+  NikIn in;
+  nik_load(a, e, leg, st, in);
+  const int pi = c_pair[s][0], pj = c_pair[s][1];
+  float sq[3] = {0.f, 0.f, 0.f};
+  if (tp.servo) for (int k = 0; k < 3; k++) sq[k] = tp.servo[(size_t)e * 18 + 3 * leg + k];
+  for (int t = 0; t < tp.K; t++) {
+    in.now = (double)(tp.tick0 + t) * tp.dt;
+    const double pix = __shfl(st.P[0], pi, 16), piy = __shfl(st.P[1], pi, 16), pjx = __shfl(st.P[0], pj, 16), pjy = __shfl(st.P[1], pj, 16);
+    double q[3];
+    nik_tick(st, in, s, pix, piy, pjx, pjy, q);
+    const size_t row = ((size_t)t * a.N + e) * 18;
+    if (tp.out64) row_store(tp.out64 + row, q, s, live);
+    float q32[3] = {(float)q[0], (float)q[1], (float)q[2]};
+    if (tp.out32) row_store(tp.out32 + row, q32, s, live);
+    if (tp.servo) {
+      float act[3];
+      for (int k = 0; k < 3; k++) act[k] = servo_step(q32[k], sq[k], tp.rate, tp.dp[k], tp.inv_scale);
+      row_store(tp.actions + row, act, s, live);
+    }
+  }
+  nik_store(a, e, leg, live && s == 0, isleg, st);
+  if (tp.servo && isleg) for (int k = 0; k < 3; k++) tp.servo[(size_t)e * 18 + 3 * leg + k] = sq[k];
 }
 
 __global__ void k_nik_set_gait(NikArgs a, const int* ids, int n, int gait) {
@@ -345,6 +449,30 @@ extern "C" int nm_nik_update(nm_nik* h, const double* lin_dev, const double* ang
   a.out32 = angles_f32_dev; a.out64 = angles_f64_dev;
   hipLaunchKernelGGL(k_nik_update, dim3((h->N + 3) / 4), dim3(64), 0, (hipStream_t)stream, a);
   NIK_CHECK(hipGetLastError(), "nm_nik_update: launch failed");
+  return 0;
+}
+
+// K ticks of nm_nik_update in one launch (reference custom_play.py:66-76: the engine reads commands and the clock, never the env)
+extern "C" int nm_nik_tape(nm_nik* h, const nm_nik_tape_args* r, void* stream) {
+  if (!h) return nm_policy_set_error("nm_nik_tape: null handle");
+  if (!r) return nm_policy_set_error("nm_nik_tape: args is NULL");
+  if (r->steps < 1) return nm_policy_set_error("nm_nik_tape: steps must be at least 1");
+  if (!r->lin_dev || !r->ang_dev) return nm_policy_set_error("nm_nik_tape: lin_dev / ang_dev are NULL");
+  if (!(r->engine_fps > 0)) return nm_policy_set_error("nm_nik_tape: engine_fps must be positive");
+  if ((r->servo_targets_dev == nullptr) != (r->actions_dev == nullptr))
+    return nm_policy_set_error("nm_nik_tape: the servo stage needs servo_targets_dev and actions_dev, both or neither");
+  NIK_CHECK(hipSetDevice(h->device), "nm_nik_tape: hipSetDevice failed");
+  NikArgs a = h->a;
+  a.lin = r->lin_dev; a.ang = r->ang_dev; a.awake = r->awake_dev; a.walk = r->walk_dev; a.now = 0; a.fps = r->engine_fps;
+  a.out32 = nullptr; a.out64 = nullptr;
+  NikTape tp;
+  tp.K = r->steps; tp.tick0 = r->tick0; tp.dt = r->dt;
+  tp.out64 = r->angles_f64_dev; tp.out32 = r->angles_f32_dev;
+  tp.servo = r->servo_targets_dev; tp.actions = r->actions_dev;
+  tp.rate = r->action_rate; tp.inv_scale = r->inv_action_scale;
+  for (int k = 0; k < 3; k++) tp.dp[k] = r->default_pos[k];
+  hipLaunchKernelGGL(k_nik_tape, dim3((h->N + 3) / 4), dim3(64), 0, (hipStream_t)stream, a, tp);
+  NIK_CHECK(hipGetLastError(), "nm_nik_tape: launch failed");
   return 0;
 }
 

@@ -254,6 +254,9 @@ struct RollArgs {
   float* last_values;                                          // [N] or null: the critic's value of the observation after the last step (PPO.compute_returns)
   unsigned long long* wave_clock;                              // measurement (nm_set_debug_buffer on): [waves][2] s_memtime at the wave's start / end, else null
   float* rec_log;                                              // [K,kRecRow] or null: the state log (Args::rec of step t = row t; env.py:261-272)
+  // what the episode books of nm_env_loop.h file for this launch: kPlayBooks = per-env return sums + the logged env's reset flag (else the
+  // rollout's storage rows), kStepRecord = optional [K,N] reward / done rows
+  static constexpr bool kPlayBooks = false, kStepRecord = false;
 };
 constexpr int kRecRow = 50;            // qpos 25 | qvel 24 | bad-state resets of the step (what wave_step files through Args::rec)
 // k_env_play (nm_play_kernels.h): K x [policy on the observation the previous step left, env.step], nothing collected - reference play.py:118-132
@@ -269,6 +272,22 @@ struct PlayArgs {
   int* to_step;                                                // [N]: the LATEST step at which the env timed out in this launch, or -1
   float* rec_log;                                              // [K,kRecRow] or null
   unsigned char* rec_done; int rec_env;                        // [K] or null: the logged env's reset flag per step (the log's reader dumps a file there)
+  static constexpr bool kPlayBooks = true, kStepRecord = false;
+};
+// k_env_tape (nm_tape_kernels.h): K x env.step with the actions of step t read from row t of a [K,N,18] tape - no policy, no sampling
+// (reference custom_play.py:66-76 around envs/nightmare_v3_env.py:145-311). The books are play's.
+struct TapeArgs {
+  int K;
+  const float* tape;                                           // [K,N,18]: row t = the actions of step t
+  float* rec_obs;                                              // [K,N,66] or null: step t files its observation in row t (null: every step in Args::obs)
+  float* rec_rew; unsigned char* rec_dones;                    // [K,N], [K,N] or null: the reward / reset flag every step returned
+  float *cur_ret, *cur_len, *fin3;
+  float *ret_sum, *ret_cnt;
+  float* st_sum; int* st_cnt;
+  int* to_step;
+  float* rec_log;
+  unsigned char* rec_done; int rec_env;
+  static constexpr bool kPlayBooks = true, kStepRecord = true;
 };
 struct TailArgs {
   int N, K;
@@ -314,5 +333,8 @@ int launch_act(const float* wp, const float* bp, const float* stdv, const float*
 int launch_rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, const TailArgs& t, int act, hipStream_t s);
 // k_env_play + the rollout's closing launches (k_rollout_tail without the time-out bootstrap, k_rollout_clear)
 int launch_play(const nm::Model<float>* M_dev, const nm::Args<float>& a, const PlayArgs& P, const TailArgs& t, int act, hipStream_t s);
+// the launch of k_env_tape (nm_tape.hip), and launch_tape = that + the same closing launches as launch_play
+int tape_kernel(const nm::Model<float>* M_dev, const nm::Args<float>& a, const TapeArgs& T, hipStream_t s);
+int launch_tape(const nm::Model<float>* M_dev, const nm::Args<float>& a, const TapeArgs& T, const TailArgs& t, hipStream_t s);
 
 }  // namespace nmr

@@ -118,5 +118,10 @@ int launch_play(const nm::Model<float>* M_dev, const nm::Args<float>& a, const P
   if (with_act(act, [&](auto ACT) { return PlayKernels<decltype(ACT)::value>::play(M_dev, a, P, s); })) return 1;
   return launch_tail(t, s);
 }
+// nm_step_tape: k_env_tape (nm_tape.hip) and the closing launches of nm_play - the books are the same
+int launch_tape(const nm::Model<float>* M_dev, const nm::Args<float>& a, const TapeArgs& T, const TailArgs& t, hipStream_t s) {
+  if (tape_kernel(M_dev, a, T, s)) return 1;
+  return launch_tail(t, s);
+}
 
 }  // namespace nmr

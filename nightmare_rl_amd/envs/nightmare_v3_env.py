@@ -344,6 +344,79 @@ class NightmareV3Env:
             self._fill_extras()
         return self.obs_buf
 
+    # ------------------------------------------------------------------ K steps per launch from an action tape
+    def step_tape(self, actions, *, record=None, stats=None):
+        """K x step(actions[t]) (reference custom_play.py:66-76 around :145-311; any caller that already has its actions) in launches of up to
+        4096 steps each (nm_step_tape): no policy, no sampling, the env's wavefront reads row t of the tape before step t. Returns the last
+        observation and leaves obs_buf / rew_buf / reset_buf / extras / episode_length_buf / common_step_counter as the K calls of step()
+        would, bit for bit. K may exceed the episode length.
+        actions: contiguous float32 [K, num_envs, 18] on the env's device (it must stay alive until the launch has run).
+        record (all optional, tensors owned by the caller, contiguous, on the env's device): 'obs' float32 [K,N,66], 'rew' float32 [K,N],
+        'done' uint8 [K,N] - what every step returned. stats: as policy_play's. With cfg.viewer.record_states every launch's log rows are
+        read after it has been enqueued (one host synchronisation per launch)."""
+        N, dev = self.num_envs, self.device
+        if not torch.is_tensor(actions) or actions.dim() != 3 or actions.shape[1] != N or actions.shape[2] != self.num_actions:
+            raise ValueError(f"step_tape: actions must be a [K, {N}, {self.num_actions}] tensor, got {tuple(getattr(actions, 'shape', ()))}")
+        if actions.dtype != torch.float32 or actions.device != dev or not actions.is_contiguous():
+            raise ValueError("step_tape: actions must be a contiguous float32 tensor on the env's device")
+        T = int(actions.shape[0])
+        if T < 1:
+            raise ValueError("step_tape: the tape must hold at least 1 step")
+        rec = dict(record or {})
+        unknown = set(rec) - {"obs", "rew", "done"}
+        if unknown:
+            raise ValueError(f"step_tape: unknown record {sorted(unknown)}")
+        shapes = {"obs": ((T, N, self.num_obs), torch.float32), "rew": ((T, N), torch.float32), "done": ((T, N), torch.uint8)}
+        for k, t in rec.items():
+            shp, dt = shapes[k]
+            if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != shp or t.dtype != dt or not t.is_contiguous() or t.device != dev):
+                raise ValueError(f"step_tape: record[{k!r}] must be a contiguous {str(dt).split('.')[-1]} tensor of shape {shp} on the env's device")
+        st = dict(stats or {})
+        unknown = set(st) - {"cur_ret", "cur_len", "fin", "ret_sum", "ret_cnt", "ep"}
+        if unknown:
+            raise ValueError(f"step_tape: unknown stats {sorted(unknown)}")
+        for k in ("cur_ret", "cur_len", "ret_sum", "ret_cnt", "fin"):
+            t = st.get(k)
+            if t is not None and (t.dtype != torch.float32 or t.numel() != (3 if k == "fin" else N) or not t.is_contiguous() or t.device != dev):
+                raise ValueError(f"step_tape: stats[{k!r}] must be a contiguous float32 tensor of {3 if k == 'fin' else N} entries on the env's device")
+        if (st.get("cur_ret") is None) != (st.get("cur_len") is None) or (st.get("ret_sum") is None) != (st.get("ret_cnt") is None):
+            raise ValueError("step_tape: stats 'cur_ret' / 'cur_len' and 'ret_sum' / 'ret_cnt' come in pairs")
+        if self.time_out_buf is not self._to_bound:
+            self._ck(self._L.nm_invalidate_time_outs(self._h, self._stream()))
+            self._to_bound = self.time_out_buf
+        ptr = lambda t: None if t is None else t.data_ptr()
+        a = _lib.NmTapeArgs()
+        self._obs_idx ^= 1
+        self.obs_buf = self._obs_pair[self._obs_idx]           # the tensor handed out before the launch stays what it was
+        a.obs_dev = self.obs_buf.data_ptr()
+        a.episode_length_dev = self._eplen().data_ptr()
+        a.rew_dev, a.done_dev = self.rew_buf.data_ptr(), self.reset_buf.data_ptr()
+        a.time_outs_dev, a.ep_stats_dev = self.time_out_buf.data_ptr(), self._ep_stats.data_ptr()
+        ep_idx, ep_acc = st["ep"] if st.get("ep") is not None else (None, None)
+        a.ep_idx_dev, a.n_ep, a.ep_acc_dev = (ep_idx.data_ptr(), int(ep_idx.numel()), ep_acc.data_ptr()) if ep_idx is not None else (None, 0, None)
+        a.cur_ret, a.cur_len, a.fin3, a.ret_sum, a.ret_cnt = (ptr(st.get(k)) for k in ("cur_ret", "cur_len", "fin", "ret_sum", "ret_cnt"))
+        self._keep_tape = (actions, rec, st)
+        done = 0
+        while done < T:
+            k = min(T - done, 4096)
+            a.steps, a.actions_dev = k, actions[done].data_ptr()
+            a.rec_obs_dev, a.rec_rew_dev, a.rec_done_dev = (ptr(rec[n][done]) if rec.get(n) is not None else None for n in ("obs", "rew", "done"))
+            self._ck(self._L.nm_step_tape(self._h, C.byref(a), self._stream()))
+            self.common_step_counter += k
+            done += k
+            if self.state_log is not None:
+                self._record_launch(k)
+        if "episode" not in self.extras:
+            self._fill_extras()
+        return self.obs_buf
+
+    def joint_target_servo(self, action_rate):
+        """The `servo` argument of nikengine.EngineNode.tape for this env: custom_play.py:72's rate limit (`action_rate` rad per step) followed
+        by the inverse of step()'s action -> joint target mapping (actions_from_joint_targets, as a multiplication by float32(1 /
+        action_scale)), with a zeroed [N,18] float32 `targets` tensor - the rate limiter's memory, updated by every tape."""
+        return dict(targets=torch.zeros((self.num_envs, 18), dtype=torch.float32, device=self.device), action_rate=float(action_rate),
+                    default_pos=[float(x) for x in self.default_dof_pos[:3]], action_scale=float(self.cfg.control.action_scale))
+
     def set_fixed_commands(self, cmd):
         """Hold the velocity command (vx, yaw) for ALL envs across the periodic resample (:235) and the resample at a reset (:356):
         the uniforms that map onto it are injected at every resample (nm_set_command_uniforms) and `commands` is written once, now.

@@ -92,6 +92,47 @@ class EngineNode:
             return self.angles[0].double().cpu().numpy()
         return self.angles
 
+    def tape(self, lin_speed, ang_speed, state="awake", mode="walk", *, steps, tick0, dt, out=None, servo=None):
+        """`steps` ticks of `update` in ONE launch (nm_nik_tape): the commands and flags are held, tick t runs at the engine clock
+        (tick0 + t) * dt (one float64 multiply) and `config.ENGINE_FPS` is read now. Returns the [steps, N, 18] joint targets - bit for bit
+        what `steps` calls of update(time_s=(tick0 + t) * dt) return - in the handle's dtype, written into `out` if given; afterwards the
+        engines are where those calls would have left them.
+        servo = dict(targets=[N,18] float32 device tensor, action_rate=, default_pos=(3 floats), action_scale=) (NightmareV3Env.
+        joint_target_servo builds it): the float32 targets go through custom_play.py:72's rate limit (`targets` is its memory, updated in
+        place) and the env's joint target -> action mapping, and the [steps, N, 18] float32 ACTIONS are returned instead - what
+        NightmareV3Env.step_tape reads."""
+        K, N = int(steps), self.num_envs
+        if K < 1:
+            raise ValueError("tape: steps must be at least 1")
+        want = torch.float32 if servo is not None else self.dtype
+        if out is None:
+            out = torch.empty((K, N, 18), dtype=want, device=self.device)
+        elif tuple(out.shape) != (K, N, 18) or out.dtype != want or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"tape: out must be a contiguous {str(want).split('.')[-1]} tensor of shape {(K, N, 18)} on the engine's device")
+        a = _lib.NmNikTapeArgs()
+        a.steps, a.tick0, a.dt, a.engine_fps = K, int(tick0), float(dt), float(config.ENGINE_FPS)
+        a.lin_dev, a.ang_dev = self._vec(self._lin, lin_speed), self._vec(self._ang, ang_speed)
+        a.awake_dev, a.walk_dev = self._flags("awake", state, "awake"), self._flags("walk", mode, "walk")
+        if servo is not None:
+            unknown = set(servo) - {"targets", "action_rate", "default_pos", "action_scale"}
+            if unknown or len(servo) != 4:
+                raise ValueError("tape: servo takes exactly targets, action_rate, default_pos, action_scale")
+            tg = servo["targets"]
+            if tuple(tg.shape) != (N, 18) or tg.dtype != torch.float32 or not tg.is_contiguous() or tg.device != self.device:
+                raise ValueError(f"tape: servo['targets'] must be a contiguous float32 tensor of shape {(N, 18)} on the engine's device")
+            a.servo_targets_dev, a.actions_dev = tg.data_ptr(), out.data_ptr()
+            a.action_rate = float(servo["action_rate"])
+            for i in range(3):
+                a.default_pos[i] = float(servo["default_pos"][i])
+            a.inv_action_scale = float(np.float32(1.0 / float(servo["action_scale"])))
+        elif self.dtype == torch.float64:
+            a.angles_f64_dev = out.data_ptr()
+        else:
+            a.angles_f32_dev = out.data_ptr()
+        self._keep_tape = (out, servo)
+        _lib.check(self.L.nm_nik_tape(self.h, C.byref(a), torch.cuda.current_stream(self.device).cuda_stream))
+        return out
+
     def set_gait(self, gait, env_ids=None):
         """state.cmd.gait (engine.py:297) of all or the listed engines: 'tripod' (default), 'ripple' or 'wave'. A walking engine takes
         the new gait over when its current step completes (:627), a starting one when it begins to walk (:543). Upstream the Command
