@@ -125,6 +125,18 @@ int nm_set_observation_noise(nm_env* env, const double* noise_scale_vec_host);
 /* RNG-free noise for parity tests: HOST [N,66] uniforms used by the following steps instead of the counter RNG
  * (what np.random.rand(N,66) returned at :305). NULL = RNG. */
 int nm_set_noise_uniforms(nm_env* env, const double* u_host);
+/* Push perturbations - the `domain_rand.push_robots` / `push_interval_s` / `max_push_vel_xy` of legged_gym-shaped config trees, the other
+ * half of SURVEY 8(f) row 4 next to the observation noise above; the reference has no such line. Every `interval_steps` env steps the
+ * base's world-frame linear velocity qvel[env, 0:2] of every env is SET to (vx, vy), each uniform in [-max_vel_xy, +max_vel_xy), before
+ * the physics of that step; nothing else of the state changes. It works alike in nm_step, nm_rollout, nm_play and nm_step_tape.
+ * The env counts its full env steps in a push step index s (K per K-step launch; nm_step_physics and nm_reset leave it alone): step s is
+ * pushed iff interval_steps > 0 && s > 0 && s % interval_steps == 0, with v = (2u - 1) * max_vel_xy in the env's precision (fp32: max
+ * rounded to float first), u ~ U[0,1) from the counter RNG keyed by (seed + "PUSH", global env id, 2 * (s / interval_steps) + axis).
+ * The observation the PREVIOUS step returned does not show the push.
+ * interval_steps == 0 switches pushes off (the default); a negative interval or a negative / non-finite max_vel_xy is refused. The call
+ * sets s = start_step. nm_get_push returns the setting and the current s (any pointer may be NULL): a checkpoint's three numbers. */
+int nm_set_push(nm_env* env, int32_t interval_steps, double max_vel_xy, uint64_t start_step);
+int nm_get_push(nm_env* env, int32_t* interval_steps, double* max_vel_xy, uint64_t* step);
 /* State log (envs/nightmare_v3_env.py:261-272 records data[0]): env_index >= 0 makes every nm_step keep that env's
  * post-physics, pre-reset qpos/qvel; -1 = off. nm_get_state_record copies the last record to HOST qpos[25], qvel[24] and
  * the number of MuJoCo bad-state resets inside that step (data.time restarts there). Synchronous. */

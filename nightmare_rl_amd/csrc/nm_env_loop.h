@@ -1,6 +1,6 @@
 // nm_env_loop.h - what the K-step launches k_env_rollout (nm_rollout_kernels.h), k_env_play (nm_play_kernels.h) and k_env_tape
-// (nm_tape_kernels.h) share: the wave index, the launch prologue, the episode books of the wave's two envs and the per-step update of the
-// env step's launch arguments. X below is the launch's own argument struct, RollArgs, PlayArgs or TapeArgs (nm_rollout.h): the helpers read
+// (nm_tape_kernels.h) share: the wave index, the launch prologue, the episode books of the wave's two envs, the per-step update of the
+// env step's launch arguments and the push perturbation of a step (nm_push.h). X below is the launch's own argument struct, RollArgs, PlayArgs or TapeArgs (nm_rollout.h): the helpers read
 // the fields all carry (cur_ret, cur_len, fin3, to_step, st_sum, st_cnt, rec_log) and `if constexpr` on the struct's traits (kPlayBooks,
 // kStepRecord) decides what only some of them file.
 #pragma once
@@ -9,6 +9,7 @@
 #include <type_traits>
 
 #include "nm_core.h"
+#include "nm_push.h"
 #include "nm_rollout.h"
 
 namespace nmr {
@@ -114,6 +115,25 @@ __device__ __forceinline__ void step_args(nm::Args<float>* As, const X* Xs, int 
   As->stat_cnt = Xs->st_cnt + (size_t)t * 4;
   As->noise_step = noise0 + (uint64_t)t;
   As->rec = Xs->rec_log ? Xs->rec_log + (size_t)t * kRecRow : nullptr;           // the state log's row of this step (env.py:261-272)
+}
+// The push of env step t, if one is due (nm_push.h; X::push says when): lanes 0..3 of the wave own (env 2 wave + (lane >> 1), axis lane & 1)
+// and store their draw into qvel. Called after the wait at the head of the policy step (the previous step's state rows of this wave
+// are stored - and a store of the same lane to the same word stays behind them anyway) and before step_close, whose wait puts the push
+// in L2 before the load stage of wave_step asks for qvel; at t = 0 stream order covers the previous launch. The branch is wave-uniform.
+// Out of line, like books_last: taken once per `interval` steps, and its registers are nobody else's.
+template <class X>
+__device__ __noinline__ void push_store(const X* Xs, const nm::Args<float>* As, uint32_t q, int wave) {
+  const int lane = threadIdx.x, env = wave * 2 + (lane >> 1);
+  if (lane < 4 && env < As->N)
+    simt::gst1(As->qvel, (size_t)env * nm::kNV + (lane & 1),
+               nm::push_value<float>(As->seed, (uint64_t)(As->env_offset + env), Xs->push.ctr0 + 2u * q + (uint32_t)(lane & 1), Xs->push.maxv));
+}
+template <class X>
+__device__ __forceinline__ void step_push(const X* Xs, const nm::Args<float>* As, int t, int wave) {
+  const uint32_t iv = (uint32_t)__builtin_amdgcn_readfirstlane(Xs->push.interval);
+  if (iv == 0) return;
+  const uint32_t p = (uint32_t)__builtin_amdgcn_readfirstlane((int)Xs->push.phase) + (uint32_t)t, q = p / iv;
+  if (q * iv == p && (t > 0 || __builtin_amdgcn_readfirstlane(Xs->push.past0) != 0)) push_store(Xs, As, q, wave);
 }
 __device__ __forceinline__ void step_close() {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the actions are in L2 before the load stage asks for them (other lanes of this wave)

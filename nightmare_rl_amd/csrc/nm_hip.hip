@@ -1,6 +1,7 @@
 // nm_hip.hip - gfx950 kernels + the C ABI of include/nightmare_hip.h. Device-only: there is no CPU path.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -10,6 +11,7 @@
 #include "../../include/nightmare_hip.h"
 #include "nm_host_model.h"
 #include "nm_env_loop.h"
+#include "nm_push.h"
 #include "nm_rollout.h"
 
 static thread_local std::string g_err;
@@ -249,6 +251,11 @@ struct nm_env {
   virtual int tape(const nm_tape_args* r, hipStream_t s) = 0;
   virtual int get_log(int first, int count, double* rows) = 0;
   virtual int get_log_dones(int first, int count, unsigned char* dones) = 0;
+  // push perturbations (nm_push.h): the setting and the push step index - full env steps taken, K per K-step launch; physics-only
+  // launches and nm_reset leave it alone
+  int push_interval = 0;
+  double push_max = 0.0;
+  uint64_t push_step = 0;
 };
 
 template <class real> struct Env : nm_env {
@@ -390,6 +397,12 @@ template <class real> struct Env : nm_env {
       a.rec = rec_env >= 0 ? rec_dev : nullptr;
       a.rec_env = rec_env;
       if (rec_env >= 0) rec_last = rec_dev;
+      const uint64_t ps = push_step++;
+      if (nm::push_due(push_interval, ps)) {   // a launch of its own on due steps only; every other step launches nothing extra
+        hipLaunchKernelGGL(nm::k_push<real>, dim3((2 * N + 255) / 256), dim3(256), 0, s, A.qvel, N, A.seed, A.env_offset,
+                           nm::push_counter(push_interval, ps), (real)push_max);
+        HIPCHK(hipGetLastError());
+      }
     }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (prof_on) {  // HIP events on the launch stream around the dominant kernel only (bench.py's roofline leg)
@@ -613,6 +626,19 @@ template <class real> struct Env : nm_env {
     a.rec = log; a.rec_env = log ? rec_env : -1; a.dbg = nullptr; a.ret_acc = nullptr;    // (rec: row t, set by the kernel before every step)
     return a;
   }
+  // the push arguments of a K-step launch (nmr::PushArgs says how the step index travels); advances push_step by K
+  nmr::PushArgs kstep_push(int K) {
+    nmr::PushArgs p{};
+    if (push_interval > 0) {
+      p.interval = push_interval;
+      p.phase = (uint32_t)(push_step % (uint64_t)push_interval);
+      p.ctr0 = nm::push_counter(push_interval, push_step);
+      p.past0 = push_step > 0;
+      p.maxv = (float)push_max;
+    }
+    push_step += (uint64_t)K;
+    return p;
+  }
   int rollout(const nm_rollout_args* r, int act, hipStream_t s) override {
     HIPCHK(hipSetDevice(device));
     if constexpr (sizeof(real) == 8 || NM_ENVS_PER_WAVE != 2) {
@@ -637,6 +663,7 @@ template <class real> struct Env : nm_env {
       R.st_sum = roll_sum; R.st_cnt = roll_cnt; R.to_step = roll_to;
       R.last_values = r->last_values_dev;
       R.rec_log = log;
+      R.push = kstep_push(K);
       R.wave_clock = A.dbg ? reinterpret_cast<unsigned long long*>(A.dbg) : nullptr;   // measurement: the debug buffer ([N,256] reals) takes the waves' clocks instead
       nmr::TailArgs ta{N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, r->bootstrap_time_outs ? r->gamma : -1.0f, r->s_values, r->s_rewards,
                        r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
@@ -674,6 +701,7 @@ template <class real> struct Env : nm_env {
       P.fin3 = r->fin3 ? r->fin3 : play_scratch + 4 * n_;
       P.st_sum = roll_sum; P.st_cnt = roll_cnt; P.to_step = roll_to;
       P.rec_log = log; P.rec_done = log ? rec_done : nullptr; P.rec_env = rec_env;
+      P.push = kstep_push(K);
       rec_done_valid = log != nullptr;
       nmr::TailArgs ta{N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, -1.0f, nullptr, nullptr,
                        r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
@@ -706,6 +734,7 @@ template <class real> struct Env : nm_env {
       T.fin3 = r->fin3 ? r->fin3 : play_scratch + 4 * n_;
       T.st_sum = roll_sum; T.st_cnt = roll_cnt; T.to_step = roll_to;
       T.rec_log = log; T.rec_done = log ? rec_done : nullptr; T.rec_env = rec_env;
+      T.push = kstep_push(K);
       rec_done_valid = log != nullptr;
       nmr::TailArgs ta{N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, -1.0f, nullptr, nullptr,
                        r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
@@ -879,6 +908,21 @@ int nm_play(nm_env* env, const nm_play_args* args, int32_t activation, void* str
   NEED(env);
   if (!nmact::valid(activation)) return bad_activation("nm_play", activation);
   return env->play(args, activation, (hipStream_t)stream);
+}
+int nm_set_push(nm_env* env, int32_t interval_steps, double max_vel_xy, uint64_t start_step) {
+  if (!env) return fail("nm_set_push: env is NULL");
+  if (interval_steps < 0) return fail("nm_set_push: interval_steps must be >= 0 (0 = off)");
+  if (!(max_vel_xy >= 0.0) || !std::isfinite(max_vel_xy) || (env->dtype == NM_DTYPE_F32 && !std::isfinite((float)max_vel_xy)))
+    return fail("nm_set_push: max_vel_xy must be finite and >= 0");
+  env->push_interval = interval_steps; env->push_max = max_vel_xy; env->push_step = start_step;
+  return 0;
+}
+int nm_get_push(nm_env* env, int32_t* interval_steps, double* max_vel_xy, uint64_t* step) {
+  if (!env) return fail("nm_get_push: env is NULL");
+  if (interval_steps) *interval_steps = env->push_interval;
+  if (max_vel_xy) *max_vel_xy = env->push_max;
+  if (step) *step = env->push_step;
+  return 0;
 }
 int nm_step_tape(nm_env* env, const nm_tape_args* args, void* stream) {
   if (!env) return fail("nm_step_tape: env is NULL");

@@ -37,6 +37,7 @@ __device__ __noinline__ void play_step(float* xb, const PlayArgs* Ps, nm::Args<f
                                    (uint64_t)simt::gld1(Ps->iter_dev, 0) * 4096ull + Ps->step0 + (uint64_t)t, o, Ps->deterministic != 0);
   if (t > 0) books_file(rec, Ps, As, t - 1, wave);
   if (threadIdx.x == 0) step_args(As, Ps, t, noise0);
+  step_push(Ps, As, t, wave);
   step_close();
 }
 

@@ -239,6 +239,16 @@ __device__ __forceinline__ void policy_wave(float* xb, const f32x4* __restrict__
   }
 }
 
+// Push perturbations inside a K-step launch (nm_push.h; step_push of nm_env_loop.h): the env's push step index at the launch's first step,
+// push0, travels as phase = push0 % interval, ctr0 = 2 * (push0 / interval) and past0 = (push0 > 0), so that the wave needs 32-bit
+// arithmetic only. Step t is pushed iff interval > 0 && (phase + t) % interval == 0 && (past0 || t > 0), with the draws
+// ctr0 + 2 * ((phase + t) / interval) + axis (mod 2^32: the host's push_counter). phase < 2^31 and t < 4096: no overflow.
+struct PushArgs {
+  int interval;                 // env steps between two pushes; 0 = off
+  uint32_t phase, ctr0;
+  int past0;
+  float maxv;                   // float32(max_vel_xy)
+};
 // ---- the K-step launch (kernels in nm_rollout.hip - a translation unit of its own, so that the code generation of k_env_step in
 // nm_hip.hip is not touched by a second kernel around the same physics; host launchers below)
 struct RollArgs {
@@ -254,6 +264,7 @@ struct RollArgs {
   float* last_values;                                          // [N] or null: the critic's value of the observation after the last step (PPO.compute_returns)
   unsigned long long* wave_clock;                              // measurement (nm_set_debug_buffer on): [waves][2] s_memtime at the wave's start / end, else null
   float* rec_log;                                              // [K,kRecRow] or null: the state log (Args::rec of step t = row t; env.py:261-272)
+  PushArgs push;
   // what the episode books of nm_env_loop.h file for this launch: kPlayBooks = per-env return sums + the logged env's reset flag (else the
   // rollout's storage rows), kStepRecord = optional [K,N] reward / done rows
   static constexpr bool kPlayBooks = false, kStepRecord = false;
@@ -272,6 +283,7 @@ struct PlayArgs {
   int* to_step;                                                // [N]: the LATEST step at which the env timed out in this launch, or -1
   float* rec_log;                                              // [K,kRecRow] or null
   unsigned char* rec_done; int rec_env;                        // [K] or null: the logged env's reset flag per step (the log's reader dumps a file there)
+  PushArgs push;
   static constexpr bool kPlayBooks = true, kStepRecord = false;
 };
 // k_env_tape (nm_tape_kernels.h): K x env.step with the actions of step t read from row t of a [K,N,18] tape - no policy, no sampling
@@ -287,6 +299,7 @@ struct TapeArgs {
   int* to_step;
   float* rec_log;
   unsigned char* rec_done; int rec_env;
+  PushArgs push;
   static constexpr bool kPlayBooks = true, kStepRecord = true;
 };
 struct TailArgs {

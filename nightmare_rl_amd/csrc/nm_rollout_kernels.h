@@ -38,6 +38,7 @@ __device__ __noinline__ void policy_step(float* xb, const RollArgs* Rs, nm::Args
     As->obs = t + 1 < Rs->K ? Rs->s_obs + (so + N) * nm::kNOBS : Rs->obs_final;     // the step files its observation where the next act reads it
     step_args(As, Rs, t, noise0);
   }
+  step_push(Rs, As, t, wave);
   step_close();
 }
 // PPO.compute_returns' `last_values = actor_critic.evaluate(last_critic_obs)` for the wave's envs: the forward once more, on the observation the

@@ -34,6 +34,7 @@ __device__ __noinline__ void tape_step(const TapeArgs* Ts, nm::Args<float>* As, 
     if (Ts->rec_obs) As->obs = Ts->rec_obs + so * nm::kNOBS;
     step_args(As, Ts, t, noise0);
   }
+  step_push(Ts, As, t, wave);
   step_close();
 }
 

@@ -12,6 +12,9 @@ Differences a caller can observe (all documented in DESIGN.md):
     at the price of one device sync per step() - or one per K-step launch (policy_rollout, policy_play), which keep the log on the device
   * observation noise (`cfg.noise.add_noise`, :304-305) draws from the same counter generator; `cfg.noise.layout`
     chooses between the reference's noise_scale_vec (written for a 12-dof robot, :113-119) and the 18-dof one
+  * an OPTIONAL `cfg.domain_rand` (push_robots, push_interval_s, max_push_vel_xy - the names of legged_gym-shaped config trees; the
+    reference has none) switches on push perturbations of the base velocity (set_push); the observation returned by the step before
+    a push does not show it
 """
 import ctypes as C
 import numpy as np
@@ -21,6 +24,24 @@ from .. import _lib
 from .helpers import class_to_dict
 from .nightmare_v3_config import NightmareV3Config
 from .state_log import ROW as _LOG_ROW, StateLog
+
+
+def push_config(cfg, dt):
+    """(interval_steps, max_vel_xy) of the optional cfg.domain_rand, (0, 0.0) when the class is missing or push_robots is false.
+    push_interval_s is converted with the env's dt (whole steps, rounded down; 1e-9 of a step absorbs the division's rounding, so that
+    0.048 s at dt 0.016 is 3 steps); an interval below one step or a negative / non-finite velocity is a ValueError."""
+    dr = getattr(cfg, "domain_rand", None)
+    if dr is None or not getattr(dr, "push_robots", False):
+        return 0, 0.0
+    steps = float(dr.push_interval_s) / float(dt) + 1e-9
+    if not steps >= 1:
+        raise ValueError("cfg.domain_rand.push_interval_s must be at least one env step (dt)")
+    vel = float(dr.max_push_vel_xy)
+    if not (vel >= 0 and np.isfinite(vel)):
+        raise ValueError("cfg.domain_rand.max_push_vel_xy must be finite and >= 0")
+    if steps >= 2 ** 31:
+        raise ValueError("cfg.domain_rand.push_interval_s is more than 2^31 env steps")
+    return int(steps), vel
 
 
 class NightmareV3Env:
@@ -60,6 +81,7 @@ class NightmareV3Env:
         self.default_dof_pos = np.array(cfg.control.default_pos, dtype=np.float64)
         if int(cfg.commands.resampling_time / self.dt) < 1:
             raise ValueError("cfg.commands.resampling_time must be at least one env step (reference :235 takes a modulo by it)")
+        push_steps, push_vel = push_config(cfg, self.dt)       # optional cfg.domain_rand: checked before anything is created
         # reward table: zero scales dropped, the rest x dt (reference :123-128). Every name the reference has a _reward_ function
         # for (:399-497) is compiled; a name without one (`collision`, `feet_stumble`, config :95-96) fails like upstream's getattr.
         names = [L.nm_reward_name(i).decode() for i in range(_lib.NUM_REWARDS)]
@@ -120,6 +142,10 @@ class NightmareV3Env:
         self.add_noise = bool(cfg.noise.add_noise)
         if self.add_noise:
             self._ck(L.nm_set_observation_noise(h, self.noise_scale_vec.ctypes.data_as(C.c_void_p)))
+        # push perturbations (optional cfg.domain_rand; no reference line)
+        self.push_interval, self.max_push_vel_xy = 0, 0.0
+        if push_steps:
+            self.set_push(push_steps, push_vel)
         # state log of env 0 (reference :261-272; reader open_custom_play.py:50-66)
         self.state_log = None
         self._rec_env = 0
@@ -165,6 +191,19 @@ class NightmareV3Env:
         """RNG-free noise for parity tests: [N,66] uniforms in [0,1) used instead of the generator (None = generator)."""
         u = None if u is None else np.ascontiguousarray(u, np.float64).reshape(self.num_envs, self.num_obs)
         self._ck(self._L.nm_set_noise_uniforms(self._h, None if u is None else u.ctypes.data_as(C.c_void_p)))
+
+    def set_push(self, interval_steps, max_vel_xy, start_step=0):
+        """Push perturbations (nm_set_push): every `interval_steps` env steps qvel[:, 0:2] of every env is set to a draw from
+        U[-max_vel_xy, max_vel_xy) before the physics of that step, in step(), policy_rollout, policy_play and step_tape alike.
+        0 steps = off. The env's push step index restarts at start_step."""
+        self._ck(self._L.nm_set_push(self._h, int(interval_steps), float(max_vel_xy), int(start_step)))
+        self.push_interval, self.max_push_vel_xy = int(interval_steps), float(max_vel_xy)
+
+    def push_state(self):
+        """(interval_steps, max_vel_xy, step) as nm_get_push returns them: what a checkpoint needs to continue the push schedule."""
+        iv, mx, st = C.c_int32(0), C.c_double(0), C.c_uint64(0)
+        self._ck(self._L.nm_get_push(self._h, C.byref(iv), C.byref(mx), C.byref(st)))
+        return iv.value, mx.value, st.value
 
     def _record_state(self):
         # reference :261-272: when env 0 resets, dump what was logged so far, then log (time, qpos, qvel, act) of env 0

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """train.py - the reference's training entry point (reference train.py:1-54) on the MI355X backend.
 Same flags (-r resume, -v render [rejected: no viewer], -n num_threads [accepted, unused], -e envs, -p resume_path) plus
---iters / --seed / --gpus. Multi-GPU: `python train.py --gpus G -e <total envs>` (starts its G ranks as child processes) or
+--iters / --seed / --gpus / --push-interval-s / --push-vel. Multi-GPU: `python train.py --gpus G -e <total envs>` (starts its G ranks as child processes) or
 `python -m torch.distributed.run --nproc-per-node G train.py -e <total envs>`."""
 import argparse
 import datetime
@@ -27,6 +27,9 @@ def main():
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--record-states", action="store_true", default=False, dest="record_states",
                     help="upstream's viewer.record_states: pickle env 0's states into the run's log directory whenever it resets (envs/nightmare_v3_env.py:261-272)")
+    ap.add_argument("--push-interval-s", type=float, default=0.0, dest="push_interval_s",
+                    help="push perturbations: seconds between two pushes of every robot's base velocity (0 = off, the default)")
+    ap.add_argument("--push-vel", type=float, default=1.0, dest="push_vel", help="push perturbations: max |vx|, |vy| of a push in m/s")
     ap.add_argument("--gpus", type=int, default=None, help="ranks (one per GPU); without torch.distributed.run, train.py starts them itself")
     args = ap.parse_args()
 
@@ -59,12 +62,18 @@ def main():
     cfg, train_cfg = NightmareV3Config(), NightmareV3ConfigPPO()
     cfg.viewer.render = args.render
     cfg.viewer.record_states = bool(args.record_states) and rank == 0        # one log: rank 0's env 0
+    if args.push_interval_s > 0:
+        class domain_rand:      # the optional class NightmareV3Env reads
+            push_robots, push_interval_s, max_push_vel_xy = True, args.push_interval_s, args.push_vel
+        cfg.domain_rand = domain_rand
     lo, hi = shard_range(args.num_envs, rank, world)
     cfg.env.num_envs = hi - lo
     train_cfg.runner.resume = args.resume
     seed = train_cfg.seed if args.seed is None else args.seed
     torch.manual_seed(seed + rank)
     env = NightmareV3Env(cfg, log_dir=log_dir, num_threads=args.num_threads, device=f"cuda:{local_rank}", seed=seed, env_id_offset=lo)
+    if rank == 0:
+        print(f"push perturbations: every {env.push_interval} steps, |v| < {env.max_push_vel_xy} m/s" if env.push_interval else "push perturbations: off", flush=True)
     runner = OnPolicyRunner(env, class_to_dict(train_cfg), log_dir=log_dir, device=f"cuda:{local_rank}")
     if train_cfg.runner.resume:
         path = get_load_path(args.resume_path or log_root, load_run=train_cfg.runner.load_run, checkpoint=train_cfg.runner.checkpoint)
