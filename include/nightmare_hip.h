@@ -137,6 +137,25 @@ int nm_set_noise_uniforms(nm_env* env, const double* u_host);
  * sets s = start_step. nm_get_push returns the setting and the current s (any pointer may be NULL): a checkpoint's three numbers. */
 int nm_set_push(nm_env* env, int32_t interval_steps, double max_vel_xy, uint64_t start_step);
 int nm_get_push(nm_env* env, int32_t* interval_steps, double* max_vel_xy, uint64_t* step);
+/* Per-env friction and servo-gain randomisation - the `domain_rand.randomize_friction` / `friction_range` of legged_gym-shaped config
+ * trees and the stiffness / damping multipliers their forks add; it replaces nothing upstream (the reference has one floor and one servo).
+ * Each env e carries three values in the env's dtype:
+ *   mu[e]      sliding friction of every contact of the env (pyramid rows n +- mu t, diagApprox = tran + mu^2 tran, R = 2 mu^2 R0):
+ *              what setting the friction of every geom of that env's model would give;
+ *   p_gain[e]  in place of control.p_gain in ctrl = ((a - default_pos) - dof_pos) * p_gain (envs/nightmare_v3_env.py:183);
+ *   kv[e]      in place of the actuators' kv = 0.8: the force kv (clamp(ctrl) - qvel) and the implicitfast matrix M + h kv I.
+ * They hold until the caller changes them: no reset resamples them. It works alike in nm_step, nm_step_physics, nm_rollout, nm_play and
+ * nm_step_tape. Off is the default, and off equals "on with (1.0, cfg.p_gain, 0.8) in every env" bit for bit.
+ * nm_set_env_params: DEVICE arrays [N] in the env's dtype, copied on `stream`; a NULL array sets that column to its default; all three
+ *   NULL switch the feature off (nothing is freed). The values are NOT validated: mu <= 1e-5, a negative gain or a non-finite value is the
+ *   caller's responsibility (the physics then divides by zero or diverges, and the bad-state resets of mj_check* take over).
+ * nm_get_env_params: the three columns into DEVICE arrays [N] (any may be NULL) on `stream`; the defaults while the feature is off.
+ * nm_draw_env_params: value = lo[c] + u (hi[c] - lo[c]) for column c = 0 (mu), 1 (p_gain), 2 (kv) in the env's precision, product and sum
+ *   rounded separately, u ~ U[0,1) from the counter RNG keyed by (seed + "ENVP", global env id, c): sharding changes nothing; lo == hi
+ *   pins a column. Refused before any device call, named by nm_last_error: non-finite bounds, lo > hi, mu <= 1e-5, negative p_gain / kv. */
+int nm_set_env_params(nm_env* env, const void* mu_dev, const void* p_gain_dev, const void* kv_dev, void* stream);
+int nm_get_env_params(nm_env* env, void* mu_dev, void* p_gain_dev, void* kv_dev, void* stream);
+int nm_draw_env_params(nm_env* env, const double lo[3], const double hi[3], void* stream);
 /* State log (envs/nightmare_v3_env.py:261-272 records data[0]): env_index >= 0 makes every nm_step keep that env's
  * post-physics, pre-reset qpos/qvel; -1 = off. nm_get_state_record copies the last record to HOST qpos[25], qvel[24] and
  * the number of MuJoCo bad-state resets inside that step (data.time restarts there). Synchronous. */

@@ -88,6 +88,7 @@ template <class real> struct Model {
 // per-launch arguments (device pointers, AoS-by-env rows so one wave reads contiguous bytes)
 template <class real> struct Args {
   int N;
+  int rec_env;           // (state log, below; it sits here, in the padding behind N, so that `envp` fits without the struct growing)
   uint64_t seed;
   int64_t env_offset;
   // physics state
@@ -129,15 +130,25 @@ template <class real> struct Args {
   uint64_t noise_step;   // step index of this launch (RNG counter = noise_step*66 + k)
   // state log of one env (env.py:261-272): post-physics, pre-reset qpos[25] qvel[24] + bad-state-reset count; null = off
   real* rec;
-  int rec_env;
+  // per-env physics parameters (friction and servo-gain randomisation): [N,4] rows (mu, p_gain, kv, pad), 16 bytes; null = off, every env
+  // takes M.mu / M.p_gain / M.kv
+  const real* envp;
 };
 constexpr int kTicketGroup = 64, kTicketStride = 32, kTicketTop = 0;   // group g's counter at [(g + 1) * kTicketStride] (own 128 B line)
 constexpr uint64_t kNoiseKey = 0x4E4F495345ull;
+constexpr uint64_t kEnvParamKey = 0x454E5650ull;   // nm_draw_env_params: rand_u24_bits(seed + kEnvParamKey, global env id, column)
+constexpr int EP_MU = 0, EP_PGAIN = 1, EP_KV = 2, kEnvP = 4, kEnvPS = 3;   // columns of an Args::envp row (the fourth is padding) and of Sh::envp
 constexpr int kDbgN = 256;
 
 // ----------------------------------------------------------------------------------------- LDS image of one env
 template <class real> struct Sh {
-  real qpos[28], qvel[24], warm[24], ctrl[20];
+  real qpos[kNQ];
+  // this env's sliding friction, servo stiffness and damping (EP_*): the load stage copies the env's Args::envp row, or M.mu / M.p_gain /
+  // M.kv when there is none; every stage reads these, never M's. The block takes the three words that used to pad qpos to 28: the image
+  // keeps its size and every other field its offset (these 256-VGPR kernels' register allocation follows the struct sizes: a larger
+  // image costs k_env_rollout / k_env_tape a third spilled VGPR whether or not anything reads the block)
+  real envp[kEnvPS];
+  real qvel[24], warm[24], ctrl[20];
   real Rb[9], wv[6];             // base rotation; base spatial velocity [w_world; v_origin]
   real anc[kNU * 3], axs[kNU * 3];  // hinge anchors (relative to base origin) and axes, world-aligned
   real colR[kNCOL * 9], colp[kNCOL * 3];
@@ -177,6 +188,7 @@ template <class real> struct Sh {
 };
 
 static_assert(kNLEG * 66 >= 9 * kMaxConBig, "contact list must fit the leg staging area");
+static_assert(offsetof(Sh<float>, qvel) == 28 * sizeof(float) && offsetof(Sh<double>, qvel) == 28 * sizeof(double), "qpos + envp keep the 28 words qpos had");
 // LDS of one wavefront: G env images (the leg-lane stages run all G envs at once, lanes 8g..8g+5 = legs of env g; collision,
 // constraints and the env epilogue take the envs one after the other on all 64 lanes) + one shared row buffer.
 template <class real, int G> struct ShW {
@@ -185,6 +197,13 @@ template <class real, int G> struct ShW {
 };
 #define NM_OFS(field) ((int)(offsetof(Sh<real>, field) / sizeof(real)))
 #define NM_IOFS(field) ((int)(offsetof(Sh<real>, field) / sizeof(int)))
+
+// Per-env parameters are a template parameter EP of the step: the default instantiation (EP = false, launched while no rows are set)
+// reads M.mu / M.kv / M.p_gain exactly as before and never touches Sh::envp or Args::envp - its instruction stream is the one it had
+// before the feature; the EP = true instantiation, launched when rows are set, reads the env image.
+template <bool EP, class real> NM_FN real env_mu(const Sh<real>& sh, const Model<real>& M) {
+  if constexpr (EP) return sh.envp[EP_MU]; else return M.mu;
+}
 
 // ----------------------------------------------------------------------------------------- small algebra
 template <class A, class B, class C> NM_FN void cross3(A* r, const B* a, const C* b) {
@@ -379,7 +398,7 @@ template <class real> NM_FN V<real> legsum(const V<real>& x, const VB& isleg) { 
   return gsum8(sel(isleg, x, V<real>(real(0))));
 }
 
-template <class real, int G> NM_FN void stage_smooth(ShW<real, G>& w, const Model<real>& M, bool last) {
+template <bool EP, class real, int G> NM_FN void stage_smooth(ShW<real, G>& w, const Model<real>& M, bool last) {
   typedef V<real> vr;
   real* lds = reinterpret_cast<real*>(&w.e[0]);
   // Lane groups of 8: group g works on env g % G; groups [0, G) factor M, groups [G, 2G) factor M + h*kv*I (implicitfast) - the two
@@ -693,7 +712,9 @@ template <class real, int G> NM_FN void stage_smooth(ShW<real, G>& w, const Mode
     const V<int> eoQ = eo + sel(pass1, V<int>(NM_OFS(legtmp) + 36), V<int>(NM_OFS(qfs)));
     const V<int> eoA = eo + sel(pass1, V<int>(NM_OFS(legtmp) + 60), V<int>(NM_OFS(qas)));
     vr Mh[6];
-    const vr dg = sel(pass1, vr(M.h * M.kv), vr(real(0)));
+    vr dg;
+    if constexpr (EP) dg = sel(pass1, M.h * LDG(envp, EP_KV), vr(real(0)));   // the env's own kv: lanes 8g..8g+7 are env g % G
+    else dg = sel(pass1, vr(M.h * M.kv), vr(real(0)));
     Mh[0] = Ml[0] + dg; Mh[1] = Ml[1]; Mh[2] = Ml[2]; Mh[3] = Ml[3] + dg; Mh[4] = Ml[4]; Mh[5] = Ml[5] + dg;
     vr Mi[6], W[3][6];
     ldl3(Mi, Mh, real(1));
@@ -732,7 +753,10 @@ template <class real, int G> NM_FN void stage_smooth(ShW<real, G>& w, const Mode
       for (int k = 0; k < 3; k++) {
         vr ctrl = LDL(ctrl, leg * 3 + k), qd = LDL(qvel, leg * 3 + (6 + k));
         ctrl = vmin(vmax(ctrl, vr(-M.ctrl_max)), vr(M.ctrl_max));
-        y[k] = M.kv * ctrl - M.kv * qd - cl[k];
+        if constexpr (EP) {
+          const vr kv = LDG(envp, EP_KV);
+          y[k] = kv * ctrl - kv * qd - cl[k];
+        } else y[k] = M.kv * ctrl - M.kv * qd - cl[k];
         stsv(lds, eoQ + leg * 3 + (6 + k), y[k], st_leg);
       }
       ldl3_solve(t, Mi, y);
@@ -1457,7 +1481,7 @@ template <class X> NM_FN X noslip_pair_cost(const X& d, const X& hK1, const X& d
 template <class real, class X> NM_FN auto noslip_pair_bad(const X& change) { return change > X(real(1e-10)); }   // costChange: revert an update that does not decrease the cost
 
 // Contact rows on lanes: build, project (A = J M^-1 J'), warm start, PGS, NoSlip, map back, sensors.
-template <class real, bool PAIR> NM_FN void stage_constraint_body(Sh<real>& sh, real* jrow, const Model<real>& M, bool last, bool nosweep) {
+template <class real, bool PAIR, bool EP> NM_FN void stage_constraint_body(Sh<real>& sh, real* jrow, const Model<real>& M, bool last, bool nosweep) {
   typedef V<real> vr;
   const V<int> lane = lane_id();
   const int ncon = uniform(sh.ncon), nefc = 4 * ncon;
@@ -1488,7 +1512,7 @@ template <class real, bool PAIR> NM_FN void stage_constraint_body(Sh<real>& sh, 
   // builds the Jacobian row of ONE frame axis (q: n, t1, t2, n) and publishes it for the projection sweep; its own pyramid
   // row is then J(n) +- mu J(t_k) (mj_instantiateContact's formula), fetched from the quad by DPP.
   const V<int> q4 = lane & 3;
-  vr smu = sel(sg == 0, vr(M.mu), vr(-M.mu));
+  vr smu = sel(sg == 0, vr(env_mu<EP>(sh, M)), vr(-env_mu<EP>(sh, M)));
   vr nrm[3] = {vr(real(0)), vr(real(0)), vr(real(1))};
   vr e[3] = {sel(q4 == 2, vr(real(-1)), vr(real(0))), sel(q4 == 1, vr(real(1)), vr(real(0))), sel((q4 == 0) | (q4 == 3), vr(real(1)), vr(real(0)))};
   if (anypair) {
@@ -1603,7 +1627,7 @@ template <class real, bool PAIR> NM_FN void stage_constraint_body(Sh<real>& sh, 
   }
   vr invw = ldsv(M.colc, (Lc + sel(onleg, V<int>(1), V<int>(0))) * kColN + 4);
   if (anypair) invw = invw + sel(onleg1, ldsv(M.colc, (Lc1 + 1) * kColN + 4), vr(real(0)));
-  vr Rr = vmax((vr(real(1)) - imp) * (invw + M.mu * M.mu * invw) * vrcp(imp), vr(real(1e-15))) * (real(2) * M.mu * M.mu);
+  vr Rr = vmax((vr(real(1)) - imp) * (invw + env_mu<EP>(sh, M) * env_mu<EP>(sh, M) * invw) * vrcp(imp), vr(real(1e-15))) * (real(2) * env_mu<EP>(sh, M) * env_mu<EP>(sh, M));
   vr Dd = vrcp(Rr);
   // sparse dots with the wave-uniform vectors qvel, qacc_smooth, qacc_warmstart
   vr vel = vr(real(0)), jas = vr(real(0)), jaw = vr(real(0));
@@ -1675,10 +1699,10 @@ template <class real, bool PAIR> NM_FN void stage_constraint_body(Sh<real>& sh, 
         }
         a3[r] = a;
       }
-      A[4 * cc] = a3[0] + M.mu * a3[1];
-      A[4 * cc + 1] = a3[0] - M.mu * a3[1];
-      A[4 * cc + 2] = a3[0] + M.mu * a3[2];
-      A[4 * cc + 3] = a3[0] - M.mu * a3[2];
+      A[4 * cc] = a3[0] + env_mu<EP>(sh, M) * a3[1];
+      A[4 * cc + 1] = a3[0] - env_mu<EP>(sh, M) * a3[1];
+      A[4 * cc + 2] = a3[0] + env_mu<EP>(sh, M) * a3[2];
+      A[4 * cc + 3] = a3[0] - env_mu<EP>(sh, M) * a3[2];
     }
   };
   // a flat chain of 16 guarded bodies: nesting them (one exit branch instead of one skipped test per unused contact) makes the
@@ -1875,8 +1899,8 @@ template <class real, bool PAIR> NM_FN void stage_constraint_body(Sh<real>& sh, 
   wave_sync();
 }
 
-template <class real> NM_COLD void stage_constraint_pairs(Sh<real>& sh, real* jrow, const Model<real>& M, bool last, bool nosweep) {
-  stage_constraint_body<real, true>(sh, jrow, M, last, nosweep);
+template <class real, bool EP> NM_COLD void stage_constraint_pairs(Sh<real>& sh, real* jrow, const Model<real>& M, bool last, bool nosweep) {
+  stage_constraint_body<real, true, EP>(sh, jrow, M, last, nosweep);
 }
 
 // =========================================================================================  stage C, two envs at once
@@ -1890,7 +1914,7 @@ constexpr int kMaxCon2 = 8, kMaxRow2 = 4 * kMaxCon2;
 #ifdef NM_EMUL
 inline long& nm_emul_together() { static long n = 0; return n; }   // host emulation only: how often the two-env pass ran (tests assert it did)
 #endif
-template <class real> NM_FN void stage_constraint2(ShW<real, 2>& w, const Model<real>& M, bool last, bool nosweep) {
+template <bool EP, class real> NM_FN void stage_constraint2(ShW<real, 2>& w, const Model<real>& M, bool last, bool nosweep) {
   typedef V<real> vr;
   constexpr int kSR = (int)(sizeof(Sh<real>) / sizeof(real)), kSI = (int)(sizeof(Sh<real>) / sizeof(int));
   const V<int> lane = lane_id();
@@ -1924,7 +1948,11 @@ template <class real> NM_FN void stage_constraint2(ShW<real, 2>& w, const Model<
   const VB onleg = L >= 0;
   const V<int> Lc = vmax(L, V<int>(0));
   const V<int> q4 = hl & 3;
-  vr smu = sel(sg == 0, vr(M.mu), vr(-M.mu));
+  // the friction of the half's env, per lane; read again at every use (an LDS read each, as M.mu was) so that no register holds it
+  // across the row build
+  auto mu2 = [&]() -> vr { if constexpr (EP) return SHR(envp, V<int>(EP_MU)); else return vr(M.mu); };
+#define MU2 mu2()
+  vr smu = sel(sg == 0, MU2, -MU2);
   vr nrm[3] = {vr(real(0)), vr(real(0)), vr(real(1))};
   vr e[3] = {sel(q4 == 2, vr(real(-1)), vr(real(0))), sel(q4 == 1, vr(real(1)), vr(real(0))), sel((q4 == 0) | (q4 == 3), vr(real(1)), vr(real(0)))};
   // frame-axis Jacobian row: base translation, base rotation (body axes), the 3 hinges of the contact's own leg
@@ -1993,7 +2021,7 @@ template <class real> NM_FN void stage_constraint2(ShW<real, 2>& w, const Model<
     imp = sel(x <= vr(real(0)), vr(M.si_d0), imp);
   }
   vr invw = ldsv(M.colc, (Lc + sel(onleg, V<int>(1), V<int>(0))) * kColN + 4);
-  vr Rr = vmax((vr(real(1)) - imp) * (invw + M.mu * M.mu * invw) * vrcp(imp), vr(real(1e-15))) * (real(2) * M.mu * M.mu);
+  vr Rr = vmax((vr(real(1)) - imp) * (invw + MU2 * MU2 * invw) * vrcp(imp), vr(real(1e-15))) * (real(2) * MU2 * MU2);
   vr Dd = vrcp(Rr);
   vr vel = vr(real(0)), jas = vr(real(0)), jaw = vr(real(0));
 #pragma unroll
@@ -2043,10 +2071,10 @@ template <class real> NM_FN void stage_constraint2(ShW<real, 2>& w, const Model<
         a += sel(same, ldsv(jrow, jr + 6) * t[0] + ldsv(jrow, jr + 7) * t[1] + ldsv(jrow, jr + 8) * t[2], vr(real(0)));
         a3[r] = a;
       }
-      A[4 * cc] = sel(has, a3[0] + M.mu * a3[1], vr(real(0)));
-      A[4 * cc + 1] = sel(has, a3[0] - M.mu * a3[1], vr(real(0)));
-      A[4 * cc + 2] = sel(has, a3[0] + M.mu * a3[2], vr(real(0)));
-      A[4 * cc + 3] = sel(has, a3[0] - M.mu * a3[2], vr(real(0)));
+      A[4 * cc] = sel(has, a3[0] + MU2 * a3[1], vr(real(0)));
+      A[4 * cc + 1] = sel(has, a3[0] - MU2 * a3[1], vr(real(0)));
+      A[4 * cc + 2] = sel(has, a3[0] + MU2 * a3[2], vr(real(0)));
+      A[4 * cc + 3] = sel(has, a3[0] - MU2 * a3[2], vr(real(0)));
     }
   };
 #define NM_BUILD4(c0) build_contact(std::integral_constant<int, c0>{}); build_contact(std::integral_constant<int, c0 + 1>{}); \
@@ -2220,6 +2248,7 @@ template <class real> NM_FN void stage_constraint2(ShW<real, 2>& w, const Model<
     }
   }
   wave_sync();
+#undef MU2
 #undef SHR
 #undef SHI
 }
@@ -2318,13 +2347,13 @@ template <class real> NM_FN void big_jtf(Sh<real>& sh, const BigRows<real>& r) {
     }
   wave_sync();
 }
-template <class real> NM_COLD void stage_constraint_big(Sh<real>& sh, const Model<real>& M, bool last, bool nosweep) {
+template <class real, bool EP> NM_COLD void stage_constraint_big(Sh<real>& sh, const Model<real>& M, bool last, bool nosweep) {
   typedef V<real> vr;
   const V<int> lane = opaque_lane();
   const int ncon = uniform(sh.ncon), nefc = 4 * ncon;
   BigRows<real> r;
   const V<int> q4 = lane & 3;
-  const vr smu = sel((lane & 1) == 0, vr(M.mu), vr(-M.mu));
+  const vr smu = sel((lane & 1) == 0, vr(env_mu<EP>(sh, M)), vr(-env_mu<EP>(sh, M)));
   const VB even = (lane & 1) == 0;
   // ---- rows: frame-axis Jacobians, pyramid rows, impedance / R / aref, diagonal of A and the pair coupling for NoSlip
 #pragma unroll
@@ -2412,7 +2441,7 @@ template <class real> NM_COLD void stage_constraint_big(Sh<real>& sh, const Mode
     }
     vr invw = ldsv(M.colc, (Lc + sel(onleg, V<int>(1), V<int>(0))) * kColN + 4);
     invw = invw + sel(onleg1, ldsv(M.colc, (Lc1 + 1) * kColN + 4), vr(real(0)));
-    const vr Rr = vmax((vr(real(1)) - imp) * (invw + M.mu * M.mu * invw) * vrcp(imp), vr(real(1e-15))) * (real(2) * M.mu * M.mu);
+    const vr Rr = vmax((vr(real(1)) - imp) * (invw + env_mu<EP>(sh, M) * env_mu<EP>(sh, M) * invw) * vrcp(imp), vr(real(1e-15))) * (real(2) * env_mu<EP>(sh, M) * env_mu<EP>(sh, M));
     vr vel = vr(real(0)), jas = vr(real(0)), jaw = vr(real(0));
 #pragma unroll
     for (int j = 0; j < 6; j++) {
@@ -2603,10 +2632,10 @@ template <class real> NM_COLD void floor_frames(Sh<real>& sh) {
   stsv(sh.cnrm(), c * 3 + 2, V<real>(real(1)), on);
   wave_sync();
 }
-template <class real> NM_FN void stage_constraint(Sh<real>& sh, real* jrow, const Model<real>& M, bool last, bool nosweep = false) {
-  if (uniform(sh.ncon) > kMaxCon) { floor_frames(sh); stage_constraint_big<real>(sh, M, last, nosweep); }
-  else if (uniform(sh.anypair) != 0) { floor_frames(sh); stage_constraint_pairs<real>(sh, jrow, M, last, nosweep); }
-  else stage_constraint_body<real, false>(sh, jrow, M, last, nosweep);
+template <class real, bool EP> NM_FN void stage_constraint(Sh<real>& sh, real* jrow, const Model<real>& M, bool last, bool nosweep = false) {
+  if (uniform(sh.ncon) > kMaxCon) { floor_frames(sh); stage_constraint_big<real, EP>(sh, M, last, nosweep); }
+  else if (uniform(sh.anypair) != 0) { floor_frames(sh); stage_constraint_pairs<real, EP>(sh, jrow, M, last, nosweep); }
+  else stage_constraint_body<real, false, EP>(sh, jrow, M, last, nosweep);
 }
 
 // =========================================================================================  stage D
@@ -2774,7 +2803,7 @@ inline void nm_set_priority(int) {}
 #endif
 
 // mj_step(model, data, 1) for the G envs of the wave
-template <class real, int G> NM_FN void substep(ShW<real, G>& w, const Model<real>& M, bool last, int* dropped, int ablate) {
+template <bool EP, class real, int G> NM_FN void substep(ShW<real, G>& w, const Model<real>& M, bool last, int* dropped, int ablate) {
   const V<int> lane = opaque_lane();
   if constexpr (G == 2) {   // both envs at once on half-waves (lanes 0..31 | 32..63), as in env_load2
     constexpr int kSR = (int)(sizeof(Sh<real>) / sizeof(real));
@@ -2803,7 +2832,7 @@ template <class real, int G> NM_FN void substep(ShW<real, G>& w, const Model<rea
   }
   wave_sync();
   nm_stamp(1);
-  if (!(ablate & 8)) stage_smooth(w, M, last);
+  if (!(ablate & 8)) stage_smooth<EP>(w, M, last);
   nm_stamp(2);
   // collision of every env of the wave, then the constraint stage: both envs in one pass when each has 1..kMaxCon2 floor contacts
   // (stage_constraint2), else one after the other
@@ -2828,13 +2857,13 @@ template <class real, int G> NM_FN void substep(ShW<real, G>& w, const Model<rea
       nm_emul_together() += 1;
 #endif
       w.e[0].ntog += 1;
-      stage_constraint2(w, M, last, (ablate & 2) != 0);
+      stage_constraint2<EP>(w, M, last, (ablate & 2) != 0);
       nm_stamp(8);
     }
   }
   if (!together)
     for (int e = 0; e < G; e++) {
-      stage_constraint(w.e[e], w.jrow, M, last, (ablate & 2) != 0);
+      stage_constraint<real, EP>(w.e[e], w.jrow, M, last, (ablate & 2) != 0);
       nm_stamp(8);
     }
   stage_integrate(w, M);
@@ -2844,7 +2873,7 @@ template <class real, int G> NM_FN void substep(ShW<real, G>& w, const Model<rea
 // =========================================================================================  env step
 
 // load one env's state into its LDS image, action -> servo command (E1)
-template <class real> NM_FN void env_load(Sh<real>& sh, const Model<real>& M, const Args<real>& A, int env) {
+template <bool EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real>& M, const Args<real>& A, int env) {
   typedef V<real> vr;
   const V<int> lane = opaque_lane();   // index math stays local to this function (not kept live across the physics)
   const VB l18 = lane < kNU;
@@ -2856,6 +2885,8 @@ template <class real> NM_FN void env_load(Sh<real>& sh, const Model<real>& M, co
   const vr w_in = gldv(A.qwarm, sel(lane < kNV, lane, V<int>(0)) + env * kNV);
   const V<int> hc_in = gldv(A.hullcache, sel(lane < 8, lane, V<int>(0)) + env * 8);
   const V<float> a_in = gldv(A.actions, l18c + env * kNU);
+  vr envp_in = vr(real(0));
+  if constexpr (EP) envp_in = gldv(A.envp, sel(lane < kEnvP, lane, V<int>(0)) + env * kEnvP);     // the env's (mu, p_gain, kv, pad) row: 16 bytes, lanes 0..3
   vr cmd_in = vr(real(0)), eps_in = vr(real(0)), prev_act = vr(real(0)), prev_dofvel = vr(real(0)), dofpos_old = vr(real(0));
   int64_t ep = 0;
   uint32_t ctr_in = 0;
@@ -2875,6 +2906,12 @@ template <class real> NM_FN void env_load(Sh<real>& sh, const Model<real>& M, co
   sh.nwarn = 0;
   sh.nhop = 0;
   sh.ntog = 0;
+  // per-env parameters: the env's row into its image; the stiffness of this step's command stays in a register
+  real p_gain = M.p_gain;
+  if constexpr (EP) {
+    stsv(sh.envp, lane, envp_in, lane < kEnvPS);
+    p_gain = rdlane(envp_in, EP_PGAIN);
+  }
   // ---- E1 (env.py:152-156,181-192): float32 scale + clip; PD -> velocity command from the env's own dof_pos buffer
   V<float> af = a_in * M.action_scale;
   af = vmin(vmax(af, V<float>(-M.clip_actions)), V<float>(M.clip_actions));
@@ -2895,10 +2932,10 @@ template <class real> NM_FN void env_load(Sh<real>& sh, const Model<real>& M, co
     sh.eplen_lo = (int)(uint32_t)(ep & 0xffffffffll);
     sh.eplen_hi = (int)(ep >> 32);
     sh.ectr = ctr_in;
-    stsv(sh.ctrl, lane, ((act - defp) - dofpos_old) * M.p_gain, l18);
+    stsv(sh.ctrl, lane, ((act - defp) - dofpos_old) * p_gain, l18);
   } else {  // dynamics-only mode (BASELINE config 2): same PD law on the current joint angles, no env buffers
     wave_sync();
-    stsv(sh.ctrl, lane, ((act - defp) - ldsv(sh.qpos, l18c + 7)) * M.p_gain, l18);
+    stsv(sh.ctrl, lane, ((act - defp) - ldsv(sh.qpos, l18c + 7)) * p_gain, l18);
   }
   // carried to the epilogue through LDS, not in registers: nothing stays live across the physics
   stsv(sh.eact, lane, act, l18); stsv(sh.epact, lane, prev_act, l18); stsv(sh.epdv, lane, prev_dofvel, l18);
@@ -3201,7 +3238,7 @@ template <class real> NM_FN void env_finish(Sh<real>& sh, const Model<real>& M, 
 // `mid()` runs after every HBM read has been issued and before the first of them is waited for: the kernel copies the model constants
 // (L2 -> LDS, `M` is that copy) there, so the two round trips of a wave's start-up overlap instead of following each other.
 struct NoMid { NM_FN void operator()() const {} NM_FN void operator()(int) const {} };
-template <class real, class Mid> NM_FN void env_load2(ShW<real, 2>& w, const Model<real>& M, const Args<real>& A, int wave, Mid&& mid) {
+template <bool EP, class real, class Mid> NM_FN void env_load2(ShW<real, 2>& w, const Model<real>& M, const Args<real>& A, int wave, Mid&& mid) {
   typedef V<real> vr;
   constexpr int kSR = (int)(sizeof(Sh<real>) / sizeof(real)), kSI = (int)(sizeof(Sh<real>) / sizeof(int));
   const V<int> lane = opaque_lane();
@@ -3218,6 +3255,8 @@ template <class real, class Mid> NM_FN void env_load2(ShW<real, 2>& w, const Mod
   const vr w_in = gldv(A.qwarm, sel(hl < kNV, hl, V<int>(0)) + env * kNV);
   const V<int> hc_in = gldv(A.hullcache, sel(hl < 8, hl, V<int>(0)) + env * 8);
   const V<float> a_in = gldv(A.actions, l18c + env * kNU);
+  vr envp_in = vr(real(0));
+  if constexpr (EP) envp_in = gldv(A.envp, sel(hl < kEnvP, hl, V<int>(0)) + env * kEnvP);     // each env's (mu, p_gain, kv, pad) row: 16 bytes, lanes 0..3 of its half
   vr cmd_in = vr(real(0)), eps_in = vr(real(0)), prev_act = vr(real(0)), prev_dofvel = vr(real(0)), dofpos_old = vr(real(0));
 #ifndef NM_EMUL
   int64_t ep = 0;
@@ -3245,6 +3284,13 @@ template <class real, class Mid> NM_FN void env_load2(ShW<real, 2>& w, const Mod
   w.e[0].nwarn = 0; w.e[1].nwarn = 0;
   w.e[0].nhop = 0; w.e[1].nhop = 0;
   w.e[0].ntog = 0; w.e[1].ntog = 0;
+  // per-env parameters: each env's row into its image; the servo stiffness of this step's command goes to the lanes of the env's half in
+  // registers
+  vr p_gain = vr(M.p_gain);
+  if constexpr (EP) {
+    stsv(rb, ho + (hl + NM_OFS(envp)), envp_in, hl < kEnvPS);
+    p_gain = sel(h != 0, vr(rdlane(envp_in, 32 + EP_PGAIN)), vr(rdlane(envp_in, EP_PGAIN)));
+  }
   // ---- E1 (env.py:152-156,181-192): float32 scale + clip; PD -> velocity command from the env's own dof_pos buffer
   V<float> af = a_in * M.action_scale;
   af = vmin(vmax(af, V<float>(-M.clip_actions)), V<float>(M.clip_actions));
@@ -3275,10 +3321,10 @@ template <class real, class Mid> NM_FN void env_load2(ShW<real, 2>& w, const Mod
     stsv(ib, hoi + NM_IOFS(eplen_hi), (int)(ep >> 32), hl == 0);
     stsv(ib, hoi + NM_IOFS(ectr), (int)ctr_in, hl == 0);
 #endif
-    stsv(rb, ho + (hl + NM_OFS(ctrl)), ((act - defp) - dofpos_old) * M.p_gain, l18);
+    stsv(rb, ho + (hl + NM_OFS(ctrl)), ((act - defp) - dofpos_old) * p_gain, l18);
   } else {
     wave_sync();
-    stsv(rb, ho + (hl + NM_OFS(ctrl)), ((act - defp) - ldsv(rb, ho + (l18c + (7 + NM_OFS(qpos))))) * M.p_gain, l18);
+    stsv(rb, ho + (hl + NM_OFS(ctrl)), ((act - defp) - ldsv(rb, ho + (l18c + (7 + NM_OFS(qpos))))) * p_gain, l18);
   }
   stsv(rb, ho + (hl + NM_OFS(eact)), act, l18); stsv(rb, ho + (hl + NM_OFS(epact)), prev_act, l18); stsv(rb, ho + (hl + NM_OFS(epdv)), prev_dofvel, l18);
   wave_sync();
@@ -3581,24 +3627,24 @@ template <class real, class Pub> NM_FN void env_finish2(ShW<real, 2>& w, const M
 }
 
 // one wavefront = G consecutive envs (E2, env.py:200: mj_step(model, data, decimation) between load and epilogue)
-template <class real, int G, class Mid = NoMid, class Pub = NoMid>
+template <class real, int G, bool EP = false, class Mid = NoMid, class Pub = NoMid>
 NM_FN void wave_step(ShW<real, G>& w, const Model<real>& M, const Args<real>& A, int wave, Mid&& mid = Mid(), Pub&& published = Pub()) {
   nm_stamp(-1);
   if constexpr (G == 2) {
-    env_load2(w, M, A, wave, mid);
+    env_load2<EP>(w, M, A, wave, mid);
   } else {
     mid();
 #pragma unroll
     for (int e = 0; e < G; e++) {
       int env = wave * G + e;
-      env_load(w.e[e], M, A, env < A.N ? env : A.N - 1);
+      env_load<EP>(w.e[e], M, A, env < A.N ? env : A.N - 1);
     }
   }
   nm_stamp(0);
   int dropped = 0;
   if (NM_ABLATE(A.ablate) & 1024) return;   // measurement only: load stage alone
   if (!(NM_ABLATE(A.ablate) & 2048))
-  for (int s = 0; s < A.nsub; s++) substep(w, M, s == A.nsub - 1, &dropped, NM_ABLATE(A.ablate));
+  for (int s = 0; s < A.nsub; s++) substep<EP>(w, M, s == A.nsub - 1, &dropped, NM_ABLATE(A.ablate));
   if constexpr (G == 2) {
     env_finish2(w, M, A, wave, dropped, published);
   } else {

@@ -88,7 +88,8 @@ constexpr int kWG = NM_WG_WAVES;
 #else
 constexpr int kWG = 1;
 #endif
-template <class real, int G>
+// EP: per-env physics parameters (nm::Args::envp) - the host launches the EP instantiation only while rows are set (nm_core.h env_mu)
+template <class real, int G, bool EP>
 __global__ void __launch_bounds__(64 * (sizeof(real) == 8 ? 1 : kWG), NM_WAVES_PER_SIMD) k_env_step(const nm::Model<real>* __restrict__ Mp, nm::Args<real> A) {
   constexpr int kWG = sizeof(real) == 8 ? 1 : ::kWG;     // the fp64 verification build keeps one wave per workgroup
   __shared__ nm::ShW<real, G> shs[kWG];
@@ -143,7 +144,7 @@ __global__ void __launch_bounds__(64 * (sizeof(real) == 8 ? 1 : kWG), NM_WAVES_P
       stage = 2;
     }
   };
-  nm::wave_step<real, G>(sh, Ms, As, wave, copy_model, draw);
+  nm::wave_step<real, G, EP>(sh, Ms, As, wave, copy_model, draw);
   if (As.dbg && NM_TID == 0) {   // debug buffer only: start / end clock of this wave as exact 24-bit pieces (scripts/wavetimes.py)
     const unsigned long long t_end = __builtin_amdgcn_s_memtime();
     real* d = As.dbg + (size_t)(wave * G) * nm::kDbgN + 250;
@@ -220,6 +221,48 @@ __global__ void k_finalize(int N, real* stat_sum, int* stat_cnt, float* ep_stats
   }
 }
 
+// Per-env physics parameters (nm::Args::envp rows: mu, p_gain, kv, pad), one thread per (env, column). `set`: a column comes from the
+// caller's [N] array, or is the default where there is none. `get`: the columns of the rows, or the defaults where there are no rows.
+// `draw`: lo + u (hi - lo) in the env's precision, product and sum rounded separately (contraction switched off: a host restatement in
+// plain arithmetic gives the same bits), u = rand_u24_bits(seed + kEnvParamKey, global env id, column) * 2^-24.
+template <class real> struct EnvP3 { real v[3]; };
+template <class real> struct EnvP3P { const real* p[3]; };
+template <class real> struct EnvP3W { real* p[3]; };
+template <class real>
+__global__ void k_envp_set(real* __restrict__ rows, int N, EnvP3P<real> src, EnvP3<real> dflt) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 4 * N) return;
+  const int env = i >> 2, col = i & 3;
+  real v = real(0);
+  if (col < 3) v = src.p[col] ? src.p[col][env] : dflt.v[col];
+  rows[i] = v;
+}
+template <class real>
+__global__ void k_envp_get(const real* __restrict__ rows, int N, EnvP3W<real> dst, EnvP3<real> dflt) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 4 * N) return;
+  const int env = i >> 2, col = i & 3;
+  if (col < 3 && dst.p[col]) dst.p[col][env] = rows ? rows[i] : dflt.v[col];
+}
+// (the pragma, not __fmul_rn / __fadd_rn: those are plain inline * and + here and fuse into one v_fma once inlined)
+template <class real> __device__ __forceinline__ real envp_lerp(real lo, real u, real d) {
+#pragma clang fp contract(off)
+  const real p = u * d;
+  return lo + p;
+}
+template <class real>
+__global__ void k_envp_draw(real* __restrict__ rows, int N, uint64_t seed, int64_t env_offset, EnvP3<real> lo, EnvP3<real> hi) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 4 * N) return;
+  const int env = i >> 2, col = i & 3;
+  real v = real(0);
+  if (col < 3) {
+    const real u = (real)nm::rand_u24_bits(seed + nm::kEnvParamKey, (uint64_t)(env_offset + env), (uint32_t)col) * real(1.0 / 16777216.0);
+    v = envp_lerp(lo.v[col], u, hi.v[col] - lo.v[col]);
+  }
+  rows[i] = v;
+}
+
 // ------------------------------------------------------------------------------------------------ host object
 struct nm_env {
   int N = 0, device = 0, dtype = 0;
@@ -251,6 +294,9 @@ struct nm_env {
   virtual int tape(const nm_tape_args* r, hipStream_t s) = 0;
   virtual int get_log(int first, int count, double* rows) = 0;
   virtual int get_log_dones(int first, int count, unsigned char* dones) = 0;
+  virtual int set_env_params(const void* mu, const void* p_gain, const void* kv, hipStream_t s) = 0;
+  virtual int get_env_params(void* mu, void* p_gain, void* kv, hipStream_t s) = 0;
+  virtual int draw_env_params(const double* lo, const double* hi, hipStream_t s) = 0;
   // push perturbations (nm_push.h): the setting and the push step index - full env steps taken, K per K-step launch; physics-only
   // launches and nm_reset leave it alone
   int push_interval = 0;
@@ -417,7 +463,8 @@ template <class real> struct Env : nm_env {
     }
     constexpr int G = sizeof(real) == 8 ? 1 : NM_ENVS_PER_WAVE;  // the fp64 verification build keeps one env per wave (LDS)
     constexpr int W = sizeof(real) == 8 ? 1 : kWG;
-    hipLaunchKernelGGL((k_env_step<real, G>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
+    if (a.envp) hipLaunchKernelGGL((k_env_step<real, G, true>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
+    else hipLaunchKernelGGL((k_env_step<real, G, false>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
     HIPCHK(hipGetLastError());
     if (prof_on) HIPCHK(hipEventRecord(e1, s));
     return 0;
@@ -745,6 +792,37 @@ template <class real> struct Env : nm_env {
       return 0;
     }
   }
+  // ---- per-env physics parameters: the rows live in A.envp, which every launch copies with the rest of A (null = off)
+  real* envp_dev = nullptr;
+  EnvP3<real> envp_default() const { return EnvP3<real>{{M.mu, M.p_gain, M.kv}}; }
+  int set_env_params(const void* mu, const void* p_gain, const void* kv, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (!mu && !p_gain && !kv) { A.envp = nullptr; return 0; }     // off; the rows stay allocated (a launch in flight may read them)
+    if (!envp_dev && dalloc(&envp_dev, (size_t)N * nm::kEnvP)) return 1;
+    EnvP3P<real> src{{(const real*)mu, (const real*)p_gain, (const real*)kv}};
+    hipLaunchKernelGGL(k_envp_set<real>, dim3((4 * N + 255) / 256), dim3(256), 0, s, envp_dev, N, src, envp_default());
+    HIPCHK(hipGetLastError());
+    A.envp = envp_dev;
+    return 0;
+  }
+  int get_env_params(void* mu, void* p_gain, void* kv, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (!mu && !p_gain && !kv) return 0;
+    EnvP3W<real> dst{{(real*)mu, (real*)p_gain, (real*)kv}};
+    hipLaunchKernelGGL(k_envp_get<real>, dim3((4 * N + 255) / 256), dim3(256), 0, s, A.envp, N, dst, envp_default());
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  int draw_env_params(const double* lo, const double* hi, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (!envp_dev && dalloc(&envp_dev, (size_t)N * nm::kEnvP)) return 1;
+    EnvP3<real> l, h;
+    for (int k = 0; k < 3; k++) { l.v[k] = (real)lo[k]; h.v[k] = (real)hi[k]; }
+    hipLaunchKernelGGL(k_envp_draw<real>, dim3((4 * N + 255) / 256), dim3(256), 0, s, envp_dev, N, A.seed, A.env_offset, l, h);
+    HIPCHK(hipGetLastError());
+    A.envp = envp_dev;
+    return 0;
+  }
   void set_dbg(void* p) override { A.dbg = (real*)p; }
   void set_ret_acc(float* p) override { A.ret_acc = p; }
   int invalidate_time_outs(hipStream_t s) override {
@@ -923,6 +1001,30 @@ int nm_get_push(nm_env* env, int32_t* interval_steps, double* max_vel_xy, uint64
   if (max_vel_xy) *max_vel_xy = env->push_max;
   if (step) *step = env->push_step;
   return 0;
+}
+int nm_set_env_params(nm_env* env, const void* mu_dev, const void* p_gain_dev, const void* kv_dev, void* stream) {
+  if (!env) return fail("nm_set_env_params: env is NULL");
+  return env->set_env_params(mu_dev, p_gain_dev, kv_dev, (hipStream_t)stream);
+}
+int nm_get_env_params(nm_env* env, void* mu_dev, void* p_gain_dev, void* kv_dev, void* stream) {
+  if (!env) return fail("nm_get_env_params: env is NULL");
+  return env->get_env_params(mu_dev, p_gain_dev, kv_dev, (hipStream_t)stream);
+}
+int nm_draw_env_params(nm_env* env, const double lo[3], const double hi[3], void* stream) {
+  // every refusal comes before the first device call; the bounds are judged first, so a bad range is named whatever the handle is
+  if (!lo || !hi) return fail("nm_draw_env_params: lo / hi is NULL");
+  static const char* kCol[3] = {"mu", "p_gain", "kv"};
+  for (int k = 0; k < 3; k++) {
+    if (!std::isfinite(lo[k]) || !std::isfinite(hi[k])) return fail(std::string("nm_draw_env_params: the bounds of ") + kCol[k] + " must be finite");
+    if (lo[k] > hi[k]) return fail(std::string("nm_draw_env_params: lo > hi for ") + kCol[k]);
+    if (k == 0 && !(lo[k] > 1e-5)) return fail("nm_draw_env_params: mu must be above 1e-5");
+    if (k != 0 && lo[k] < 0.0) return fail(std::string("nm_draw_env_params: ") + kCol[k] + " must not be negative");
+  }
+  if (!env) return fail("nm_draw_env_params: env is NULL");
+  if (env->dtype == NM_DTYPE_F32)
+    for (int k = 0; k < 3; k++)
+      if (!std::isfinite((float)hi[k])) return fail(std::string("nm_draw_env_params: the bounds of ") + kCol[k] + " must be finite in float32");
+  return env->draw_env_params(lo, hi, (hipStream_t)stream);
 }
 int nm_step_tape(nm_env* env, const nm_tape_args* args, void* stream) {
   if (!env) return fail("nm_step_tape: env is NULL");

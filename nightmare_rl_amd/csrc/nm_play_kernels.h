@@ -41,7 +41,7 @@ __device__ __noinline__ void play_step(float* xb, const PlayArgs* Ps, nm::Args<f
   step_close();
 }
 
-template <class S, int ACT>
+template <class S, int ACT, bool EP>      // EP: per-env physics parameters, launched only while rows are set (nm_core.h env_mu)
 __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_play(const nm::Model<float>* __restrict__ Mp, nm::Args<float> A, PlayArgs P) {
   __shared__ nm::ShW<float, 2> sh;
   __shared__ nm::Model<float> Ms;
@@ -55,14 +55,15 @@ __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_play(const nm::Mo
   const int K = P.K;
   for (int t = 0; t < K; t++) {
     play_step<S, ACT>(xb, &Ps, &As, t, wave, noise0);     // (+ the bookkeeping of step t - 1)
-    nm::wave_step<float, 2>(sh, Ms, As, wave);        // env.step: load, decimation x mj_step, epilogue - the code of k_env_step
+    nm::wave_step<float, 2, EP>(sh, Ms, As, wave);        // env.step: load, decimation x mj_step, epilogue - the code of k_env_step
   }
   books_last(&Ps, &As, K - 1, wave);
 }
 
 template <int ACT>
 int PlayKernels<ACT>::play(const nm::Model<float>* M_dev, const nm::Args<float>& a, const PlayArgs& P, hipStream_t s) {
-  hipLaunchKernelGGL((k_env_play<RefShape, ACT>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, P);
+  if (a.envp) hipLaunchKernelGGL((k_env_play<RefShape, ACT, true>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, P);
+  else hipLaunchKernelGGL((k_env_play<RefShape, ACT, false>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, P);
   return hipGetLastError() != hipSuccess;
 }
 template struct PlayKernels<NM_PLAY_ACT>;

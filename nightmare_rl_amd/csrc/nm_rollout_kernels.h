@@ -50,7 +50,7 @@ __device__ __noinline__ void value_last(float* xb, const RollArgs* Rs, const nm:
   policy_wave<S, ACT, kPolicyValueOnly>(xb, Rs->wp, Rs->bp, Rs->stdv, Rs->obs_final, As->N, wave, 0, 0, o);
 }
 
-template <class S, int ACT>
+template <class S, int ACT, bool EP>      // EP: per-env physics parameters, launched only while rows are set (nm_core.h env_mu)
 __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_rollout(const nm::Model<float>* __restrict__ Mp, nm::Args<float> A, RollArgs R) {
   __shared__ nm::ShW<float, 2> sh;
   __shared__ nm::Model<float> Ms;
@@ -65,7 +65,7 @@ __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_rollout(const nm:
   if (R.wave_clock && threadIdx.x == 0) R.wave_clock[2 * wave] = __builtin_amdgcn_s_memtime();
   for (int t = 0; t < K; t++) {
     policy_step<S, ACT>(xb, &Rs, &As, t, wave, noise0);    // (+ the record of step t - 1)
-    nm::wave_step<float, 2>(sh, Ms, As, wave);        // env.step: load, decimation x mj_step, epilogue - the code of k_env_step
+    nm::wave_step<float, 2, EP>(sh, Ms, As, wave);        // env.step: load, decimation x mj_step, epilogue - the code of k_env_step
   }
   books_last(&Rs, &As, K - 1, wave);
   if (Rs.last_values) value_last<S, ACT>(xb, &Rs, &As, wave);
@@ -88,7 +88,8 @@ int RollKernels<ACT>::act(const float* wp, const float* bp, const float* stdv, c
 }
 template <int ACT>
 int RollKernels<ACT>::rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, hipStream_t s) {
-  hipLaunchKernelGGL((k_env_rollout<RefShape, ACT>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, R);
+  if (a.envp) hipLaunchKernelGGL((k_env_rollout<RefShape, ACT, true>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, R);
+  else hipLaunchKernelGGL((k_env_rollout<RefShape, ACT, false>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, R);
   return hipGetLastError() != hipSuccess;
 }
 template struct RollKernels<NM_ROLLOUT_ACT>;

@@ -38,6 +38,7 @@ __device__ __noinline__ void tape_step(const TapeArgs* Ts, nm::Args<float>* As, 
   step_close();
 }
 
+template <bool EP>      // EP: per-env physics parameters, launched only while rows are set (nm_core.h env_mu)
 __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_tape(const nm::Model<float>* __restrict__ Mp, nm::Args<float> A, TapeArgs T) {
   __shared__ nm::ShW<float, 2> sh;
   __shared__ nm::Model<float> Ms;
@@ -49,13 +50,14 @@ __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_tape(const nm::Mo
   const int K = T.K;
   for (int t = 0; t < K; t++) {
     tape_step(&Ts, &As, t, wave, noise0);             // (+ the bookkeeping of step t - 1)
-    nm::wave_step<float, 2>(sh, Ms, As, wave);        // env.step: load, decimation x mj_step, epilogue - the code of k_env_step
+    nm::wave_step<float, 2, EP>(sh, Ms, As, wave);        // env.step: load, decimation x mj_step, epilogue - the code of k_env_step
   }
   books_last(&Ts, &As, K - 1, wave);
 }
 
 int tape_kernel(const nm::Model<float>* M_dev, const nm::Args<float>& a, const TapeArgs& T, hipStream_t s) {
-  hipLaunchKernelGGL(k_env_tape, dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, T);
+  if (a.envp) hipLaunchKernelGGL(k_env_tape<true>, dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, T);
+  else hipLaunchKernelGGL(k_env_tape<false>, dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, T);
   return hipGetLastError() != hipSuccess;
 }
 

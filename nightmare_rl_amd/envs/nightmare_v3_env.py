@@ -15,6 +15,8 @@ Differences a caller can observe (all documented in DESIGN.md):
   * an OPTIONAL `cfg.domain_rand` (push_robots, push_interval_s, max_push_vel_xy - the names of legged_gym-shaped config trees; the
     reference has none) switches on push perturbations of the base velocity (set_push); the observation returned by the step before
     a push does not show it
+  * the same optional class may carry randomize_friction / friction_range and randomize_gains / stiffness_multiplier_range /
+    damping_multiplier_range: per-env sliding friction and servo gains, drawn once at construction (set_env_params, draw_env_params)
 """
 import ctypes as C
 import numpy as np
@@ -42,6 +44,39 @@ def push_config(cfg, dt):
     if steps >= 2 ** 31:
         raise ValueError("cfg.domain_rand.push_interval_s is more than 2^31 env steps")
     return int(steps), vel
+
+
+def env_param_config(cfg):
+    """(friction_range, stiffness_multiplier_range, damping_multiplier_range) of the optional cfg.domain_rand, each a (lo, hi) pair or None:
+    what draw_env_params takes. randomize_friction needs friction_range; randomize_gains takes the multiplier ranges that are there (a
+    missing one leaves that gain alone). A range that is not two finite numbers lo <= hi, a friction at or below 1e-5 or a negative
+    multiplier is a ValueError."""
+    dr = getattr(cfg, "domain_rand", None)
+    if dr is None:
+        return None, None, None
+
+    def rng(name, lowest, strict):
+        r = getattr(dr, name, None)
+        if r is None:
+            return None
+        try:
+            lo, hi = (float(x) for x in r)
+        except (TypeError, ValueError):
+            raise ValueError(f"cfg.domain_rand.{name} must be a pair (lo, hi)") from None
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi and (lo > lowest if strict else lo >= lowest)):
+            raise ValueError(f"cfg.domain_rand.{name} must be finite with {lowest} {'<' if strict else '<='} lo <= hi")
+        return lo, hi
+
+    fr = st = da = None
+    if getattr(dr, "randomize_friction", False):
+        fr = rng("friction_range", 1e-5, True)
+        if fr is None:
+            raise ValueError("cfg.domain_rand.randomize_friction needs friction_range")
+    if getattr(dr, "randomize_gains", False):
+        st, da = rng("stiffness_multiplier_range", 0.0, False), rng("damping_multiplier_range", 0.0, False)
+        if st is None and da is None:
+            raise ValueError("cfg.domain_rand.randomize_gains needs stiffness_multiplier_range or damping_multiplier_range")
+    return fr, st, da
 
 
 class NightmareV3Env:
@@ -82,6 +117,7 @@ class NightmareV3Env:
         if int(cfg.commands.resampling_time / self.dt) < 1:
             raise ValueError("cfg.commands.resampling_time must be at least one env step (reference :235 takes a modulo by it)")
         push_steps, push_vel = push_config(cfg, self.dt)       # optional cfg.domain_rand: checked before anything is created
+        envp_ranges = env_param_config(cfg)
         # reward table: zero scales dropped, the rest x dt (reference :123-128). Every name the reference has a _reward_ function
         # for (:399-497) is compiled; a name without one (`collision`, `feet_stumble`, config :95-96) fails like upstream's getattr.
         names = [L.nm_reward_name(i).decode() for i in range(_lib.NUM_REWARDS)]
@@ -119,6 +155,7 @@ class NightmareV3Env:
         c.body_contact_mode, c.body_max_contact_force = int(cfg.env.body_contact_mode), float(cfg.env.body_max_contact_force)
         c.base_height_target, c.max_contact_force = float(cfg.rewards.base_height_target), float(cfg.rewards.max_contact_force)
         self._dtype = _lib.DTYPE_F64 if dtype == torch.float64 else _lib.DTYPE_F32
+        self._real = torch.float64 if dtype == torch.float64 else torch.float32
         h = C.c_void_p()
         self._ck(L.nm_create(C.byref(c), self.num_envs, self.device.index or 0, int(seed), int(env_id_offset), self._dtype, C.byref(h)))
         self._h = h
@@ -146,6 +183,12 @@ class NightmareV3Env:
         self.push_interval, self.max_push_vel_xy = 0, 0.0
         if push_steps:
             self.set_push(push_steps, push_vel)
+        # per-env friction and servo gains (optional cfg.domain_rand; no reference line): drawn once, here, like legged_gym's friction
+        self._envp_keep = None
+        # the library's own defaults (the model's mu and kv, the config's p_gain): what it reports while the feature is off, read once here
+        self._envp_default = tuple(float(v[0]) for v in self.env_params().values()) if hasattr(L, "nm_get_env_params") else None
+        if any(r is not None for r in envp_ranges):
+            self.draw_env_params(*envp_ranges)
         # state log of env 0 (reference :261-272; reader open_custom_play.py:50-66)
         self.state_log = None
         self._rec_env = 0
@@ -204,6 +247,43 @@ class NightmareV3Env:
         iv, mx, st = C.c_int32(0), C.c_double(0), C.c_uint64(0)
         self._ck(self._L.nm_get_push(self._h, C.byref(iv), C.byref(mx), C.byref(st)))
         return iv.value, mx.value, st.value
+
+    def set_env_params(self, mu=None, p_gain=None, kv=None):
+        """Per-env sliding friction, servo stiffness (in place of cfg.control.p_gain) and servo damping (in place of kv = 0.8), honoured by
+        step(), step_physics, policy_rollout, policy_play and step_tape alike (nm_set_env_params). Each: a tensor / array of num_envs values, a
+        scalar for every env, or None = the default. All three None switch the feature off. The values hold until they are set again (no reset
+        resamples them) and are not validated: mu <= 1e-5 or a negative gain is the caller's responsibility."""
+        cols = []
+        for x in (mu, p_gain, kv):
+            if x is None:
+                cols.append(None)
+                continue
+            t = torch.as_tensor(x, dtype=self._real).to(self.device)
+            t = t.expand(self.num_envs) if t.dim() == 0 else t.reshape(-1)
+            if t.numel() != self.num_envs:
+                raise ValueError("set_env_params: one value per env (or a scalar)")
+            cols.append(t.contiguous())
+        self._envp_keep = cols        # the copy is stream-ordered: the sources live until the next call
+        p = [C.c_void_p(t.data_ptr()) if t is not None else None for t in cols]
+        self._ck(self._L.nm_set_env_params(self._h, p[0], p[1], p[2], self._stream()))
+
+    def env_params(self):
+        """{'mu', 'p_gain', 'kv'}: tensors [num_envs] in the env's dtype (nm_get_env_params); the defaults while the feature is off."""
+        out = {k: torch.empty(self.num_envs, dtype=self._real, device=self.device) for k in ("mu", "p_gain", "kv")}
+        self._ck(self._L.nm_get_env_params(self._h, *[C.c_void_p(out[k].data_ptr()) for k in ("mu", "p_gain", "kv")], self._stream()))
+        return out
+
+    def draw_env_params(self, friction_range=None, stiffness_multiplier_range=None, damping_multiplier_range=None):
+        """Draw every env's parameters on the device (nm_draw_env_params): mu uniform in friction_range, p_gain = cfg.control.p_gain x a
+        multiplier uniform in stiffness_multiplier_range, kv = 0.8 x a multiplier uniform in damping_multiplier_range. None pins that value
+        to its default. Keyed by the global env id: shards of one population draw what the whole would."""
+        mu0, pg, kv0 = self._envp_default          # (mu, p_gain, kv) the library runs with while the feature is off
+        fr = (mu0, mu0) if friction_range is None else tuple(float(x) for x in friction_range)
+        st = (1.0, 1.0) if stiffness_multiplier_range is None else tuple(float(x) for x in stiffness_multiplier_range)
+        da = (1.0, 1.0) if damping_multiplier_range is None else tuple(float(x) for x in damping_multiplier_range)
+        lo = (C.c_double * 3)(fr[0], pg * st[0], kv0 * da[0])
+        hi = (C.c_double * 3)(fr[1], pg * st[1], kv0 * da[1])
+        self._ck(self._L.nm_draw_env_params(self._h, C.byref(lo), C.byref(hi), self._stream()))
 
     def _record_state(self):
         # reference :261-272: when env 0 resets, dump what was logged so far, then log (time, qpos, qvel, act) of env 0

@@ -7,7 +7,7 @@ once, no viewer. Like upstream the actions are SAMPLED (`nn.act`, not `act_infer
 
   python scripts/play.py [checkpoint.pt | --log-root logs/nightmare_v3] [-e 64] [--steps 1300] [--decimation 2] [--cmd 0.3 0.0 0.2]
                          [--activation elu] [--one-launch [--launch-steps K]] [--record-states DIR]
-                         [--push-interval-s S [--push-vel V]]
+                         [--push-interval-s S [--push-vel V]] [--friction-range LO HI] [--gain-range LO HI]
 
 --one-launch runs the same loop inside the env's own wavefronts (NightmareV3Env.policy_play -> nm_play: policy and step, K steps per
 launch, no host round trip per step) and prints the same summary from the device bookkeeping; the actions are then drawn by the
@@ -104,6 +104,9 @@ def main():
     ap.add_argument("--record-states", default=None, metavar="DIR", help="write upstream's state log of env 0 (pickle files) into DIR")
     ap.add_argument("--push-interval-s", type=float, default=0.0, help="push every robot's base velocity every S seconds (0 = off, the default)")
     ap.add_argument("--push-vel", type=float, default=1.0, help="max |vx|, |vy| of a push in m/s")
+    ap.add_argument("--friction-range", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="per-env sliding friction, drawn once from U[LO, HI) (default: 1.0)")
+    ap.add_argument("--gain-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="per-env multipliers of the servo stiffness and damping, each drawn once from U[LO, HI) (default: 1.0)")
     a = ap.parse_args()
     path = a.checkpoint or get_load_path(a.log_root)
     dev = torch.device("cuda", 0)
@@ -113,12 +116,17 @@ def main():
         cfg.control.decimation = a.decimation
     if a.record_states is not None:
         cfg.viewer.record_states = True
-    if a.push_interval_s > 0:
+    if a.push_interval_s > 0 or a.friction_range or a.gain_range:
         class domain_rand:      # the optional class NightmareV3Env reads
-            push_robots, push_interval_s, max_push_vel_xy = True, a.push_interval_s, a.push_vel
+            push_robots, push_interval_s, max_push_vel_xy = a.push_interval_s > 0, a.push_interval_s, a.push_vel
+            randomize_friction, friction_range = a.friction_range is not None, a.friction_range
+            randomize_gains = a.gain_range is not None
+            stiffness_multiplier_range = damping_multiplier_range = a.gain_range
         cfg.domain_rand = domain_rand
     env = NightmareV3Env(cfg, device=dev, seed=a.seed, **({"log_dir": a.record_states} if a.record_states is not None else {}))
     print(f"push perturbations: every {env.push_interval} steps, |v| < {env.max_push_vel_xy} m/s" if env.push_interval else "push perturbations: off")
+    if a.friction_range or a.gain_range:
+        print(f"per-env friction range {a.friction_range or 'off'}, gain multiplier range {a.gain_range or 'off'}")
     if a.one_launch:
         return play_one_launch(a, path, env, cfg, dev)
     net, std = actor_from_checkpoint(path, dev, a.activation)

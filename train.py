@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """train.py - the reference's training entry point (reference train.py:1-54) on the MI355X backend.
 Same flags (-r resume, -v render [rejected: no viewer], -n num_threads [accepted, unused], -e envs, -p resume_path) plus
---iters / --seed / --gpus / --push-interval-s / --push-vel. Multi-GPU: `python train.py --gpus G -e <total envs>` (starts its G ranks as child processes) or
+--iters / --seed / --gpus / --push-interval-s / --push-vel / --friction-range / --gain-range. Multi-GPU: `python train.py --gpus G -e <total envs>` (starts its G ranks as child processes) or
 `python -m torch.distributed.run --nproc-per-node G train.py -e <total envs>`."""
 import argparse
 import datetime
@@ -30,6 +30,10 @@ def main():
     ap.add_argument("--push-interval-s", type=float, default=0.0, dest="push_interval_s",
                     help="push perturbations: seconds between two pushes of every robot's base velocity (0 = off, the default)")
     ap.add_argument("--push-vel", type=float, default=1.0, dest="push_vel", help="push perturbations: max |vx|, |vy| of a push in m/s")
+    ap.add_argument("--friction-range", type=float, nargs=2, default=None, metavar=("LO", "HI"), dest="friction_range",
+                    help="per-env sliding friction, drawn once from U[LO, HI) (default: 1.0 in every env)")
+    ap.add_argument("--gain-range", type=float, nargs=2, default=None, metavar=("LO", "HI"), dest="gain_range",
+                    help="per-env multipliers of the servo stiffness (p_gain) and damping (kv), each drawn once from U[LO, HI) (default: 1.0)")
     ap.add_argument("--gpus", type=int, default=None, help="ranks (one per GPU); without torch.distributed.run, train.py starts them itself")
     args = ap.parse_args()
 
@@ -62,9 +66,12 @@ def main():
     cfg, train_cfg = NightmareV3Config(), NightmareV3ConfigPPO()
     cfg.viewer.render = args.render
     cfg.viewer.record_states = bool(args.record_states) and rank == 0        # one log: rank 0's env 0
-    if args.push_interval_s > 0:
+    if args.push_interval_s > 0 or args.friction_range or args.gain_range:
         class domain_rand:      # the optional class NightmareV3Env reads
-            push_robots, push_interval_s, max_push_vel_xy = True, args.push_interval_s, args.push_vel
+            push_robots, push_interval_s, max_push_vel_xy = args.push_interval_s > 0, args.push_interval_s, args.push_vel
+            randomize_friction, friction_range = args.friction_range is not None, args.friction_range
+            randomize_gains = args.gain_range is not None
+            stiffness_multiplier_range = damping_multiplier_range = args.gain_range
         cfg.domain_rand = domain_rand
     lo, hi = shard_range(args.num_envs, rank, world)
     cfg.env.num_envs = hi - lo
@@ -74,6 +81,8 @@ def main():
     env = NightmareV3Env(cfg, log_dir=log_dir, num_threads=args.num_threads, device=f"cuda:{local_rank}", seed=seed, env_id_offset=lo)
     if rank == 0:
         print(f"push perturbations: every {env.push_interval} steps, |v| < {env.max_push_vel_xy} m/s" if env.push_interval else "push perturbations: off", flush=True)
+        if args.friction_range or args.gain_range:
+            print(f"per-env friction range {args.friction_range or 'off'}, gain multiplier range {args.gain_range or 'off'}", flush=True)
     runner = OnPolicyRunner(env, class_to_dict(train_cfg), log_dir=log_dir, device=f"cuda:{local_rank}")
     if train_cfg.runner.resume:
         path = get_load_path(args.resume_path or log_root, load_run=train_cfg.runner.load_run, checkpoint=train_cfg.runner.checkpoint)
