@@ -156,6 +156,31 @@ int nm_get_push(nm_env* env, int32_t* interval_steps, double* max_vel_xy, uint64
 int nm_set_env_params(nm_env* env, const void* mu_dev, const void* p_gain_dev, const void* kv_dev, void* stream);
 int nm_get_env_params(nm_env* env, void* mu_dev, void* p_gain_dev, void* kv_dev, void* stream);
 int nm_draw_env_params(nm_env* env, const double lo[3], const double hi[3], void* stream);
+/* Per-env base payload - the `domain_rand.randomize_base_mass` / `added_mass_range` and `randomize_com_displacement` of legged_gym-shaped
+ * config trees. There is no reference line: upstream shares one MjModel among all envs and has no payload.
+ * Semantics: a payload is a point mass dm (kg, may be negative) rigidly attached to the base body at r (m, base body frame). An env with
+ * payload (dm, r) behaves as if mjmodel.xml had been recompiled with that mass added to base_link: NOTHING stays stale. Per env change
+ *   the base body: m' = m + dm, ipos' = (m ipos + dm r) / m', I' = I + m P(ipos - ipos') + dm P(r - ipos'), P(d) = (d.d) 1 - d d'
+ *     (body frame, about the new COM);
+ *   total_mass (subtree COM, cvel of the base);
+ *   body_invweight0[b][0] of the 7 colliding bodies (base and six tibias: the base floats, so the tibias' values move too);
+ *   pgs_scale = 1 / (meaninertia' nv), the scale of the six PGS / NoSlip exit tests.
+ * Link bodies, hull tables, rbound, qpos0, the reset pose and every config value do not change. A row (20 words in the env's dtype) is
+ *   ipos[3], I[6] (xx yy zz xy xz yz), mass, total_mass, invweight0[7] (base, tibia 1..6), pgs_scale, pad
+ * and is derived on the host (nightmare_rl_amd/model/payload.py payload_rows). Rows hold until the caller changes them; no reset touches
+ * them. It works alike in nm_step, nm_step_physics, nm_rollout, nm_play and nm_step_tape, alone or with nm_set_env_params. Off is the
+ * default, and off equals "on with the default row in every env" bit for bit.
+ * nm_set_body_params: `rows` is a DEVICE array [N,20] in the env's dtype, copied on `stream`; NULL switches the feature off (nothing is
+ *   freed). Refused, named by nm_last_error, before anything of the env changes (the rows are read back and judged on the host, which
+ *   waits for `stream`): a non-finite word, mass <= 0, total_mass < mass, a non-positive inertia diagonal, invweight0 or pgs_scale.
+ * nm_get_body_params: the rows into a DEVICE array [N,20] on `stream`; the model's own row for every env while the feature is off.
+ * nm_draw_payload: out[e] = (dm, rx, ry, rz), value = lo[c] + u (hi[c] - lo[c]) in the env's precision, product and sum rounded
+ *   separately, u ~ U[0,1) from the counter RNG keyed by (seed + "PAYLO", global env id, c): sharding changes nothing; lo == hi pins a
+ *   column. `out` is a DEVICE array [N,4]; the env itself is not changed (derive rows from the draw, then nm_set_body_params). Refused
+ *   before any device call: non-finite bounds, lo > hi. */
+int nm_set_body_params(nm_env* env, const void* rows_dev, void* stream);
+int nm_get_body_params(nm_env* env, void* out_dev, void* stream);
+int nm_draw_payload(nm_env* env, const double lo[4], const double hi[4], void* out_dev, void* stream);
 /* State log (envs/nightmare_v3_env.py:261-272 records data[0]): env_index >= 0 makes every nm_step keep that env's
  * post-physics, pre-reset qpos/qvel; -1 = off. nm_get_state_record copies the last record to HOST qpos[25], qvel[24] and
  * the number of MuJoCo bad-state resets inside that step (data.time restarts there). Synchronous. */

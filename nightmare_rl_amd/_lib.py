@@ -28,7 +28,8 @@ EXPORTS = ["nm_default_config", "nm_reward_name", "nm_last_error", "nm_create", 
            "nm_get_state_log", "nm_get_state_log_dones", "nm_play", "nm_play_supported",
            "nm_nik_create", "nm_nik_destroy", "nm_nik_reset", "nm_nik_set_gait", "nm_nik_update", "nm_nik_get_state",
            "nm_step_tape", "nm_nik_tape", "nm_set_push", "nm_get_push",
-           "nm_set_env_params", "nm_get_env_params", "nm_draw_env_params"]
+           "nm_set_env_params", "nm_get_env_params", "nm_draw_env_params",
+           "nm_set_body_params", "nm_get_body_params", "nm_draw_payload"]
 
 
 class NmConfig(C.Structure):
@@ -171,6 +172,10 @@ def _bind(L, full):
         L.nm_set_env_params.argtypes = [vp, vp, vp, vp, vp]
         L.nm_get_env_params.argtypes = [vp, vp, vp, vp, vp]
         L.nm_draw_env_params.argtypes = [vp, C.POINTER(C.c_double * 3), C.POINTER(C.c_double * 3), vp]
+    if hasattr(L, "nm_set_body_params"):
+        L.nm_set_body_params.argtypes = [vp, vp, vp]
+        L.nm_get_body_params.argtypes = [vp, vp, vp]
+        L.nm_draw_payload.argtypes = [vp, C.POINTER(C.c_double * 4), C.POINTER(C.c_double * 4), vp, vp]
     if not full:        # the measurement build holds the env entry points only
         return L
     L.nm_gae.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_float, vp, vp]

@@ -131,13 +131,18 @@ template <class real> struct Args {
   // state log of one env (env.py:261-272): post-physics, pre-reset qpos[25] qvel[24] + bad-state-reset count; null = off
   real* rec;
   // per-env physics parameters (friction and servo-gain randomisation): [N,4] rows (mu, p_gain, kv, pad), 16 bytes; null = off, every env
-  // takes M.mu / M.p_gain / M.kv
+  // takes M.mu / M.p_gain / M.kv. While per-env body rows are set (base payload, level EP = 2 of the step) the same allocation goes on
+  // behind the N envp rows with [N,kBodyP] body rows, at envp + N * kEnvP: the struct has no word left for a pointer of their own
   const real* envp;
 };
 constexpr int kTicketGroup = 64, kTicketStride = 32, kTicketTop = 0;   // group g's counter at [(g + 1) * kTicketStride] (own 128 B line)
 constexpr uint64_t kNoiseKey = 0x4E4F495345ull;
 constexpr uint64_t kEnvParamKey = 0x454E5650ull;   // nm_draw_env_params: rand_u24_bits(seed + kEnvParamKey, global env id, column)
 constexpr int EP_MU = 0, EP_PGAIN = 1, EP_KV = 2, kEnvP = 4, kEnvPS = 3;   // columns of an Args::envp row (the fourth is padding) and of Sh::envp
+// Per-env body rows (base payload: a point mass on the base body, compiled in - nm_set_body_params): what of the model differs in an
+// env whose base carries a payload. ipos3 I6 mass are basec's ten words in basec's order; invweight0 in the collision table's order.
+constexpr int kBodyP = 20, BP_IPOS = 0, BP_I6 = 3, BP_MASS = 9, BP_TOTAL = 10, BP_INVW = 11, BP_PGS = 18;
+constexpr uint64_t kPayloadKey = 0x5041594C4Full;   // nm_draw_payload: rand_u24_bits(seed + kPayloadKey, global env id, column)
 constexpr int kDbgN = 256;
 
 // ----------------------------------------------------------------------------------------- LDS image of one env
@@ -195,14 +200,50 @@ template <class real, int G> struct ShW {
   Sh<real> e[G];
   alignas(16) real jrow[kMaxRow * kJRow];
 };
+// Level 2 of the step (per-env body rows) keeps the G rows of the wave's envs in LDS right behind the wave's images: a kernel of that
+// level declares ShWB and hands its `w` on; body_rows() finds the block again. The lower levels declare ShW alone and never call it.
+template <class real, int G> struct ShWB {
+  ShW<real, G> w;
+  real body[G * kBodyP];
+};
+template <class real, int G> NM_FN real* body_rows(ShW<real, G>& w) { return reinterpret_cast<ShWB<real, G>*>(&w)->body; }
+// what a kernel of level EP declares in LDS, and the wave's images in it
+template <class real, int G, int EP> struct ShWSel {
+  typedef ShW<real, G> type;
+  static NM_FN ShW<real, G>& images(type& s) { return s; }
+};
+template <class real, int G> struct ShWSel<real, G, 2> {
+  typedef ShWB<real, G> type;
+  static NM_FN ShW<real, G>& images(type& s) { return s.w; }
+};
 #define NM_OFS(field) ((int)(offsetof(Sh<real>, field) / sizeof(real)))
 #define NM_IOFS(field) ((int)(offsetof(Sh<real>, field) / sizeof(int)))
 
-// Per-env parameters are a template parameter EP of the step: the default instantiation (EP = false, launched while no rows are set)
-// reads M.mu / M.kv / M.p_gain exactly as before and never touches Sh::envp or Args::envp - its instruction stream is the one it had
-// before the feature; the EP = true instantiation, launched when rows are set, reads the env image.
-template <bool EP, class real> NM_FN real env_mu(const Sh<real>& sh, const Model<real>& M) {
-  if constexpr (EP) return sh.envp[EP_MU]; else return M.mu;
+// Per-env parameters are a template parameter EP of the step, a level: 0 (launched while no rows are set) reads M.mu / M.kv / M.p_gain
+// exactly as before and never touches Sh::envp or Args::envp - its instruction stream is the one it had before the feature; 1, launched
+// when friction / gain rows are set, reads them from the env image; 2, launched while body rows are set, does that and takes the base
+// body's constants, total_mass, the colliding bodies' invweight0 and pgs_scale from the env's body row (the host supplies default envp
+// rows when only a payload is set).
+template <int EP, class real> NM_FN real env_mu(const Sh<real>& sh, const Model<real>& M) {
+  if constexpr (EP != 0) return sh.envp[EP_MU]; else return M.mu;
+}
+// The body row of ONE env, handed to the stages that take one env at a time. Below level 2 it is an empty object: the out-of-line
+// stages keep their argument registers.
+template <int EP, class real> struct BodyRef {
+  NM_FN BodyRef() {}
+  NM_FN explicit BodyRef(const real*) {}
+};
+template <class real> struct BodyRef<2, real> {
+  const real* p;
+  NM_FN BodyRef() : p(nullptr) {}
+  NM_FN explicit BodyRef(const real* q) : p(q) {}
+};
+// body_invweight0[.][0] of colliding mesh g (0 = base, 1..6 = tibias), per lane
+template <int EP, class real> NM_FN V<real> body_invw(const BodyRef<EP, real>& b, const Model<real>& M, const V<int>& g) {
+  if constexpr (EP == 2) return ldsv(b.p, g + BP_INVW); else return ldsv(M.colc, g * kColN + 4);
+}
+template <int EP, class real> NM_FN real body_pgs(const BodyRef<EP, real>& b, const Model<real>& M) {
+  if constexpr (EP == 2) return b.p[BP_PGS]; else return M.pgs_scale;
 }
 
 // ----------------------------------------------------------------------------------------- small algebra
@@ -398,7 +439,7 @@ template <class real> NM_FN V<real> legsum(const V<real>& x, const VB& isleg) { 
   return gsum8(sel(isleg, x, V<real>(real(0))));
 }
 
-template <bool EP, class real, int G> NM_FN void stage_smooth(ShW<real, G>& w, const Model<real>& M, bool last) {
+template <int EP, class real, int G> NM_FN void stage_smooth(ShW<real, G>& w, const Model<real>& M, bool last) {
   typedef V<real> vr;
   real* lds = reinterpret_cast<real*>(&w.e[0]);
   // Lane groups of 8: group g works on env g % G; groups [0, G) factor M, groups [G, 2G) factor M + h*kv*I (implicitfast) - the two
@@ -411,6 +452,9 @@ template <bool EP, class real, int G> NM_FN void stage_smooth(ShW<real, G>& w, c
   const VB pass1 = (grp & G) != 0;
   const VB isleg = sub < V<int>(6);
 #define LDG(field, i) ldsv(lds, eo + (NM_OFS(field) + (i)))
+  // level 2: word i of the body row of the lane group's env (the rows lie behind the wave's images, body_rows)
+  const V<int> bo = (grp & (G - 1)) * kBodyP + (int)(sizeof(ShW<real, G>) / sizeof(real));
+#define LDB(i) ldsv(lds, bo + (i))
   // Stores of this stage are NOT masked: the lanes outside the legs / the first lane of a group hold exact duplicates (sub 6, 7 compute
   // leg 5 again, per-env values are computed by all eight lanes of every group of the env), so they write the same value to
   // the same address. A masked store is an exec-mask branch: 70 of them cut this stage into ~45-instruction scheduling regions.
@@ -583,6 +627,13 @@ template <bool EP, class real, int G> NM_FN void stage_smooth(ShW<real, G>& w, c
 #pragma unroll
         for (int j = 0; j < 6; j++) Ib[j] = ldsv(M.legc, cbm + 18 + j);
         vr mass = ldsv(M.legc, cbm + 24);
+        if constexpr (EP == 2) {   // the base-role lanes take ipos / Ibody / mass from their env's body row instead of M.basec
+#pragma unroll
+          for (int j = 0; j < 3; j++) ipos[j] = sel(isbase, LDB(BP_IPOS + j), ipos[j]);
+#pragma unroll
+          for (int j = 0; j < 6; j++) Ib[j] = sel(isbase, LDB(BP_I6 + j), Ib[j]);
+          mass = sel(isbase, LDB(BP_MASS), mass);
+        }
         vr d[3], t3[3];
         matvec3(t3, cR, ipos);
         d[0] = cpos[0] + t3[0]; d[1] = cpos[1] + t3[1]; d[2] = cpos[2] + t3[2];
@@ -654,11 +705,15 @@ template <bool EP, class real, int G> NM_FN void stage_smooth(ShW<real, G>& w, c
     for (int j = 0; j < 10; j++) Ib10[j] = LDG(sc, 15 + j);
     if (last) {  // subtree COM (relative to the base origin) -> cvel[1] as MuJoCo reports it (about the COM)
       vr ipos[3] = {vr(M.basec[0]), vr(M.basec[1]), vr(M.basec[2])};
+      if constexpr (EP == 2) { ipos[0] = LDB(BP_IPOS); ipos[1] = LDB(BP_IPOS + 1); ipos[2] = LDB(BP_IPOS + 2); }
       vr d[3];
       matvec3(d, Rb, ipos);
       vr cr[3], t[3];
 #pragma unroll
-      for (int j = 0; j < 3; j++) cr[j] = (M.basec[9] * d[j] + (LDG(sc, j) + LDG(sc, 3 + j) + LDG(sc, 6 + j))) / M.total_mass;
+      for (int j = 0; j < 3; j++) {
+        if constexpr (EP == 2) cr[j] = (LDB(BP_MASS) * d[j] + (LDG(sc, j) + LDG(sc, 3 + j) + LDG(sc, 6 + j))) / LDB(BP_TOTAL);
+        else cr[j] = (M.basec[9] * d[j] + (LDG(sc, j) + LDG(sc, 3 + j) + LDG(sc, 6 + j))) / M.total_mass;
+      }
       cross3(t, vb, cr);
 #pragma unroll
       for (int j = 0; j < 3; j++) { STG(cvb, j, vb[j]); STG(cvb, 3 + j, vb[3 + j] + t[j]); }
@@ -713,7 +768,7 @@ template <bool EP, class real, int G> NM_FN void stage_smooth(ShW<real, G>& w, c
     const V<int> eoA = eo + sel(pass1, V<int>(NM_OFS(legtmp) + 60), V<int>(NM_OFS(qas)));
     vr Mh[6];
     vr dg;
-    if constexpr (EP) dg = sel(pass1, M.h * LDG(envp, EP_KV), vr(real(0)));   // the env's own kv: lanes 8g..8g+7 are env g % G
+    if constexpr (EP != 0) dg = sel(pass1, M.h * LDG(envp, EP_KV), vr(real(0)));   // the env's own kv: lanes 8g..8g+7 are env g % G
     else dg = sel(pass1, vr(M.h * M.kv), vr(real(0)));
     Mh[0] = Ml[0] + dg; Mh[1] = Ml[1]; Mh[2] = Ml[2]; Mh[3] = Ml[3] + dg; Mh[4] = Ml[4]; Mh[5] = Ml[5] + dg;
     vr Mi[6], W[3][6];
@@ -753,7 +808,7 @@ template <bool EP, class real, int G> NM_FN void stage_smooth(ShW<real, G>& w, c
       for (int k = 0; k < 3; k++) {
         vr ctrl = LDL(ctrl, leg * 3 + k), qd = LDL(qvel, leg * 3 + (6 + k));
         ctrl = vmin(vmax(ctrl, vr(-M.ctrl_max)), vr(M.ctrl_max));
-        if constexpr (EP) {
+        if constexpr (EP != 0) {
           const vr kv = LDG(envp, EP_KV);
           y[k] = kv * ctrl - kv * qd - cl[k];
         } else y[k] = M.kv * ctrl - M.kv * qd - cl[k];
@@ -781,6 +836,7 @@ template <bool EP, class real, int G> NM_FN void stage_smooth(ShW<real, G>& w, c
   }
   wave_sync();
 #undef LDG
+#undef LDB
 #undef STG
 #undef LDL
 #undef STL
@@ -1481,7 +1537,7 @@ template <class X> NM_FN X noslip_pair_cost(const X& d, const X& hK1, const X& d
 template <class real, class X> NM_FN auto noslip_pair_bad(const X& change) { return change > X(real(1e-10)); }   // costChange: revert an update that does not decrease the cost
 
 // Contact rows on lanes: build, project (A = J M^-1 J'), warm start, PGS, NoSlip, map back, sensors.
-template <class real, bool PAIR, bool EP> NM_FN void stage_constraint_body(Sh<real>& sh, real* jrow, const Model<real>& M, bool last, bool nosweep) {
+template <class real, bool PAIR, int EP> NM_FN void stage_constraint_body(Sh<real>& sh, real* jrow, const Model<real>& M, bool last, bool nosweep, BodyRef<EP, real> br) {
   typedef V<real> vr;
   const V<int> lane = lane_id();
   const int ncon = uniform(sh.ncon), nefc = 4 * ncon;
@@ -1625,8 +1681,8 @@ template <class real, bool PAIR, bool EP> NM_FN void stage_constraint_body(Sh<re
     imp = sel(x >= vr(real(1)), vr(M.si_dmax), imp);
     imp = sel(x <= vr(real(0)), vr(M.si_d0), imp);
   }
-  vr invw = ldsv(M.colc, (Lc + sel(onleg, V<int>(1), V<int>(0))) * kColN + 4);
-  if (anypair) invw = invw + sel(onleg1, ldsv(M.colc, (Lc1 + 1) * kColN + 4), vr(real(0)));
+  vr invw = body_invw(br, M, Lc + sel(onleg, V<int>(1), V<int>(0)));
+  if (anypair) invw = invw + sel(onleg1, body_invw(br, M, Lc1 + 1), vr(real(0)));
   vr Rr = vmax((vr(real(1)) - imp) * (invw + env_mu<EP>(sh, M) * env_mu<EP>(sh, M) * invw) * vrcp(imp), vr(real(1e-15))) * (real(2) * env_mu<EP>(sh, M) * env_mu<EP>(sh, M));
   vr Dd = vrcp(Rr);
   // sparse dots with the wave-uniform vectors qvel, qacc_smooth, qacc_warmstart
@@ -1762,7 +1818,7 @@ template <class real, bool PAIR, bool EP> NM_FN void stage_constraint_body(Sh<re
     const vr ccap = pgs_row_cost(dcap, hA, gcap, Rr, f);
     f = f + dcap;
     sh.it_pgs = iter + 1;
-    if (-wsum<real>(ccap) * M.pgs_scale < M.pgs_tol) break;
+    if (-wsum<real>(ccap) * body_pgs(br, M) < M.pgs_tol) break;
   }
   nm_stamp(6);
   // ---- mj_solNoSlip: per opposing pyramid pair (lanes 2p, 2p+1), exact 1-D minimisation along (f0 - f1) without R.
@@ -1813,7 +1869,7 @@ template <class real, bool PAIR, bool EP> NM_FN void stage_constraint_body(Sh<re
       f = f + dcap;
       improvement = improvement - wsum<real>(sel(even, noslip_pair_cost(dcap, hK1, dgcap), vr(real(0))));     // a reverted pair kept d = 0: no change
       sh.it_noslip = iter + 1;
-      if (improvement * M.pgs_scale < M.noslip_tol) break;
+      if (improvement * body_pgs(br, M) < M.noslip_tol) break;
     }
   }
   nm_stamp(7);
@@ -1899,8 +1955,8 @@ template <class real, bool PAIR, bool EP> NM_FN void stage_constraint_body(Sh<re
   wave_sync();
 }
 
-template <class real, bool EP> NM_COLD void stage_constraint_pairs(Sh<real>& sh, real* jrow, const Model<real>& M, bool last, bool nosweep) {
-  stage_constraint_body<real, true, EP>(sh, jrow, M, last, nosweep);
+template <class real, int EP> NM_COLD void stage_constraint_pairs(Sh<real>& sh, real* jrow, const Model<real>& M, bool last, bool nosweep, BodyRef<EP, real> br) {
+  stage_constraint_body<real, true, EP>(sh, jrow, M, last, nosweep, br);
 }
 
 // =========================================================================================  stage C, two envs at once
@@ -1914,7 +1970,7 @@ constexpr int kMaxCon2 = 8, kMaxRow2 = 4 * kMaxCon2;
 #ifdef NM_EMUL
 inline long& nm_emul_together() { static long n = 0; return n; }   // host emulation only: how often the two-env pass ran (tests assert it did)
 #endif
-template <bool EP, class real> NM_FN void stage_constraint2(ShW<real, 2>& w, const Model<real>& M, bool last, bool nosweep) {
+template <int EP, class real> NM_FN void stage_constraint2(ShW<real, 2>& w, const Model<real>& M, bool last, bool nosweep) {
   typedef V<real> vr;
   constexpr int kSR = (int)(sizeof(Sh<real>) / sizeof(real)), kSI = (int)(sizeof(Sh<real>) / sizeof(int));
   const V<int> lane = lane_id();
@@ -1950,8 +2006,14 @@ template <bool EP, class real> NM_FN void stage_constraint2(ShW<real, 2>& w, con
   const V<int> q4 = hl & 3;
   // the friction of the half's env, per lane; read again at every use (an LDS read each, as M.mu was) so that no register holds it
   // across the row build
-  auto mu2 = [&]() -> vr { if constexpr (EP) return SHR(envp, V<int>(EP_MU)); else return vr(M.mu); };
+  auto mu2 = [&]() -> vr { if constexpr (EP != 0) return SHR(envp, V<int>(EP_MU)); else return vr(M.mu); };
 #define MU2 mu2()
+  // level 2: the body rows of the two envs (body_rows), the half's own through hb; pgs_scale of the half's env per lane
+  const real* bp2 = nullptr;
+  if constexpr (EP == 2) bp2 = body_rows(w);
+  const V<int> hb = h * kBodyP;
+  auto pgs2 = [&]() { if constexpr (EP == 2) return ldsv(bp2, hb + BP_PGS); else return M.pgs_scale; };
+#define PGS2 pgs2()
   vr smu = sel(sg == 0, MU2, -MU2);
   vr nrm[3] = {vr(real(0)), vr(real(0)), vr(real(1))};
   vr e[3] = {sel(q4 == 2, vr(real(-1)), vr(real(0))), sel(q4 == 1, vr(real(1)), vr(real(0))), sel((q4 == 0) | (q4 == 3), vr(real(1)), vr(real(0)))};
@@ -2020,7 +2082,9 @@ template <bool EP, class real> NM_FN void stage_constraint2(ShW<real, 2>& w, con
     imp = sel(x >= vr(real(1)), vr(M.si_dmax), imp);
     imp = sel(x <= vr(real(0)), vr(M.si_d0), imp);
   }
-  vr invw = ldsv(M.colc, (Lc + sel(onleg, V<int>(1), V<int>(0))) * kColN + 4);
+  vr invw;
+  if constexpr (EP == 2) invw = ldsv(bp2, hb + (Lc + sel(onleg, V<int>(1), V<int>(0)) + BP_INVW));   // the half's env's own invweight0
+  else invw = ldsv(M.colc, (Lc + sel(onleg, V<int>(1), V<int>(0))) * kColN + 4);
   vr Rr = vmax((vr(real(1)) - imp) * (invw + MU2 * MU2 * invw) * vrcp(imp), vr(real(1e-15))) * (real(2) * MU2 * MU2);
   vr Dd = vrcp(Rr);
   vr vel = vr(real(0)), jas = vr(real(0)), jaw = vr(real(0));
@@ -2125,7 +2189,7 @@ template <bool EP, class real> NM_FN void stage_constraint2(ShW<real, 2>& w, con
       const vr ccap = pgs_row_cost(dcap, hA, gcap, Rr, f);
       f = f + dcap;
       itp = itp + sel(run, V<int>(1), V<int>(0));
-      run = run & !((-hsum32(ccap)) * M.pgs_scale < vr(M.pgs_tol));
+      run = run & !((-hsum32(ccap)) * PGS2 < vr(M.pgs_tol));
       if (!wany(run)) break;
     }
   }
@@ -2181,7 +2245,7 @@ template <bool EP, class real> NM_FN void stage_constraint2(ShW<real, 2>& w, con
       f = f + dcap;
       improvement = improvement - hsum32(sel(even, noslip_pair_cost(dcap, hK1, dgcap), vr(real(0))));
       itn = itn + sel(run, V<int>(1), V<int>(0));
-      run = run & !(improvement * M.pgs_scale < vr(M.noslip_tol));
+      run = run & !(improvement * PGS2 < vr(M.noslip_tol));
       if (!wany(run)) break;
     }
   }
@@ -2249,6 +2313,7 @@ template <bool EP, class real> NM_FN void stage_constraint2(ShW<real, 2>& w, con
   }
   wave_sync();
 #undef MU2
+#undef PGS2
 #undef SHR
 #undef SHI
 }
@@ -2347,7 +2412,7 @@ template <class real> NM_FN void big_jtf(Sh<real>& sh, const BigRows<real>& r) {
     }
   wave_sync();
 }
-template <class real, bool EP> NM_COLD void stage_constraint_big(Sh<real>& sh, const Model<real>& M, bool last, bool nosweep) {
+template <class real, int EP> NM_COLD void stage_constraint_big(Sh<real>& sh, const Model<real>& M, bool last, bool nosweep, BodyRef<EP, real> br) {
   typedef V<real> vr;
   const V<int> lane = opaque_lane();
   const int ncon = uniform(sh.ncon), nefc = 4 * ncon;
@@ -2439,8 +2504,8 @@ template <class real, bool EP> NM_COLD void stage_constraint_big(Sh<real>& sh, c
       imp = sel(x >= vr(real(1)), vr(M.si_dmax), imp);
       imp = sel(x <= vr(real(0)), vr(M.si_d0), imp);
     }
-    vr invw = ldsv(M.colc, (Lc + sel(onleg, V<int>(1), V<int>(0))) * kColN + 4);
-    invw = invw + sel(onleg1, ldsv(M.colc, (Lc1 + 1) * kColN + 4), vr(real(0)));
+    vr invw = body_invw(br, M, Lc + sel(onleg, V<int>(1), V<int>(0)));
+    invw = invw + sel(onleg1, body_invw(br, M, Lc1 + 1), vr(real(0)));
     const vr Rr = vmax((vr(real(1)) - imp) * (invw + env_mu<EP>(sh, M) * env_mu<EP>(sh, M) * invw) * vrcp(imp), vr(real(1e-15))) * (real(2) * env_mu<EP>(sh, M) * env_mu<EP>(sh, M));
     vr vel = vr(real(0)), jas = vr(real(0)), jaw = vr(real(0));
 #pragma unroll
@@ -2532,7 +2597,7 @@ template <class real, bool EP> NM_COLD void stage_constraint_big(Sh<real>& sh, c
       }
     }
     sh.it_pgs = iter + 1;
-    if (improvement * M.pgs_scale < M.pgs_tol) break;
+    if (improvement * body_pgs(br, M) < M.pgs_tol) break;
   }
   // ---- mj_solNoSlip, pair by pair (the Newton form derived above)
   for (int iter = 0; iter < (nosweep ? 0 : M.noslip_iters); iter++) {
@@ -2570,7 +2635,7 @@ template <class real, bool EP> NM_COLD void stage_constraint_big(Sh<real>& sh, c
       }
     }
     sh.it_noslip = iter + 1;
-    if (improvement * M.pgs_scale < M.noslip_tol) break;
+    if (improvement * body_pgs(br, M) < M.noslip_tol) break;
   }
   // ---- qfrc_constraint = J' f and the touch sensors
   big_jtf(sh, r);
@@ -2632,10 +2697,10 @@ template <class real> NM_COLD void floor_frames(Sh<real>& sh) {
   stsv(sh.cnrm(), c * 3 + 2, V<real>(real(1)), on);
   wave_sync();
 }
-template <class real, bool EP> NM_FN void stage_constraint(Sh<real>& sh, real* jrow, const Model<real>& M, bool last, bool nosweep = false) {
-  if (uniform(sh.ncon) > kMaxCon) { floor_frames(sh); stage_constraint_big<real, EP>(sh, M, last, nosweep); }
-  else if (uniform(sh.anypair) != 0) { floor_frames(sh); stage_constraint_pairs<real, EP>(sh, jrow, M, last, nosweep); }
-  else stage_constraint_body<real, false, EP>(sh, jrow, M, last, nosweep);
+template <class real, int EP> NM_FN void stage_constraint(Sh<real>& sh, real* jrow, const Model<real>& M, bool last, bool nosweep, BodyRef<EP, real> br) {
+  if (uniform(sh.ncon) > kMaxCon) { floor_frames(sh); stage_constraint_big<real, EP>(sh, M, last, nosweep, br); }
+  else if (uniform(sh.anypair) != 0) { floor_frames(sh); stage_constraint_pairs<real, EP>(sh, jrow, M, last, nosweep, br); }
+  else stage_constraint_body<real, false, EP>(sh, jrow, M, last, nosweep, br);
 }
 
 // =========================================================================================  stage D
@@ -2803,7 +2868,7 @@ inline void nm_set_priority(int) {}
 #endif
 
 // mj_step(model, data, 1) for the G envs of the wave
-template <bool EP, class real, int G> NM_FN void substep(ShW<real, G>& w, const Model<real>& M, bool last, int* dropped, int ablate) {
+template <int EP, class real, int G> NM_FN void substep(ShW<real, G>& w, const Model<real>& M, bool last, int* dropped, int ablate) {
   const V<int> lane = opaque_lane();
   if constexpr (G == 2) {   // both envs at once on half-waves (lanes 0..31 | 32..63), as in env_load2
     constexpr int kSR = (int)(sizeof(Sh<real>) / sizeof(real));
@@ -2863,7 +2928,9 @@ template <bool EP, class real, int G> NM_FN void substep(ShW<real, G>& w, const 
   }
   if (!together)
     for (int e = 0; e < G; e++) {
-      stage_constraint<real, EP>(w.e[e], w.jrow, M, last, (ablate & 2) != 0);
+      BodyRef<EP, real> br;
+      if constexpr (EP == 2) br = BodyRef<EP, real>(body_rows(w) + e * kBodyP);
+      stage_constraint<real, EP>(w.e[e], w.jrow, M, last, (ablate & 2) != 0, br);
       nm_stamp(8);
     }
   stage_integrate(w, M);
@@ -2873,7 +2940,7 @@ template <bool EP, class real, int G> NM_FN void substep(ShW<real, G>& w, const 
 // =========================================================================================  env step
 
 // load one env's state into its LDS image, action -> servo command (E1)
-template <bool EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real>& M, const Args<real>& A, int env) {
+template <int EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real>& M, const Args<real>& A, int env, real* bp = nullptr) {
   typedef V<real> vr;
   const V<int> lane = opaque_lane();   // index math stays local to this function (not kept live across the physics)
   const VB l18 = lane < kNU;
@@ -2886,7 +2953,9 @@ template <bool EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<rea
   const V<int> hc_in = gldv(A.hullcache, sel(lane < 8, lane, V<int>(0)) + env * 8);
   const V<float> a_in = gldv(A.actions, l18c + env * kNU);
   vr envp_in = vr(real(0));
-  if constexpr (EP) envp_in = gldv(A.envp, sel(lane < kEnvP, lane, V<int>(0)) + env * kEnvP);     // the env's (mu, p_gain, kv, pad) row: 16 bytes, lanes 0..3
+  if constexpr (EP != 0) envp_in = gldv(A.envp, sel(lane < kEnvP, lane, V<int>(0)) + env * kEnvP);     // the env's (mu, p_gain, kv, pad) row: 16 bytes, lanes 0..3
+  vr body_in = vr(real(0));
+  if constexpr (EP == 2) body_in = gldv(A.envp, sel(lane < kBodyP, lane, V<int>(0)) + (A.N * kEnvP + env * kBodyP));   // the env's body row, behind the N envp rows
   vr cmd_in = vr(real(0)), eps_in = vr(real(0)), prev_act = vr(real(0)), prev_dofvel = vr(real(0)), dofpos_old = vr(real(0));
   int64_t ep = 0;
   uint32_t ctr_in = 0;
@@ -2908,8 +2977,9 @@ template <bool EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<rea
   sh.ntog = 0;
   // per-env parameters: the env's row into its image; the stiffness of this step's command stays in a register
   real p_gain = M.p_gain;
-  if constexpr (EP) {
+  if constexpr (EP != 0) {
     stsv(sh.envp, lane, envp_in, lane < kEnvPS);
+    if constexpr (EP == 2) stsv(bp, lane, body_in, lane < kBodyP);
     p_gain = rdlane(envp_in, EP_PGAIN);
   }
   // ---- E1 (env.py:152-156,181-192): float32 scale + clip; PD -> velocity command from the env's own dof_pos buffer
@@ -3238,7 +3308,7 @@ template <class real> NM_FN void env_finish(Sh<real>& sh, const Model<real>& M, 
 // `mid()` runs after every HBM read has been issued and before the first of them is waited for: the kernel copies the model constants
 // (L2 -> LDS, `M` is that copy) there, so the two round trips of a wave's start-up overlap instead of following each other.
 struct NoMid { NM_FN void operator()() const {} NM_FN void operator()(int) const {} };
-template <bool EP, class real, class Mid> NM_FN void env_load2(ShW<real, 2>& w, const Model<real>& M, const Args<real>& A, int wave, Mid&& mid) {
+template <int EP, class real, class Mid> NM_FN void env_load2(ShW<real, 2>& w, const Model<real>& M, const Args<real>& A, int wave, Mid&& mid) {
   typedef V<real> vr;
   constexpr int kSR = (int)(sizeof(Sh<real>) / sizeof(real)), kSI = (int)(sizeof(Sh<real>) / sizeof(int));
   const V<int> lane = opaque_lane();
@@ -3256,7 +3326,9 @@ template <bool EP, class real, class Mid> NM_FN void env_load2(ShW<real, 2>& w, 
   const V<int> hc_in = gldv(A.hullcache, sel(hl < 8, hl, V<int>(0)) + env * 8);
   const V<float> a_in = gldv(A.actions, l18c + env * kNU);
   vr envp_in = vr(real(0));
-  if constexpr (EP) envp_in = gldv(A.envp, sel(hl < kEnvP, hl, V<int>(0)) + env * kEnvP);     // each env's (mu, p_gain, kv, pad) row: 16 bytes, lanes 0..3 of its half
+  if constexpr (EP != 0) envp_in = gldv(A.envp, sel(hl < kEnvP, hl, V<int>(0)) + env * kEnvP);     // each env's (mu, p_gain, kv, pad) row: 16 bytes, lanes 0..3 of its half
+  vr body_in = vr(real(0));
+  if constexpr (EP == 2) body_in = gldv(A.envp, sel(hl < kBodyP, hl, V<int>(0)) + (env * kBodyP + A.N * kEnvP));   // each env's body row (behind the N envp rows), lanes 0..19 of its half
   vr cmd_in = vr(real(0)), eps_in = vr(real(0)), prev_act = vr(real(0)), prev_dofvel = vr(real(0)), dofpos_old = vr(real(0));
 #ifndef NM_EMUL
   int64_t ep = 0;
@@ -3287,8 +3359,9 @@ template <bool EP, class real, class Mid> NM_FN void env_load2(ShW<real, 2>& w, 
   // per-env parameters: each env's row into its image; the servo stiffness of this step's command goes to the lanes of the env's half in
   // registers
   vr p_gain = vr(M.p_gain);
-  if constexpr (EP) {
+  if constexpr (EP != 0) {
     stsv(rb, ho + (hl + NM_OFS(envp)), envp_in, hl < kEnvPS);
+    if constexpr (EP == 2) stsv(body_rows(w), h * kBodyP + hl, body_in, hl < kBodyP);
     p_gain = sel(h != 0, vr(rdlane(envp_in, 32 + EP_PGAIN)), vr(rdlane(envp_in, EP_PGAIN)));
   }
   // ---- E1 (env.py:152-156,181-192): float32 scale + clip; PD -> velocity command from the env's own dof_pos buffer
@@ -3627,7 +3700,7 @@ template <class real, class Pub> NM_FN void env_finish2(ShW<real, 2>& w, const M
 }
 
 // one wavefront = G consecutive envs (E2, env.py:200: mj_step(model, data, decimation) between load and epilogue)
-template <class real, int G, bool EP = false, class Mid = NoMid, class Pub = NoMid>
+template <class real, int G, int EP = 0, class Mid = NoMid, class Pub = NoMid>
 NM_FN void wave_step(ShW<real, G>& w, const Model<real>& M, const Args<real>& A, int wave, Mid&& mid = Mid(), Pub&& published = Pub()) {
   nm_stamp(-1);
   if constexpr (G == 2) {
@@ -3637,7 +3710,9 @@ NM_FN void wave_step(ShW<real, G>& w, const Model<real>& M, const Args<real>& A,
 #pragma unroll
     for (int e = 0; e < G; e++) {
       int env = wave * G + e;
-      env_load<EP>(w.e[e], M, A, env < A.N ? env : A.N - 1);
+      real* bp = nullptr;
+      if constexpr (EP == 2) bp = body_rows(w) + e * kBodyP;
+      env_load<EP>(w.e[e], M, A, env < A.N ? env : A.N - 1, bp);
     }
   }
   nm_stamp(0);

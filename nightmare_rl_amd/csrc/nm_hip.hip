@@ -88,14 +88,15 @@ constexpr int kWG = NM_WG_WAVES;
 #else
 constexpr int kWG = 1;
 #endif
-// EP: per-env physics parameters (nm::Args::envp) - the host launches the EP instantiation only while rows are set (nm_core.h env_mu)
-template <class real, int G, bool EP>
+// EP: level of per-env physics parameters (nm_core.h env_mu): 0 none, 1 friction / gain rows (nm::Args::envp), 2 those and body rows - the
+// host launches a level above 0 only while its rows are set
+template <class real, int G, int EP>
 __global__ void __launch_bounds__(64 * (sizeof(real) == 8 ? 1 : kWG), NM_WAVES_PER_SIMD) k_env_step(const nm::Model<real>* __restrict__ Mp, nm::Args<real> A) {
   constexpr int kWG = sizeof(real) == 8 ? 1 : ::kWG;     // the fp64 verification build keeps one wave per workgroup
-  __shared__ nm::ShW<real, G> shs[kWG];
+  __shared__ typename nm::ShWSel<real, G, EP>::type shs[kWG];
   __shared__ nm::Model<real> Ms;   // this workgroup's copy of the model constants
   __shared__ nm::Args<real> As;    // ... and of the launch arguments: ~30 pointers would otherwise pin 60 SGPRs for the whole kernel
-  nm::ShW<real, G>& sh = shs[kWG == 1 ? 0 : (int)(threadIdx.x >> 6)];
+  nm::ShW<real, G>& sh = nm::ShWSel<real, G, EP>::images(shs[kWG == 1 ? 0 : (int)(threadIdx.x >> 6)]);
   int wave = nmr::wave_index(A.nxcd);      // XCD-aware block -> wave mapping (nm_env_loop.h)
   if (kWG > 1) wave = wave * kWG + (int)(threadIdx.x >> 6);
 #ifdef NM_MEASURE
@@ -263,6 +264,25 @@ __global__ void k_envp_draw(real* __restrict__ rows, int N, uint64_t seed, int64
   rows[i] = v;
 }
 
+// Per-env body rows (base payload, nm::kBodyP words per env). `fill`: the default row for every env (what nm_get_body_params reports while
+// the feature is off). `draw`: (dm, rx, ry, rz) per env by k_envp_draw's generator under its own key, lo + u (hi - lo) through envp_lerp.
+template <class real> struct BodyRow { real v[nm::kBodyP]; };
+template <class real> struct Pay4 { real v[4]; };
+template <class real>
+__global__ void k_body_fill(real* __restrict__ rows, int N, BodyRow<real> dflt) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nm::kBodyP * N) return;
+  rows[i] = dflt.v[i % nm::kBodyP];
+}
+template <class real>
+__global__ void k_payload_draw(real* __restrict__ out, int N, uint64_t seed, int64_t env_offset, Pay4<real> lo, Pay4<real> hi) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 4 * N) return;
+  const int env = i >> 2, col = i & 3;
+  const real u = (real)nm::rand_u24_bits(seed + nm::kPayloadKey, (uint64_t)(env_offset + env), (uint32_t)col) * real(1.0 / 16777216.0);
+  out[i] = envp_lerp(lo.v[col], u, hi.v[col] - lo.v[col]);
+}
+
 // ------------------------------------------------------------------------------------------------ host object
 struct nm_env {
   int N = 0, device = 0, dtype = 0;
@@ -297,6 +317,9 @@ struct nm_env {
   virtual int set_env_params(const void* mu, const void* p_gain, const void* kv, hipStream_t s) = 0;
   virtual int get_env_params(void* mu, void* p_gain, void* kv, hipStream_t s) = 0;
   virtual int draw_env_params(const double* lo, const double* hi, hipStream_t s) = 0;
+  virtual int set_body_params(const void* rows, hipStream_t s) = 0;
+  virtual int get_body_params(void* out, hipStream_t s) = 0;
+  virtual int draw_payload(const double* lo, const double* hi, void* out, hipStream_t s) = 0;
   // push perturbations (nm_push.h): the setting and the push step index - full env steps taken, K per K-step launch; physics-only
   // launches and nm_reset leave it alone
   int push_interval = 0;
@@ -463,8 +486,9 @@ template <class real> struct Env : nm_env {
     }
     constexpr int G = sizeof(real) == 8 ? 1 : NM_ENVS_PER_WAVE;  // the fp64 verification build keeps one env per wave (LDS)
     constexpr int W = sizeof(real) == 8 ? 1 : kWG;
-    if (a.envp) hipLaunchKernelGGL((k_env_step<real, G, true>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
-    else hipLaunchKernelGGL((k_env_step<real, G, false>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
+    if (body_on) hipLaunchKernelGGL((k_env_step<real, G, 2>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
+    else if (a.envp) hipLaunchKernelGGL((k_env_step<real, G, 1>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
+    else hipLaunchKernelGGL((k_env_step<real, G, 0>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
     HIPCHK(hipGetLastError());
     if (prof_on) HIPCHK(hipEventRecord(e1, s));
     return 0;
@@ -714,7 +738,7 @@ template <class real> struct Env : nm_env {
       R.wave_clock = A.dbg ? reinterpret_cast<unsigned long long*>(A.dbg) : nullptr;   // measurement: the debug buffer ([N,256] reals) takes the waves' clocks instead
       nmr::TailArgs ta{N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, r->bootstrap_time_outs ? r->gamma : -1.0f, r->s_values, r->s_rewards,
                        r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
-      if (nmr::launch_rollout(M_dev, a, R, ta, act, s)) return fail("nm_rollout: launch failed");
+      if (nmr::launch_rollout(M_dev, a, R, ta, act, level(), s)) return fail("nm_rollout: launch failed");
       return 0;
     }
   }
@@ -752,7 +776,7 @@ template <class real> struct Env : nm_env {
       rec_done_valid = log != nullptr;
       nmr::TailArgs ta{N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, -1.0f, nullptr, nullptr,
                        r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
-      if (nmr::launch_play(M_dev, a, P, ta, act, s)) return fail("nm_play: launch failed");
+      if (nmr::launch_play(M_dev, a, P, ta, act, level(), s)) return fail("nm_play: launch failed");
       return 0;
     }
   }
@@ -785,24 +809,99 @@ template <class real> struct Env : nm_env {
       rec_done_valid = log != nullptr;
       nmr::TailArgs ta{N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, -1.0f, nullptr, nullptr,
                        r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
-      if (nmr::launch_tape(M_dev, a, T, ta, s)) return fail("nm_step_tape: launch failed");
+      if (nmr::launch_tape(M_dev, a, T, ta, level(), s)) return fail("nm_step_tape: launch failed");
       // with an observation record every step filed its observation in its row: the env's own buffer receives the last one
       if (r->rec_obs_dev)
         HIPCHK(hipMemcpyAsync(r->obs_dev, r->rec_obs_dev + (size_t)(K - 1) * n_ * nm::kNOBS, n_ * nm::kNOBS * sizeof(float), hipMemcpyDeviceToDevice, s));
       return 0;
     }
   }
-  // ---- per-env physics parameters: the rows live in A.envp, which every launch copies with the rest of A (null = off)
+  // ---- per-env physics parameters: the rows live in A.envp, which every launch copies with the rest of A (null = off). ONE allocation
+  // holds the N friction / gain rows and, behind them, the N body rows (nm::Args has no word for a second pointer): A.envp is set while
+  // either kind is on, and while only body rows are the friction / gain rows hold the defaults.
   real* envp_dev = nullptr;
+  bool envp_on = false, body_on = false;
+  int level() const { return body_on ? 2 : (A.envp ? 1 : 0); }     // which instantiation of the step a launch takes (nm_core.h env_mu)
+  int envp_alloc() { return !envp_dev && dalloc(&envp_dev, (size_t)N * (nm::kEnvP + nm::kBodyP)); }
+  real* body_dev() const { return envp_dev + (size_t)N * nm::kEnvP; }
   EnvP3<real> envp_default() const { return EnvP3<real>{{M.mu, M.p_gain, M.kv}}; }
+  int envp_fill_default(hipStream_t s) {
+    hipLaunchKernelGGL(k_envp_set<real>, dim3((4 * N + 255) / 256), dim3(256), 0, s, envp_dev, N, EnvP3P<real>{{nullptr, nullptr, nullptr}}, envp_default());
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
   int set_env_params(const void* mu, const void* p_gain, const void* kv, hipStream_t s) override {
     HIPCHK(hipSetDevice(device));
-    if (!mu && !p_gain && !kv) { A.envp = nullptr; return 0; }     // off; the rows stay allocated (a launch in flight may read them)
-    if (!envp_dev && dalloc(&envp_dev, (size_t)N * nm::kEnvP)) return 1;
+    if (!mu && !p_gain && !kv) {     // off; the rows stay allocated (a launch in flight may read them)
+      envp_on = false;
+      if (body_on) return envp_fill_default(s);      // level 2 goes on reading rows: the defaults
+      A.envp = nullptr;
+      return 0;
+    }
+    if (envp_alloc()) return 1;
     EnvP3P<real> src{{(const real*)mu, (const real*)p_gain, (const real*)kv}};
     hipLaunchKernelGGL(k_envp_set<real>, dim3((4 * N + 255) / 256), dim3(256), 0, s, envp_dev, N, src, envp_default());
     HIPCHK(hipGetLastError());
     A.envp = envp_dev;
+    envp_on = true;
+    return 0;
+  }
+  // ---- per-env body rows (base payload)
+  BodyRow<real> body_default() const {
+    BodyRow<real> r;
+    for (int j = 0; j < nm::kBodyP; j++) r.v[j] = real(0);
+    for (int j = 0; j < 10; j++) r.v[nm::BP_IPOS + j] = M.basec[j];
+    r.v[nm::BP_TOTAL] = M.total_mass;
+    for (int g = 0; g < nm::kNCOL; g++) r.v[nm::BP_INVW + g] = M.colc[g * nm::kColN + 4];
+    r.v[nm::BP_PGS] = M.pgs_scale;
+    return r;
+  }
+  int set_body_params(const void* rows, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (!rows) {       // off; nothing is freed
+      body_on = false;
+      if (!envp_on) A.envp = nullptr;
+      return 0;
+    }
+    // the rows are judged on the host before anything of the env changes
+    std::vector<real> h((size_t)N * nm::kBodyP);
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpy(h.data(), rows, h.size() * sizeof(real), hipMemcpyDeviceToHost));
+    for (int e = 0; e < N; e++) {
+      const real* r = &h[(size_t)e * nm::kBodyP];
+      const char* why = nullptr;
+      for (int j = 0; j < nm::kBodyP; j++) if (!std::isfinite((double)r[j])) why = "a non-finite value";
+      if (!why && !(r[nm::BP_MASS] > 0)) why = "mass <= 0";
+      if (!why && r[nm::BP_TOTAL] < r[nm::BP_MASS]) why = "total_mass < mass";
+      if (!why && !(r[nm::BP_I6] > 0 && r[nm::BP_I6 + 1] > 0 && r[nm::BP_I6 + 2] > 0)) why = "a non-positive inertia diagonal";
+      for (int g = 0; g < nm::kNCOL && !why; g++) if (!(r[nm::BP_INVW + g] > 0)) why = "a non-positive invweight0";
+      if (!why && !(r[nm::BP_PGS] > 0)) why = "a non-positive pgs_scale";
+      if (why) return fail(std::string("nm_set_body_params: row ") + std::to_string(e) + ": " + why);
+    }
+    if (envp_alloc()) return 1;
+    if (!envp_on && envp_fill_default(s)) return 1;
+    HIPCHK(hipMemcpyAsync(body_dev(), rows, h.size() * sizeof(real), hipMemcpyDeviceToDevice, s));
+    A.envp = envp_dev;
+    body_on = true;
+    return 0;
+  }
+  int get_body_params(void* out, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (!out) return 0;
+    if (body_on) {
+      HIPCHK(hipMemcpyAsync(out, body_dev(), (size_t)N * nm::kBodyP * sizeof(real), hipMemcpyDeviceToDevice, s));
+      return 0;
+    }
+    hipLaunchKernelGGL(k_body_fill<real>, dim3((nm::kBodyP * N + 255) / 256), dim3(256), 0, s, (real*)out, N, body_default());
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  int draw_payload(const double* lo, const double* hi, void* out, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    Pay4<real> l, h;
+    for (int k = 0; k < 4; k++) { l.v[k] = (real)lo[k]; h.v[k] = (real)hi[k]; }
+    hipLaunchKernelGGL(k_payload_draw<real>, dim3((4 * N + 255) / 256), dim3(256), 0, s, (real*)out, N, A.seed, A.env_offset, l, h);
+    HIPCHK(hipGetLastError());
     return 0;
   }
   int get_env_params(void* mu, void* p_gain, void* kv, hipStream_t s) override {
@@ -815,12 +914,13 @@ template <class real> struct Env : nm_env {
   }
   int draw_env_params(const double* lo, const double* hi, hipStream_t s) override {
     HIPCHK(hipSetDevice(device));
-    if (!envp_dev && dalloc(&envp_dev, (size_t)N * nm::kEnvP)) return 1;
+    if (envp_alloc()) return 1;
     EnvP3<real> l, h;
     for (int k = 0; k < 3; k++) { l.v[k] = (real)lo[k]; h.v[k] = (real)hi[k]; }
     hipLaunchKernelGGL(k_envp_draw<real>, dim3((4 * N + 255) / 256), dim3(256), 0, s, envp_dev, N, A.seed, A.env_offset, l, h);
     HIPCHK(hipGetLastError());
     A.envp = envp_dev;
+    envp_on = true;
     return 0;
   }
   void set_dbg(void* p) override { A.dbg = (real*)p; }
@@ -1025,6 +1125,29 @@ int nm_draw_env_params(nm_env* env, const double lo[3], const double hi[3], void
     for (int k = 0; k < 3; k++)
       if (!std::isfinite((float)hi[k])) return fail(std::string("nm_draw_env_params: the bounds of ") + kCol[k] + " must be finite in float32");
   return env->draw_env_params(lo, hi, (hipStream_t)stream);
+}
+int nm_set_body_params(nm_env* env, const void* rows_dev, void* stream) {
+  if (!env) return fail("nm_set_body_params: env is NULL");
+  return env->set_body_params(rows_dev, (hipStream_t)stream);
+}
+int nm_get_body_params(nm_env* env, void* out_dev, void* stream) {
+  if (!env) return fail("nm_get_body_params: env is NULL");
+  return env->get_body_params(out_dev, (hipStream_t)stream);
+}
+int nm_draw_payload(nm_env* env, const double lo[4], const double hi[4], void* out_dev, void* stream) {
+  // every refusal comes before the first device call; the bounds are judged first, so a bad range is named whatever the handle is
+  if (!lo || !hi) return fail("nm_draw_payload: lo / hi is NULL");
+  static const char* kCol[4] = {"dm", "rx", "ry", "rz"};
+  for (int k = 0; k < 4; k++) {
+    if (!std::isfinite(lo[k]) || !std::isfinite(hi[k])) return fail(std::string("nm_draw_payload: the bounds of ") + kCol[k] + " must be finite");
+    if (lo[k] > hi[k]) return fail(std::string("nm_draw_payload: lo > hi for ") + kCol[k]);
+  }
+  if (!env) return fail("nm_draw_payload: env is NULL");
+  if (!out_dev) return fail("nm_draw_payload: out is NULL");
+  if (env->dtype == NM_DTYPE_F32)
+    for (int k = 0; k < 4; k++)
+      if (!std::isfinite((float)lo[k]) || !std::isfinite((float)hi[k])) return fail(std::string("nm_draw_payload: the bounds of ") + kCol[k] + " must be finite in float32");
+  return env->draw_payload(lo, hi, out_dev, (hipStream_t)stream);
 }
 int nm_step_tape(nm_env* env, const nm_tape_args* args, void* stream) {
   if (!env) return fail("nm_step_tape: env is NULL");

@@ -41,9 +41,10 @@ __device__ __noinline__ void play_step(float* xb, const PlayArgs* Ps, nm::Args<f
   step_close();
 }
 
-template <class S, int ACT, bool EP>      // EP: per-env physics parameters, launched only while rows are set (nm_core.h env_mu)
+template <class S, int ACT, int EP>      // EP: level of per-env physics parameters, above 0 launched only while rows are set (nm_core.h env_mu)
 __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_play(const nm::Model<float>* __restrict__ Mp, nm::Args<float> A, PlayArgs P) {
-  __shared__ nm::ShW<float, 2> sh;
+  __shared__ typename nm::ShWSel<float, 2, EP>::type shl;
+  nm::ShW<float, 2>& sh = nm::ShWSel<float, 2, EP>::images(shl);
   __shared__ nm::Model<float> Ms;
   __shared__ nm::Args<float> As;
   __shared__ PlayArgs Ps;
@@ -61,9 +62,10 @@ __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_play(const nm::Mo
 }
 
 template <int ACT>
-int PlayKernels<ACT>::play(const nm::Model<float>* M_dev, const nm::Args<float>& a, const PlayArgs& P, hipStream_t s) {
-  if (a.envp) hipLaunchKernelGGL((k_env_play<RefShape, ACT, true>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, P);
-  else hipLaunchKernelGGL((k_env_play<RefShape, ACT, false>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, P);
+int PlayKernels<ACT>::play(const nm::Model<float>* M_dev, const nm::Args<float>& a, const PlayArgs& P, int level, hipStream_t s) {
+  if (level == 2) hipLaunchKernelGGL((k_env_play<RefShape, ACT, 2>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, P);
+  else if (level == 1) hipLaunchKernelGGL((k_env_play<RefShape, ACT, 1>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, P);
+  else hipLaunchKernelGGL((k_env_play<RefShape, ACT, 0>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, P);
   return hipGetLastError() != hipSuccess;
 }
 template struct PlayKernels<NM_PLAY_ACT>;

@@ -322,11 +322,11 @@ int launch_pack(const float* flat, float* wp, float* bp, hipStream_t s);
 template <int ACT> struct RollKernels {
   static int act(const float* wp, const float* bp, const float* stdv, const float* obs, int N, uint64_t seed, const int64_t* iter_dev, int step,
                  const ActOut& o, hipStream_t s);
-  static int rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, hipStream_t s);
+  static int rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, int level, hipStream_t s);
 };
 // the launch of k_env_play for one hidden activation: defined in nm_play_kernels.h, instantiated once per code by nm_play_<activation>.hip
 template <int ACT> struct PlayKernels {
-  static int play(const nm::Model<float>* M_dev, const nm::Args<float>& a, const PlayArgs& P, hipStream_t s);
+  static int play(const nm::Model<float>* M_dev, const nm::Args<float>& a, const PlayArgs& P, int level, hipStream_t s);
 };
 extern template struct PlayKernels<NM_ACT_ELU>;
 extern template struct PlayKernels<NM_ACT_SELU>;
@@ -340,14 +340,16 @@ extern template struct RollKernels<NM_ACT_RELU>;
 extern template struct RollKernels<NM_ACT_LRELU>;
 extern template struct RollKernels<NM_ACT_TANH>;
 extern template struct RollKernels<NM_ACT_SIGMOID>;
-// act: the hidden activation (NM_ACT_*); a code this build has no instantiation for (the measurement build: ELU only) fails the launch
+// act: the hidden activation (NM_ACT_*); a code this build has no instantiation for (the measurement build: ELU only) fails the launch.
+// level: which instantiation of the step the K-step kernel carries (nm_core.h env_mu): 0 no per-env rows, 1 friction / gain rows
+// (a.envp), 2 those and body rows behind them - the env object knows, nm::Args has no word for it
 int launch_act(const float* wp, const float* bp, const float* stdv, const float* obs, int N, uint64_t seed, const int64_t* iter_dev, int step, const ActOut& o,
                int act, hipStream_t s);
-int launch_rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, const TailArgs& t, int act, hipStream_t s);
+int launch_rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, const TailArgs& t, int act, int level, hipStream_t s);
 // k_env_play + the rollout's closing launches (k_rollout_tail without the time-out bootstrap, k_rollout_clear)
-int launch_play(const nm::Model<float>* M_dev, const nm::Args<float>& a, const PlayArgs& P, const TailArgs& t, int act, hipStream_t s);
+int launch_play(const nm::Model<float>* M_dev, const nm::Args<float>& a, const PlayArgs& P, const TailArgs& t, int act, int level, hipStream_t s);
 // the launch of k_env_tape (nm_tape.hip), and launch_tape = that + the same closing launches as launch_play
-int tape_kernel(const nm::Model<float>* M_dev, const nm::Args<float>& a, const TapeArgs& T, hipStream_t s);
-int launch_tape(const nm::Model<float>* M_dev, const nm::Args<float>& a, const TapeArgs& T, const TailArgs& t, hipStream_t s);
+int tape_kernel(const nm::Model<float>* M_dev, const nm::Args<float>& a, const TapeArgs& T, int level, hipStream_t s);
+int launch_tape(const nm::Model<float>* M_dev, const nm::Args<float>& a, const TapeArgs& T, const TailArgs& t, int level, hipStream_t s);
 
 }  // namespace nmr

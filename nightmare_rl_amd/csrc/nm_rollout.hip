@@ -108,19 +108,19 @@ static int launch_tail(const TailArgs& t, hipStream_t s) {
   hipLaunchKernelGGL(k_rollout_clear, dim3((t.K * nm::kNREW + 255) / 256), dim3(256), 0, s, t.K, t.st_sum, t.st_cnt);
   return hipGetLastError() != hipSuccess;
 }
-int launch_rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, const TailArgs& t, int act, hipStream_t s) {
-  if (with_act(act, [&](auto ACT) { return RollKernels<decltype(ACT)::value>::rollout(M_dev, a, R, s); })) return 1;
+int launch_rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, const TailArgs& t, int act, int level, hipStream_t s) {
+  if (with_act(act, [&](auto ACT) { return RollKernels<decltype(ACT)::value>::rollout(M_dev, a, R, level, s); })) return 1;
   return launch_tail(t, s);
 }
 // nm_play: the same closing launches. Without the bootstrap (t.gamma < 0) k_rollout_tail needs each env's LATEST time-out step only: the
 // time-out buffer is refreshed by the last step in which some env reset, and an env's flag there is "it timed out in that very step".
-int launch_play(const nm::Model<float>* M_dev, const nm::Args<float>& a, const PlayArgs& P, const TailArgs& t, int act, hipStream_t s) {
-  if (with_act(act, [&](auto ACT) { return PlayKernels<decltype(ACT)::value>::play(M_dev, a, P, s); })) return 1;
+int launch_play(const nm::Model<float>* M_dev, const nm::Args<float>& a, const PlayArgs& P, const TailArgs& t, int act, int level, hipStream_t s) {
+  if (with_act(act, [&](auto ACT) { return PlayKernels<decltype(ACT)::value>::play(M_dev, a, P, level, s); })) return 1;
   return launch_tail(t, s);
 }
 // nm_step_tape: k_env_tape (nm_tape.hip) and the closing launches of nm_play - the books are the same
-int launch_tape(const nm::Model<float>* M_dev, const nm::Args<float>& a, const TapeArgs& T, const TailArgs& t, hipStream_t s) {
-  if (tape_kernel(M_dev, a, T, s)) return 1;
+int launch_tape(const nm::Model<float>* M_dev, const nm::Args<float>& a, const TapeArgs& T, const TailArgs& t, int level, hipStream_t s) {
+  if (tape_kernel(M_dev, a, T, level, s)) return 1;
   return launch_tail(t, s);
 }
 

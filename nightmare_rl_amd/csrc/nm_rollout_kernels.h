@@ -50,9 +50,10 @@ __device__ __noinline__ void value_last(float* xb, const RollArgs* Rs, const nm:
   policy_wave<S, ACT, kPolicyValueOnly>(xb, Rs->wp, Rs->bp, Rs->stdv, Rs->obs_final, As->N, wave, 0, 0, o);
 }
 
-template <class S, int ACT, bool EP>      // EP: per-env physics parameters, launched only while rows are set (nm_core.h env_mu)
+template <class S, int ACT, int EP>      // EP: level of per-env physics parameters, above 0 launched only while rows are set (nm_core.h env_mu)
 __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_rollout(const nm::Model<float>* __restrict__ Mp, nm::Args<float> A, RollArgs R) {
-  __shared__ nm::ShW<float, 2> sh;
+  __shared__ typename nm::ShWSel<float, 2, EP>::type shl;
+  nm::ShW<float, 2>& sh = nm::ShWSel<float, 2, EP>::images(shl);
   __shared__ nm::Model<float> Ms;
   __shared__ nm::Args<float> As;
   __shared__ RollArgs Rs;
@@ -87,9 +88,10 @@ int RollKernels<ACT>::act(const float* wp, const float* bp, const float* stdv, c
   return hipGetLastError() != hipSuccess;
 }
 template <int ACT>
-int RollKernels<ACT>::rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, hipStream_t s) {
-  if (a.envp) hipLaunchKernelGGL((k_env_rollout<RefShape, ACT, true>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, R);
-  else hipLaunchKernelGGL((k_env_rollout<RefShape, ACT, false>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, R);
+int RollKernels<ACT>::rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, int level, hipStream_t s) {
+  if (level == 2) hipLaunchKernelGGL((k_env_rollout<RefShape, ACT, 2>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, R);
+  else if (level == 1) hipLaunchKernelGGL((k_env_rollout<RefShape, ACT, 1>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, R);
+  else hipLaunchKernelGGL((k_env_rollout<RefShape, ACT, 0>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, R);
   return hipGetLastError() != hipSuccess;
 }
 template struct RollKernels<NM_ROLLOUT_ACT>;

@@ -38,9 +38,10 @@ __device__ __noinline__ void tape_step(const TapeArgs* Ts, nm::Args<float>* As, 
   step_close();
 }
 
-template <bool EP>      // EP: per-env physics parameters, launched only while rows are set (nm_core.h env_mu)
+template <int EP>      // EP: level of per-env physics parameters, above 0 launched only while rows are set (nm_core.h env_mu)
 __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_tape(const nm::Model<float>* __restrict__ Mp, nm::Args<float> A, TapeArgs T) {
-  __shared__ nm::ShW<float, 2> sh;
+  __shared__ typename nm::ShWSel<float, 2, EP>::type shl;
+  nm::ShW<float, 2>& sh = nm::ShWSel<float, 2, EP>::images(shl);
   __shared__ nm::Model<float> Ms;
   __shared__ nm::Args<float> As;
   __shared__ TapeArgs Ts;
@@ -55,9 +56,10 @@ __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_tape(const nm::Mo
   books_last(&Ts, &As, K - 1, wave);
 }
 
-int tape_kernel(const nm::Model<float>* M_dev, const nm::Args<float>& a, const TapeArgs& T, hipStream_t s) {
-  if (a.envp) hipLaunchKernelGGL(k_env_tape<true>, dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, T);
-  else hipLaunchKernelGGL(k_env_tape<false>, dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, T);
+int tape_kernel(const nm::Model<float>* M_dev, const nm::Args<float>& a, const TapeArgs& T, int level, hipStream_t s) {
+  if (level == 2) hipLaunchKernelGGL(k_env_tape<2>, dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, T);
+  else if (level == 1) hipLaunchKernelGGL(k_env_tape<1>, dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, T);
+  else hipLaunchKernelGGL(k_env_tape<0>, dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, T);
   return hipGetLastError() != hipSuccess;
 }
 

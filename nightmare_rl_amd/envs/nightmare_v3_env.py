@@ -17,6 +17,8 @@ Differences a caller can observe (all documented in DESIGN.md):
     a push does not show it
   * the same optional class may carry randomize_friction / friction_range and randomize_gains / stiffness_multiplier_range /
     damping_multiplier_range: per-env sliding friction and servo gains, drawn once at construction (set_env_params, draw_env_params)
+  * and randomize_base_mass / added_mass_range, randomize_com_displacement / com_displacement_range: a per-env point mass on the base
+    body, compiled into the env's model constants (set_base_payload, draw_base_payload), drawn once at construction
 """
 import ctypes as C
 import numpy as np
@@ -79,6 +81,39 @@ def env_param_config(cfg):
     return fr, st, da
 
 
+def payload_config(cfg):
+    """(mass_range, com_range) of the optional cfg.domain_rand, each a (lo, hi) pair or None: what draw_base_payload takes.
+    randomize_base_mass needs added_mass_range (kg, may be negative), randomize_com_displacement needs com_displacement_range (m, the
+    same range for x, y and z in the base body frame). A range that is not two finite numbers lo <= hi is a ValueError; whether the
+    heaviest negative mass is admissible is judged when the rows are derived (model/payload.py)."""
+    dr = getattr(cfg, "domain_rand", None)
+    if dr is None:
+        return None, None
+
+    def rng(name):
+        r = getattr(dr, name, None)
+        if r is None:
+            return None
+        try:
+            lo, hi = (float(x) for x in r)
+        except (TypeError, ValueError):
+            raise ValueError(f"cfg.domain_rand.{name} must be a pair (lo, hi)") from None
+        if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi):
+            raise ValueError(f"cfg.domain_rand.{name} must be finite with lo <= hi")
+        return lo, hi
+
+    ma = co = None
+    if getattr(dr, "randomize_base_mass", False):
+        ma = rng("added_mass_range")
+        if ma is None:
+            raise ValueError("cfg.domain_rand.randomize_base_mass needs added_mass_range")
+    if getattr(dr, "randomize_com_displacement", False):
+        co = rng("com_displacement_range")
+        if co is None:
+            raise ValueError("cfg.domain_rand.randomize_com_displacement needs com_displacement_range")
+    return ma, co
+
+
 class NightmareV3Env:
     def __init__(self, cfg: NightmareV3Config, log_dir="/tmp/nightmare_v3/logs", num_threads=1, *, device=None, seed=0,
                  env_id_offset=0, dtype=torch.float32, lib=None):
@@ -118,6 +153,7 @@ class NightmareV3Env:
             raise ValueError("cfg.commands.resampling_time must be at least one env step (reference :235 takes a modulo by it)")
         push_steps, push_vel = push_config(cfg, self.dt)       # optional cfg.domain_rand: checked before anything is created
         envp_ranges = env_param_config(cfg)
+        payload_ranges = payload_config(cfg)
         # reward table: zero scales dropped, the rest x dt (reference :123-128). Every name the reference has a _reward_ function
         # for (:399-497) is compiled; a name without one (`collision`, `feet_stumble`, config :95-96) fails like upstream's getattr.
         names = [L.nm_reward_name(i).decode() for i in range(_lib.NUM_REWARDS)]
@@ -189,6 +225,11 @@ class NightmareV3Env:
         self._envp_default = tuple(float(v[0]) for v in self.env_params().values()) if hasattr(L, "nm_get_env_params") else None
         if any(r is not None for r in envp_ranges):
             self.draw_env_params(*envp_ranges)
+        # per-env base payload (optional cfg.domain_rand; no reference line): drawn once, here
+        self._payload = None
+        self._body_keep = None
+        if any(r is not None for r in payload_ranges):
+            self.draw_base_payload(*payload_ranges)
         # state log of env 0 (reference :261-272; reader open_custom_play.py:50-66)
         self.state_log = None
         self._rec_env = 0
@@ -284,6 +325,52 @@ class NightmareV3Env:
         lo = (C.c_double * 3)(fr[0], pg * st[0], kv0 * da[0])
         hi = (C.c_double * 3)(fr[1], pg * st[1], kv0 * da[1])
         self._ck(self._L.nm_draw_env_params(self._h, C.byref(lo), C.byref(hi), self._stream()))
+
+    def set_base_payload(self, dm=None, r=None):
+        """Per-env base payload: a point mass dm (kg, may be negative) rigidly attached to the base body at r (m, base body frame). The env
+        then behaves as if mjmodel.xml had been recompiled with that mass added to base_link - base mass, COM and inertia, total mass,
+        the colliding bodies' invweight0 and the solver's scale all follow (model/payload.py derives the rows on the host;
+        nm_set_body_params) - in step(), step_physics, policy_rollout, policy_play and step_tape alike. dm: num_envs values or a scalar;
+        r: [num_envs, 3], one [3] for every env, or None = the base origin. dm None switches the feature off. The payload holds until
+        it is set again (no reset touches it). ValueError: a non-finite value, a base mass <= 0, an inertia that is not positive definite
+        or violates the triangle inequality (what MuJoCo's compiler refuses)."""
+        if dm is None:
+            self._payload = self._body_keep = None
+            self._ck(self._L.nm_set_body_params(self._h, None, self._stream()))
+            return
+        from ..model import payload
+        dm = np.asarray(dm.detach().cpu().numpy() if isinstance(dm, torch.Tensor) else dm, dtype=np.float64)
+        dm = np.full(self.num_envs, float(dm)) if dm.ndim == 0 else dm.reshape(-1)
+        r = np.zeros(3) if r is None else np.asarray(r.detach().cpu().numpy() if isinstance(r, torch.Tensor) else r, dtype=np.float64)
+        r = np.tile(r, (self.num_envs, 1)) if r.ndim == 1 else r.reshape(-1, 3)
+        if dm.shape[0] != self.num_envs or r.shape != (self.num_envs, 3):
+            raise ValueError("set_base_payload: one dm per env (or a scalar) and one r[3] per env (or one for all)")
+        rows = payload.payload_rows(dm, r)
+        t = torch.from_numpy(rows).to(dtype=self._real).to(self.device).contiguous()
+        self._ck(self._L.nm_set_body_params(self._h, C.c_void_p(t.data_ptr()), self._stream()))
+        self._body_keep = t           # the copy is stream-ordered: the source lives until the next call
+        self._payload = (dm.copy(), r.copy())
+
+    def base_payload(self):
+        """{'dm': [num_envs], 'r': [num_envs, 3]} (float64 numpy, what was set: zeros while the feature is off) and 'rows': the
+        [num_envs, 20] body rows the kernels read, a tensor in the env's dtype (nm_get_body_params; the model's own row while off)."""
+        rows = torch.empty(self.num_envs, 20, dtype=self._real, device=self.device)
+        self._ck(self._L.nm_get_body_params(self._h, C.c_void_p(rows.data_ptr()), self._stream()))
+        dm, r = self._payload if self._payload is not None else (np.zeros(self.num_envs), np.zeros((self.num_envs, 3)))
+        return {"dm": dm.copy(), "r": r.copy(), "rows": rows}
+
+    def draw_base_payload(self, mass_range=None, com_range=None):
+        """Draw every env's payload on the device (nm_draw_payload: dm uniform in mass_range kg, each of r's components uniform in
+        com_range m; None pins that part to 0), derive the rows on the host and set them. Keyed by the global env id: shards of one
+        population draw what the whole would. Returns what base_payload() then reports."""
+        ma = (0.0, 0.0) if mass_range is None else tuple(float(x) for x in mass_range)
+        co = (0.0, 0.0) if com_range is None else tuple(float(x) for x in com_range)
+        lo, hi = (C.c_double * 4)(ma[0], co[0], co[0], co[0]), (C.c_double * 4)(ma[1], co[1], co[1], co[1])
+        out = torch.empty(self.num_envs, 4, dtype=self._real, device=self.device)
+        self._ck(self._L.nm_draw_payload(self._h, C.byref(lo), C.byref(hi), C.c_void_p(out.data_ptr()), self._stream()))
+        d = out.to(torch.float64).cpu().numpy()
+        self.set_base_payload(d[:, 0], d[:, 1:])
+        return self.base_payload()
 
     def _record_state(self):
         # reference :261-272: when env 0 resets, dump what was logged so far, then log (time, qpos, qvel, act) of env 0
