@@ -181,6 +181,32 @@ int nm_draw_env_params(nm_env* env, const double lo[3], const double hi[3], void
 int nm_set_body_params(nm_env* env, const void* rows_dev, void* stream);
 int nm_get_body_params(nm_env* env, void* out_dev, void* stream);
 int nm_draw_payload(nm_env* env, const double lo[4], const double hi[4], void* out_dev, void* stream);
+/* Per-env actuation latency: the servo targets of an env lag the policy's actions by d physics substeps. There is no reference line:
+ * upstream applies every action in the tick it was computed; the real robot's serial servo bus does not.
+ * Semantics: a_t is step t's action after scale and clip (float32). Each env has an integer delay d, 0 <= d <= H nsub, H = 3 past
+ * actions kept, nsub = decimation (6 substeps = 48 ms at the defaults). With k = d / nsub, r = d % nsub, substep s of step t aims the
+ * servos at a_{t-k-1} while s < r and at a_{t-k} from s = r on; either command is ((real(a) - default) - dof_pos buffer) p_gain, today's
+ * expression on the step-start dof_pos snapshot and the env's own p_gain, computed from its own action (a delayed env's command has the
+ * bits an undelayed env would give the same action). Everything else - observation slots 48..65, action_rate, default_position, the
+ * actions buffer, the transition and state-log records - keeps a_t: the policy meets latency through the physics alone.
+ * History: hist[e][j] = a_{t-1-j}, j = 0..H-1, float32, zero at construction. Every full step taken WHILE THE FEATURE IS ON shifts it
+ * and puts a_t in front; steps taken while it is off leave it alone, and so do resets (upstream's reset_idx keeps self.actions),
+ * physics-only launches (which ignore latency altogether) and switching the feature on or off. The MuJoCo bad-state path (ctrl = 0
+ * for the rest of that substep) is unchanged. It works alike in nm_step, nm_rollout, nm_play and nm_step_tape, alone or with
+ * nm_set_env_params / nm_set_body_params. Off is the default, and off equals "on with delay 0 in every env" bit for bit.
+ * nm_set_action_latency: `substeps` is a DEVICE array [N] int32, copied on `stream`; NULL switches the feature off (nothing is freed).
+ *   Refused, named by nm_last_error, before anything of the env changes (the delays are read back and judged on the host, which waits
+ *   for `stream`): a delay outside [0, H nsub].
+ * nm_get_action_latency: the delays into a DEVICE array [N] int32 on `stream`; zeros while the feature is off.
+ * nm_draw_action_latency: delay[e] uniform on the integers [lo, hi], lo + floor(u (hi - lo + 1)) with u = bits 2^-24, bits from the
+ *   counter RNG keyed by (seed + "LATEN", global env id, 0) - in integers lo + ((bits (hi - lo + 1)) >> 24): sharding changes nothing;
+ *   switches the feature on. Refused before the handle is looked at: lo < 0, lo > hi; with the handle: hi > H nsub.
+ * nm_set_action_history / nm_get_action_history: DEVICE arrays [N,H,18] float32 in the logical order above (row 0 the latest). */
+int nm_set_action_latency(nm_env* env, const int32_t* substeps_dev, void* stream);
+int nm_get_action_latency(nm_env* env, int32_t* out_dev, void* stream);
+int nm_draw_action_latency(nm_env* env, int32_t lo, int32_t hi, void* stream);
+int nm_set_action_history(nm_env* env, const float* hist_dev, void* stream);
+int nm_get_action_history(nm_env* env, float* out_dev, void* stream);
 /* State log (envs/nightmare_v3_env.py:261-272 records data[0]): env_index >= 0 makes every nm_step keep that env's
  * post-physics, pre-reset qpos/qvel; -1 = off. nm_get_state_record copies the last record to HOST qpos[25], qvel[24] and
  * the number of MuJoCo bad-state resets inside that step (data.time restarts there). Synchronous. */

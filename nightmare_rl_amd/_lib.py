@@ -29,7 +29,8 @@ EXPORTS = ["nm_default_config", "nm_reward_name", "nm_last_error", "nm_create", 
            "nm_nik_create", "nm_nik_destroy", "nm_nik_reset", "nm_nik_set_gait", "nm_nik_update", "nm_nik_get_state",
            "nm_step_tape", "nm_nik_tape", "nm_set_push", "nm_get_push",
            "nm_set_env_params", "nm_get_env_params", "nm_draw_env_params",
-           "nm_set_body_params", "nm_get_body_params", "nm_draw_payload"]
+           "nm_set_body_params", "nm_get_body_params", "nm_draw_payload",
+           "nm_set_action_latency", "nm_get_action_latency", "nm_draw_action_latency", "nm_set_action_history", "nm_get_action_history"]
 
 
 class NmConfig(C.Structure):
@@ -176,6 +177,12 @@ def _bind(L, full):
         L.nm_set_body_params.argtypes = [vp, vp, vp]
         L.nm_get_body_params.argtypes = [vp, vp, vp]
         L.nm_draw_payload.argtypes = [vp, C.POINTER(C.c_double * 4), C.POINTER(C.c_double * 4), vp, vp]
+    if hasattr(L, "nm_set_action_latency"):
+        L.nm_set_action_latency.argtypes = [vp, vp, vp]
+        L.nm_get_action_latency.argtypes = [vp, vp, vp]
+        L.nm_draw_action_latency.argtypes = [vp, C.c_int32, C.c_int32, vp]
+        L.nm_set_action_history.argtypes = [vp, vp, vp]
+        L.nm_get_action_history.argtypes = [vp, vp, vp]
     if not full:        # the measurement build holds the env entry points only
         return L
     L.nm_gae.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_float, vp, vp]

@@ -143,6 +143,15 @@ constexpr int EP_MU = 0, EP_PGAIN = 1, EP_KV = 2, kEnvP = 4, kEnvPS = 3;   // co
 // env whose base carries a payload. ipos3 I6 mass are basec's ten words in basec's order; invweight0 in the collision table's order.
 constexpr int kBodyP = 20, BP_IPOS = 0, BP_I6 = 3, BP_MASS = 9, BP_TOTAL = 10, BP_INVW = 11, BP_PGS = 18;
 constexpr uint64_t kPayloadKey = 0x5041594C4Full;   // nm_draw_payload: rand_u24_bits(seed + kPayloadKey, global env id, column)
+// Per-env actuation latency (nm_set_action_latency, level EP = 3 of the step): an env's servo target is the action of d physics substeps
+// ago, 0 <= d <= kLatH * nsub. The words live in the envp allocation behind the body rows, as 4-byte words whatever the env's dtype:
+// int delay[N], then float hist[N][kLatH][kNU] with hist[j] = a_{t-1-j}, the scaled and clipped float actions of the last kLatH steps.
+constexpr int kLatH = 3, kLatP = 1 + kLatH * 18;   // 4-byte words per env
+constexpr uint64_t kLatencyKey = 0x4C4154454Eull;   // nm_draw_action_latency: rand_u24_bits(seed + kLatencyKey, global env id, 0)
+template <class real> NM_FN int* lat_delay(const Args<real>& A) {
+  return reinterpret_cast<int*>(const_cast<real*>(A.envp) + (size_t)A.N * (kEnvP + kBodyP));
+}
+template <class real> NM_FN float* lat_hist(const Args<real>& A) { return reinterpret_cast<float*>(lat_delay(A) + A.N); }
 constexpr int kDbgN = 256;
 
 // ----------------------------------------------------------------------------------------- LDS image of one env
@@ -216,6 +225,20 @@ template <class real, int G> struct ShWSel<real, G, 2> {
   typedef ShWB<real, G> type;
   static NM_FN ShW<real, G>& images(type& s) { return s.w; }
 };
+// Level 3 (level 2 plus actuation latency) parks, behind the body rows, the servo command an env switches to inside the step and the
+// substep at which it does (0 = never: one command for the whole step). The physics stages of level 3 read what level 2's read, but
+// are instantiations of their own: a stage shared between the kernels of two levels would no longer have ONE caller, and level 2's
+// kernels would be inlined differently from the parent's (their kstats lines moved when that was tried).
+template <class real, int G> struct ShWL {
+  ShWB<real, G> b;
+  real late[G * 18];
+  int rsw[G];
+};
+template <class real, int G> NM_FN ShWL<real, G>& lat_rows(ShW<real, G>& w) { return *reinterpret_cast<ShWL<real, G>*>(&w); }
+template <class real, int G> struct ShWSel<real, G, 3> {
+  typedef ShWL<real, G> type;
+  static NM_FN ShW<real, G>& images(type& s) { return s.b.w; }
+};
 #define NM_OFS(field) ((int)(offsetof(Sh<real>, field) / sizeof(real)))
 #define NM_IOFS(field) ((int)(offsetof(Sh<real>, field) / sizeof(int)))
 
@@ -223,7 +246,8 @@ template <class real, int G> struct ShWSel<real, G, 2> {
 // exactly as before and never touches Sh::envp or Args::envp - its instruction stream is the one it had before the feature; 1, launched
 // when friction / gain rows are set, reads them from the env image; 2, launched while body rows are set, does that and takes the base
 // body's constants, total_mass, the colliding bodies' invweight0 and pgs_scale from the env's body row (the host supplies default envp
-// rows when only a payload is set).
+// rows when only a payload is set); 3, launched while actuation delays are set, is level 2 plus the delayed servo command (env_load*,
+// latency_switch; the host supplies default rows of both kinds where the caller set none).
 template <int EP, class real> NM_FN real env_mu(const Sh<real>& sh, const Model<real>& M) {
   if constexpr (EP != 0) return sh.envp[EP_MU]; else return M.mu;
 }
@@ -238,12 +262,17 @@ template <class real> struct BodyRef<2, real> {
   NM_FN BodyRef() : p(nullptr) {}
   NM_FN explicit BodyRef(const real* q) : p(q) {}
 };
+template <class real> struct BodyRef<3, real> {
+  const real* p;
+  NM_FN BodyRef() : p(nullptr) {}
+  NM_FN explicit BodyRef(const real* q) : p(q) {}
+};
 // body_invweight0[.][0] of colliding mesh g (0 = base, 1..6 = tibias), per lane
 template <int EP, class real> NM_FN V<real> body_invw(const BodyRef<EP, real>& b, const Model<real>& M, const V<int>& g) {
-  if constexpr (EP == 2) return ldsv(b.p, g + BP_INVW); else return ldsv(M.colc, g * kColN + 4);
+  if constexpr (EP >= 2) return ldsv(b.p, g + BP_INVW); else return ldsv(M.colc, g * kColN + 4);
 }
 template <int EP, class real> NM_FN real body_pgs(const BodyRef<EP, real>& b, const Model<real>& M) {
-  if constexpr (EP == 2) return b.p[BP_PGS]; else return M.pgs_scale;
+  if constexpr (EP >= 2) return b.p[BP_PGS]; else return M.pgs_scale;
 }
 
 // ----------------------------------------------------------------------------------------- small algebra
@@ -627,7 +656,7 @@ template <int EP, class real, int G> NM_FN void stage_smooth(ShW<real, G>& w, co
 #pragma unroll
         for (int j = 0; j < 6; j++) Ib[j] = ldsv(M.legc, cbm + 18 + j);
         vr mass = ldsv(M.legc, cbm + 24);
-        if constexpr (EP == 2) {   // the base-role lanes take ipos / Ibody / mass from their env's body row instead of M.basec
+        if constexpr (EP >= 2) {   // the base-role lanes take ipos / Ibody / mass from their env's body row instead of M.basec
 #pragma unroll
           for (int j = 0; j < 3; j++) ipos[j] = sel(isbase, LDB(BP_IPOS + j), ipos[j]);
 #pragma unroll
@@ -705,13 +734,13 @@ template <int EP, class real, int G> NM_FN void stage_smooth(ShW<real, G>& w, co
     for (int j = 0; j < 10; j++) Ib10[j] = LDG(sc, 15 + j);
     if (last) {  // subtree COM (relative to the base origin) -> cvel[1] as MuJoCo reports it (about the COM)
       vr ipos[3] = {vr(M.basec[0]), vr(M.basec[1]), vr(M.basec[2])};
-      if constexpr (EP == 2) { ipos[0] = LDB(BP_IPOS); ipos[1] = LDB(BP_IPOS + 1); ipos[2] = LDB(BP_IPOS + 2); }
+      if constexpr (EP >= 2) { ipos[0] = LDB(BP_IPOS); ipos[1] = LDB(BP_IPOS + 1); ipos[2] = LDB(BP_IPOS + 2); }
       vr d[3];
       matvec3(d, Rb, ipos);
       vr cr[3], t[3];
 #pragma unroll
       for (int j = 0; j < 3; j++) {
-        if constexpr (EP == 2) cr[j] = (LDB(BP_MASS) * d[j] + (LDG(sc, j) + LDG(sc, 3 + j) + LDG(sc, 6 + j))) / LDB(BP_TOTAL);
+        if constexpr (EP >= 2) cr[j] = (LDB(BP_MASS) * d[j] + (LDG(sc, j) + LDG(sc, 3 + j) + LDG(sc, 6 + j))) / LDB(BP_TOTAL);
         else cr[j] = (M.basec[9] * d[j] + (LDG(sc, j) + LDG(sc, 3 + j) + LDG(sc, 6 + j))) / M.total_mass;
       }
       cross3(t, vb, cr);
@@ -2010,9 +2039,9 @@ template <int EP, class real> NM_FN void stage_constraint2(ShW<real, 2>& w, cons
 #define MU2 mu2()
   // level 2: the body rows of the two envs (body_rows), the half's own through hb; pgs_scale of the half's env per lane
   const real* bp2 = nullptr;
-  if constexpr (EP == 2) bp2 = body_rows(w);
+  if constexpr (EP >= 2) bp2 = body_rows(w);
   const V<int> hb = h * kBodyP;
-  auto pgs2 = [&]() { if constexpr (EP == 2) return ldsv(bp2, hb + BP_PGS); else return M.pgs_scale; };
+  auto pgs2 = [&]() { if constexpr (EP >= 2) return ldsv(bp2, hb + BP_PGS); else return M.pgs_scale; };
 #define PGS2 pgs2()
   vr smu = sel(sg == 0, MU2, -MU2);
   vr nrm[3] = {vr(real(0)), vr(real(0)), vr(real(1))};
@@ -2083,7 +2112,7 @@ template <int EP, class real> NM_FN void stage_constraint2(ShW<real, 2>& w, cons
     imp = sel(x <= vr(real(0)), vr(M.si_d0), imp);
   }
   vr invw;
-  if constexpr (EP == 2) invw = ldsv(bp2, hb + (Lc + sel(onleg, V<int>(1), V<int>(0)) + BP_INVW));   // the half's env's own invweight0
+  if constexpr (EP >= 2) invw = ldsv(bp2, hb + (Lc + sel(onleg, V<int>(1), V<int>(0)) + BP_INVW));   // the half's env's own invweight0
   else invw = ldsv(M.colc, (Lc + sel(onleg, V<int>(1), V<int>(0))) * kColN + 4);
   vr Rr = vmax((vr(real(1)) - imp) * (invw + MU2 * MU2 * invw) * vrcp(imp), vr(real(1e-15))) * (real(2) * MU2 * MU2);
   vr Dd = vrcp(Rr);
@@ -2929,7 +2958,7 @@ template <int EP, class real, int G> NM_FN void substep(ShW<real, G>& w, const M
   if (!together)
     for (int e = 0; e < G; e++) {
       BodyRef<EP, real> br;
-      if constexpr (EP == 2) br = BodyRef<EP, real>(body_rows(w) + e * kBodyP);
+      if constexpr (EP >= 2) br = BodyRef<EP, real>(body_rows(w) + e * kBodyP);
       stage_constraint<real, EP>(w.e[e], w.jrow, M, last, (ablate & 2) != 0, br);
       nm_stamp(8);
     }
@@ -2940,7 +2969,8 @@ template <int EP, class real, int G> NM_FN void substep(ShW<real, G>& w, const M
 // =========================================================================================  env step
 
 // load one env's state into its LDS image, action -> servo command (E1)
-template <int EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real>& M, const Args<real>& A, int env, real* bp = nullptr) {
+template <int EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real>& M, const Args<real>& A, int env, real* bp = nullptr,
+                                                real* late = nullptr, int* rsw = nullptr, bool live = true) {
   typedef V<real> vr;
   const V<int> lane = opaque_lane();   // index math stays local to this function (not kept live across the physics)
   const VB l18 = lane < kNU;
@@ -2955,10 +2985,20 @@ template <int EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real
   vr envp_in = vr(real(0));
   if constexpr (EP != 0) envp_in = gldv(A.envp, sel(lane < kEnvP, lane, V<int>(0)) + env * kEnvP);     // the env's (mu, p_gain, kv, pad) row: 16 bytes, lanes 0..3
   vr body_in = vr(real(0));
-  if constexpr (EP == 2) body_in = gldv(A.envp, sel(lane < kBodyP, lane, V<int>(0)) + (A.N * kEnvP + env * kBodyP));   // the env's body row, behind the N envp rows
+  if constexpr (EP >= 2) body_in = gldv(A.envp, sel(lane < kBodyP, lane, V<int>(0)) + (A.N * kEnvP + env * kBodyP));   // the env's body row, behind the N envp rows
   vr cmd_in = vr(real(0)), eps_in = vr(real(0)), prev_act = vr(real(0)), prev_dofvel = vr(real(0)), dofpos_old = vr(real(0));
   int64_t ep = 0;
   uint32_t ctr_in = 0;
+  // level 3: the env's delay and its whole action history (three rows, lane = joint) with the step's other reads: no read waits for the delay
+  int dl = 0;
+  V<float> h0 = V<float>(0.0f), h1 = V<float>(0.0f), h2 = V<float>(0.0f);
+  if constexpr (EP == 3)
+    if (!A.physics_only) {
+      dl = gld1(lat_delay(A), env);
+      h0 = gldv(lat_hist(A), l18c + env * (kLatH * kNU));
+      h1 = gldv(lat_hist(A), l18c + (env * (kLatH * kNU) + kNU));
+      h2 = gldv(lat_hist(A), l18c + (env * (kLatH * kNU) + 2 * kNU));
+    }
   if (!A.physics_only) {   // what the epilogue needs from HBM is fetched now, under the physics, not when it is needed
     cmd_in = gldv(A.cmd, sel(lane < 3, lane, V<int>(0)) + env * 3);
     eps_in = gldv(A.epsum, sel(lane < kNREW, lane, V<int>(0)) + env * kNREW);
@@ -2979,7 +3019,7 @@ template <int EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real
   real p_gain = M.p_gain;
   if constexpr (EP != 0) {
     stsv(sh.envp, lane, envp_in, lane < kEnvPS);
-    if constexpr (EP == 2) stsv(bp, lane, body_in, lane < kBodyP);
+    if constexpr (EP >= 2) stsv(bp, lane, body_in, lane < kBodyP);
     p_gain = rdlane(envp_in, EP_PGAIN);
   }
   // ---- E1 (env.py:152-156,181-192): float32 scale + clip; PD -> velocity command from the env's own dof_pos buffer
@@ -3002,10 +3042,28 @@ template <int EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real
     sh.eplen_lo = (int)(uint32_t)(ep & 0xffffffffll);
     sh.eplen_hi = (int)(ep >> 32);
     sh.ectr = ctr_in;
+    if constexpr (EP == 3) {
+      // delay d = k nsub + r: substeps s < r aim at a_{t-k-1}, substeps s >= r at a_{t-k} (a_t itself where k = 0). Each command comes
+      // from its own action by today's expression, so it has the bits an undelayed env would give that action.
+      const int nsub = A.nsub;
+      const int k = (dl >= nsub ? 1 : 0) + (dl >= 2 * nsub ? 1 : 0) + (dl >= 3 * nsub ? 1 : 0), r = dl - k * nsub;
+      const V<float> fl = k == 0 ? af : (k == 1 ? h0 : (k == 2 ? h1 : h2));
+      const V<float> fe = r > 0 ? (k == 0 ? h0 : (k == 1 ? h1 : h2)) : fl;
+      stsv(sh.ctrl, lane, ((vcvt<real>(fe) - defp) - dofpos_old) * p_gain, l18);
+      stsv(late, lane, ((vcvt<real>(fl) - defp) - dofpos_old) * p_gain, l18);
+      *rsw = r;
+      // the history takes this step's action now: all three rows are in registers here, and a launch runs whole or not at all
+      float* hist = lat_hist(A);
+      const VB st = l18 & VB(live);
+      gstv(hist, lane + (env * (kLatH * kNU) + 2 * kNU), h1, st);
+      gstv(hist, lane + (env * (kLatH * kNU) + kNU), h0, st);
+      gstv(hist, lane + env * (kLatH * kNU), af, st);
+    } else
     stsv(sh.ctrl, lane, ((act - defp) - dofpos_old) * p_gain, l18);
   } else {  // dynamics-only mode (BASELINE config 2): same PD law on the current joint angles, no env buffers
     wave_sync();
     stsv(sh.ctrl, lane, ((act - defp) - ldsv(sh.qpos, l18c + 7)) * p_gain, l18);
+    if constexpr (EP == 3) *rsw = 0;     // a physics-only launch ignores latency
   }
   // carried to the epilogue through LDS, not in registers: nothing stays live across the physics
   stsv(sh.eact, lane, act, l18); stsv(sh.epact, lane, prev_act, l18); stsv(sh.epdv, lane, prev_dofvel, l18);
@@ -3328,8 +3386,18 @@ template <int EP, class real, class Mid> NM_FN void env_load2(ShW<real, 2>& w, c
   vr envp_in = vr(real(0));
   if constexpr (EP != 0) envp_in = gldv(A.envp, sel(hl < kEnvP, hl, V<int>(0)) + env * kEnvP);     // each env's (mu, p_gain, kv, pad) row: 16 bytes, lanes 0..3 of its half
   vr body_in = vr(real(0));
-  if constexpr (EP == 2) body_in = gldv(A.envp, sel(hl < kBodyP, hl, V<int>(0)) + (env * kBodyP + A.N * kEnvP));   // each env's body row (behind the N envp rows), lanes 0..19 of its half
+  if constexpr (EP >= 2) body_in = gldv(A.envp, sel(hl < kBodyP, hl, V<int>(0)) + (env * kBodyP + A.N * kEnvP));   // each env's body row (behind the N envp rows), lanes 0..19 of its half
   vr cmd_in = vr(real(0)), eps_in = vr(real(0)), prev_act = vr(real(0)), prev_dofvel = vr(real(0)), dofpos_old = vr(real(0));
+  // level 3: each env's delay and its whole action history (three rows, lane of the half = joint) with the step's other reads
+  V<int> dl = V<int>(0);
+  V<float> h0 = V<float>(0.0f), h1 = V<float>(0.0f), h2 = V<float>(0.0f);
+  if constexpr (EP == 3)
+    if (!A.physics_only) {
+      dl = gldv(lat_delay(A), env);
+      h0 = gldv(lat_hist(A), l18c + env * (kLatH * kNU));
+      h1 = gldv(lat_hist(A), l18c + (env * (kLatH * kNU) + kNU));
+      h2 = gldv(lat_hist(A), l18c + (env * (kLatH * kNU) + 2 * kNU));
+    }
 #ifndef NM_EMUL
   int64_t ep = 0;
   uint32_t ctr_in = 0;
@@ -3361,7 +3429,7 @@ template <int EP, class real, class Mid> NM_FN void env_load2(ShW<real, 2>& w, c
   vr p_gain = vr(M.p_gain);
   if constexpr (EP != 0) {
     stsv(rb, ho + (hl + NM_OFS(envp)), envp_in, hl < kEnvPS);
-    if constexpr (EP == 2) stsv(body_rows(w), h * kBodyP + hl, body_in, hl < kBodyP);
+    if constexpr (EP >= 2) stsv(body_rows(w), h * kBodyP + hl, body_in, hl < kBodyP);
     p_gain = sel(h != 0, vr(rdlane(envp_in, 32 + EP_PGAIN)), vr(rdlane(envp_in, EP_PGAIN)));
   }
   // ---- E1 (env.py:152-156,181-192): float32 scale + clip; PD -> velocity command from the env's own dof_pos buffer
@@ -3394,10 +3462,30 @@ template <int EP, class real, class Mid> NM_FN void env_load2(ShW<real, 2>& w, c
     stsv(ib, hoi + NM_IOFS(eplen_hi), (int)(ep >> 32), hl == 0);
     stsv(ib, hoi + NM_IOFS(ectr), (int)ctr_in, hl == 0);
 #endif
+    if constexpr (EP == 3) {
+      // delay d = k nsub + r, per half: substeps s < r aim at a_{t-k-1}, substeps s >= r at a_{t-k} (a_t itself where k = 0). Each
+      // command comes from its own action by today's expression, so it has the bits an undelayed env would give that action.
+      const V<int> ns = V<int>(A.nsub), one = V<int>(1), zero = V<int>(0);
+      const V<int> k = sel(dl >= ns, one, zero) + sel(dl >= ns + ns, one, zero) + sel(dl >= ns + ns + ns, one, zero), r = dl - k * ns;
+      const V<float> fl = sel(k == zero, af, sel(k == one, h0, sel(k == V<int>(2), h1, h2)));
+      const V<float> fe = sel(r > zero, sel(k == zero, h0, sel(k == one, h1, h2)), fl);
+      ShWL<real, 2>& L = lat_rows(w);
+      stsv(rb, ho + (hl + NM_OFS(ctrl)), ((vcvt<real>(fe) - defp) - dofpos_old) * p_gain, l18);
+      stsv(L.late, h * kNU + hl, ((vcvt<real>(fl) - defp) - dofpos_old) * p_gain, l18);
+      stsv(L.rsw, h, r, hl == zero);
+      // the history takes this step's action now: all three rows are in registers here, and a launch runs whole or not at all. A
+      // padded slot (it recomputes the last env) stores nothing
+      float* hist = lat_hist(A);
+      const VB st = l18 & (env0 < V<int>(A.N));
+      gstv(hist, hl + (env * (kLatH * kNU) + 2 * kNU), h1, st);
+      gstv(hist, hl + (env * (kLatH * kNU) + kNU), h0, st);
+      gstv(hist, hl + env * (kLatH * kNU), af, st);
+    } else
     stsv(rb, ho + (hl + NM_OFS(ctrl)), ((act - defp) - dofpos_old) * p_gain, l18);
   } else {
     wave_sync();
     stsv(rb, ho + (hl + NM_OFS(ctrl)), ((act - defp) - ldsv(rb, ho + (l18c + (7 + NM_OFS(qpos))))) * p_gain, l18);
+    if constexpr (EP == 3) stsv(lat_rows(w).rsw, h, V<int>(0), hl == V<int>(0));     // a physics-only launch ignores latency
   }
   stsv(rb, ho + (hl + NM_OFS(eact)), act, l18); stsv(rb, ho + (hl + NM_OFS(epact)), prev_act, l18); stsv(rb, ho + (hl + NM_OFS(epdv)), prev_dofvel, l18);
   wave_sync();
@@ -3700,6 +3788,27 @@ template <class real, class Pub> NM_FN void env_finish2(ShW<real, 2>& w, const M
 }
 
 // one wavefront = G consecutive envs (E2, env.py:200: mj_step(model, data, decimation) between load and epilogue)
+// Level 3: at the top of substep s the 18 joint lanes of an env whose switch substep is s (0 < r = s) replace the servo command by the
+// parked one. The halves of a two-env wave switch independently. Between two wave_syncs: stage A of the substep before has read sh.ctrl,
+// stage A of this one reads it next.
+template <class real, int G> NM_FN void latency_switch(ShW<real, G>& w, int s) {
+  ShWL<real, G>& L = lat_rows(w);
+  const V<int> lane = opaque_lane();
+  wave_sync();
+  if constexpr (G == 2) {
+    constexpr int kSR = (int)(sizeof(Sh<real>) / sizeof(real));
+    real* rb = reinterpret_cast<real*>(&w.e[0]);
+    const V<int> h = lane >> 5, hl = lane & 31;
+    const VB on = (hl < kNU) & (ldsv(L.rsw, h) == V<int>(s));
+    const V<real> cmd = ldsv(L.late, h * kNU + sel(hl < kNU, hl, V<int>(0)));
+    stsv(rb, h * kSR + (hl + NM_OFS(ctrl)), cmd, on);
+  } else {
+    for (int e = 0; e < G; e++)
+      if (uniform(L.rsw[e]) == s) stsv(w.e[e].ctrl, lane, ldsv(L.late, sel(lane < kNU, lane, V<int>(0)) + e * kNU), lane < kNU);
+  }
+  wave_sync();
+}
+
 template <class real, int G, int EP = 0, class Mid = NoMid, class Pub = NoMid>
 NM_FN void wave_step(ShW<real, G>& w, const Model<real>& M, const Args<real>& A, int wave, Mid&& mid = Mid(), Pub&& published = Pub()) {
   nm_stamp(-1);
@@ -3711,7 +3820,9 @@ NM_FN void wave_step(ShW<real, G>& w, const Model<real>& M, const Args<real>& A,
     for (int e = 0; e < G; e++) {
       int env = wave * G + e;
       real* bp = nullptr;
-      if constexpr (EP == 2) bp = body_rows(w) + e * kBodyP;
+      if constexpr (EP >= 2) bp = body_rows(w) + e * kBodyP;
+      if constexpr (EP == 3) env_load<EP>(w.e[e], M, A, env < A.N ? env : A.N - 1, bp, lat_rows(w).late + e * kNU, lat_rows(w).rsw + e, env < A.N);
+      else
       env_load<EP>(w.e[e], M, A, env < A.N ? env : A.N - 1, bp);
     }
   }
@@ -3719,7 +3830,10 @@ NM_FN void wave_step(ShW<real, G>& w, const Model<real>& M, const Args<real>& A,
   int dropped = 0;
   if (NM_ABLATE(A.ablate) & 1024) return;   // measurement only: load stage alone
   if (!(NM_ABLATE(A.ablate) & 2048))
-  for (int s = 0; s < A.nsub; s++) substep<EP>(w, M, s == A.nsub - 1, &dropped, NM_ABLATE(A.ablate));
+  for (int s = 0; s < A.nsub; s++) {
+    if constexpr (EP == 3) { if (s > 0) latency_switch(w, s); }
+    substep<EP>(w, M, s == A.nsub - 1, &dropped, NM_ABLATE(A.ablate));
+  }
   if constexpr (G == 2) {
     env_finish2(w, M, A, wave, dropped, published);
   } else {

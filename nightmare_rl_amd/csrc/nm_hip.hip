@@ -88,8 +88,8 @@ constexpr int kWG = NM_WG_WAVES;
 #else
 constexpr int kWG = 1;
 #endif
-// EP: level of per-env physics parameters (nm_core.h env_mu): 0 none, 1 friction / gain rows (nm::Args::envp), 2 those and body rows - the
-// host launches a level above 0 only while its rows are set
+// EP: level of per-env physics parameters (nm_core.h env_mu): 0 none, 1 friction / gain rows (nm::Args::envp), 2 those and body rows, 3 those
+// and actuation latency - the host launches a level above 0 only while its rows are set
 template <class real, int G, int EP>
 __global__ void __launch_bounds__(64 * (sizeof(real) == 8 ? 1 : kWG), NM_WAVES_PER_SIMD) k_env_step(const nm::Model<real>* __restrict__ Mp, nm::Args<real> A) {
   constexpr int kWG = sizeof(real) == 8 ? 1 : ::kWG;     // the fp64 verification build keeps one wave per workgroup
@@ -283,6 +283,15 @@ __global__ void k_payload_draw(real* __restrict__ out, int N, uint64_t seed, int
   out[i] = envp_lerp(lo.v[col], u, hi.v[col] - lo.v[col]);
 }
 
+// Per-env actuation latency (nm_core.h kLatP): delay[e] = lo + floor(u (hi - lo + 1)), u = bits * 2^-24 with bits =
+// rand_u24_bits(seed + kLatencyKey, global env id, 0): in integers, lo + ((bits * (hi - lo + 1)) >> 24) - exact, the same in either dtype.
+__global__ void k_latency_draw(int* __restrict__ delay, int N, uint64_t seed, int64_t env_offset, int lo, int hi) {
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= N) return;
+  const uint64_t bits = nm::rand_u24_bits(seed + nm::kLatencyKey, (uint64_t)(env_offset + e), 0u);
+  delay[e] = lo + (int)((bits * (uint64_t)(hi - lo + 1)) >> 24);
+}
+
 // ------------------------------------------------------------------------------------------------ host object
 struct nm_env {
   int N = 0, device = 0, dtype = 0;
@@ -320,6 +329,11 @@ struct nm_env {
   virtual int set_body_params(const void* rows, hipStream_t s) = 0;
   virtual int get_body_params(void* out, hipStream_t s) = 0;
   virtual int draw_payload(const double* lo, const double* hi, void* out, hipStream_t s) = 0;
+  virtual int set_action_latency(const int* substeps, hipStream_t s) = 0;
+  virtual int get_action_latency(int* out, hipStream_t s) = 0;
+  virtual int draw_action_latency(int lo, int hi, hipStream_t s) = 0;
+  virtual int set_action_history(const float* h, hipStream_t s) = 0;
+  virtual int get_action_history(float* out, hipStream_t s) = 0;
   // push perturbations (nm_push.h): the setting and the push step index - full env steps taken, K per K-step launch; physics-only
   // launches and nm_reset leave it alone
   int push_interval = 0;
@@ -486,7 +500,9 @@ template <class real> struct Env : nm_env {
     }
     constexpr int G = sizeof(real) == 8 ? 1 : NM_ENVS_PER_WAVE;  // the fp64 verification build keeps one env per wave (LDS)
     constexpr int W = sizeof(real) == 8 ? 1 : kWG;
-    if (body_on) hipLaunchKernelGGL((k_env_step<real, G, 2>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
+    const int lv = level();      // a physics-only launch ignores latency: level 2 on the rows level 3 reads
+    if (lv == 3 && !physics_only) hipLaunchKernelGGL((k_env_step<real, G, 3>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
+    else if (lv >= 2) hipLaunchKernelGGL((k_env_step<real, G, 2>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
     else if (a.envp) hipLaunchKernelGGL((k_env_step<real, G, 1>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
     else hipLaunchKernelGGL((k_env_step<real, G, 0>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
     HIPCHK(hipGetLastError());
@@ -820,9 +836,13 @@ template <class real> struct Env : nm_env {
   // holds the N friction / gain rows and, behind them, the N body rows (nm::Args has no word for a second pointer): A.envp is set while
   // either kind is on, and while only body rows are the friction / gain rows hold the defaults.
   real* envp_dev = nullptr;
-  bool envp_on = false, body_on = false;
-  int level() const { return body_on ? 2 : (A.envp ? 1 : 0); }     // which instantiation of the step a launch takes (nm_core.h env_mu)
-  int envp_alloc() { return !envp_dev && dalloc(&envp_dev, (size_t)N * (nm::kEnvP + nm::kBodyP)); }
+  // Behind the body rows come the latency words (nm_core.h kLatP: N delays, then N action histories, 4-byte words in either dtype).
+  // Level 3 (latency) reads all three kinds: whichever of the first two the caller has not set holds the defaults while it is on.
+  bool envp_on = false, body_on = false, lat_on = false;
+  int level() const { return lat_on ? 3 : (body_on ? 2 : (A.envp ? 1 : 0)); }     // which instantiation of the step a launch takes (nm_core.h env_mu)
+  int envp_alloc() {
+    return !envp_dev && dalloc(&envp_dev, (size_t)N * (nm::kEnvP + nm::kBodyP) + ((size_t)N * nm::kLatP * 4 + sizeof(real) - 1) / sizeof(real));
+  }
   real* body_dev() const { return envp_dev + (size_t)N * nm::kEnvP; }
   EnvP3<real> envp_default() const { return EnvP3<real>{{M.mu, M.p_gain, M.kv}}; }
   int envp_fill_default(hipStream_t s) {
@@ -834,7 +854,7 @@ template <class real> struct Env : nm_env {
     HIPCHK(hipSetDevice(device));
     if (!mu && !p_gain && !kv) {     // off; the rows stay allocated (a launch in flight may read them)
       envp_on = false;
-      if (body_on) return envp_fill_default(s);      // level 2 goes on reading rows: the defaults
+      if (body_on || lat_on) return envp_fill_default(s);      // levels 2 and 3 go on reading rows: the defaults
       A.envp = nullptr;
       return 0;
     }
@@ -860,6 +880,7 @@ template <class real> struct Env : nm_env {
     HIPCHK(hipSetDevice(device));
     if (!rows) {       // off; nothing is freed
       body_on = false;
+      if (lat_on) return body_fill_default(s);      // level 3 goes on reading rows: the defaults
       if (!envp_on) A.envp = nullptr;
       return 0;
     }
@@ -883,6 +904,70 @@ template <class real> struct Env : nm_env {
     HIPCHK(hipMemcpyAsync(body_dev(), rows, h.size() * sizeof(real), hipMemcpyDeviceToDevice, s));
     A.envp = envp_dev;
     body_on = true;
+    return 0;
+  }
+  int body_fill_default(hipStream_t s) {
+    hipLaunchKernelGGL(k_body_fill<real>, dim3((nm::kBodyP * N + 255) / 256), dim3(256), 0, s, body_dev(), N, body_default());
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  // ---- per-env actuation latency
+  int* lat_delay_dev() const { return reinterpret_cast<int*>(envp_dev + (size_t)N * (nm::kEnvP + nm::kBodyP)); }
+  float* lat_hist_dev() const { return reinterpret_cast<float*>(lat_delay_dev() + N); }
+  int lat_max() const { return nm::kLatH * A.nsub; }
+  int lat_switch_on(hipStream_t s) {       // the rows level 3 reads besides its own
+    if (!envp_on && envp_fill_default(s)) return 1;
+    if (!body_on && body_fill_default(s)) return 1;
+    A.envp = envp_dev;
+    lat_on = true;
+    return 0;
+  }
+  int set_action_latency(const int* substeps, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (!substeps) {       // off; nothing is freed, the history keeps what it holds
+      lat_on = false;
+      if (!envp_on && !body_on) A.envp = nullptr;
+      return 0;
+    }
+    // the delays are judged on the host before anything of the env changes
+    std::vector<int> h((size_t)N);
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpy(h.data(), substeps, h.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int e = 0; e < N; e++)
+      if (h[e] < 0 || h[e] > lat_max())
+        return fail("nm_set_action_latency: env " + std::to_string(e) + ": delay " + std::to_string(h[e]) + " outside [0, " + std::to_string(lat_max()) + "] substeps");
+    if (envp_alloc()) return 1;
+    HIPCHK(hipMemcpyAsync(lat_delay_dev(), substeps, h.size() * sizeof(int), hipMemcpyDeviceToDevice, s));
+    return lat_switch_on(s);
+  }
+  int get_action_latency(int* out, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (!out) return 0;
+    if (lat_on) HIPCHK(hipMemcpyAsync(out, lat_delay_dev(), (size_t)N * sizeof(int), hipMemcpyDeviceToDevice, s));
+    else HIPCHK(hipMemsetAsync(out, 0, (size_t)N * sizeof(int), s));
+    return 0;
+  }
+  int draw_action_latency(int lo, int hi, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (hi > lat_max()) return fail("nm_draw_action_latency: hi " + std::to_string(hi) + " above " + std::to_string(lat_max()) + " substeps");
+    if (envp_alloc()) return 1;
+    hipLaunchKernelGGL(k_latency_draw, dim3((N + 255) / 256), dim3(256), 0, s, lat_delay_dev(), N, A.seed, A.env_offset, lo, hi);
+    HIPCHK(hipGetLastError());
+    return lat_switch_on(s);
+  }
+  int set_action_history(const float* h, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (!h) return fail("nm_set_action_history: the history is NULL");
+    if (envp_alloc()) return 1;
+    HIPCHK(hipMemcpyAsync(lat_hist_dev(), h, (size_t)N * nm::kLatH * nm::kNU * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+  }
+  int get_action_history(float* out, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (!out) return 0;
+    const size_t bytes = (size_t)N * nm::kLatH * nm::kNU * sizeof(float);
+    if (envp_dev) HIPCHK(hipMemcpyAsync(out, lat_hist_dev(), bytes, hipMemcpyDeviceToDevice, s));
+    else HIPCHK(hipMemsetAsync(out, 0, bytes, s));      // never allocated: zero, as at construction
     return 0;
   }
   int get_body_params(void* out, hipStream_t s) override {
@@ -1148,6 +1233,29 @@ int nm_draw_payload(nm_env* env, const double lo[4], const double hi[4], void* o
     for (int k = 0; k < 4; k++)
       if (!std::isfinite((float)lo[k]) || !std::isfinite((float)hi[k])) return fail(std::string("nm_draw_payload: the bounds of ") + kCol[k] + " must be finite in float32");
   return env->draw_payload(lo, hi, out_dev, (hipStream_t)stream);
+}
+int nm_set_action_latency(nm_env* env, const int32_t* substeps_dev, void* stream) {
+  if (!env) return fail("nm_set_action_latency: env is NULL");
+  return env->set_action_latency(substeps_dev, (hipStream_t)stream);
+}
+int nm_get_action_latency(nm_env* env, int32_t* out_dev, void* stream) {
+  if (!env) return fail("nm_get_action_latency: env is NULL");
+  return env->get_action_latency(out_dev, (hipStream_t)stream);
+}
+int nm_draw_action_latency(nm_env* env, int32_t lo, int32_t hi, void* stream) {
+  // the bounds are judged first, so a bad range is named whatever the handle is; the upper limit (history x decimation) needs the env
+  if (lo < 0) return fail("nm_draw_action_latency: lo < 0");
+  if (lo > hi) return fail("nm_draw_action_latency: lo > hi");
+  if (!env) return fail("nm_draw_action_latency: env is NULL");
+  return env->draw_action_latency(lo, hi, (hipStream_t)stream);
+}
+int nm_set_action_history(nm_env* env, const float* hist_dev, void* stream) {
+  if (!env) return fail("nm_set_action_history: env is NULL");
+  return env->set_action_history(hist_dev, (hipStream_t)stream);
+}
+int nm_get_action_history(nm_env* env, float* out_dev, void* stream) {
+  if (!env) return fail("nm_get_action_history: env is NULL");
+  return env->get_action_history(out_dev, (hipStream_t)stream);
 }
 int nm_step_tape(nm_env* env, const nm_tape_args* args, void* stream) {
   if (!env) return fail("nm_step_tape: env is NULL");

@@ -19,6 +19,8 @@ Differences a caller can observe (all documented in DESIGN.md):
     damping_multiplier_range: per-env sliding friction and servo gains, drawn once at construction (set_env_params, draw_env_params)
   * and randomize_base_mass / added_mass_range, randomize_com_displacement / com_displacement_range: a per-env point mass on the base
     body, compiled into the env's model constants (set_base_payload, draw_base_payload), drawn once at construction
+  * and randomize_action_latency / action_latency_range (whole physics substeps): per-env actuation latency - the servo targets lag the
+    policy's actions (set_action_latency, draw_action_latency), drawn once at construction
 """
 import ctypes as C
 import numpy as np
@@ -114,6 +116,25 @@ def payload_config(cfg):
     return ma, co
 
 
+def latency_config(cfg):
+    """(lo, hi) in whole physics substeps from the optional cfg.domain_rand, or None: what draw_action_latency takes.
+    randomize_action_latency needs action_latency_range; a range that is not two integers 0 <= lo <= hi is a ValueError (the upper limit,
+    three env steps, is the library's to judge: it depends on the decimation)."""
+    dr = getattr(cfg, "domain_rand", None)
+    if dr is None or not getattr(dr, "randomize_action_latency", False):
+        return None
+    r = getattr(dr, "action_latency_range", None)
+    if r is None:
+        raise ValueError("cfg.domain_rand.randomize_action_latency needs action_latency_range")
+    try:
+        lo, hi = (float(x) for x in r)
+    except (TypeError, ValueError):
+        raise ValueError("cfg.domain_rand.action_latency_range must be a pair (lo, hi)") from None
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo == int(lo) and hi == int(hi) and 0 <= lo <= hi):
+        raise ValueError("cfg.domain_rand.action_latency_range must be whole substeps with 0 <= lo <= hi")
+    return int(lo), int(hi)
+
+
 class NightmareV3Env:
     def __init__(self, cfg: NightmareV3Config, log_dir="/tmp/nightmare_v3/logs", num_threads=1, *, device=None, seed=0,
                  env_id_offset=0, dtype=torch.float32, lib=None):
@@ -154,6 +175,7 @@ class NightmareV3Env:
         push_steps, push_vel = push_config(cfg, self.dt)       # optional cfg.domain_rand: checked before anything is created
         envp_ranges = env_param_config(cfg)
         payload_ranges = payload_config(cfg)
+        latency_range = latency_config(cfg)
         # reward table: zero scales dropped, the rest x dt (reference :123-128). Every name the reference has a _reward_ function
         # for (:399-497) is compiled; a name without one (`collision`, `feet_stumble`, config :95-96) fails like upstream's getattr.
         names = [L.nm_reward_name(i).decode() for i in range(_lib.NUM_REWARDS)]
@@ -230,6 +252,10 @@ class NightmareV3Env:
         self._body_keep = None
         if any(r is not None for r in payload_ranges):
             self.draw_base_payload(*payload_ranges)
+        # per-env actuation latency (optional cfg.domain_rand; no reference line): drawn once, here
+        self._lat_keep = None
+        if latency_range is not None:
+            self.draw_action_latency(*latency_range)
         # state log of env 0 (reference :261-272; reader open_custom_play.py:50-66)
         self.state_log = None
         self._rec_env = 0
@@ -371,6 +397,60 @@ class NightmareV3Env:
         d = out.to(torch.float64).cpu().numpy()
         self.set_base_payload(d[:, 0], d[:, 1:])
         return self.base_payload()
+
+    ACTION_HISTORY = 3       # past actions an env keeps (nm_core.h kLatH): the longest delay is this many env steps
+
+    def set_action_latency(self, substeps=None):
+        """Per-env actuation latency: env e's servo targets lag the policy's actions by substeps[e] physics substeps, 0 <= d <=
+        ACTION_HISTORY x decimation (nm_set_action_latency; include/nightmare_hip.h states the semantics). With k = d // decimation and r =
+        d % decimation, substep s of step t aims at a_{t-k-1} while s < r and at a_{t-k} afterwards. Observations, rewards, the actions
+        buffer and the logs keep a_t: the policy meets latency through the physics alone. Honoured by step(), policy_rollout,
+        policy_play and step_tape alike; step_physics ignores it. substeps: num_envs integers, one integer for every env, or None =
+        off. The delays hold until they are set again; no reset touches them or the action history."""
+        if substeps is None:
+            self._lat_keep = None
+            self._ck(self._L.nm_set_action_latency(self._h, None, self._stream()))
+            return
+        t = torch.as_tensor(substeps)
+        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+            raise ValueError("set_action_latency: whole substeps (an integer per env)")
+        t = t.to(torch.int32).to(self.device)
+        t = t.expand(self.num_envs) if t.dim() == 0 else t.reshape(-1)
+        if t.numel() != self.num_envs:
+            raise ValueError("set_action_latency: one delay per env (or one for all)")
+        t = t.contiguous()
+        self._ck(self._L.nm_set_action_latency(self._h, C.c_void_p(t.data_ptr()), self._stream()))
+        self._lat_keep = t            # the copy is stream-ordered: the source lives until the next call
+
+    def action_latency(self):
+        """The delays, an int32 tensor [num_envs] in physics substeps (nm_get_action_latency); zeros while the feature is off."""
+        out = torch.empty(self.num_envs, dtype=torch.int32, device=self.device)
+        self._ck(self._L.nm_get_action_latency(self._h, C.c_void_p(out.data_ptr()), self._stream()))
+        return out
+
+    def draw_action_latency(self, lo, hi):
+        """Draw every env's delay on the device, uniform on the integers [lo, hi] (nm_draw_action_latency), and switch the feature on.
+        Keyed by the global env id: shards of one population draw what the whole would. Returns what action_latency() then reports."""
+        if int(lo) != lo or int(hi) != hi:
+            raise ValueError("draw_action_latency: whole substeps")
+        self._ck(self._L.nm_draw_action_latency(self._h, int(lo), int(hi), self._stream()))
+        return self.action_latency()
+
+    def action_history(self):
+        """float32 tensor [num_envs, ACTION_HISTORY, 18]: row j is a_{t-1-j}, the scaled and clipped action of j + 1 steps ago
+        (nm_get_action_history). Zero at construction; it follows the steps taken while latency is on. reset_idx() leaves it alone;
+        reset() is reset_idx() and one step under zero actions, which shifts it like any other step."""
+        out = torch.empty(self.num_envs, self.ACTION_HISTORY, 18, dtype=torch.float32, device=self.device)
+        self._ck(self._L.nm_get_action_history(self._h, C.c_void_p(out.data_ptr()), self._stream()))
+        return out
+
+    def set_action_history(self, h):
+        """Overwrite the action history ([num_envs, ACTION_HISTORY, 18], the order of action_history()): checkpoints and tests."""
+        t = torch.as_tensor(h, dtype=torch.float32).to(self.device).contiguous()
+        if tuple(t.shape) != (self.num_envs, self.ACTION_HISTORY, 18):
+            raise ValueError("set_action_history: [num_envs, 3, 18]")
+        self._ck(self._L.nm_set_action_history(self._h, C.c_void_p(t.data_ptr()), self._stream()))
+        self._hist_keep = t           # the copy is stream-ordered: the source lives until the next call
 
     def _record_state(self):
         # reference :261-272: when env 0 resets, dump what was logged so far, then log (time, qpos, qvel, act) of env 0

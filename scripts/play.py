@@ -109,6 +109,8 @@ def main():
                     help="per-env point mass on the base body in kg (may be negative), drawn once from U[LO, HI) (default: none)")
     ap.add_argument("--com-range", type=float, default=None, metavar="R", dest="com_range",
                     help="where the added mass sits: each coordinate in the base body frame drawn once from U[-R, R) m (default: the base origin)")
+    ap.add_argument("--latency-range", type=int, nargs=2, default=None, metavar=("LO", "HI"), dest="latency_range",
+                    help="per-env actuation latency in physics substeps, drawn once from the integers LO..HI, at most 3 x decimation (default: none)")
     ap.add_argument("--gain-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                     help="per-env multipliers of the servo stiffness and damping, each drawn once from U[LO, HI) (default: 1.0)")
     a = ap.parse_args()
@@ -120,7 +122,7 @@ def main():
         cfg.control.decimation = a.decimation
     if a.record_states is not None:
         cfg.viewer.record_states = True
-    if a.push_interval_s > 0 or a.friction_range or a.gain_range or a.added_mass_range or a.com_range is not None:
+    if a.push_interval_s > 0 or a.friction_range or a.gain_range or a.added_mass_range or a.com_range is not None or a.latency_range:
         class domain_rand:      # the optional class NightmareV3Env reads
             push_robots, push_interval_s, max_push_vel_xy = a.push_interval_s > 0, a.push_interval_s, a.push_vel
             randomize_friction, friction_range = a.friction_range is not None, a.friction_range
@@ -129,6 +131,7 @@ def main():
             randomize_base_mass, added_mass_range = a.added_mass_range is not None, a.added_mass_range
             randomize_com_displacement = a.com_range is not None
             com_displacement_range = None if a.com_range is None else (-a.com_range, a.com_range)
+            randomize_action_latency, action_latency_range = a.latency_range is not None, a.latency_range
         cfg.domain_rand = domain_rand
     env = NightmareV3Env(cfg, device=dev, seed=a.seed, **({"log_dir": a.record_states} if a.record_states is not None else {}))
     print(f"push perturbations: every {env.push_interval} steps, |v| < {env.max_push_vel_xy} m/s" if env.push_interval else "push perturbations: off")

@@ -36,6 +36,8 @@ def main():
                     help="per-env point mass on the base body in kg (may be negative), drawn once from U[LO, HI) (default: none)")
     ap.add_argument("--com-range", type=float, default=None, metavar="R", dest="com_range",
                     help="where the added mass sits: each coordinate in the base body frame drawn once from U[-R, R) m (default: the base origin)")
+    ap.add_argument("--latency-range", type=int, nargs=2, default=None, metavar=("LO", "HI"), dest="latency_range",
+                    help="per-env actuation latency in physics substeps, drawn once from the integers LO..HI, at most 3 x decimation (default: none)")
     ap.add_argument("--gain-range", type=float, nargs=2, default=None, metavar=("LO", "HI"), dest="gain_range",
                     help="per-env multipliers of the servo stiffness (p_gain) and damping (kv), each drawn once from U[LO, HI) (default: 1.0)")
     ap.add_argument("--gpus", type=int, default=None, help="ranks (one per GPU); without torch.distributed.run, train.py starts them itself")
@@ -70,7 +72,7 @@ def main():
     cfg, train_cfg = NightmareV3Config(), NightmareV3ConfigPPO()
     cfg.viewer.render = args.render
     cfg.viewer.record_states = bool(args.record_states) and rank == 0        # one log: rank 0's env 0
-    if args.push_interval_s > 0 or args.friction_range or args.gain_range or args.added_mass_range or args.com_range is not None:
+    if args.push_interval_s > 0 or args.friction_range or args.gain_range or args.added_mass_range or args.com_range is not None or args.latency_range:
         class domain_rand:      # the optional class NightmareV3Env reads
             push_robots, push_interval_s, max_push_vel_xy = args.push_interval_s > 0, args.push_interval_s, args.push_vel
             randomize_friction, friction_range = args.friction_range is not None, args.friction_range
@@ -79,6 +81,7 @@ def main():
             randomize_base_mass, added_mass_range = args.added_mass_range is not None, args.added_mass_range
             randomize_com_displacement = args.com_range is not None
             com_displacement_range = None if args.com_range is None else (-args.com_range, args.com_range)
+            randomize_action_latency, action_latency_range = args.latency_range is not None, args.latency_range
         cfg.domain_rand = domain_rand
     lo, hi = shard_range(args.num_envs, rank, world)
     cfg.env.num_envs = hi - lo
