@@ -1,0 +1,85 @@
+// nm_env_rows.h - host side, plain C++17, no HIP header: the one owner of what the host decides about the per-env rows behind
+// nm::Args::envp (friction / gains, body rows, actuation latency) - layout, default rows, admission, which kinds are on and which level of
+// the step a launch takes. Used by the env object (nm_hip.hip), the K-step launchers and the host emulation (tests/emul, -DNM_EMUL).
+//
+// The invariant every owner of a block keeps: ONCE THE BLOCK IS ALLOCATED, EVERY REGION WHOSE KIND IS OFF HOLDS THAT KIND'S DEFAULTS -
+// default friction / gain rows, default body rows, zero delays - so a transition writes or refills its own region and looks at no other
+// kind's flag. The action history is exempt: it is state, not a parameter, and keeps what it holds.
+#pragma once
+#include <cmath>
+#include <cstddef>
+#include <string>
+#include <type_traits>
+
+#include "nm_core.h"
+
+namespace nmrows {
+
+// ---- layout: one block of `real`s - N friction / gain rows, N body rows, then the latency words (4 bytes each in either dtype): N
+// delays, N action histories. The device finds the last two through nm::lat_delay / nm::lat_hist (nm_core.h), which tests/emul checks
+// against these.
+template <class real> constexpr size_t block_reals(size_t N) {
+  return N * (nm::kEnvP + nm::kBodyP) + (N * nm::kLatP * 4 + sizeof(real) - 1) / sizeof(real);
+}
+template <class real> inline real* fric_rows(real* base, int) { return base; }
+template <class real> inline real* body_rows(real* base, int N) { return base + (size_t)N * nm::kEnvP; }
+template <class real> inline int* delays(real* base, int N) { return reinterpret_cast<int*>(base + (size_t)N * (nm::kEnvP + nm::kBodyP)); }
+template <class real> inline float* histories(real* base, int N) { return reinterpret_cast<float*>(delays(base, N) + N); }
+constexpr size_t hist_words(size_t N) { return N * nm::kLatH * nm::kNU; }
+
+// ---- default rows: the model's own values (the fourth word of a friction / gain row is padding, zero)
+template <class real> inline void fric_default(const nm::Model<real>& M, real out[3]) {
+  out[nm::EP_MU] = M.mu; out[nm::EP_PGAIN] = M.p_gain; out[nm::EP_KV] = M.kv;
+}
+template <class real> inline void body_default(const nm::Model<real>& M, real out[nm::kBodyP]) {
+  for (int j = 0; j < nm::kBodyP; j++) out[j] = real(0);
+  for (int j = 0; j < 10; j++) out[nm::BP_IPOS + j] = M.basec[j];
+  out[nm::BP_TOTAL] = M.total_mass;
+  for (int g = 0; g < nm::kNCOL; g++) out[nm::BP_INVW + g] = M.colc[g * nm::kColN + 4];
+  out[nm::BP_PGS] = M.pgs_scale;
+}
+
+// ---- admission: pure functions of the caller's rows; empty = admitted, otherwise what the entry point reports behind its own name
+template <class real> inline std::string body_rows_fault(const real* rows, int N) {
+  for (int e = 0; e < N; e++) {
+    const real* r = rows + (size_t)e * nm::kBodyP;
+    const char* why = nullptr;
+    for (int j = 0; j < nm::kBodyP; j++) if (!std::isfinite((double)r[j])) why = "a non-finite value";
+    if (!why && !(r[nm::BP_MASS] > 0)) why = "mass <= 0";
+    if (!why && r[nm::BP_TOTAL] < r[nm::BP_MASS]) why = "total_mass < mass";
+    if (!why && !(r[nm::BP_I6] > 0 && r[nm::BP_I6 + 1] > 0 && r[nm::BP_I6 + 2] > 0)) why = "a non-positive inertia diagonal";
+    for (int g = 0; g < nm::kNCOL && !why; g++) if (!(r[nm::BP_INVW + g] > 0)) why = "a non-positive invweight0";
+    if (!why && !(r[nm::BP_PGS] > 0)) why = "a non-positive pgs_scale";
+    if (why) return "row " + std::to_string(e) + ": " + why;
+  }
+  return std::string();
+}
+inline int delay_max(int nsub) { return nm::kLatH * nsub; }     // the history holds kLatH steps of nsub substeps
+inline std::string delays_fault(const int* d, int N, int nsub) {
+  for (int e = 0; e < N; e++)
+    if (d[e] < 0 || d[e] > delay_max(nsub))
+      return "env " + std::to_string(e) + ": delay " + std::to_string(d[e]) + " outside [0, " + std::to_string(delay_max(nsub)) + "] substeps";
+  return std::string();
+}
+
+// ---- state: which kinds are on, and what follows from that for a launch
+enum Kind { kFric = 0, kBody = 1, kLat = 2 };
+struct State {
+  bool on[3] = {false, false, false};
+  // the level of the step a launch takes: the highest kind that is on; a physics-only launch ignores latency (level 2 on the rows level 3 reads)
+  int level(bool physics_only = false) const { return on[kLat] ? (physics_only ? 2 : 3) : (on[kBody] ? 2 : (on[kFric] ? 1 : 0)); }
+  // nm::Args::envp of a launch: the block while any kind is on, null (level 0 never looks) otherwise
+  template <class real> real* envp(real* base) const { return level() ? base : nullptr; }
+};
+
+// f(std::integral_constant<int, L>{}) for the level: the one place a run-time level becomes a template argument
+template <class F> inline auto with_level(int level, F&& f) {
+  switch (level) {
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 1: return f(std::integral_constant<int, 1>{});
+    default: return f(std::integral_constant<int, 0>{});
+  }
+}
+
+}  // namespace nmrows

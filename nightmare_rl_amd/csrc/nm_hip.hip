@@ -11,6 +11,7 @@
 #include "../../include/nightmare_hip.h"
 #include "nm_host_model.h"
 #include "nm_env_loop.h"
+#include "nm_env_rows.h"
 #include "nm_push.h"
 #include "nm_rollout.h"
 
@@ -500,11 +501,9 @@ template <class real> struct Env : nm_env {
     }
     constexpr int G = sizeof(real) == 8 ? 1 : NM_ENVS_PER_WAVE;  // the fp64 verification build keeps one env per wave (LDS)
     constexpr int W = sizeof(real) == 8 ? 1 : kWG;
-    const int lv = level();      // a physics-only launch ignores latency: level 2 on the rows level 3 reads
-    if (lv == 3 && !physics_only) hipLaunchKernelGGL((k_env_step<real, G, 3>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
-    else if (lv >= 2) hipLaunchKernelGGL((k_env_step<real, G, 2>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
-    else if (a.envp) hipLaunchKernelGGL((k_env_step<real, G, 1>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
-    else hipLaunchKernelGGL((k_env_step<real, G, 0>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
+    nmrows::with_level(rows.level(physics_only), [&](auto L) {
+      hipLaunchKernelGGL((k_env_step<real, G, decltype(L)::value>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
+    });
     HIPCHK(hipGetLastError());
     if (prof_on) HIPCHK(hipEventRecord(e1, s));
     return 0;
@@ -754,7 +753,7 @@ template <class real> struct Env : nm_env {
       R.wave_clock = A.dbg ? reinterpret_cast<unsigned long long*>(A.dbg) : nullptr;   // measurement: the debug buffer ([N,256] reals) takes the waves' clocks instead
       nmr::TailArgs ta{N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, r->bootstrap_time_outs ? r->gamma : -1.0f, r->s_values, r->s_rewards,
                        r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
-      if (nmr::launch_rollout(M_dev, a, R, ta, act, level(), s)) return fail("nm_rollout: launch failed");
+      if (nmr::launch_rollout(M_dev, a, R, ta, act, rows.level(), s)) return fail("nm_rollout: launch failed");
       return 0;
     }
   }
@@ -792,7 +791,7 @@ template <class real> struct Env : nm_env {
       rec_done_valid = log != nullptr;
       nmr::TailArgs ta{N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, -1.0f, nullptr, nullptr,
                        r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
-      if (nmr::launch_play(M_dev, a, P, ta, act, level(), s)) return fail("nm_play: launch failed");
+      if (nmr::launch_play(M_dev, a, P, ta, act, rows.level(), s)) return fail("nm_play: launch failed");
       return 0;
     }
   }
@@ -825,160 +824,90 @@ template <class real> struct Env : nm_env {
       rec_done_valid = log != nullptr;
       nmr::TailArgs ta{N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, -1.0f, nullptr, nullptr,
                        r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
-      if (nmr::launch_tape(M_dev, a, T, ta, level(), s)) return fail("nm_step_tape: launch failed");
+      if (nmr::launch_tape(M_dev, a, T, ta, rows.level(), s)) return fail("nm_step_tape: launch failed");
       // with an observation record every step filed its observation in its row: the env's own buffer receives the last one
       if (r->rec_obs_dev)
         HIPCHK(hipMemcpyAsync(r->obs_dev, r->rec_obs_dev + (size_t)(K - 1) * n_ * nm::kNOBS, n_ * nm::kNOBS * sizeof(float), hipMemcpyDeviceToDevice, s));
       return 0;
     }
   }
-  // ---- per-env physics parameters: the rows live in A.envp, which every launch copies with the rest of A (null = off). ONE allocation
-  // holds the N friction / gain rows and, behind them, the N body rows (nm::Args has no word for a second pointer): A.envp is set while
-  // either kind is on, and while only body rows are the friction / gain rows hold the defaults.
+  // ---- per-env rows (friction / gains, body rows, actuation latency): ONE lazily allocated block behind A.envp, which every launch copies
+  // with the rest of A. Where each kind lies in it, what an unset kind holds, which rows are admitted and which level of the step a launch
+  // takes: nm_env_rows.h, and its invariant - once the block exists, every region whose kind is off holds that kind's defaults - is what
+  // the functions below keep: each writes or refills its own region and looks at no other kind.
   real* envp_dev = nullptr;
-  // Behind the body rows come the latency words (nm_core.h kLatP: N delays, then N action histories, 4-byte words in either dtype).
-  // Level 3 (latency) reads all three kinds: whichever of the first two the caller has not set holds the defaults while it is on.
-  bool envp_on = false, body_on = false, lat_on = false;
-  int level() const { return lat_on ? 3 : (body_on ? 2 : (A.envp ? 1 : 0)); }     // which instantiation of the step a launch takes (nm_core.h env_mu)
-  int envp_alloc() {
-    return !envp_dev && dalloc(&envp_dev, (size_t)N * (nm::kEnvP + nm::kBodyP) + ((size_t)N * nm::kLatP * 4 + sizeof(real) - 1) / sizeof(real));
-  }
-  real* body_dev() const { return envp_dev + (size_t)N * nm::kEnvP; }
-  EnvP3<real> envp_default() const { return EnvP3<real>{{M.mu, M.p_gain, M.kv}}; }
-  int envp_fill_default(hipStream_t s) {
-    hipLaunchKernelGGL(k_envp_set<real>, dim3((4 * N + 255) / 256), dim3(256), 0, s, envp_dev, N, EnvP3P<real>{{nullptr, nullptr, nullptr}}, envp_default());
+  nmrows::State rows;
+  EnvP3<real> envp_default() const { EnvP3<real> d; nmrows::fric_default(M, d.v); return d; }
+  BodyRow<real> body_default() const { BodyRow<real> r; nmrows::body_default(M, r.v); return r; }
+  int envp_write(EnvP3P<real> src, hipStream_t s) {      // a null column = its default: all null refills the defaults
+    hipLaunchKernelGGL(k_envp_set<real>, dim3((4 * N + 255) / 256), dim3(256), 0, s, envp_dev, N, src, envp_default());
     HIPCHK(hipGetLastError());
+    return 0;
+  }
+  int body_fill_default(real* dst, hipStream_t s) {
+    hipLaunchKernelGGL(k_body_fill<real>, dim3((nm::kBodyP * N + 255) / 256), dim3(256), 0, s, dst, N, body_default());
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  // at first use, from the slab (zeroed: the delays and the history start at zero); the fills are ordered on the first caller's stream
+  int rows_alloc(hipStream_t s) {
+    if (envp_dev) return 0;
+    if (dalloc(&envp_dev, nmrows::block_reals<real>((size_t)N))) return 1;
+    return envp_write({}, s) || body_fill_default(nmrows::body_rows(envp_dev, N), s);
+  }
+  int rows_turn(nmrows::Kind k, bool on) {
+    rows.on[k] = on;
+    A.envp = rows.envp(envp_dev);
     return 0;
   }
   int set_env_params(const void* mu, const void* p_gain, const void* kv, hipStream_t s) override {
     HIPCHK(hipSetDevice(device));
     if (!mu && !p_gain && !kv) {     // off; the rows stay allocated (a launch in flight may read them)
-      envp_on = false;
-      if (body_on || lat_on) return envp_fill_default(s);      // levels 2 and 3 go on reading rows: the defaults
-      A.envp = nullptr;
-      return 0;
+      if (envp_dev && envp_write({}, s)) return 1;
+      return rows_turn(nmrows::kFric, false);
     }
-    if (envp_alloc()) return 1;
-    EnvP3P<real> src{{(const real*)mu, (const real*)p_gain, (const real*)kv}};
-    hipLaunchKernelGGL(k_envp_set<real>, dim3((4 * N + 255) / 256), dim3(256), 0, s, envp_dev, N, src, envp_default());
+    if (rows_alloc(s) || envp_write({{(const real*)mu, (const real*)p_gain, (const real*)kv}}, s)) return 1;
+    return rows_turn(nmrows::kFric, true);
+  }
+  int get_env_params(void* mu, void* p_gain, void* kv, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (!mu && !p_gain && !kv) return 0;
+    EnvP3W<real> dst{{(real*)mu, (real*)p_gain, (real*)kv}};
+    hipLaunchKernelGGL(k_envp_get<real>, dim3((4 * N + 255) / 256), dim3(256), 0, s, (const real*)envp_dev, N, dst, envp_default());
     HIPCHK(hipGetLastError());
-    A.envp = envp_dev;
-    envp_on = true;
     return 0;
   }
-  // ---- per-env body rows (base payload)
-  BodyRow<real> body_default() const {
-    BodyRow<real> r;
-    for (int j = 0; j < nm::kBodyP; j++) r.v[j] = real(0);
-    for (int j = 0; j < 10; j++) r.v[nm::BP_IPOS + j] = M.basec[j];
-    r.v[nm::BP_TOTAL] = M.total_mass;
-    for (int g = 0; g < nm::kNCOL; g++) r.v[nm::BP_INVW + g] = M.colc[g * nm::kColN + 4];
-    r.v[nm::BP_PGS] = M.pgs_scale;
-    return r;
-  }
-  int set_body_params(const void* rows, hipStream_t s) override {
+  int draw_env_params(const double* lo, const double* hi, hipStream_t s) override {
     HIPCHK(hipSetDevice(device));
-    if (!rows) {       // off; nothing is freed
-      body_on = false;
-      if (lat_on) return body_fill_default(s);      // level 3 goes on reading rows: the defaults
-      if (!envp_on) A.envp = nullptr;
-      return 0;
+    if (rows_alloc(s)) return 1;
+    EnvP3<real> l, h;
+    for (int k = 0; k < 3; k++) { l.v[k] = (real)lo[k]; h.v[k] = (real)hi[k]; }
+    hipLaunchKernelGGL(k_envp_draw<real>, dim3((4 * N + 255) / 256), dim3(256), 0, s, envp_dev, N, A.seed, A.env_offset, l, h);
+    HIPCHK(hipGetLastError());
+    return rows_turn(nmrows::kFric, true);
+  }
+  // ---- per-env body rows (base payload)
+  int set_body_params(const void* rows_in, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (!rows_in) {       // off; nothing is freed
+      if (envp_dev && body_fill_default(nmrows::body_rows(envp_dev, N), s)) return 1;
+      return rows_turn(nmrows::kBody, false);
     }
     // the rows are judged on the host before anything of the env changes
     std::vector<real> h((size_t)N * nm::kBodyP);
     HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipMemcpy(h.data(), rows, h.size() * sizeof(real), hipMemcpyDeviceToHost));
-    for (int e = 0; e < N; e++) {
-      const real* r = &h[(size_t)e * nm::kBodyP];
-      const char* why = nullptr;
-      for (int j = 0; j < nm::kBodyP; j++) if (!std::isfinite((double)r[j])) why = "a non-finite value";
-      if (!why && !(r[nm::BP_MASS] > 0)) why = "mass <= 0";
-      if (!why && r[nm::BP_TOTAL] < r[nm::BP_MASS]) why = "total_mass < mass";
-      if (!why && !(r[nm::BP_I6] > 0 && r[nm::BP_I6 + 1] > 0 && r[nm::BP_I6 + 2] > 0)) why = "a non-positive inertia diagonal";
-      for (int g = 0; g < nm::kNCOL && !why; g++) if (!(r[nm::BP_INVW + g] > 0)) why = "a non-positive invweight0";
-      if (!why && !(r[nm::BP_PGS] > 0)) why = "a non-positive pgs_scale";
-      if (why) return fail(std::string("nm_set_body_params: row ") + std::to_string(e) + ": " + why);
-    }
-    if (envp_alloc()) return 1;
-    if (!envp_on && envp_fill_default(s)) return 1;
-    HIPCHK(hipMemcpyAsync(body_dev(), rows, h.size() * sizeof(real), hipMemcpyDeviceToDevice, s));
-    A.envp = envp_dev;
-    body_on = true;
-    return 0;
-  }
-  int body_fill_default(hipStream_t s) {
-    hipLaunchKernelGGL(k_body_fill<real>, dim3((nm::kBodyP * N + 255) / 256), dim3(256), 0, s, body_dev(), N, body_default());
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  // ---- per-env actuation latency
-  int* lat_delay_dev() const { return reinterpret_cast<int*>(envp_dev + (size_t)N * (nm::kEnvP + nm::kBodyP)); }
-  float* lat_hist_dev() const { return reinterpret_cast<float*>(lat_delay_dev() + N); }
-  int lat_max() const { return nm::kLatH * A.nsub; }
-  int lat_switch_on(hipStream_t s) {       // the rows level 3 reads besides its own
-    if (!envp_on && envp_fill_default(s)) return 1;
-    if (!body_on && body_fill_default(s)) return 1;
-    A.envp = envp_dev;
-    lat_on = true;
-    return 0;
-  }
-  int set_action_latency(const int* substeps, hipStream_t s) override {
-    HIPCHK(hipSetDevice(device));
-    if (!substeps) {       // off; nothing is freed, the history keeps what it holds
-      lat_on = false;
-      if (!envp_on && !body_on) A.envp = nullptr;
-      return 0;
-    }
-    // the delays are judged on the host before anything of the env changes
-    std::vector<int> h((size_t)N);
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipMemcpy(h.data(), substeps, h.size() * sizeof(int), hipMemcpyDeviceToHost));
-    for (int e = 0; e < N; e++)
-      if (h[e] < 0 || h[e] > lat_max())
-        return fail("nm_set_action_latency: env " + std::to_string(e) + ": delay " + std::to_string(h[e]) + " outside [0, " + std::to_string(lat_max()) + "] substeps");
-    if (envp_alloc()) return 1;
-    HIPCHK(hipMemcpyAsync(lat_delay_dev(), substeps, h.size() * sizeof(int), hipMemcpyDeviceToDevice, s));
-    return lat_switch_on(s);
-  }
-  int get_action_latency(int* out, hipStream_t s) override {
-    HIPCHK(hipSetDevice(device));
-    if (!out) return 0;
-    if (lat_on) HIPCHK(hipMemcpyAsync(out, lat_delay_dev(), (size_t)N * sizeof(int), hipMemcpyDeviceToDevice, s));
-    else HIPCHK(hipMemsetAsync(out, 0, (size_t)N * sizeof(int), s));
-    return 0;
-  }
-  int draw_action_latency(int lo, int hi, hipStream_t s) override {
-    HIPCHK(hipSetDevice(device));
-    if (hi > lat_max()) return fail("nm_draw_action_latency: hi " + std::to_string(hi) + " above " + std::to_string(lat_max()) + " substeps");
-    if (envp_alloc()) return 1;
-    hipLaunchKernelGGL(k_latency_draw, dim3((N + 255) / 256), dim3(256), 0, s, lat_delay_dev(), N, A.seed, A.env_offset, lo, hi);
-    HIPCHK(hipGetLastError());
-    return lat_switch_on(s);
-  }
-  int set_action_history(const float* h, hipStream_t s) override {
-    HIPCHK(hipSetDevice(device));
-    if (!h) return fail("nm_set_action_history: the history is NULL");
-    if (envp_alloc()) return 1;
-    HIPCHK(hipMemcpyAsync(lat_hist_dev(), h, (size_t)N * nm::kLatH * nm::kNU * sizeof(float), hipMemcpyDeviceToDevice, s));
-    return 0;
-  }
-  int get_action_history(float* out, hipStream_t s) override {
-    HIPCHK(hipSetDevice(device));
-    if (!out) return 0;
-    const size_t bytes = (size_t)N * nm::kLatH * nm::kNU * sizeof(float);
-    if (envp_dev) HIPCHK(hipMemcpyAsync(out, lat_hist_dev(), bytes, hipMemcpyDeviceToDevice, s));
-    else HIPCHK(hipMemsetAsync(out, 0, bytes, s));      // never allocated: zero, as at construction
-    return 0;
+    HIPCHK(hipMemcpy(h.data(), rows_in, h.size() * sizeof(real), hipMemcpyDeviceToHost));
+    const std::string why = nmrows::body_rows_fault(h.data(), N);
+    if (!why.empty()) return fail("nm_set_body_params: " + why);
+    if (rows_alloc(s)) return 1;
+    HIPCHK(hipMemcpyAsync(nmrows::body_rows(envp_dev, N), rows_in, h.size() * sizeof(real), hipMemcpyDeviceToDevice, s));
+    return rows_turn(nmrows::kBody, true);
   }
   int get_body_params(void* out, hipStream_t s) override {
     HIPCHK(hipSetDevice(device));
     if (!out) return 0;
-    if (body_on) {
-      HIPCHK(hipMemcpyAsync(out, body_dev(), (size_t)N * nm::kBodyP * sizeof(real), hipMemcpyDeviceToDevice, s));
-      return 0;
-    }
-    hipLaunchKernelGGL(k_body_fill<real>, dim3((nm::kBodyP * N + 255) / 256), dim3(256), 0, s, (real*)out, N, body_default());
-    HIPCHK(hipGetLastError());
+    if (!envp_dev) return body_fill_default((real*)out, s);
+    HIPCHK(hipMemcpyAsync(out, nmrows::body_rows(envp_dev, N), (size_t)N * nm::kBodyP * sizeof(real), hipMemcpyDeviceToDevice, s));
     return 0;
   }
   int draw_payload(const double* lo, const double* hi, void* out, hipStream_t s) override {
@@ -989,24 +918,50 @@ template <class real> struct Env : nm_env {
     HIPCHK(hipGetLastError());
     return 0;
   }
-  int get_env_params(void* mu, void* p_gain, void* kv, hipStream_t s) override {
+  // ---- per-env actuation latency
+  int set_action_latency(const int* substeps, hipStream_t s) override {
     HIPCHK(hipSetDevice(device));
-    if (!mu && !p_gain && !kv) return 0;
-    EnvP3W<real> dst{{(real*)mu, (real*)p_gain, (real*)kv}};
-    hipLaunchKernelGGL(k_envp_get<real>, dim3((4 * N + 255) / 256), dim3(256), 0, s, A.envp, N, dst, envp_default());
-    HIPCHK(hipGetLastError());
+    if (!substeps) {       // off; nothing is freed, the history keeps what it holds
+      if (envp_dev) HIPCHK(hipMemsetAsync(nmrows::delays(envp_dev, N), 0, (size_t)N * sizeof(int), s));
+      return rows_turn(nmrows::kLat, false);
+    }
+    // the delays are judged on the host before anything of the env changes
+    std::vector<int> h((size_t)N);
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpy(h.data(), substeps, h.size() * sizeof(int), hipMemcpyDeviceToHost));
+    const std::string why = nmrows::delays_fault(h.data(), N, A.nsub);
+    if (!why.empty()) return fail("nm_set_action_latency: " + why);
+    if (rows_alloc(s)) return 1;
+    HIPCHK(hipMemcpyAsync(nmrows::delays(envp_dev, N), substeps, h.size() * sizeof(int), hipMemcpyDeviceToDevice, s));
+    return rows_turn(nmrows::kLat, true);
+  }
+  // a region of 4-byte words for the caller (src null: the block was never allocated - zero, as at construction)
+  int words_out(void* out, const void* src, size_t words, hipStream_t s) {
+    HIPCHK(hipSetDevice(device));
+    if (!out) return 0;
+    if (src) HIPCHK(hipMemcpyAsync(out, src, words * 4, hipMemcpyDeviceToDevice, s));
+    else HIPCHK(hipMemsetAsync(out, 0, words * 4, s));
     return 0;
   }
-  int draw_env_params(const double* lo, const double* hi, hipStream_t s) override {
+  int get_action_latency(int* out, hipStream_t s) override { return words_out(out, envp_dev ? nmrows::delays(envp_dev, N) : nullptr, (size_t)N, s); }
+  int draw_action_latency(int lo, int hi, hipStream_t s) override {
     HIPCHK(hipSetDevice(device));
-    if (envp_alloc()) return 1;
-    EnvP3<real> l, h;
-    for (int k = 0; k < 3; k++) { l.v[k] = (real)lo[k]; h.v[k] = (real)hi[k]; }
-    hipLaunchKernelGGL(k_envp_draw<real>, dim3((4 * N + 255) / 256), dim3(256), 0, s, envp_dev, N, A.seed, A.env_offset, l, h);
+    const int top = nmrows::delay_max(A.nsub);
+    if (hi > top) return fail("nm_draw_action_latency: hi " + std::to_string(hi) + " above " + std::to_string(top) + " substeps");
+    if (rows_alloc(s)) return 1;
+    hipLaunchKernelGGL(k_latency_draw, dim3((N + 255) / 256), dim3(256), 0, s, nmrows::delays(envp_dev, N), N, A.seed, A.env_offset, lo, hi);
     HIPCHK(hipGetLastError());
-    A.envp = envp_dev;
-    envp_on = true;
+    return rows_turn(nmrows::kLat, true);
+  }
+  int set_action_history(const float* h, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (!h) return fail("nm_set_action_history: the history is NULL");
+    if (rows_alloc(s)) return 1;
+    HIPCHK(hipMemcpyAsync(nmrows::histories(envp_dev, N), h, nmrows::hist_words((size_t)N) * sizeof(float), hipMemcpyDeviceToDevice, s));
     return 0;
+  }
+  int get_action_history(float* out, hipStream_t s) override {
+    return words_out(out, envp_dev ? nmrows::histories(envp_dev, N) : nullptr, nmrows::hist_words((size_t)N), s);
   }
   void set_dbg(void* p) override { A.dbg = (real*)p; }
   void set_ret_acc(float* p) override { A.ret_acc = p; }
@@ -1187,12 +1142,13 @@ int nm_get_push(nm_env* env, int32_t* interval_steps, double* max_vel_xy, uint64
   if (step) *step = env->push_step;
   return 0;
 }
+#define NEED_ENV(e) if (!(e)) return fail(std::string(__func__) + ": env is NULL")
 int nm_set_env_params(nm_env* env, const void* mu_dev, const void* p_gain_dev, const void* kv_dev, void* stream) {
-  if (!env) return fail("nm_set_env_params: env is NULL");
+  NEED_ENV(env);
   return env->set_env_params(mu_dev, p_gain_dev, kv_dev, (hipStream_t)stream);
 }
 int nm_get_env_params(nm_env* env, void* mu_dev, void* p_gain_dev, void* kv_dev, void* stream) {
-  if (!env) return fail("nm_get_env_params: env is NULL");
+  NEED_ENV(env);
   return env->get_env_params(mu_dev, p_gain_dev, kv_dev, (hipStream_t)stream);
 }
 int nm_draw_env_params(nm_env* env, const double lo[3], const double hi[3], void* stream) {
@@ -1205,18 +1161,18 @@ int nm_draw_env_params(nm_env* env, const double lo[3], const double hi[3], void
     if (k == 0 && !(lo[k] > 1e-5)) return fail("nm_draw_env_params: mu must be above 1e-5");
     if (k != 0 && lo[k] < 0.0) return fail(std::string("nm_draw_env_params: ") + kCol[k] + " must not be negative");
   }
-  if (!env) return fail("nm_draw_env_params: env is NULL");
+  NEED_ENV(env);
   if (env->dtype == NM_DTYPE_F32)
     for (int k = 0; k < 3; k++)
       if (!std::isfinite((float)hi[k])) return fail(std::string("nm_draw_env_params: the bounds of ") + kCol[k] + " must be finite in float32");
   return env->draw_env_params(lo, hi, (hipStream_t)stream);
 }
 int nm_set_body_params(nm_env* env, const void* rows_dev, void* stream) {
-  if (!env) return fail("nm_set_body_params: env is NULL");
+  NEED_ENV(env);
   return env->set_body_params(rows_dev, (hipStream_t)stream);
 }
 int nm_get_body_params(nm_env* env, void* out_dev, void* stream) {
-  if (!env) return fail("nm_get_body_params: env is NULL");
+  NEED_ENV(env);
   return env->get_body_params(out_dev, (hipStream_t)stream);
 }
 int nm_draw_payload(nm_env* env, const double lo[4], const double hi[4], void* out_dev, void* stream) {
@@ -1227,7 +1183,7 @@ int nm_draw_payload(nm_env* env, const double lo[4], const double hi[4], void* o
     if (!std::isfinite(lo[k]) || !std::isfinite(hi[k])) return fail(std::string("nm_draw_payload: the bounds of ") + kCol[k] + " must be finite");
     if (lo[k] > hi[k]) return fail(std::string("nm_draw_payload: lo > hi for ") + kCol[k]);
   }
-  if (!env) return fail("nm_draw_payload: env is NULL");
+  NEED_ENV(env);
   if (!out_dev) return fail("nm_draw_payload: out is NULL");
   if (env->dtype == NM_DTYPE_F32)
     for (int k = 0; k < 4; k++)
@@ -1235,26 +1191,26 @@ int nm_draw_payload(nm_env* env, const double lo[4], const double hi[4], void* o
   return env->draw_payload(lo, hi, out_dev, (hipStream_t)stream);
 }
 int nm_set_action_latency(nm_env* env, const int32_t* substeps_dev, void* stream) {
-  if (!env) return fail("nm_set_action_latency: env is NULL");
+  NEED_ENV(env);
   return env->set_action_latency(substeps_dev, (hipStream_t)stream);
 }
 int nm_get_action_latency(nm_env* env, int32_t* out_dev, void* stream) {
-  if (!env) return fail("nm_get_action_latency: env is NULL");
+  NEED_ENV(env);
   return env->get_action_latency(out_dev, (hipStream_t)stream);
 }
 int nm_draw_action_latency(nm_env* env, int32_t lo, int32_t hi, void* stream) {
   // the bounds are judged first, so a bad range is named whatever the handle is; the upper limit (history x decimation) needs the env
   if (lo < 0) return fail("nm_draw_action_latency: lo < 0");
   if (lo > hi) return fail("nm_draw_action_latency: lo > hi");
-  if (!env) return fail("nm_draw_action_latency: env is NULL");
+  NEED_ENV(env);
   return env->draw_action_latency(lo, hi, (hipStream_t)stream);
 }
 int nm_set_action_history(nm_env* env, const float* hist_dev, void* stream) {
-  if (!env) return fail("nm_set_action_history: env is NULL");
+  NEED_ENV(env);
   return env->set_action_history(hist_dev, (hipStream_t)stream);
 }
 int nm_get_action_history(nm_env* env, float* out_dev, void* stream) {
-  if (!env) return fail("nm_get_action_history: env is NULL");
+  NEED_ENV(env);
   return env->get_action_history(out_dev, (hipStream_t)stream);
 }
 int nm_step_tape(nm_env* env, const nm_tape_args* args, void* stream) {

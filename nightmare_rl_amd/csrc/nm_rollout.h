@@ -341,9 +341,7 @@ extern template struct RollKernels<NM_ACT_LRELU>;
 extern template struct RollKernels<NM_ACT_TANH>;
 extern template struct RollKernels<NM_ACT_SIGMOID>;
 // act: the hidden activation (NM_ACT_*); a code this build has no instantiation for (the measurement build: ELU only) fails the launch.
-// level: which instantiation of the step the K-step kernel carries (nm_core.h env_mu): 0 no per-env rows, 1 friction / gain rows
-// (a.envp), 2 those and body rows behind them, 3 those and the latency words behind the body rows - the env object knows, nm::Args has
-// no word for it
+// level: which instantiation of the step the K-step kernel carries - nmrows::State::level() of the env object (nm_env_rows.h)
 int launch_act(const float* wp, const float* bp, const float* stdv, const float* obs, int N, uint64_t seed, const int64_t* iter_dev, int step, const ActOut& o,
                int act, hipStream_t s);
 int launch_rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, const TailArgs& t, int act, int level, hipStream_t s);

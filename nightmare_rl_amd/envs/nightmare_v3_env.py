@@ -50,34 +50,43 @@ def push_config(cfg, dt):
     return int(steps), vel
 
 
+def _range(dr, name, lowest=None, strict=False, whole=False):
+    """cfg.domain_rand.<name> as a pair (lo, hi) of finite numbers lo <= hi, or None where there is none. lowest: lo's lower bound
+    (strict: lo must be above it); whole: whole numbers, returned as integers. Anything else is a ValueError."""
+    r = getattr(dr, name, None)
+    if r is None:
+        return None
+    try:
+        lo, hi = (float(x) for x in r)
+    except (TypeError, ValueError):
+        raise ValueError(f"cfg.domain_rand.{name} must be a pair (lo, hi)") from None
+    bound = "" if lowest is None else f"{lowest} {'<' if strict else '<='} "
+    if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi and (lowest is None or (lo > lowest if strict else lo >= lowest))
+            and (not whole or (lo == int(lo) and hi == int(hi)))):
+        raise ValueError(f"cfg.domain_rand.{name} must be {'whole substeps' if whole else 'finite'} with {bound}lo <= hi")
+    return (int(lo), int(hi)) if whole else (lo, hi)
+
+
+def _switched(dr, flag, name, **kw):
+    """The range cfg.domain_rand.<name> where cfg.domain_rand.<flag> is set - a ValueError where it is missing - and None where it is not."""
+    if not getattr(dr, flag, False):
+        return None
+    r = _range(dr, name, **kw)
+    if r is None:
+        raise ValueError(f"cfg.domain_rand.{flag} needs {name}")
+    return r
+
+
 def env_param_config(cfg):
     """(friction_range, stiffness_multiplier_range, damping_multiplier_range) of the optional cfg.domain_rand, each a (lo, hi) pair or None:
     what draw_env_params takes. randomize_friction needs friction_range; randomize_gains takes the multiplier ranges that are there (a
     missing one leaves that gain alone). A range that is not two finite numbers lo <= hi, a friction at or below 1e-5 or a negative
     multiplier is a ValueError."""
-    dr = getattr(cfg, "domain_rand", None)
-    if dr is None:
-        return None, None, None
-
-    def rng(name, lowest, strict):
-        r = getattr(dr, name, None)
-        if r is None:
-            return None
-        try:
-            lo, hi = (float(x) for x in r)
-        except (TypeError, ValueError):
-            raise ValueError(f"cfg.domain_rand.{name} must be a pair (lo, hi)") from None
-        if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi and (lo > lowest if strict else lo >= lowest)):
-            raise ValueError(f"cfg.domain_rand.{name} must be finite with {lowest} {'<' if strict else '<='} lo <= hi")
-        return lo, hi
-
-    fr = st = da = None
-    if getattr(dr, "randomize_friction", False):
-        fr = rng("friction_range", 1e-5, True)
-        if fr is None:
-            raise ValueError("cfg.domain_rand.randomize_friction needs friction_range")
+    dr = getattr(cfg, "domain_rand", None)      # (a missing class reads as every switch off)
+    st = da = None
+    fr = _switched(dr, "randomize_friction", "friction_range", lowest=1e-5, strict=True)
     if getattr(dr, "randomize_gains", False):
-        st, da = rng("stiffness_multiplier_range", 0.0, False), rng("damping_multiplier_range", 0.0, False)
+        st, da = _range(dr, "stiffness_multiplier_range", 0.0), _range(dr, "damping_multiplier_range", 0.0)
         if st is None and da is None:
             raise ValueError("cfg.domain_rand.randomize_gains needs stiffness_multiplier_range or damping_multiplier_range")
     return fr, st, da
@@ -89,50 +98,14 @@ def payload_config(cfg):
     same range for x, y and z in the base body frame). A range that is not two finite numbers lo <= hi is a ValueError; whether the
     heaviest negative mass is admissible is judged when the rows are derived (model/payload.py)."""
     dr = getattr(cfg, "domain_rand", None)
-    if dr is None:
-        return None, None
-
-    def rng(name):
-        r = getattr(dr, name, None)
-        if r is None:
-            return None
-        try:
-            lo, hi = (float(x) for x in r)
-        except (TypeError, ValueError):
-            raise ValueError(f"cfg.domain_rand.{name} must be a pair (lo, hi)") from None
-        if not (np.isfinite(lo) and np.isfinite(hi) and lo <= hi):
-            raise ValueError(f"cfg.domain_rand.{name} must be finite with lo <= hi")
-        return lo, hi
-
-    ma = co = None
-    if getattr(dr, "randomize_base_mass", False):
-        ma = rng("added_mass_range")
-        if ma is None:
-            raise ValueError("cfg.domain_rand.randomize_base_mass needs added_mass_range")
-    if getattr(dr, "randomize_com_displacement", False):
-        co = rng("com_displacement_range")
-        if co is None:
-            raise ValueError("cfg.domain_rand.randomize_com_displacement needs com_displacement_range")
-    return ma, co
+    return _switched(dr, "randomize_base_mass", "added_mass_range"), _switched(dr, "randomize_com_displacement", "com_displacement_range")
 
 
 def latency_config(cfg):
     """(lo, hi) in whole physics substeps from the optional cfg.domain_rand, or None: what draw_action_latency takes.
     randomize_action_latency needs action_latency_range; a range that is not two integers 0 <= lo <= hi is a ValueError (the upper limit,
     three env steps, is the library's to judge: it depends on the decimation)."""
-    dr = getattr(cfg, "domain_rand", None)
-    if dr is None or not getattr(dr, "randomize_action_latency", False):
-        return None
-    r = getattr(dr, "action_latency_range", None)
-    if r is None:
-        raise ValueError("cfg.domain_rand.randomize_action_latency needs action_latency_range")
-    try:
-        lo, hi = (float(x) for x in r)
-    except (TypeError, ValueError):
-        raise ValueError("cfg.domain_rand.action_latency_range must be a pair (lo, hi)") from None
-    if not (np.isfinite(lo) and np.isfinite(hi) and lo == int(lo) and hi == int(hi) and 0 <= lo <= hi):
-        raise ValueError("cfg.domain_rand.action_latency_range must be whole substeps with 0 <= lo <= hi")
-    return int(lo), int(hi)
+    return _switched(getattr(cfg, "domain_rand", None), "randomize_action_latency", "action_latency_range", lowest=0, whole=True)
 
 
 class NightmareV3Env:
@@ -242,18 +215,17 @@ class NightmareV3Env:
         if push_steps:
             self.set_push(push_steps, push_vel)
         # per-env friction and servo gains (optional cfg.domain_rand; no reference line): drawn once, here, like legged_gym's friction
-        self._envp_keep = None
+        # what the row setters hand to the library is copied stream-ordered: each kind's source tensors live here until its next call
+        self._rows_keep = {}
         # the library's own defaults (the model's mu and kv, the config's p_gain): what it reports while the feature is off, read once here
         self._envp_default = tuple(float(v[0]) for v in self.env_params().values()) if hasattr(L, "nm_get_env_params") else None
         if any(r is not None for r in envp_ranges):
             self.draw_env_params(*envp_ranges)
         # per-env base payload (optional cfg.domain_rand; no reference line): drawn once, here
         self._payload = None
-        self._body_keep = None
         if any(r is not None for r in payload_ranges):
             self.draw_base_payload(*payload_ranges)
         # per-env actuation latency (optional cfg.domain_rand; no reference line): drawn once, here
-        self._lat_keep = None
         if latency_range is not None:
             self.draw_action_latency(*latency_range)
         # state log of env 0 (reference :261-272; reader open_custom_play.py:50-66)
@@ -315,22 +287,22 @@ class NightmareV3Env:
         self._ck(self._L.nm_get_push(self._h, C.byref(iv), C.byref(mx), C.byref(st)))
         return iv.value, mx.value, st.value
 
+    def _per_env(self, x, dtype, err, device=None):
+        """num_envs values, or one scalar for every env, as a contiguous [num_envs] tensor of `dtype` on the env's device (or `device`);
+        err: the caller's ValueError text for any other count."""
+        t = torch.as_tensor(x, dtype=dtype).detach().to(self.device if device is None else device)
+        t = t.expand(self.num_envs) if t.dim() == 0 else t.reshape(-1)
+        if t.numel() != self.num_envs:
+            raise ValueError(err)
+        return t.contiguous()
+
     def set_env_params(self, mu=None, p_gain=None, kv=None):
         """Per-env sliding friction, servo stiffness (in place of cfg.control.p_gain) and servo damping (in place of kv = 0.8), honoured by
         step(), step_physics, policy_rollout, policy_play and step_tape alike (nm_set_env_params). Each: a tensor / array of num_envs values, a
         scalar for every env, or None = the default. All three None switch the feature off. The values hold until they are set again (no reset
         resamples them) and are not validated: mu <= 1e-5 or a negative gain is the caller's responsibility."""
-        cols = []
-        for x in (mu, p_gain, kv):
-            if x is None:
-                cols.append(None)
-                continue
-            t = torch.as_tensor(x, dtype=self._real).to(self.device)
-            t = t.expand(self.num_envs) if t.dim() == 0 else t.reshape(-1)
-            if t.numel() != self.num_envs:
-                raise ValueError("set_env_params: one value per env (or a scalar)")
-            cols.append(t.contiguous())
-        self._envp_keep = cols        # the copy is stream-ordered: the sources live until the next call
+        cols = [None if x is None else self._per_env(x, self._real, "set_env_params: one value per env (or a scalar)") for x in (mu, p_gain, kv)]
+        self._rows_keep["envp"] = cols
         p = [C.c_void_p(t.data_ptr()) if t is not None else None for t in cols]
         self._ck(self._L.nm_set_env_params(self._h, p[0], p[1], p[2], self._stream()))
 
@@ -361,20 +333,20 @@ class NightmareV3Env:
         it is set again (no reset touches it). ValueError: a non-finite value, a base mass <= 0, an inertia that is not positive definite
         or violates the triangle inequality (what MuJoCo's compiler refuses)."""
         if dm is None:
-            self._payload = self._body_keep = None
+            self._payload = self._rows_keep["body"] = None
             self._ck(self._L.nm_set_body_params(self._h, None, self._stream()))
             return
         from ..model import payload
-        dm = np.asarray(dm.detach().cpu().numpy() if isinstance(dm, torch.Tensor) else dm, dtype=np.float64)
-        dm = np.full(self.num_envs, float(dm)) if dm.ndim == 0 else dm.reshape(-1)
+        err = "set_base_payload: one dm per env (or a scalar) and one r[3] per env (or one for all)"
+        dm = self._per_env(dm, torch.float64, err, device="cpu").numpy()
         r = np.zeros(3) if r is None else np.asarray(r.detach().cpu().numpy() if isinstance(r, torch.Tensor) else r, dtype=np.float64)
         r = np.tile(r, (self.num_envs, 1)) if r.ndim == 1 else r.reshape(-1, 3)
-        if dm.shape[0] != self.num_envs or r.shape != (self.num_envs, 3):
-            raise ValueError("set_base_payload: one dm per env (or a scalar) and one r[3] per env (or one for all)")
+        if r.shape != (self.num_envs, 3):
+            raise ValueError(err)
         rows = payload.payload_rows(dm, r)
         t = torch.from_numpy(rows).to(dtype=self._real).to(self.device).contiguous()
         self._ck(self._L.nm_set_body_params(self._h, C.c_void_p(t.data_ptr()), self._stream()))
-        self._body_keep = t           # the copy is stream-ordered: the source lives until the next call
+        self._rows_keep["body"] = t
         self._payload = (dm.copy(), r.copy())
 
     def base_payload(self):
@@ -408,19 +380,15 @@ class NightmareV3Env:
         policy_play and step_tape alike; step_physics ignores it. substeps: num_envs integers, one integer for every env, or None =
         off. The delays hold until they are set again; no reset touches them or the action history."""
         if substeps is None:
-            self._lat_keep = None
+            self._rows_keep["lat"] = None
             self._ck(self._L.nm_set_action_latency(self._h, None, self._stream()))
             return
         t = torch.as_tensor(substeps)
         if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
             raise ValueError("set_action_latency: whole substeps (an integer per env)")
-        t = t.to(torch.int32).to(self.device)
-        t = t.expand(self.num_envs) if t.dim() == 0 else t.reshape(-1)
-        if t.numel() != self.num_envs:
-            raise ValueError("set_action_latency: one delay per env (or one for all)")
-        t = t.contiguous()
+        t = self._per_env(t, torch.int32, "set_action_latency: one delay per env (or one for all)")
         self._ck(self._L.nm_set_action_latency(self._h, C.c_void_p(t.data_ptr()), self._stream()))
-        self._lat_keep = t            # the copy is stream-ordered: the source lives until the next call
+        self._rows_keep["lat"] = t
 
     def action_latency(self):
         """The delays, an int32 tensor [num_envs] in physics substeps (nm_get_action_latency); zeros while the feature is off."""
@@ -450,7 +418,7 @@ class NightmareV3Env:
         if tuple(t.shape) != (self.num_envs, self.ACTION_HISTORY, 18):
             raise ValueError("set_action_history: [num_envs, 3, 18]")
         self._ck(self._L.nm_set_action_history(self._h, C.c_void_p(t.data_ptr()), self._stream()))
-        self._hist_keep = t           # the copy is stream-ordered: the source lives until the next call
+        self._rows_keep["hist"] = t
 
     def _record_state(self):
         # reference :261-272: when env 0 resets, dump what was logged so far, then log (time, qpos, qvel, act) of env 0

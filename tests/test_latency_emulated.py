@@ -1,5 +1,5 @@
 """Per-env actuation latency (nm_set_action_latency, level 3 of the step) in the host emulation of the device source
-(tests/emul/nm_emul_latency.cpp): the fp64 emulation of the fixture's mixed batch - delays 0..6 and 0 over eight envs - against the fp64
+(tests/emul/nm_emul_rows.cpp): the fp64 emulation of the fixture's mixed batch - delays 0..6 and 0 over eight envs - against the fp64
 fixture of the patched oracle (tests/golden/make_latency_goldens.py), delay 0 against no delays at all and the mixed batch against the
 seven uniform ones bit for bit, and the stand-alone sanitizer build of the shim. The fixture's states are teacher-forced: every step
 starts from the recorded state AND the recorded action history."""
@@ -20,9 +20,9 @@ def G():
 
 @pytest.fixture(scope="module")
 def emul():
-    from emul import emul_latency
-    emul_latency.build()
-    return emul_latency
+    from emul import emul_rows
+    emul_rows.build()
+    return emul_rows
 
 
 def load_step(env, g, pop, t, n=8):
@@ -42,7 +42,7 @@ def run_forced(emul, g, pop, delays, double, steps=None, envs_per_wave=2):
     number of two-env constraint passes."""
     n = 8 if delays is None else len(delays)
     ev = np.arange(n) % 8
-    env = emul.EmulLatency(n, double=double, seed=5, envs_per_wave=envs_per_wave)
+    env = emul.EmulRows(n, double=double, seed=5, envs_per_wave=envs_per_wave)
     env.set_action_latency(delays)
     out, oerrs, serr, ntog, flags = [], [], 0.0, 0, 0
     T = g[f"{pop}_actions"].shape[0] if steps is None else steps
@@ -123,7 +123,7 @@ def test_mixed_batch_equals_uniform_batches_bit_for_bit(G, emul, pop, double):
 def test_delays_change_the_physics(G, emul):
     """The delays are not ignored: every delayed env's next state differs from the undelayed step's, an undelayed env's does not."""
     def qvel_after(delays):
-        env = emul.EmulLatency(8, double=True, seed=5)
+        env = emul.EmulRows(8, double=True, seed=5)
         env.set_action_latency(delays)
         a, cu = load_step(env, G, "stand", 0)
         env.step(a, cmd_u=cu)
@@ -135,7 +135,7 @@ def test_delays_change_the_physics(G, emul):
 
 def test_physics_only_launch_ignores_latency(G, emul):
     def after(delays):
-        env = emul.EmulLatency(8, double=False, seed=5)
+        env = emul.EmulRows(8, double=False, seed=5)
         env.set_action_latency(delays)
         a, _ = load_step(env, G, "stand", 0)
         h0 = env.history.copy()
@@ -157,8 +157,8 @@ def test_standalone_sanitizer_build_of_the_shim_runs_clean(G, emul, tmp_path):
             parts.append(np.asarray(G[f"{pop}_{k}"][0], np.float64).ravel())
     states = tmp_path / "states.bin"
     np.concatenate(parts).tofile(states)
-    exe = emul.build_program(str(tmp_path / "nm_emul_latency_asan"), ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], opt="-O0")
-    r = subprocess.run([exe, str(states)], capture_output=True, text=True)
+    exe = emul.build_program(str(tmp_path / "nm_emul_rows_asan"), ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], opt="-O0")
+    r = subprocess.run([exe, "latency", str(states)], capture_output=True, text=True)
     print(r.stdout, r.stderr[-2000:])
     assert r.returncode == 0, (r.stdout, r.stderr[-2000:])
     assert "fp32" in r.stdout and "fp64" in r.stdout
