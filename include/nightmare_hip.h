@@ -137,6 +137,32 @@ int nm_set_noise_uniforms(nm_env* env, const double* u_host);
  * sets s = start_step. nm_get_push returns the setting and the current s (any pointer may be NULL): a checkpoint's three numbers. */
 int nm_set_push(nm_env* env, int32_t interval_steps, double max_vel_xy, uint64_t start_step);
 int nm_get_push(nm_env* env, int32_t* interval_steps, double* max_vel_xy, uint64_t* step);
+/* Randomised reset states - the `_reset_dofs` / `_reset_root_states` of legged_gym-shaped stacks, which draw the joint angles and the root
+ * velocity afresh at every reset; the reference has no such line (its reset_idx writes qpos0 and zero velocity, env.py:335-371).
+ * ranges10_host: five ranges (lo, hi) in the order base_height, dof_pos, base_lin_vel, base_ang_vel, dof_vel. While the feature is on, an
+ * env's reset - time-out, termination or nm_reset - writes qpos0 and zero velocity as before and then overwrites 43 words of that env:
+ *   column 0       qpos[2]       = qpos0[2] + d(0)           (base_height)
+ *   columns 1..18  qpos[7 + j]   = qpos0[7 + j] + d(1 + j)   (dof_pos)
+ *   columns 19..21 qvel[0:3]     = d(c)                      (base_lin_vel, world frame)
+ *   columns 22..24 qvel[3:6]     = d(c)                      (base_ang_vel)
+ *   columns 25..42 qvel[6 + j]   = d(c)                      (dof_vel)
+ * qpos[0:2] and the base quaternion keep their qpos0 values. d(c) = lo_r + u * w_r in the env's precision `real`, with lo_r = real(lo),
+ * w_r = real(hi) - real(lo), u = rand_u24_bits(seed + "RESET", global env id, 64 k + c) * 2^-24, product and sum rounded separately (the
+ * rules of nm_draw_env_params), the counter in 32 bits. k is the env's reset count: read by all 43 columns, then incremented by one.
+ * A reset draw is an edit of the state between two steps and nothing else: qacc_warmstart, the stale dof_pos / dof_vel / cvel buffers, the
+ * command resample, the command RNG counter and the feet state stay as they are; the resetting step returns the terminal observation, as
+ * upstream; the bad-state reset inside the physics still goes to qpos0; nm_step_physics never resets. It works alike in nm_step, nm_reset
+ * (distinct ids), nm_rollout, nm_play and nm_step_tape, and the state after any step of any path equals the per-step path's.
+ * Off is the default, and "on with ten zeros" equals off bit for bit (+0 offsets).
+ * nm_set_reset_noise: ranges10_host NULL switches the feature off. counts_host: HOST [N] reset counts to install, or NULL to keep the
+ * env's (zeros at first use). Refused: a NULL env, non-finite values (in fp32: after rounding to float), lo > hi.
+ * nm_get_reset_noise: the flag, the ranges in force (zeros while off) and the reset counts (HOST [N]); any pointer may be NULL. A
+ * checkpoint's content.
+ * nm_reset_noise_offsets: d(0..42) of reset k of the env with global id `global_env` as doubles, computed on the host by the function the
+ * kernels call; no env, no device. dtype: NM_DTYPE_F32 or NM_DTYPE_F64. */
+int nm_set_reset_noise(nm_env* env, const double* ranges10_host, const uint32_t* counts_host);
+int nm_get_reset_noise(nm_env* env, int32_t* on, double* ranges10, uint32_t* counts_host);
+int nm_reset_noise_offsets(const double* ranges10, uint64_t seed, int64_t global_env, uint32_t k, int32_t dtype, double* out43);
 /* Per-env friction and servo-gain randomisation - the `domain_rand.randomize_friction` / `friction_range` of legged_gym-shaped config
  * trees and the stiffness / damping multipliers their forks add; it replaces nothing upstream (the reference has one floor and one servo).
  * Each env e carries three values in the env's dtype:

@@ -30,7 +30,8 @@ EXPORTS = ["nm_default_config", "nm_reward_name", "nm_last_error", "nm_create", 
            "nm_step_tape", "nm_nik_tape", "nm_set_push", "nm_get_push",
            "nm_set_env_params", "nm_get_env_params", "nm_draw_env_params",
            "nm_set_body_params", "nm_get_body_params", "nm_draw_payload",
-           "nm_set_action_latency", "nm_get_action_latency", "nm_draw_action_latency", "nm_set_action_history", "nm_get_action_history"]
+           "nm_set_action_latency", "nm_get_action_latency", "nm_draw_action_latency", "nm_set_action_history", "nm_get_action_history",
+           "nm_set_reset_noise", "nm_get_reset_noise", "nm_reset_noise_offsets"]
 
 
 class NmConfig(C.Structure):
@@ -183,6 +184,10 @@ def _bind(L, full):
         L.nm_draw_action_latency.argtypes = [vp, C.c_int32, C.c_int32, vp]
         L.nm_set_action_history.argtypes = [vp, vp, vp]
         L.nm_get_action_history.argtypes = [vp, vp, vp]
+    if hasattr(L, "nm_set_reset_noise"):
+        L.nm_set_reset_noise.argtypes = [vp, C.POINTER(C.c_double * 10), vp]
+        L.nm_get_reset_noise.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_double * 10), vp]
+        L.nm_reset_noise_offsets.argtypes = [C.POINTER(C.c_double * 10), C.c_uint64, C.c_int64, C.c_uint32, C.c_int32, C.POINTER(C.c_double * 43)]
     if not full:        # the measurement build holds the env entry points only
         return L
     L.nm_gae.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_float, vp, vp]

@@ -410,7 +410,7 @@ template <class LT, class X> NM_FN void ldl6_solve(const LT* L, const LT* Dinv, 
 }
 
 // counter-based uniform in [0,1) with 24 random bits (same definition as oracle/nm_oracle_env.c nmo_rand_u24)
-NM_FN uint32_t rand_u24_bits(uint64_t seed, uint64_t genv, uint32_t ctr) {
+NM_HDFN uint32_t rand_u24_bits(uint64_t seed, uint64_t genv, uint32_t ctr) {
   uint64_t x = seed + 0x9E3779B97F4A7C15ull * (genv + 1) + 0xD1B54A32D192ED03ull * (uint64_t)ctr;
   x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
   x ^= x >> 27; x *= 0x94D049BB133111EBull;

@@ -1,6 +1,6 @@
 // nm_env_loop.h - what the K-step launches k_env_rollout (nm_rollout_kernels.h), k_env_play (nm_play_kernels.h) and k_env_tape
 // (nm_tape_kernels.h) share: the wave index, the launch prologue, the episode books of the wave's two envs, the per-step update of the
-// env step's launch arguments and the push perturbation of a step (nm_push.h). X below is the launch's own argument struct, RollArgs, PlayArgs or TapeArgs (nm_rollout.h): the helpers read
+// env step's launch arguments, the push perturbation of a step (nm_push.h) and the reset draw of a step (nm_reset_noise.h). X below is the launch's own argument struct, RollArgs, PlayArgs or TapeArgs (nm_rollout.h): the helpers read
 // the fields all carry (cur_ret, cur_len, fin3, to_step, st_sum, st_cnt, rec_log) and `if constexpr` on the struct's traits (kPlayBooks,
 // kStepRecord) decides what only some of them file.
 #pragma once
@@ -11,6 +11,7 @@
 #include "nm_core.h"
 #include "nm_env_rows.h"     // with_level: the launchers of the three K-step kernels pick the step's level through it
 #include "nm_push.h"
+#include "nm_reset_noise.h"
 #include "nm_rollout.h"
 
 namespace nmr {
@@ -100,6 +101,34 @@ __device__ __forceinline__ void books_file(const BookRegs& r, const X* Xs, const
       if (Xs->rec_done && e == Xs->rec_env) simt::gst1(Xs->rec_done, (size_t)t, (unsigned char)(d ? 1 : 0));
   }
 }
+// The reset draw of the step whose books were just filed (nm_reset_noise.h; X::rnoise), for the envs of this wave that the step reset:
+// `d` is the done word books_load left in lanes 0 / 1 (env 2 wave + lane). Lanes 0..42 own the 43 columns of one env at a time, lane 0 its
+// reset count. Called behind the wait at the head of the step function (or of books_last): that wait is what orders the draw behind the
+// in-kernel qpos0 store of the same words, which other lanes of this wave issued in the epilogue of the step before. The body ends with
+// a wait of its own, so that a push of the next step (other lanes again, qvel[0:2]) lands behind the draw, as it does in the per-step
+// path; step_close's wait then puts everything in L2 before the load stage asks for the state. The test is wave-uniform; the body is
+// out of line, like push_store: taken once per episode, and its registers are nobody else's.
+template <class X>
+__device__ __noinline__ void reset_noise_store(const X* Xs, const nm::Args<float>* As, int mask, int wave) {
+  const int lane = threadIdx.x;
+  mask = __builtin_amdgcn_readfirstlane(mask);
+#pragma unroll 1
+  for (int hh = 0; hh < 2; hh++) {
+    const int env = wave * 2 + hh;
+    if (!((mask >> hh) & 1) || env >= As->N) continue;
+    const uint32_t k = simt::gld1((const uint32_t*)Xs->rnoise.count, (size_t)env);
+    if (lane < nm::kResetCols)
+      nm::reset_noise_apply<float>(As->qpos, As->qvel, Xs->rnoise.qpos0, Xs->rnoise.p, As->seed, (uint64_t)(As->env_offset + env), (size_t)env, k, lane);
+    if (lane == 0) simt::gst1(Xs->rnoise.count, (size_t)env, k + 1u);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+template <class X>
+__device__ __forceinline__ void step_reset_noise(const X* Xs, const nm::Args<float>* As, long long d, int wave) {
+  if (__builtin_amdgcn_readfirstlane(Xs->rnoise.on) == 0) return;
+  const int mask = (int)(__builtin_amdgcn_ballot_w64(d > 0) & 3ull);
+  if (mask) reset_noise_store(Xs, As, mask, wave);
+}
 // the books of the launch's last step (no policy step follows it)
 template <class X>
 __device__ __noinline__ void books_last(const X* Xs, const nm::Args<float>* As, int t, int wave) {
@@ -107,6 +136,7 @@ __device__ __noinline__ void books_last(const X* Xs, const nm::Args<float>* As, 
   BookRegs rec;
   books_load(rec, Xs, As, wave);
   books_file(rec, Xs, As, t, wave);
+  step_reset_noise(Xs, As, rec.d, wave);             // a reset at the launch's last step
 }
 
 // The launch arguments of env step t that every K-step launch sets (lane 0, after the policy of step t), and what closes the policy step.

@@ -13,6 +13,7 @@
 #include "nm_env_loop.h"
 #include "nm_env_rows.h"
 #include "nm_push.h"
+#include "nm_reset_noise.h"
 #include "nm_rollout.h"
 
 static thread_local std::string g_err;
@@ -340,6 +341,11 @@ struct nm_env {
   int push_interval = 0;
   double push_max = 0.0;
   uint64_t push_step = 0;
+  // randomised reset states (nm_reset_noise.h): the setting; the envs' reset counts are device memory of the env object
+  int rnoise_on = 0;
+  double rnoise_ranges[2 * nm::kResetRanges] = {};
+  virtual int set_reset_counts(const uint32_t* counts_host) = 0;
+  virtual int get_reset_counts(uint32_t* counts_host) = 0;
 };
 
 template <class real> struct Env : nm_env {
@@ -462,6 +468,7 @@ template <class real> struct Env : nm_env {
     a.cmd_u = cmd_u_on ? cmd_u_dev : nullptr;
     hipLaunchKernelGGL(k_reset<real>, dim3((n + 255) / 256), dim3(256), 0, s, M, a, idp, n);
     HIPCHK(hipGetLastError());
+    if (rnoise_on && launch_reset_noise(nullptr, idp, n, s)) return 1;     // the same envs' reset draw (nm_reset_noise.h)
     return finalize(ep_stats, nullptr, s);
   }
   int step(const float* actions, int64_t* eplen, float* obs, float* rew, int64_t* done, float* time_outs, float* ep_stats, int physics_only,
@@ -506,6 +513,8 @@ template <class real> struct Env : nm_env {
     });
     HIPCHK(hipGetLastError());
     if (prof_on) HIPCHK(hipEventRecord(e1, s));
+    // randomised reset states: the draw of the envs this step reset, decided on the device from done[] (nm_reset_noise.h)
+    if (!physics_only && rnoise_on && launch_reset_noise(done, nullptr, N, s)) return 1;
     return 0;
   }
   int d2h(const real* dev, double* host, size_t n) {
@@ -712,6 +721,47 @@ template <class real> struct Env : nm_env {
     a.rec = log; a.rec_env = log ? rec_env : -1; a.dbg = nullptr; a.ret_acc = nullptr;    // (rec: row t, set by the kernel before every step)
     return a;
   }
+  // ---- randomised reset states (nm_reset_noise.h): the reset counts, allocated (zeroed) at first use
+  uint32_t* rnoise_count = nullptr;
+  int rnoise_reserve() {
+    if (rnoise_count) return 0;
+    if (dalloc(&rnoise_count, (size_t)N)) return 1;
+    HIPCHK(hipMemset(rnoise_count, 0, (size_t)N * sizeof(uint32_t)));
+    HIPCHK(hipDeviceSynchronize());
+    return 0;
+  }
+  int set_reset_counts(const uint32_t* counts_host) override {
+    HIPCHK(hipSetDevice(device));
+    if (rnoise_reserve()) return 1;
+    if (!counts_host) return 0;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(rnoise_count, counts_host, (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return 0;
+  }
+  int get_reset_counts(uint32_t* counts_host) override {
+    if (!counts_host) return 0;
+    if (!rnoise_count) { memset(counts_host, 0, (size_t)N * sizeof(uint32_t)); return 0; }
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(counts_host, rnoise_count, (size_t)N * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+  }
+  const real* qpos0_dev() const { return reinterpret_cast<const real*>(reinterpret_cast<const char*>(M_dev) + offsetof(nm::Model<real>, qpos0)); }
+  // the reset draw behind a step (done: the step's reset flags) or behind k_reset (done = null: the n listed envs); on the same stream
+  int launch_reset_noise(const int64_t* done, const int32_t* ids, int n, hipStream_t s) {
+    hipLaunchKernelGGL(nm::k_reset_noise<real>, dim3((unsigned)(((size_t)n * 64 + 255) / 256)), dim3(256), 0, s, A.qpos, A.qvel, rnoise_count, qpos0_dev(),
+                       nm::reset_noise_params<real>(rnoise_ranges), A.seed, A.env_offset, done, ids, n);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  // the reset-noise arguments of a K-step launch
+  nmr::ResetNoiseArgs kstep_rnoise() {
+    nmr::ResetNoiseArgs r{};
+    if constexpr (sizeof(real) == 4) {
+      if (rnoise_on) { r.on = 1; r.p = nm::reset_noise_params<float>(rnoise_ranges); r.qpos0 = qpos0_dev(); r.count = rnoise_count; }
+    }
+    return r;
+  }
   // the push arguments of a K-step launch (nmr::PushArgs says how the step index travels); advances push_step by K
   nmr::PushArgs kstep_push(int K) {
     nmr::PushArgs p{};
@@ -749,7 +799,7 @@ template <class real> struct Env : nm_env {
       R.st_sum = roll_sum; R.st_cnt = roll_cnt; R.to_step = roll_to;
       R.last_values = r->last_values_dev;
       R.rec_log = log;
-      R.push = kstep_push(K);
+      R.push = kstep_push(K); R.rnoise = kstep_rnoise();
       R.wave_clock = A.dbg ? reinterpret_cast<unsigned long long*>(A.dbg) : nullptr;   // measurement: the debug buffer ([N,256] reals) takes the waves' clocks instead
       nmr::TailArgs ta{N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, r->bootstrap_time_outs ? r->gamma : -1.0f, r->s_values, r->s_rewards,
                        r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
@@ -787,7 +837,7 @@ template <class real> struct Env : nm_env {
       P.fin3 = r->fin3 ? r->fin3 : play_scratch + 4 * n_;
       P.st_sum = roll_sum; P.st_cnt = roll_cnt; P.to_step = roll_to;
       P.rec_log = log; P.rec_done = log ? rec_done : nullptr; P.rec_env = rec_env;
-      P.push = kstep_push(K);
+      P.push = kstep_push(K); P.rnoise = kstep_rnoise();
       rec_done_valid = log != nullptr;
       nmr::TailArgs ta{N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, -1.0f, nullptr, nullptr,
                        r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
@@ -820,7 +870,7 @@ template <class real> struct Env : nm_env {
       T.fin3 = r->fin3 ? r->fin3 : play_scratch + 4 * n_;
       T.st_sum = roll_sum; T.st_cnt = roll_cnt; T.to_step = roll_to;
       T.rec_log = log; T.rec_done = log ? rec_done : nullptr; T.rec_env = rec_env;
-      T.push = kstep_push(K);
+      T.push = kstep_push(K); T.rnoise = kstep_rnoise();
       rec_done_valid = log != nullptr;
       nmr::TailArgs ta{N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, -1.0f, nullptr, nullptr,
                        r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
@@ -1143,6 +1193,48 @@ int nm_get_push(nm_env* env, int32_t* interval_steps, double* max_vel_xy, uint64
   return 0;
 }
 #define NEED_ENV(e) if (!(e)) return fail(std::string(__func__) + ": env is NULL")
+// the ranges of randomised reset states, judged for `dtype` (NM_DTYPE_*); `who`: the entry point's name
+static int reset_ranges_bad(const char* who, const double* r, int dtype) {
+  static const char* kName[nm::kResetRanges] = {"base_height", "dof_pos", "base_lin_vel", "base_ang_vel", "dof_vel"};
+  for (int k = 0; k < nm::kResetRanges; k++) {
+    const double lo = r[2 * k], hi = r[2 * k + 1];
+    if (!std::isfinite(lo) || !std::isfinite(hi) || (dtype == NM_DTYPE_F32 && (!std::isfinite((float)lo) || !std::isfinite((float)hi))))
+      return fail(std::string(who) + ": the bounds of " + kName[k] + " must be finite");
+    if (lo > hi) return fail(std::string(who) + ": lo > hi for " + kName[k]);
+    if (dtype == NM_DTYPE_F32 ? !std::isfinite((float)hi - (float)lo) : !std::isfinite(hi - lo))
+      return fail(std::string(who) + ": the width of " + kName[k] + " must be finite");
+  }
+  return 0;
+}
+int nm_set_reset_noise(nm_env* env, const double* ranges10_host, const uint32_t* counts_host) {
+  // every refusal comes before the first device call; the ranges are judged first, so a bad range is named whatever the handle is
+  if (ranges10_host && reset_ranges_bad("nm_set_reset_noise", ranges10_host, NM_DTYPE_F64)) return 1;
+  NEED_ENV(env);
+  if (ranges10_host && reset_ranges_bad("nm_set_reset_noise", ranges10_host, env->dtype)) return 1;
+  if ((ranges10_host || counts_host) && env->set_reset_counts(counts_host)) return 1;
+  env->rnoise_on = ranges10_host != nullptr;
+  for (int i = 0; i < 2 * nm::kResetRanges; i++) env->rnoise_ranges[i] = ranges10_host ? ranges10_host[i] : 0.0;
+  return 0;
+}
+int nm_get_reset_noise(nm_env* env, int32_t* on, double* ranges10, uint32_t* counts_host) {
+  NEED_ENV(env);
+  if (on) *on = env->rnoise_on;
+  if (ranges10) for (int i = 0; i < 2 * nm::kResetRanges; i++) ranges10[i] = env->rnoise_ranges[i];
+  return env->get_reset_counts(counts_host);
+}
+int nm_reset_noise_offsets(const double* ranges10, uint64_t seed, int64_t global_env, uint32_t k, int32_t dtype, double* out43) {
+  if (!ranges10 || !out43) return fail("nm_reset_noise_offsets: ranges10 / out43 is NULL");
+  if (dtype != NM_DTYPE_F32 && dtype != NM_DTYPE_F64) return fail("nm_reset_noise_offsets: dtype must be NM_DTYPE_F32 or NM_DTYPE_F64");
+  if (reset_ranges_bad("nm_reset_noise_offsets", ranges10, dtype)) return 1;
+  if (dtype == NM_DTYPE_F32) {
+    const nm::ResetNoise<float> p = nm::reset_noise_params<float>(ranges10);
+    for (int c = 0; c < nm::kResetCols; c++) out43[c] = (double)nm::reset_noise_draw<float>(p, seed, (uint64_t)global_env, k, c);
+  } else {
+    const nm::ResetNoise<double> p = nm::reset_noise_params<double>(ranges10);
+    for (int c = 0; c < nm::kResetCols; c++) out43[c] = nm::reset_noise_draw<double>(p, seed, (uint64_t)global_env, k, c);
+  }
+  return 0;
+}
 int nm_set_env_params(nm_env* env, const void* mu_dev, const void* p_gain_dev, const void* kv_dev, void* stream) {
   NEED_ENV(env);
   return env->set_env_params(mu_dev, p_gain_dev, kv_dev, (hipStream_t)stream);

@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "nm_act.h"
+#include "nm_reset_noise.h"
 #include "nm_sample.h"
 #include "nm_sfor.h"
 
@@ -249,6 +250,14 @@ struct PushArgs {
   int past0;
   float maxv;                   // float32(max_vel_xy)
 };
+// Randomised reset states inside a K-step launch (nm_reset_noise.h; step_reset_noise of nm_env_loop.h): the converted ranges, the model's
+// qpos0 row in device memory and the envs' reset counts, which the owning wave reads and advances itself.
+struct ResetNoiseArgs {
+  int on;                       // 0 = off: nothing below is read
+  nm::ResetNoise<float> p;      // lo_r, w_r per range
+  const float* qpos0;           // [kNQ]
+  uint32_t* count;              // [N]
+};
 // ---- the K-step launch (kernels in nm_rollout.hip - a translation unit of its own, so that the code generation of k_env_step in
 // nm_hip.hip is not touched by a second kernel around the same physics; host launchers below)
 struct RollArgs {
@@ -265,6 +274,7 @@ struct RollArgs {
   unsigned long long* wave_clock;                              // measurement (nm_set_debug_buffer on): [waves][2] s_memtime at the wave's start / end, else null
   float* rec_log;                                              // [K,kRecRow] or null: the state log (Args::rec of step t = row t; env.py:261-272)
   PushArgs push;
+  ResetNoiseArgs rnoise;
   // what the episode books of nm_env_loop.h file for this launch: kPlayBooks = per-env return sums + the logged env's reset flag (else the
   // rollout's storage rows), kStepRecord = optional [K,N] reward / done rows
   static constexpr bool kPlayBooks = false, kStepRecord = false;
@@ -284,6 +294,7 @@ struct PlayArgs {
   float* rec_log;                                              // [K,kRecRow] or null
   unsigned char* rec_done; int rec_env;                        // [K] or null: the logged env's reset flag per step (the log's reader dumps a file there)
   PushArgs push;
+  ResetNoiseArgs rnoise;
   static constexpr bool kPlayBooks = true, kStepRecord = false;
 };
 // k_env_tape (nm_tape_kernels.h): K x env.step with the actions of step t read from row t of a [K,N,18] tape - no policy, no sampling
@@ -300,6 +311,7 @@ struct TapeArgs {
   float* rec_log;
   unsigned char* rec_done; int rec_env;
   PushArgs push;
+  ResetNoiseArgs rnoise;
   static constexpr bool kPlayBooks = true, kStepRecord = true;
 };
 struct TailArgs {

@@ -27,6 +27,7 @@ __device__ __noinline__ void tape_step(const TapeArgs* Ts, nm::Args<float>* As, 
     BookRegs rec;
     books_load(rec, Ts, As, wave);
     books_file(rec, Ts, As, t - 1, wave);
+    step_reset_noise(Ts, As, rec.d, wave);           // the reset draw of step t - 1, before the push of step t
   }
   if (threadIdx.x == 0) {
     const size_t so = (size_t)t * As->N;

@@ -21,6 +21,9 @@ Differences a caller can observe (all documented in DESIGN.md):
     body, compiled into the env's model constants (set_base_payload, draw_base_payload), drawn once at construction
   * and randomize_action_latency / action_latency_range (whole physics substeps): per-env actuation latency - the servo targets lag the
     policy's actions (set_action_latency, draw_action_latency), drawn once at construction
+  * and randomize_reset_state with reset_base_height_range / reset_dof_pos_range / reset_base_lin_vel_range / reset_base_ang_vel_range /
+    reset_dof_vel_range: every reset draws the base height, the joint angles and all velocities afresh around qpos0 / zero
+    (set_reset_noise), from the first reset() on
 """
 import ctypes as C
 import numpy as np
@@ -108,6 +111,22 @@ def latency_config(cfg):
     return _switched(getattr(cfg, "domain_rand", None), "randomize_action_latency", "action_latency_range", lowest=0, whole=True)
 
 
+RESET_NOISE_RANGES = ("reset_base_height_range", "reset_dof_pos_range", "reset_base_lin_vel_range", "reset_base_ang_vel_range",
+                      "reset_dof_vel_range")
+
+
+def reset_noise_config(cfg):
+    """The five (lo, hi) ranges of randomised reset states from the optional cfg.domain_rand, in the order of RESET_NOISE_RANGES (what
+    set_reset_noise takes), or None when the class is missing or randomize_reset_state is false. A missing range is (0, 0); the flag with
+    no range at all, or a range that is not two finite numbers lo <= hi, is a ValueError."""
+    dr = getattr(cfg, "domain_rand", None)
+    if not getattr(dr, "randomize_reset_state", False):
+        return None
+    if all(getattr(dr, n, None) is None for n in RESET_NOISE_RANGES):
+        _switched(dr, "randomize_reset_state", " or ".join(RESET_NOISE_RANGES))       # (raises: the flag needs a range)
+    return tuple(_range(dr, n) or (0.0, 0.0) for n in RESET_NOISE_RANGES)
+
+
 class NightmareV3Env:
     def __init__(self, cfg: NightmareV3Config, log_dir="/tmp/nightmare_v3/logs", num_threads=1, *, device=None, seed=0,
                  env_id_offset=0, dtype=torch.float32, lib=None):
@@ -149,6 +168,7 @@ class NightmareV3Env:
         envp_ranges = env_param_config(cfg)
         payload_ranges = payload_config(cfg)
         latency_range = latency_config(cfg)
+        reset_ranges = reset_noise_config(cfg)
         # reward table: zero scales dropped, the rest x dt (reference :123-128). Every name the reference has a _reward_ function
         # for (:399-497) is compiled; a name without one (`collision`, `feet_stumble`, config :95-96) fails like upstream's getattr.
         names = [L.nm_reward_name(i).decode() for i in range(_lib.NUM_REWARDS)]
@@ -228,6 +248,10 @@ class NightmareV3Env:
         # per-env actuation latency (optional cfg.domain_rand; no reference line): drawn once, here
         if latency_range is not None:
             self.draw_action_latency(*latency_range)
+        # randomised reset states (optional cfg.domain_rand; no reference line): on before the first reset(), whose reset_idx(all) is
+        # draw 0 of every env
+        if reset_ranges is not None:
+            self.set_reset_noise(reset_ranges)
         # state log of env 0 (reference :261-272; reader open_custom_play.py:50-66)
         self.state_log = None
         self._rec_env = 0
@@ -286,6 +310,31 @@ class NightmareV3Env:
         iv, mx, st = C.c_int32(0), C.c_double(0), C.c_uint64(0)
         self._ck(self._L.nm_get_push(self._h, C.byref(iv), C.byref(mx), C.byref(st)))
         return iv.value, mx.value, st.value
+
+    def set_reset_noise(self, ranges=None, counts=None):
+        """Randomised reset states (nm_set_reset_noise): `ranges` = five (lo, hi) pairs in the order base_height, dof_pos, base_lin_vel,
+        base_ang_vel, dof_vel (RESET_NOISE_RANGES), or None = off. While on, every reset of an env - in step(), reset_idx, policy_rollout,
+        policy_play and step_tape alike - adds a fresh uniform draw to qpos0's base height and joint angles and sets all 24 velocities
+        to draws; the draw is keyed by (seed, global env id, the env's reset count). counts: [num_envs] reset counts to install (a
+        checkpoint's), None keeps the env's."""
+        r = None
+        if ranges is not None:
+            r = np.ascontiguousarray(ranges, np.float64)
+            if r.size != 10:
+                raise ValueError("set_reset_noise: ranges must be five (lo, hi) pairs")
+            r = (C.c_double * 10)(*r.reshape(-1))
+        k = None
+        if counts is not None:
+            k = np.ascontiguousarray(counts, np.uint32).reshape(-1)
+            if k.size != self.num_envs:
+                raise ValueError("set_reset_noise: counts must hold num_envs values")
+        self._ck(self._L.nm_set_reset_noise(self._h, None if r is None else C.byref(r), None if k is None else k.ctypes.data_as(C.c_void_p)))
+
+    def reset_noise_state(self):
+        """(on, ranges [5, 2], counts [num_envs] uint32) as nm_get_reset_noise returns them: what a checkpoint needs to continue the draws."""
+        on, r, k = C.c_int32(0), (C.c_double * 10)(), np.zeros(self.num_envs, np.uint32)
+        self._ck(self._L.nm_get_reset_noise(self._h, C.byref(on), C.byref(r), k.ctypes.data_as(C.c_void_p)))
+        return bool(on.value), np.array(r[:], np.float64).reshape(5, 2), k
 
     def _per_env(self, x, dtype, err, device=None):
         """num_envs values, or one scalar for every env, as a contiguous [num_envs] tensor of `dtype` on the env's device (or `device`);

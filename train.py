@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """train.py - the reference's training entry point (reference train.py:1-54) on the MI355X backend.
 Same flags (-r resume, -v render [rejected: no viewer], -n num_threads [accepted, unused], -e envs, -p resume_path) plus
---iters / --seed / --gpus / --push-interval-s / --push-vel / --friction-range / --gain-range. Multi-GPU: `python train.py --gpus G -e <total envs>` (starts its G ranks as child processes) or
+--iters / --seed / --gpus / --push-interval-s / --push-vel / --friction-range / --gain-range / --reset-dof-pos / --reset-vel. Multi-GPU: `python train.py --gpus G -e <total envs>` (starts its G ranks as child processes) or
 `python -m torch.distributed.run --nproc-per-node G train.py -e <total envs>`."""
 import argparse
 import datetime
@@ -38,6 +38,11 @@ def main():
                     help="where the added mass sits: each coordinate in the base body frame drawn once from U[-R, R) m (default: the base origin)")
     ap.add_argument("--latency-range", type=int, nargs=2, default=None, metavar=("LO", "HI"), dest="latency_range",
                     help="per-env actuation latency in physics substeps, drawn once from the integers LO..HI, at most 3 x decimation (default: none)")
+    ap.add_argument("--reset-dof-pos", type=float, default=0.0, metavar="R", dest="reset_dof_pos",
+                    help="randomised reset states: every reset draws each joint angle from U[-R, R) rad around the default pose (0 = off, the default)")
+    ap.add_argument("--reset-vel", type=float, default=0.0, metavar="V", dest="reset_vel",
+                    help="randomised reset states: every reset draws the base's linear (m/s) and angular (rad/s) velocity and the joint "
+                         "velocities (rad/s) from U[-V, V) (0 = off, the default)")
     ap.add_argument("--gain-range", type=float, nargs=2, default=None, metavar=("LO", "HI"), dest="gain_range",
                     help="per-env multipliers of the servo stiffness (p_gain) and damping (kv), each drawn once from U[LO, HI) (default: 1.0)")
     ap.add_argument("--gpus", type=int, default=None, help="ranks (one per GPU); without torch.distributed.run, train.py starts them itself")
@@ -72,7 +77,11 @@ def main():
     cfg, train_cfg = NightmareV3Config(), NightmareV3ConfigPPO()
     cfg.viewer.render = args.render
     cfg.viewer.record_states = bool(args.record_states) and rank == 0        # one log: rank 0's env 0
-    if args.push_interval_s > 0 or args.friction_range or args.gain_range or args.added_mass_range or args.com_range is not None or args.latency_range:
+    if args.reset_dof_pos < 0 or args.reset_vel < 0:
+        ap.error("--reset-dof-pos and --reset-vel must not be negative")
+    reset_noise = args.reset_dof_pos > 0 or args.reset_vel > 0
+    if (args.push_interval_s > 0 or args.friction_range or args.gain_range or args.added_mass_range or args.com_range is not None or args.latency_range
+            or reset_noise):
         class domain_rand:      # the optional class NightmareV3Env reads
             push_robots, push_interval_s, max_push_vel_xy = args.push_interval_s > 0, args.push_interval_s, args.push_vel
             randomize_friction, friction_range = args.friction_range is not None, args.friction_range
@@ -82,6 +91,9 @@ def main():
             randomize_com_displacement = args.com_range is not None
             com_displacement_range = None if args.com_range is None else (-args.com_range, args.com_range)
             randomize_action_latency, action_latency_range = args.latency_range is not None, args.latency_range
+            randomize_reset_state = reset_noise
+            reset_dof_pos_range = (-args.reset_dof_pos, args.reset_dof_pos)
+            reset_base_lin_vel_range = reset_base_ang_vel_range = reset_dof_vel_range = (-args.reset_vel, args.reset_vel)
         cfg.domain_rand = domain_rand
     lo, hi = shard_range(args.num_envs, rank, world)
     cfg.env.num_envs = hi - lo
@@ -91,6 +103,8 @@ def main():
     env = NightmareV3Env(cfg, log_dir=log_dir, num_threads=args.num_threads, device=f"cuda:{local_rank}", seed=seed, env_id_offset=lo)
     if rank == 0:
         print(f"push perturbations: every {env.push_interval} steps, |v| < {env.max_push_vel_xy} m/s" if env.push_interval else "push perturbations: off", flush=True)
+        if reset_noise:
+            print(f"randomised reset states: joint angles +-{args.reset_dof_pos} rad, velocities +-{args.reset_vel}", flush=True)
         if args.friction_range or args.gain_range:
             print(f"per-env friction range {args.friction_range or 'off'}, gain multiplier range {args.gain_range or 'off'}", flush=True)
     runner = OnPolicyRunner(env, class_to_dict(train_cfg), log_dir=log_dir, device=f"cuda:{local_rank}")
