@@ -19,8 +19,9 @@
 //   stage D  "lane = leg": implicitfast solve, semi-implicit Euler, quaternion integration.
 //   epilogue "lane = observation slot": frame transforms, termination, reset, rewards, obs.
 //
-// All inter-stage traffic goes through the wave's LDS (18.6 KB per wave of two envs: two env images, the row buffer, the wave's copy
-// of the model constants and of the launch arguments); HBM is touched once per env-step (state in, state + obs out).
+// All inter-stage traffic goes through the wave's LDS (18.4 KB per wave of two envs: two env images, the row buffer, the wave's copy
+// of the model constants); HBM is touched once per env-step (state in, state + obs out). The launch arguments reach the stages through
+// a source type (ArgSrc below): k_env_step reads them from its kernarg segment, the K-step kernels from a copy in LDS that they edit.
 #pragma once
 #include <type_traits>
 #include <stddef.h>
@@ -84,6 +85,18 @@ template <class real> struct Model {
   int collide_batch_min;   // floor contacts of an env go out in one batched pass from this many touching meshes on (stage_collide); 3
   real tibia_max, body_max, base_h_target, max_contact_force;
 };
+
+// The struct as the device holds it and as k_env_step copies it: padded with zeros to whole rounds of 64 lanes x 16 bytes, so that the
+// copy is unconditional global_load_dwordx4 / ds_write_b128 per lane with no bound to test. (The padding is a wrapper's, not Model's
+// own: the K-step kernels keep a plain Model in LDS, and their register allocation follows their LDS layout - see Sh::envp.)
+constexpr size_t kModelRound = 64 * 16;
+template <class real> union alignas(16) ModelBlock {
+  Model<real> m;
+  unsigned char bytes[(sizeof(Model<real>) + kModelRound - 1) / kModelRound * kModelRound];
+};
+static_assert(sizeof(ModelBlock<float>) % kModelRound == 0 && sizeof(ModelBlock<double>) % kModelRound == 0 &&
+              sizeof(ModelBlock<float>) - sizeof(Model<float>) < kModelRound && sizeof(ModelBlock<double>) - sizeof(Model<double>) < kModelRound,
+              "ModelBlock: whole copy rounds, less than one round of padding");
 
 // per-launch arguments (device pointers, AoS-by-env rows so one wave reads contiguous bytes)
 template <class real> struct Args {
@@ -153,6 +166,48 @@ template <class real> NM_FN int* lat_delay(const Args<real>& A) {
 }
 template <class real> NM_FN float* lat_hist(const Args<real>& A) { return reinterpret_cast<float*>(lat_delay(A) + A.N); }
 constexpr int kDbgN = 256;
+
+// Where a stage reads the launch arguments from: the stages that touch them (env_load*, env_finish*, wave_step) take the source as a
+// template parameter and call launch_args() on it where they begin.
+//   Args<real> itself: a copy the caller owns and may edit between steps - the LDS copy of the K-step kernels (they re-point actions /
+//     obs / statistics per step), the host emulation's struct. launch_args() is the identity; global accesses keep the 64-bit form.
+//   KernArgs<real> (device): the kernel's own kernarg segment, constant address space. Every launch_args() hides the base behind an empty
+//     asm, so the scalar loads of the pointers are issued where the stage begins and their registers are dead where it ends - without
+//     that the compiler hoists all ~35 pointers to the top of the kernel and pins (or spills) 70 SGPRs across the physics. The
+//     base pointers then sit in SGPRs: global accesses take the scalar-base form (simt.h gldx / gstx).
+template <class Src> struct ArgSrc { static constexpr bool kScalarBase = false; };
+template <class real> NM_FN const Args<real>& launch_args(const Args<real>& a) { return a; }
+template <class real> NM_FN const Args<real>& launch_args(const Args<real>* a) { return *a; }     // (an out-of-line function takes the copy by address)
+#ifndef NM_EMUL
+typedef const __attribute__((address_space(4))) char* kernarg_ptr;
+// `seg`: the kernarg segment of the running kernel (__builtin_amdgcn_kernarg_segment_ptr()), OFS: the byte its Args<real> starts at.
+// The offset is added behind the asm, where it folds into the loads' immediates: the segment pointer the wave was started with is the
+// only register that stays live.
+template <class real, int OFS> struct KernArgs { kernarg_ptr seg; };
+template <class real, int OFS> struct ArgSrc<KernArgs<real, OFS>> { static constexpr bool kScalarBase = true; };
+template <class real, int OFS> NM_FN const Args<real>& launch_args(const KernArgs<real, OFS>& k) {
+  kernarg_ptr p = k.seg;
+  asm volatile("" : "+s"(p));
+  return *(const Args<real>*)(const __attribute__((address_space(4))) Args<real>*)(p + OFS);   // (address-space inference turns every load through this reference back into a constant-space load)
+}
+// One word of every 64-byte line of the arguments, requested back to back before anything waits: the first wave on a scalar cache takes
+// the misses of the whole struct at once (as the single batch of loads did when the compiler placed them), not one per dependent group
+template <class real, int OFS> NM_FN void launch_args_touch(const KernArgs<real, OFS>& k) {
+  kernarg_ptr p = k.seg;
+  asm volatile("" : "+s"(p));
+  int x = 0;
+#pragma unroll
+  for (int o = 0; o < OFS + (int)sizeof(Args<real>); o += 64) x |= *(const __attribute__((address_space(4))) int*)(p + o);
+  asm volatile("" ::"s"(x));
+}
+// a source that arrived as a function argument (vector registers) back in scalar registers; the identity for a reference to LDS
+template <class real> NM_FN const Args<real>* scalar_src(const Args<real>* a) { return a; }
+template <class real, int OFS> NM_FN KernArgs<real, OFS> scalar_src(const KernArgs<real, OFS>& k) {
+  const uint64_t u = (uint64_t)k.seg;
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)u), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(u >> 32));
+  return KernArgs<real, OFS>{(kernarg_ptr)(((uint64_t)hi << 32) | lo)};
+}
+#endif
 
 // ----------------------------------------------------------------------------------------- LDS image of one env
 template <class real> struct Sh {
@@ -3366,8 +3421,10 @@ template <class real> NM_FN void env_finish(Sh<real>& sh, const Model<real>& M, 
 // `mid()` runs after every HBM read has been issued and before the first of them is waited for: the kernel copies the model constants
 // (L2 -> LDS, `M` is that copy) there, so the two round trips of a wave's start-up overlap instead of following each other.
 struct NoMid { NM_FN void operator()() const {} NM_FN void operator()(int) const {} };
-template <int EP, class real, class Mid> NM_FN void env_load2(ShW<real, 2>& w, const Model<real>& M, const Args<real>& A, int wave, Mid&& mid) {
+template <int EP, class real, class Src, class Mid> NM_FN void env_load2(ShW<real, 2>& w, const Model<real>& M, const Src& src, int wave, Mid&& mid) {
   typedef V<real> vr;
+  const Args<real>& A = launch_args(src);
+  constexpr bool kS = ArgSrc<Src>::kScalarBase;
   constexpr int kSR = (int)(sizeof(Sh<real>) / sizeof(real)), kSI = (int)(sizeof(Sh<real>) / sizeof(int));
   const V<int> lane = opaque_lane();
   const V<int> h = lane >> 5, hl = lane & 31;
@@ -3378,40 +3435,40 @@ template <int EP, class real, class Mid> NM_FN void env_load2(ShW<real, 2>& w, c
   const V<int> ho = h * kSR, hoi = h * kSI;
   const VB l18 = hl < kNU;
   const V<int> l18c = sel(l18, hl, V<int>(0));
-  const vr q_in = gldv(A.qpos, sel(hl < kNQ, hl, V<int>(0)) + env * kNQ);
-  const vr v_in = gldv(A.qvel, sel(hl < kNV, hl, V<int>(0)) + env * kNV);
-  const vr w_in = gldv(A.qwarm, sel(hl < kNV, hl, V<int>(0)) + env * kNV);
-  const V<int> hc_in = gldv(A.hullcache, sel(hl < 8, hl, V<int>(0)) + env * 8);
-  const V<float> a_in = gldv(A.actions, l18c + env * kNU);
+  const vr q_in = gldx<kS>(A.qpos, sel(hl < kNQ, hl, V<int>(0)) + env * kNQ);
+  const vr v_in = gldx<kS>(A.qvel, sel(hl < kNV, hl, V<int>(0)) + env * kNV);
+  const vr w_in = gldx<kS>(A.qwarm, sel(hl < kNV, hl, V<int>(0)) + env * kNV);
+  const V<int> hc_in = gldx<kS>(A.hullcache, sel(hl < 8, hl, V<int>(0)) + env * 8);
+  const V<float> a_in = gldx<kS>(A.actions, l18c + env * kNU);
   vr envp_in = vr(real(0));
-  if constexpr (EP != 0) envp_in = gldv(A.envp, sel(hl < kEnvP, hl, V<int>(0)) + env * kEnvP);     // each env's (mu, p_gain, kv, pad) row: 16 bytes, lanes 0..3 of its half
+  if constexpr (EP != 0) envp_in = gldx<kS>(A.envp, sel(hl < kEnvP, hl, V<int>(0)) + env * kEnvP);     // each env's (mu, p_gain, kv, pad) row: 16 bytes, lanes 0..3 of its half
   vr body_in = vr(real(0));
-  if constexpr (EP >= 2) body_in = gldv(A.envp, sel(hl < kBodyP, hl, V<int>(0)) + (env * kBodyP + A.N * kEnvP));   // each env's body row (behind the N envp rows), lanes 0..19 of its half
+  if constexpr (EP >= 2) body_in = gldx<kS>(A.envp, sel(hl < kBodyP, hl, V<int>(0)) + (env * kBodyP + A.N * kEnvP));   // each env's body row (behind the N envp rows), lanes 0..19 of its half
   vr cmd_in = vr(real(0)), eps_in = vr(real(0)), prev_act = vr(real(0)), prev_dofvel = vr(real(0)), dofpos_old = vr(real(0));
   // level 3: each env's delay and its whole action history (three rows, lane of the half = joint) with the step's other reads
   V<int> dl = V<int>(0);
   V<float> h0 = V<float>(0.0f), h1 = V<float>(0.0f), h2 = V<float>(0.0f);
   if constexpr (EP == 3)
     if (!A.physics_only) {
-      dl = gldv(lat_delay(A), env);
-      h0 = gldv(lat_hist(A), l18c + env * (kLatH * kNU));
-      h1 = gldv(lat_hist(A), l18c + (env * (kLatH * kNU) + kNU));
-      h2 = gldv(lat_hist(A), l18c + (env * (kLatH * kNU) + 2 * kNU));
+      dl = gldx<kS>(lat_delay(A), env);
+      h0 = gldx<kS>(lat_hist(A), l18c + env * (kLatH * kNU));
+      h1 = gldx<kS>(lat_hist(A), l18c + (env * (kLatH * kNU) + kNU));
+      h2 = gldx<kS>(lat_hist(A), l18c + (env * (kLatH * kNU) + 2 * kNU));
     }
 #ifndef NM_EMUL
   int64_t ep = 0;
   uint32_t ctr_in = 0;
 #endif
   if (!A.physics_only) {
-    cmd_in = gldv(A.cmd, sel(hl < 3, hl, V<int>(0)) + env * 3);
-    eps_in = gldv(A.epsum, sel(hl < kNREW, hl, V<int>(0)) + env * kNREW);
+    cmd_in = gldx<kS>(A.cmd, sel(hl < 3, hl, V<int>(0)) + env * 3);
+    eps_in = gldx<kS>(A.epsum, sel(hl < kNREW, hl, V<int>(0)) + env * kNREW);
 #ifndef NM_EMUL
-    ep = gld1(A.eplen, (size_t)env);
-    ctr_in = gld1(A.rngctr, (size_t)env);
+    ep = gld1x<kS>(A.eplen, env);
+    ctr_in = gld1x<kS>(A.rngctr, env);
 #endif
-    prev_act = gldv(A.act, l18c + env * kNU);
-    prev_dofvel = gldv(A.dofvel, l18c + env * kNU);
-    dofpos_old = gldv(A.dofpos, l18c + env * kNU);
+    prev_act = gldx<kS>(A.act, l18c + env * kNU);
+    prev_dofvel = gldx<kS>(A.dofvel, l18c + env * kNU);
+    dofpos_old = gldx<kS>(A.dofpos, l18c + env * kNU);
   }
   mid();
   stsv(rb, ho + (hl + NM_OFS(qpos)), q_in, hl < kNQ);
@@ -3477,9 +3534,9 @@ template <int EP, class real, class Mid> NM_FN void env_load2(ShW<real, 2>& w, c
       // padded slot (it recomputes the last env) stores nothing
       float* hist = lat_hist(A);
       const VB st = l18 & (env0 < V<int>(A.N));
-      gstv(hist, hl + (env * (kLatH * kNU) + 2 * kNU), h1, st);
-      gstv(hist, hl + (env * (kLatH * kNU) + kNU), h0, st);
-      gstv(hist, hl + env * (kLatH * kNU), af, st);
+      gstx<kS>(hist, hl + (env * (kLatH * kNU) + 2 * kNU), h1, st);
+      gstx<kS>(hist, hl + (env * (kLatH * kNU) + kNU), h0, st);
+      gstx<kS>(hist, hl + env * (kLatH * kNU), af, st);
     } else
     stsv(rb, ho + (hl + NM_OFS(ctrl)), ((act - defp) - dofpos_old) * p_gain, l18);
   } else {
@@ -3495,8 +3552,10 @@ template <int EP, class real, class Mid> NM_FN void env_load2(ShW<real, 2>& w, c
 // the counters) is out: the kernel takes the wave's end-of-step ticket there, so the ticket's round trip is hidden under E7 / E8.
 // `published(1)` comes again after E7, a microsecond later: the group ticket is back by then, and the wave that turns out to be the last of
 // its group draws the top-level ticket there - under E8 and the buffer stores.
-template <class real, class Pub> NM_FN void env_finish2(ShW<real, 2>& w, const Model<real>& M, const Args<real>& A, int wave, int dropped, Pub&& published) {
+template <class real, class Src, class Pub> NM_FN void env_finish2(ShW<real, 2>& w, const Model<real>& M, const Src& src, int wave, int dropped, Pub&& published) {
   typedef V<real> vr;
+  const Args<real>& A = launch_args(src);
+  constexpr bool kS = ArgSrc<Src>::kScalarBase;
   constexpr int kSR = (int)(sizeof(Sh<real>) / sizeof(real)), kSI = (int)(sizeof(Sh<real>) / sizeof(int));
   const V<int> lane = opaque_lane();
   const V<int> h = lane >> 5, hl = lane & 31;
@@ -3524,15 +3583,15 @@ template <class real, class Pub> NM_FN void env_finish2(ShW<real, 2>& w, const M
     V<int> hc = SHI(hcache, sel(hl < 8, hl, V<int>(0)));
     hc = sel(hl == 0, hc | (SHI(ncon, V<int>(0)) << 16), hc);     // the load hint for the next step
     const vr q = SHR(qpos, sel(hl < kNQ, hl, V<int>(0))), v = SHR(qvel, sel(hl < kNV, hl, V<int>(0))), wq = SHR(warm, sel(hl < kNV, hl, V<int>(0)));
-    gstv(A.hullcache, hl + env * 8, hc, live & (hl < 8));
-    gstv(A.qpos, hl + env * kNQ, q, live & (hl < kNQ));
-    gstv(A.qvel, hl + env * kNV, v, live & (hl < kNV));
-    gstv(A.qwarm, hl + env * kNV, wq, live & (hl < kNV));
+    gstx<kS>(A.hullcache, hl + env * 8, hc, live & (hl < 8));
+    gstx<kS>(A.qpos, hl + env * kNQ, q, live & (hl < kNQ));
+    gstx<kS>(A.qvel, hl + env * kNV, v, live & (hl < kNV));
+    gstx<kS>(A.qwarm, hl + env * kNV, wq, live & (hl < kNV));
     if (A.rec) {
       const VB r = live & (env == V<int>(A.rec_env));
-      gstv(A.rec, hl, q, r & (hl < kNQ));
-      gstv(A.rec, hl + kNQ, v, r & (hl < kNV));
-      gstv(A.rec, V<int>(kNQ + kNV), to_real<real>(nwarn), r & (hl == 0));
+      gstx<kS>(A.rec, hl, q, r & (hl < kNQ));
+      gstx<kS>(A.rec, hl + kNQ, v, r & (hl < kNV));
+      gstx<kS>(A.rec, V<int>(kNQ + kNV), to_real<real>(nwarn), r & (hl == 0));
     }
   }
   if (A.dbg) {
@@ -3635,8 +3694,8 @@ template <class real, class Pub> NM_FN void env_finish2(ShW<real, 2>& w, const M
   const VB resetL = reset & live;
   const uint64_t rmask = ballot(resetL);
   if (rmask) {
-    gstv(A.qpos, hl + env * kNQ, ldsv(M.qpos0, sel(hl < kNQ, hl, V<int>(0))), resetL & (hl < kNQ));
-    gstv(A.qvel, hl + env * kNV, real(0), resetL & (hl < kNV));
+    gstx<kS>(A.qpos, hl + env * kNQ, ldsv(M.qpos0, sel(hl < kNQ, hl, V<int>(0))), resetL & (hl < kNQ));
+    gstx<kS>(A.qvel, hl + env * kNV, real(0), resetL & (hl < kNV));
 #pragma unroll
     for (int hh = 0; hh < 2; hh++)
       if ((rmask >> (32 * hh)) & 1) { resample(hh, 1); ep[hh] = 0; }
@@ -3694,8 +3753,8 @@ template <class real, class Pub> NM_FN void env_finish2(ShW<real, 2>& w, const M
       vr over = sel(ff > vr(M.max_contact_force), ff - M.max_contact_force, vr(real(0)));
       rt[R_FEET_CONTACT] = hsum32(sel(l6, over * over, vr(real(0)))) * M.rew_scale[R_FEET_CONTACT];         // env.py:491-493
       if (M.rew_scale[R_FEET_AIR_TIME] != real(0)) {   // env.py:458-477; stateful: runs only while it is in the reward table
-        vr air = gldv(A.feetair, l6c + envc * kNLEG);
-        const V<int> fl = gldv(A.feetflags, envc);
+        vr air = gldx<kS>(A.feetair, l6c + envc * kNLEG);
+        const V<int> fl = gldx<kS>(A.feetflags, envc);
         air = sel(reset, vr(real(0)), air);            // reset_idx zeroes feet_air_time (env.py:359) before the rewards run
         const VB contact = ff > vr(real(1));
         const VB filt = contact | (((fl >> l6c) & 1) != 0);
@@ -3704,10 +3763,10 @@ template <class real, class Pub> NM_FN void env_finish2(ShW<real, 2>& w, const M
         air = sel(filt == lastf, air, vr(real(0)));    // reset air time if the filtered contact changes
         const vr single = sel(air > vr(real(1)), air - real(1), vr(real(0))) + sel(air < vr(real(0.5)), real(0.5) - air, vr(real(0)));
         rt[R_FEET_AIR_TIME] = hsum32(sel(l6, single * single, vr(real(0)))) * M.rew_scale[R_FEET_AIR_TIME];
-        gstv(A.feetair, l6c + env * kNLEG, air, live & l6);
+        gstx<kS>(A.feetair, l6c + env * kNLEG, air, live & l6);
         const uint64_t bc = ballot(l6 & contact), bf = ballot(l6 & filt);
         const int nf0 = (int)((bc & 63) | ((bf & 63) << kNLEG)), nf1 = (int)(((bc >> 32) & 63) | (((bf >> 32) & 63) << kNLEG));
-        gstv(A.feetflags, env, sel(h1, V<int>(nf1), V<int>(nf0)), live & (hl == 0));
+        gstx<kS>(A.feetflags, env, sel(h1, V<int>(nf1), V<int>(nf0)), live & (hl == 0));
       }
     }
   }
@@ -3718,7 +3777,7 @@ template <class real, class Pub> NM_FN void env_finish2(ShW<real, 2>& w, const M
     vr add = vr(real(0));
 #pragma unroll
     for (int k = 0; k < kNREW; k++) add = sel(hl == k, rt[k], add);
-    gstv(A.epsum, hl + env * kNREW, epsum + add, live & (hl < kNREW));
+    gstx<kS>(A.epsum, hl + env * kNREW, epsum + add, live & (hl < kNREW));
   }
   published(1);
   NM_ESTAMP(14);
@@ -3748,7 +3807,8 @@ template <class real, class Pub> NM_FN void env_finish2(ShW<real, 2>& w, const M
 #ifdef NM_EMUL
       for (int i = 0; i < NM_WAVE; i++) if (m.v[i]) A.obs[(size_t)env.v[i] * kNOBS + idx.v[i]] = (float)cx.v[i];
 #else
-      if (m) gst1(A.obs, (size_t)env * kNOBS + idx, (float)cx);
+      if constexpr (kS) { if (m) gst1x<true>(A.obs, env * kNOBS + idx, (float)cx); }
+      else if (m) gst1(A.obs, (size_t)env * kNOBS + idx, (float)cx);
 #endif
     };
     put(o, hl, hl < 12);
@@ -3758,12 +3818,12 @@ template <class real, class Pub> NM_FN void env_finish2(ShW<real, 2>& w, const M
   }
   NM_ESTAMP(15);
   // ---- buffers the reference keeps between steps
-  gstv(A.dofpos, hl + env * kNU, dofpos, live & l18);
-  gstv(A.dofvel, hl + env * kNU, dofvel, live & l18);
-  gstv(A.act, hl + env * kNU, act, live & l18);
+  gstx<kS>(A.dofpos, hl + env * kNU, dofpos, live & l18);
+  gstx<kS>(A.dofvel, hl + env * kNU, dofvel, live & l18);
+  gstx<kS>(A.act, hl + env * kNU, act, live & l18);
   {
     vr cv = sel(hl == 0, cmd[0], sel(hl == 1, cmd[1], cmd[2]));
-    gstv(A.cmd, hl + env * 3, cv, live & (hl < 3));
+    gstx<kS>(A.cmd, hl + env * 3, cv, live & (hl < 3));
   }
 #ifdef NM_EMUL
   for (int hh = 0; hh < 2; hh++)
@@ -3775,12 +3835,12 @@ template <class real, class Pub> NM_FN void env_finish2(ShW<real, 2>& w, const M
     }
 #else
   if (hl == 0 && live) {
-    gst1(A.eplen, (size_t)env, h1 ? ep[1] : ep[0]);
-    gst1(A.rngctr, (size_t)env, h1 ? ctr[1] : ctr[0]);
-    gst1(A.rew, (size_t)env, (float)rew);
-    if (A.ret_acc) gadd1(A.ret_acc, (size_t)env, (float)rew);
-    gst1(A.done, (size_t)env, (int64_t)(reset ? 1 : 0));
-    gst1(A.timeout_now, (size_t)env, time_out ? 1.0f : 0.0f);
+    gst1x<kS>(A.eplen, env, h1 ? ep[1] : ep[0]);
+    gst1x<kS>(A.rngctr, env, h1 ? ctr[1] : ctr[0]);
+    gst1x<kS>(A.rew, env, (float)rew);
+    if (A.ret_acc) gadd1x<kS>(A.ret_acc, env, (float)rew);
+    gst1x<kS>(A.done, env, (int64_t)(reset ? 1 : 0));
+    gst1x<kS>(A.timeout_now, env, time_out ? 1.0f : 0.0f);
   }
 #endif
 #undef SHR
@@ -3809,11 +3869,14 @@ template <class real, int G> NM_FN void latency_switch(ShW<real, G>& w, int s) {
   wave_sync();
 }
 
-template <class real, int G, int EP = 0, class Mid = NoMid, class Pub = NoMid>
-NM_FN void wave_step(ShW<real, G>& w, const Model<real>& M, const Args<real>& A, int wave, Mid&& mid = Mid(), Pub&& published = Pub()) {
+// `src`: where the launch arguments are read from (ArgSrc above). The two-env stages fetch what they need where they begin; what the
+// substep loop itself reads (nsub, and the ablation mask of a measurement build) is fetched once here and stays in a scalar register.
+template <class real, int G, int EP = 0, class Mid = NoMid, class Pub = NoMid, class Src = Args<real>>
+NM_FN void wave_step(ShW<real, G>& w, const Model<real>& M, const Src& src, int wave, Mid&& mid = Mid(), Pub&& published = Pub()) {
+  const Args<real>& A = launch_args(src);
   nm_stamp(-1);
   if constexpr (G == 2) {
-    env_load2<EP>(w, M, A, wave, mid);
+    env_load2<EP>(w, M, src, wave, mid);
   } else {
     mid();
 #pragma unroll
@@ -3835,7 +3898,7 @@ NM_FN void wave_step(ShW<real, G>& w, const Model<real>& M, const Args<real>& A,
     substep<EP>(w, M, s == A.nsub - 1, &dropped, NM_ABLATE(A.ablate));
   }
   if constexpr (G == 2) {
-    env_finish2(w, M, A, wave, dropped, published);
+    env_finish2(w, M, src, wave, dropped, published);
   } else {
 #pragma unroll
     for (int e = 0; e < G; e++) {

@@ -34,7 +34,9 @@ static int fail(const std::string& m) { g_err = m; return 1; }
 #endif
 // extras: like the reference, 'episode' and 'time_outs' are refreshed only by a step in which >= 1 env reset (env.py:344-371);
 // then the per-step accumulators are cleared for the next launch. One wave, after all others have published.
-template <class real> __device__ __noinline__ void step_tail(const nm::Args<real>& A, real ep_len_s) {
+// (`src` by value: one pointer in registers, nothing through the stack)
+template <class real, class Src> __device__ __noinline__ void step_tail(Src src, real ep_len_s) {
+  const nm::Args<real>& A = nm::launch_args(nm::scalar_src(src));
   const int lane = NM_TID;
   // This runs behind the launch's last wave, alone: every global access is a full round trip that nothing hides. So the reads are
   // issued in two batches - everything that is addressed by the lane alone, then the two lists those counts index - not one by one.
@@ -92,42 +94,65 @@ constexpr int kWG = 1;
 #endif
 // EP: level of per-env physics parameters (nm_core.h env_mu): 0 none, 1 friction / gain rows (nm::Args::envp), 2 those and body rows, 3 those
 // and actuation latency - the host launches a level above 0 only while its rows are set
+//
+// The launch arguments are read where they are used, by scalar loads from the kernel's own kernarg segment (nm::KernArgs): the wave's
+// first instructions are the loads of the base pointers and then the env rows' HBM reads, the epilogue fetches its pointers again from
+// the scalar cache, and nothing of them is live across the physics. (Until DESIGN.md 6.13 the kernel copied them into LDS first, like
+// the K-step kernels, which edit their copy between steps: ~150 issue slots, a barrier and two LDS round trips in front of the first
+// HBM request.) `A` is the second explicit argument, so it starts at byte 8 of the segment.
+struct NoArgsCopy {};
+template <class real> __device__ __forceinline__ nm::KernArgs<real, 8> step_src(NoArgsCopy&) { return {(nm::kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr()}; }
+template <class real> __device__ __forceinline__ const nm::Args<real>& step_src(nm::Args<real>& a) { return a; }
 template <class real, int G, int EP>
 __global__ void __launch_bounds__(64 * (sizeof(real) == 8 ? 1 : kWG), NM_WAVES_PER_SIMD) k_env_step(const nm::Model<real>* __restrict__ Mp, nm::Args<real> A) {
   constexpr int kWG = sizeof(real) == 8 ? 1 : ::kWG;     // the fp64 verification build keeps one wave per workgroup
+  static_assert(sizeof(Mp) == 8 && alignof(nm::Args<real>) == 8, "k_env_step: Args starts at byte 8 of the kernarg segment");
   __shared__ typename nm::ShWSel<real, G, EP>::type shs[kWG];
-  __shared__ nm::Model<real> Ms;   // this workgroup's copy of the model constants
-  __shared__ nm::Args<real> As;    // ... and of the launch arguments: ~30 pointers would otherwise pin 60 SGPRs for the whole kernel
+  __shared__ nm::ModelBlock<real> Mb;   // this workgroup's copy of the model constants
+  const nm::Model<real>& Ms = Mb.m;
+  // The fp64 verification build keeps the copy in LDS: read from the kernarg segment its kernels spill 14 more scalar registers (71 for 57).
+  constexpr bool kKern = sizeof(real) == 4;
+  __shared__ std::conditional_t<kKern, NoArgsCopy, nm::Args<real>> As;
+  decltype(auto) KA = step_src<real>(As);
   nm::ShW<real, G>& sh = nm::ShWSel<real, G, EP>::images(shs[kWG == 1 ? 0 : (int)(threadIdx.x >> 6)]);
-  int wave = nmr::wave_index(A.nxcd);      // XCD-aware block -> wave mapping (nm_env_loop.h)
-  if (kWG > 1) wave = wave * kWG + (int)(threadIdx.x >> 6);
+  if constexpr (kKern) nm::launch_args_touch(KA);
+  else { As = A; __syncthreads(); }
+  int wave;
+  unsigned long long t_start = 0ull;
+  {  // what the kernel's own first lines need, in one batch of scalar loads; nothing of it but `wave` and the debug clock lives on
+    const nm::Args<real>& A0 = nm::launch_args(KA);
+    const int N = A0.N, nxcd = A0.nxcd;
+    const bool dbg_on = A0.dbg != nullptr;
 #ifdef NM_MEASURE
-  if (A.ablate & 512) return;      // measurement only: the empty launch
+    if (A0.ablate & 512) return;      // measurement only: the empty launch
 #endif
-  const unsigned long long t_start = A.dbg ? __builtin_amdgcn_s_memtime() : 0ull;
-  if (kWG == 1 || threadIdx.x < 64) As = A;
-  __syncthreads();
-  if (wave * G >= A.N) return;     // (a wave that has left does not count for the barrier of the model copy below)
-  // the model copy (L2 -> LDS) runs inside the load stage, after the env rows' HBM reads have been issued: one start-up round trip, not two
+    wave = nmr::wave_index(nxcd);      // XCD-aware block -> wave mapping (nm_env_loop.h)
+    if (kWG > 1) wave = wave * kWG + (int)(threadIdx.x >> 6);
+    if (dbg_on) t_start = __builtin_amdgcn_s_memtime();
+    if (wave * G >= N) return;       // (a wave that has left does not count for the barrier of the model copy below; only -DNM_WG_WAVES has one)
+  }
+  // the model copy (L2 -> LDS) runs inside the load stage, after the env rows' HBM reads have been issued: one start-up round trip, not two.
+  // The block is padded to whole rounds of 64 lanes x 16 bytes on both sides (nm::ModelBlock), so every lane moves 16 bytes per round
+  // and no round tests a bound.
   auto copy_model = [&]() {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(Mp);
-    uint32_t* dst = reinterpret_cast<uint32_t*>(&Ms);
-    constexpr int kWords = (int)(sizeof(nm::Model<real>) / 4);
-    uint32_t tmp[(kWords + 63) / 64];
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    constexpr int kRounds = (int)(sizeof(nm::ModelBlock<real>) / (64 * 16));
+    const NM_GLOBAL(u4)* src = (const NM_GLOBAL(u4)*)Mp;
+    u4* dst = reinterpret_cast<u4*>(&Mb);
+    u4 tmp[kRounds];
 #pragma unroll
-    for (int k = 0; k < (kWords + 63) / 64; k++) { const int i = NM_TID + 64 * k; tmp[k] = i < kWords ? src[i] : 0u; }
+    for (int k = 0; k < kRounds; k++) tmp[k] = src[NM_TID + 64 * k];
     if (kWG == 1 || threadIdx.x < 64) {     // one wave fills the workgroup's copy
 #pragma unroll
-      for (int k = 0; k < (kWords + 63) / 64; k++) { const int i = NM_TID + 64 * k; if (i < kWords) dst[i] = tmp[k]; }
+      for (int k = 0; k < kRounds; k++) dst[NM_TID + 64 * k] = tmp[k];
     }
-    __syncthreads();
+    if (kWG == 1) nm::wave_sync(); else __syncthreads();
   };
   // Two-level ticket for "which wave closes the step": waves draw from their group's counter, the last wave of a group from the top
   // counter - at most 64 + 32 same-address atomics in a row instead of gridDim.x. A wave draws its group ticket as soon as everything
   // it contributes to the bookkeeping is published (inside the epilogue, before rewards and observation), so the round trip of that
   // atomic is off the critical path of the wave that finishes last.
-  const int nw = (As.N + G - 1) / G, grp = wave / nm::kTicketGroup, ngrp = (nw + nm::kTicketGroup - 1) / nm::kTicketGroup;
-  const int gsize = min(nm::kTicketGroup, nw - grp * nm::kTicketGroup);
+  const int grp = wave / nm::kTicketGroup;
   int ticket = 0, top = 0;
   int stage = 0;                       // 0: nothing drawn, 1: group ticket drawn, 2: group ticket resolved (and the top one drawn if this wave closes its group)
   bool closes_group = false;
@@ -135,37 +160,43 @@ __global__ void __launch_bounds__(64 * (sizeof(real) == 8 ? 1 : kWG), NM_WAVES_P
 #ifdef NM_NO_TICKETS   // measurement only (results without extras): what the end-of-step tickets cost
     stage = 2; (void)phase; return;
 #endif
+    const nm::Args<real>& Ad = nm::launch_args(KA);
+    int* wave_done = Ad.wave_done;
     if (phase == 0) {
-      if (NM_TID == 0) ticket = atomicAdd(As.wave_done + (grp + 1) * nm::kTicketStride, 1);
+      if (NM_TID == 0) ticket = atomicAdd(wave_done + (grp + 1) * nm::kTicketStride, 1);
       stage = 1;
     } else {
+      const int nw = (Ad.N + G - 1) / G, gsize = min(nm::kTicketGroup, nw - grp * nm::kTicketGroup);
       closes_group = __builtin_amdgcn_readfirstlane(ticket) == gsize - 1;
       if (closes_group && NM_TID == 0) {
-        As.wave_done[(grp + 1) * nm::kTicketStride] = 0;     // every member has drawn: re-arm for the next launch
-        top = atomicAdd(As.wave_done + nm::kTicketTop, 1);
+        wave_done[(grp + 1) * nm::kTicketStride] = 0;     // every member has drawn: re-arm for the next launch
+        top = atomicAdd(wave_done + nm::kTicketTop, 1);
       }
       stage = 2;
     }
   };
-  nm::wave_step<real, G, EP>(sh, Ms, As, wave, copy_model, draw);
-  if (As.dbg && NM_TID == 0) {   // debug buffer only: start / end clock of this wave as exact 24-bit pieces (scripts/wavetimes.py)
+  nm::wave_step<real, G, EP>(sh, Ms, KA, wave, copy_model, draw);
+  const nm::Args<real>& A1 = nm::launch_args(KA);
+  if (A1.dbg && NM_TID == 0) {   // debug buffer only: start / end clock of this wave as exact 24-bit pieces (scripts/wavetimes.py)
     const unsigned long long t_end = __builtin_amdgcn_s_memtime();
-    real* d = As.dbg + (size_t)(wave * G) * nm::kDbgN + 250;
+    real* d = A1.dbg + (size_t)(wave * G) * nm::kDbgN + 250;
     d[0] = (real)(unsigned)(t_start & 0xFFFFFF); d[1] = (real)(unsigned)((t_start >> 24) & 0xFFFFFF);
     d[2] = (real)(unsigned)(t_end & 0xFFFFFF); d[3] = (real)(unsigned)((t_end >> 24) & 0xFFFFFF);
     // where the wave ran: HW_ID (hwreg 4: wave[3:0] simd[5:4] pipe[7:6] cu[11:8] sh[12] se[15:13]) and XCC_ID (hwreg 20)
     d[4] = (real)(__builtin_amdgcn_s_getreg(4 | (0 << 6) | (15 << 11)) & 0xFFFF);
     d[5] = (real)(__builtin_amdgcn_s_getreg(20 | (0 << 6) | (3 << 11)) & 0xF);
   }
-  if (As.physics_only) return;
+  if (A1.physics_only) return;
   // The wave that finishes last closes the step (what used to be a second launch). What it needs from the others went through
   // device-scope atomics whose results each wave has already consumed (nm_consume), so the tickets need no fence.
   if (stage < 1) draw(0);              // paths that do not run the two-env epilogue draw here
   if (stage < 2) draw(1);
   if (!closes_group) return;
+  const int ngrp = ((A1.N + G - 1) / G + nm::kTicketGroup - 1) / nm::kTicketGroup;
   if (__builtin_amdgcn_readfirstlane(top) != ngrp - 1) return;
 #ifndef NM_SKIP_TAIL2
-  step_tail<real>(As, Ms.ep_len_s);
+  if constexpr (kKern) step_tail<real>(KA, Ms.ep_len_s);
+  else step_tail<real>(&As, Ms.ep_len_s);
 #endif
 }
 
@@ -431,7 +462,11 @@ template <class real> struct Env : nm_env {
         dalloc(&A.rngctr, n_) || dalloc(&A.hullcache, n_ * 8) || dalloc(&A.stat_sum, nm::kNREW) || dalloc(&A.stat_cnt, 4) || dalloc(&cmd_u_dev, n_ * 4) ||
         dalloc(&timeout_now, n_) || dalloc(&ids_dev, n_) || dalloc(&counters_dev, 4) || dalloc(&A.wave_done, ((n_ + nm::kTicketGroup - 1) / nm::kTicketGroup + 2) * nm::kTicketStride) || dalloc(&A.nto, 1) || dalloc(&A.to_list, n_) || dalloc(&A.nprev, 1) || dalloc(&A.to_prev, n_) || dalloc(&A.to_owner, 1))
       return 1;
-    if (dalloc(&M_dev, 1)) return 1;
+    {
+      nm::ModelBlock<real>* mb = nullptr;      // the struct and its padding (zeros) up to the step kernel's whole copy rounds
+      if (dalloc(&mb, 1)) return 1;
+      M_dev = &mb->m;
+    }
     HIPCHK(hipMemcpy(M_dev, &M, sizeof M, hipMemcpyHostToDevice));
     std::vector<real> q0(n_ * 25);
     for (size_t i = 0; i < n_; i++)

@@ -244,6 +244,22 @@ template <class T> NM_FN void gst1(T* p, size_t i, T v) { ((NM_GLOBAL(T)*)p)[i] 
 // p[i] += v by the hardware's non-returning float atomic (global_atomic_add_f32): nothing to wait for. The caller is the only writer
 // of that word during the launch, so the sum is the same as a load / add / store.
 NM_FN void gadd1(float* p, size_t i, float v) { __builtin_amdgcn_global_atomic_fadd_f32((NM_GLOBAL(float)*)p + i, v); }
+// The same accessors for a base pointer that sits in scalar registers (a launch argument read from the kernarg segment, nm_core.h
+// KernArgs): S = true forms the byte offset in 32 bits and adds it zero-extended, which is the `global_load v, v_off, s[base:base+1]`
+// form - no 64-bit address arithmetic per access. The element index is the same; every array here is far below 2^32 bytes and no
+// index is negative. S = false is the accessor above, instruction for instruction.
+template <class T> NM_FN const NM_GLOBAL(T)* gofs(const T* p, int i) {
+  return (const NM_GLOBAL(T)*)((const NM_GLOBAL(char)*)p + (uint32_t)i * (uint32_t)sizeof(T));
+}
+template <bool S, class T> NM_FN T gldx(const T* p, int i) { if constexpr (S) return *gofs(p, i); else return gldv(p, i); }
+template <bool S, class T> NM_FN void gstx(T* p, int i, T v, bool m) {
+  if constexpr (S) { if (m) *(NM_GLOBAL(T)*)gofs(p, i) = v; } else gstv(p, i, v, m);
+}
+template <bool S, class T> NM_FN T gld1x(const T* p, int i) { if constexpr (S) return *gofs(p, i); else return gld1(p, (size_t)i); }
+template <bool S, class T> NM_FN void gst1x(T* p, int i, T v) { if constexpr (S) *(NM_GLOBAL(T)*)gofs(p, i) = v; else gst1(p, (size_t)i, v); }
+template <bool S> NM_FN void gadd1x(float* p, int i, float v) {
+  if constexpr (S) __builtin_amdgcn_global_atomic_fadd_f32((NM_GLOBAL(float)*)gofs(p, i), v); else gadd1(p, (size_t)i, v);
+}
 NM_FN void gld3(const float* p, int i, float* o) { const nm_f4 t = *(const NM_GLOBAL(nm_f4)*)((const NM_GLOBAL(float)*)p + i); o[0] = t.x; o[1] = t.y; o[2] = t.z; }
 NM_FN void gld3(const double* p, int i, double* o) { const nm_d4 t = *(const NM_GLOBAL(nm_d4)*)((const NM_GLOBAL(double)*)p + i); o[0] = t.x; o[1] = t.y; o[2] = t.z; }
 NM_FN void gld4(const float* p, int i, float* o) { const nm_f4 t = *(const NM_GLOBAL(nm_f4)*)((const NM_GLOBAL(float)*)p + i); o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w; }
@@ -397,6 +413,10 @@ NM_FN void gadd1(float* p, size_t i, float v) { p[i] += v; }
 template <class T> NM_FN V<T> gldv(const T* p, const V<int>& i) { return ldsv(p, i); }
 template <class T> NM_FN void gstv(T* p, const V<int>& i, const V<T>& v, const VB& m) { stsv(p, i, v, m); }
 template <class T> NM_FN void gstv(T* p, const V<int>& i, T v, const VB& m) { stsv(p, i, v, m); }
+// (the device's scalar-base forms of these accessors: one address space here)
+template <bool S, class T> NM_FN V<T> gldx(const T* p, const V<int>& i) { return gldv(p, i); }
+template <bool S, class T> NM_FN void gstx(T* p, const V<int>& i, const V<T>& v, const VB& m) { gstv(p, i, v, m); }
+template <bool S, class T> NM_FN void gstx(T* p, const V<int>& i, T v, const VB& m) { gstv(p, i, v, m); }
 template <class T> NM_FN void gld4(const T* p, const V<int>& i, V<T>* o) { for (int k = 0; k < NM_WAVE; k++) for (int c = 0; c < 4; c++) o[c].v[k] = p[i.v[k] + c]; }
 template <class T> NM_FN V<int> to_int(const V<T>& a) { V<int> r; for (int i = 0; i < NM_WAVE; i++) r.v[i] = (int)a.v[i]; return r; }
 template <class T> NM_FN void gld3(const T* p, const V<int>& i, V<T>* o) { for (int k = 0; k < NM_WAVE; k++) for (int c = 0; c < 3; c++) o[c].v[k] = p[i.v[k] + c]; }
