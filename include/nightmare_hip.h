@@ -233,6 +233,35 @@ int nm_get_action_latency(nm_env* env, int32_t* out_dev, void* stream);
 int nm_draw_action_latency(nm_env* env, int32_t lo, int32_t hi, void* stream);
 int nm_set_action_history(nm_env* env, const float* hist_dev, void* stream);
 int nm_get_action_history(nm_env* env, float* out_dev, void* stream);
+/* Per-env gravity vectors: slopes and the `domain_rand.randomize_gravity` / `gravity_range` of legged_gym-shaped config trees. There is no
+ * reference line for the physics: upstream has one level floor under (0, 0, -9.81). For an infinite plane a floor inclined by theta is
+ * exactly a level floor under a gravity vector tilted by theta, written in the floor's frame: the env's x, y are then the floor's own
+ * axes and z its normal. One plane per env; there is no terrain mesh.
+ * Each env carries two 3-vectors in the env's dtype, one row of 8 words: g[3], pad, gravity_vec[3], pad.
+ *   g            the gravity the physics sees (m/s^2, frame of the floor). It replaces the model's gravity everywhere the physics uses it:
+ *                the base's bias acceleration (all three components), and the MuJoCo bad-state path, whose free-fall step from qpos0
+ *                becomes qvel[0:3] = g h, qpos[0:3] += g h^2, qacc_warmstart[0:3] = g. Nothing else of the model changes.
+ *   gravity_vec  the vector the env layer rotates into the body frame (envs/nightmare_v3_env.py:46, :219): observation slots 6..8, the
+ *                `orientation` reward and the 60 degree termination. A caller who wants an IMU's view sets it equal to g (on a slope the
+ *                policy then sees the tilt); a caller who keeps upstream's constant (0, 0, -9.81) has upstream's env layer line for line
+ *                while only the physics tilts.
+ * Rows hold until the caller changes them; no reset touches them. It works alike in nm_step, nm_step_physics, nm_rollout, nm_play and
+ * nm_step_tape, alone or with any other per-env kind (a physics-only launch still ignores latency). Off is the default, and off equals
+ * "on with (0, 0, -9.81) twice in every env" under == in every output (the additions are t + (-g): exact zeros change no rounding; a
+ * zero may differ from today's in sign only).
+ * nm_set_gravity: `rows` is a DEVICE array [N,8] in the env's dtype, copied on `stream`; NULL switches the feature off (nothing is
+ *   freed). Refused, named by nm_last_error, before anything of the env changes (the rows are read back and judged on the host, which
+ *   waits for `stream`): a non-finite word, a zero gravity_vec (the termination divides by its norm). A zero g is admitted: free float.
+ * nm_get_gravity: the rows into a DEVICE array [N,8] on `stream`; (0, 0, -9.81) twice for every env while the feature is off. A
+ *   checkpoint's content.
+ * nm_draw_gravity: out[e] = (offset x, y, z in m/s^2, tilt theta, azimuth phi in rad), value = lo[c] + u (hi[c] - lo[c]) in the env's
+ *   precision, product and sum rounded separately, u ~ U[0,1) from the counter RNG keyed by (seed + "GRAV", global env id, c): sharding
+ *   changes nothing; lo == hi pins a column. `out` is a DEVICE array [N,5]; the env itself is not changed (derive rows from the draw -
+ *   g = 9.81 (sin theta cos phi, sin theta sin phi, -cos theta) + offset, on the host in float64 - then nm_set_gravity). Refused before
+ *   any device call: non-finite bounds, lo > hi. */
+int nm_set_gravity(nm_env* env, const void* rows_dev, void* stream);
+int nm_get_gravity(nm_env* env, void* out_dev, void* stream);
+int nm_draw_gravity(nm_env* env, const double lo[5], const double hi[5], void* out_dev, void* stream);
 /* State log (envs/nightmare_v3_env.py:261-272 records data[0]): env_index >= 0 makes every nm_step keep that env's
  * post-physics, pre-reset qpos/qvel; -1 = off. nm_get_state_record copies the last record to HOST qpos[25], qvel[24] and
  * the number of MuJoCo bad-state resets inside that step (data.time restarts there). Synchronous. */

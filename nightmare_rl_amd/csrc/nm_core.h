@@ -165,6 +165,14 @@ template <class real> NM_FN int* lat_delay(const Args<real>& A) {
   return reinterpret_cast<int*>(const_cast<real*>(A.envp) + (size_t)A.N * (kEnvP + kBodyP));
 }
 template <class real> NM_FN float* lat_hist(const Args<real>& A) { return reinterpret_cast<float*>(lat_delay(A) + A.N); }
+// Per-env gravity (nm_set_gravity, level EP = 4 of the step): one row of kGravP words per env in the env's dtype - g[3] (what the physics
+// sees, m/s^2, frame of the floor), pad, gravity_vec[3] (what the env layer rotates into the body frame), pad. The rows are appended to
+// the envp allocation behind the action histories, at the next multiple of sizeof(real): nothing in front of them moves.
+constexpr int kGravP = 8, GP_G = 0, GP_VEC = 4;
+constexpr uint64_t kGravityKey = 0x47524156ull;   // nm_draw_gravity: rand_u24_bits(seed + kGravityKey, global env id, column)
+template <class real> NM_FN const real* grav_rows_of(const Args<real>& A) {
+  return A.envp + ((size_t)A.N * (kEnvP + kBodyP) + ((size_t)A.N * kLatP * 4 + sizeof(real) - 1) / sizeof(real));
+}
 constexpr int kDbgN = 256;
 
 // Where a stage reads the launch arguments from: the stages that touch them (env_load*, env_finish*, wave_step) take the source as a
@@ -294,6 +302,16 @@ template <class real, int G> struct ShWSel<real, G, 3> {
   typedef ShWL<real, G> type;
   static NM_FN ShW<real, G>& images(type& s) { return s.b.w; }
 };
+// Level 4 (level 3 plus per-env gravity) keeps the G gravity rows of the wave's envs behind level 3's block.
+template <class real, int G> struct ShWG {
+  ShWL<real, G> l;
+  real grav[G * kGravP];
+};
+template <class real, int G> NM_FN real* grav_rows(ShW<real, G>& w) { return reinterpret_cast<ShWG<real, G>*>(&w)->grav; }
+template <class real, int G> struct ShWSel<real, G, 4> {
+  typedef ShWG<real, G> type;
+  static NM_FN ShW<real, G>& images(type& s) { return s.l.b.w; }
+};
 #define NM_OFS(field) ((int)(offsetof(Sh<real>, field) / sizeof(real)))
 #define NM_IOFS(field) ((int)(offsetof(Sh<real>, field) / sizeof(int)))
 
@@ -302,7 +320,9 @@ template <class real, int G> struct ShWSel<real, G, 3> {
 // when friction / gain rows are set, reads them from the env image; 2, launched while body rows are set, does that and takes the base
 // body's constants, total_mass, the colliding bodies' invweight0 and pgs_scale from the env's body row (the host supplies default envp
 // rows when only a payload is set); 3, launched while actuation delays are set, is level 2 plus the delayed servo command (env_load*,
-// latency_switch; the host supplies default rows of both kinds where the caller set none).
+// latency_switch; the host supplies default rows of both kinds where the caller set none); 4, launched while gravity rows are set, is
+// level 3 plus the env's own gravity in the base's bias acceleration, in the bad-state free-fall step and in the epilogue's projected
+// gravity (the host supplies defaults for every kind that is off: zero delays, so a level-4 launch without latency commands as level 2).
 template <int EP, class real> NM_FN real env_mu(const Sh<real>& sh, const Model<real>& M) {
   if constexpr (EP != 0) return sh.envp[EP_MU]; else return M.mu;
 }
@@ -318,6 +338,11 @@ template <class real> struct BodyRef<2, real> {
   NM_FN explicit BodyRef(const real* q) : p(q) {}
 };
 template <class real> struct BodyRef<3, real> {
+  const real* p;
+  NM_FN BodyRef() : p(nullptr) {}
+  NM_FN explicit BodyRef(const real* q) : p(q) {}
+};
+template <class real> struct BodyRef<4, real> {
   const real* p;
   NM_FN BodyRef() : p(nullptr) {}
   NM_FN explicit BodyRef(const real* q) : p(q) {}
@@ -571,7 +596,13 @@ template <int EP, class real, int G> NM_FN void stage_smooth(ShW<real, G>& w, co
     vr t[3];
     cross3(t, vb + 3, vb);
     ab[0] = ab[1] = ab[2] = vr(real(0));
+    if constexpr (EP >= 4) {   // the env's own gravity, all three components: t + (-g), so that (0, 0, -M.grav) gives today's bits
+      typedef ShWG<real, G> WG;
+      const V<int> go = (grp & (G - 1)) * kGravP + (int)(offsetof(WG, grav) / sizeof(real));
+      ab[3] = t[0] + (-ldsv(lds, go + GP_G)); ab[4] = t[1] + (-ldsv(lds, go + (GP_G + 1))); ab[5] = t[2] + (-ldsv(lds, go + (GP_G + 2)));
+    } else {
     ab[3] = t[0]; ab[4] = t[1]; ab[5] = t[2] + M.grav;
+    }
   }
 #pragma unroll
   for (int j = 0; j < 9; j++) { STG(colR, j, Rb[j]); STG(Rb, j, Rb[j]); }
@@ -2791,7 +2822,7 @@ template <class real, int EP> NM_FN void stage_constraint(Sh<real>& sh, real* jr
 // qacc (for the warm start), implicitfast velocity update, position integration - all G envs of the wave at once
 // (lane groups as in stage A). An env whose qacc is bad (mj_checkAcc) is reset and advanced by the closed form of
 // "mj_resetData; mj_forward; integrate": free fall from qpos0 with zero ctrl.
-template <class real, int G> NM_FN void stage_integrate(ShW<real, G>& w, const Model<real>& M) {
+template <class real, int G, int EP = 0> NM_FN void stage_integrate(ShW<real, G>& w, const Model<real>& M) {
   typedef V<real> vr;
   real* lds = reinterpret_cast<real*>(&w.e[0]);
   // lane groups as in stage A: group g works on env g % G; groups [0, G) solve with the factor of M (qacc, for the warm start and
@@ -2910,11 +2941,20 @@ template <class real, int G> NM_FN void stage_integrate(ShW<real, G>& w, const M
       const V<int> lane = opaque_lane();   // cold path: keep its address math out of the hot loop's live ranges
       sh.nwarn += 1;
       vr q0 = ldsv(M.qpos0, sel(lane < kNQ, lane, V<int>(0)));
+      if constexpr (EP >= 4) {   // the free-fall step under the env's own gravity: qvel[0:3] = g h, qpos[0:3] += g h h, qacc_warmstart[0:3] = g
+        const vr gl = ldsv(grav_rows(w), sel(lane < 3, lane, V<int>(0)) + (e * kGravP + GP_G));
+        const vr vl = gl * M.h;
+        q0 = sel(lane < 3, q0 + vl * M.h, q0);
+        stsv(sh.qpos, lane, q0, lane < kNQ);
+        stsv(sh.qvel, lane, sel(lane < 3, vl, vr(real(0))), lane < kNV);
+        stsv(sh.warm, lane, sel(lane < 3, gl, vr(real(0))), lane < kNV);
+      } else {
       real vz = -M.grav * M.h;
       q0 = sel(lane == 2, q0 + vz * M.h, q0);
       stsv(sh.qpos, lane, q0, lane < kNQ);
       stsv(sh.qvel, lane, sel(lane == 2, vr(vz), vr(real(0))), lane < kNV);
       stsv(sh.warm, lane, sel(lane == 2, vr(-M.grav), vr(real(0))), lane < kNV);
+      }
       stsv(sh.ctrl, lane, real(0), lane < kNU);
       wave_sync();
     }
@@ -3017,6 +3057,8 @@ template <int EP, class real, int G> NM_FN void substep(ShW<real, G>& w, const M
       stage_constraint<real, EP>(w.e[e], w.jrow, M, last, (ablate & 2) != 0, br);
       nm_stamp(8);
     }
+  if constexpr (EP >= 4) stage_integrate<real, G, EP>(w, M);
+  else
   stage_integrate(w, M);
   nm_stamp(9);
 }
@@ -3025,7 +3067,7 @@ template <int EP, class real, int G> NM_FN void substep(ShW<real, G>& w, const M
 
 // load one env's state into its LDS image, action -> servo command (E1)
 template <int EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real>& M, const Args<real>& A, int env, real* bp = nullptr,
-                                                real* late = nullptr, int* rsw = nullptr, bool live = true) {
+                                                real* late = nullptr, int* rsw = nullptr, bool live = true, real* gp = nullptr) {
   typedef V<real> vr;
   const V<int> lane = opaque_lane();   // index math stays local to this function (not kept live across the physics)
   const VB l18 = lane < kNU;
@@ -3041,13 +3083,15 @@ template <int EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real
   if constexpr (EP != 0) envp_in = gldv(A.envp, sel(lane < kEnvP, lane, V<int>(0)) + env * kEnvP);     // the env's (mu, p_gain, kv, pad) row: 16 bytes, lanes 0..3
   vr body_in = vr(real(0));
   if constexpr (EP >= 2) body_in = gldv(A.envp, sel(lane < kBodyP, lane, V<int>(0)) + (A.N * kEnvP + env * kBodyP));   // the env's body row, behind the N envp rows
+  vr grav_in = vr(real(0));
+  if constexpr (EP >= 4) grav_in = gldv(grav_rows_of(A), sel(lane < kGravP, lane, V<int>(0)) + env * kGravP);   // the env's gravity row, behind the histories
   vr cmd_in = vr(real(0)), eps_in = vr(real(0)), prev_act = vr(real(0)), prev_dofvel = vr(real(0)), dofpos_old = vr(real(0));
   int64_t ep = 0;
   uint32_t ctr_in = 0;
   // level 3: the env's delay and its whole action history (three rows, lane = joint) with the step's other reads: no read waits for the delay
   int dl = 0;
   V<float> h0 = V<float>(0.0f), h1 = V<float>(0.0f), h2 = V<float>(0.0f);
-  if constexpr (EP == 3)
+  if constexpr (EP >= 3)
     if (!A.physics_only) {
       dl = gld1(lat_delay(A), env);
       h0 = gldv(lat_hist(A), l18c + env * (kLatH * kNU));
@@ -3075,6 +3119,7 @@ template <int EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real
   if constexpr (EP != 0) {
     stsv(sh.envp, lane, envp_in, lane < kEnvPS);
     if constexpr (EP >= 2) stsv(bp, lane, body_in, lane < kBodyP);
+    if constexpr (EP >= 4) stsv(gp, lane, grav_in, lane < kGravP);
     p_gain = rdlane(envp_in, EP_PGAIN);
   }
   // ---- E1 (env.py:152-156,181-192): float32 scale + clip; PD -> velocity command from the env's own dof_pos buffer
@@ -3097,7 +3142,7 @@ template <int EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real
     sh.eplen_lo = (int)(uint32_t)(ep & 0xffffffffll);
     sh.eplen_hi = (int)(ep >> 32);
     sh.ectr = ctr_in;
-    if constexpr (EP == 3) {
+    if constexpr (EP >= 3) {
       // delay d = k nsub + r: substeps s < r aim at a_{t-k-1}, substeps s >= r at a_{t-k} (a_t itself where k = 0). Each command comes
       // from its own action by today's expression, so it has the bits an undelayed env would give that action.
       const int nsub = A.nsub;
@@ -3118,7 +3163,7 @@ template <int EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real
   } else {  // dynamics-only mode (BASELINE config 2): same PD law on the current joint angles, no env buffers
     wave_sync();
     stsv(sh.ctrl, lane, ((act - defp) - ldsv(sh.qpos, l18c + 7)) * p_gain, l18);
-    if constexpr (EP == 3) *rsw = 0;     // a physics-only launch ignores latency
+    if constexpr (EP >= 3) *rsw = 0;     // a physics-only launch ignores latency
   }
   // carried to the epilogue through LDS, not in registers: nothing stays live across the physics
   stsv(sh.eact, lane, act, l18); stsv(sh.epact, lane, prev_act, l18); stsv(sh.epdv, lane, prev_dofvel, l18);
@@ -3158,8 +3203,8 @@ template <class real> NM_FN void env_debug(Sh<real>& sh, const Args<real>& A, in
 }
 
 // store one env's state, run the env epilogue (E3-E8). `live` = the slot holds a real env (last wave may be padded)
-template <class real> NM_FN void env_finish(Sh<real>& sh, const Model<real>& M, const Args<real>& A, int env,
-                                            int dropped, bool live) {
+template <int EP = 0, class real> NM_FN void env_finish(Sh<real>& sh, const Model<real>& M, const Args<real>& A, int env,
+                                            int dropped, bool live, const real* gp = nullptr) {
   typedef V<real> vr;
   if (!live) return;
   const V<int> lane = opaque_lane();
@@ -3209,6 +3254,7 @@ template <class real> NM_FN void env_finish(Sh<real>& sh, const Model<real>& M, 
   real blv[3], bav[3], pg[3];
   {
     real lin[3] = {sh.cvb[3], sh.cvb[4], sh.cvb[5]}, ang[3] = {sh.cvb[0], sh.cvb[1], sh.cvb[2]}, gv[3] = {real(0), real(0), -M.grav};
+    if constexpr (EP >= 4) { gv[0] = gp[GP_VEC]; gv[1] = gp[GP_VEC + 1]; gv[2] = gp[GP_VEC + 2]; }   // the env's own gravity_vec
     rot(blv, lin); rot(bav, ang); rot(pg, gv);
   }
   vr dofpos = ldsv(sh.qpos, l18c + 7), dofvel = ldsv(sh.qvel, l18c + 6);
@@ -3444,11 +3490,13 @@ template <int EP, class real, class Src, class Mid> NM_FN void env_load2(ShW<rea
   if constexpr (EP != 0) envp_in = gldx<kS>(A.envp, sel(hl < kEnvP, hl, V<int>(0)) + env * kEnvP);     // each env's (mu, p_gain, kv, pad) row: 16 bytes, lanes 0..3 of its half
   vr body_in = vr(real(0));
   if constexpr (EP >= 2) body_in = gldx<kS>(A.envp, sel(hl < kBodyP, hl, V<int>(0)) + (env * kBodyP + A.N * kEnvP));   // each env's body row (behind the N envp rows), lanes 0..19 of its half
+  vr grav_in = vr(real(0));
+  if constexpr (EP >= 4) grav_in = gldx<kS>(grav_rows_of(A), sel(hl < kGravP, hl, V<int>(0)) + env * kGravP);   // each env's gravity row (behind the histories), lanes 0..7 of its half
   vr cmd_in = vr(real(0)), eps_in = vr(real(0)), prev_act = vr(real(0)), prev_dofvel = vr(real(0)), dofpos_old = vr(real(0));
   // level 3: each env's delay and its whole action history (three rows, lane of the half = joint) with the step's other reads
   V<int> dl = V<int>(0);
   V<float> h0 = V<float>(0.0f), h1 = V<float>(0.0f), h2 = V<float>(0.0f);
-  if constexpr (EP == 3)
+  if constexpr (EP >= 3)
     if (!A.physics_only) {
       dl = gldx<kS>(lat_delay(A), env);
       h0 = gldx<kS>(lat_hist(A), l18c + env * (kLatH * kNU));
@@ -3487,6 +3535,7 @@ template <int EP, class real, class Src, class Mid> NM_FN void env_load2(ShW<rea
   if constexpr (EP != 0) {
     stsv(rb, ho + (hl + NM_OFS(envp)), envp_in, hl < kEnvPS);
     if constexpr (EP >= 2) stsv(body_rows(w), h * kBodyP + hl, body_in, hl < kBodyP);
+    if constexpr (EP >= 4) stsv(grav_rows(w), h * kGravP + hl, grav_in, hl < kGravP);
     p_gain = sel(h != 0, vr(rdlane(envp_in, 32 + EP_PGAIN)), vr(rdlane(envp_in, EP_PGAIN)));
   }
   // ---- E1 (env.py:152-156,181-192): float32 scale + clip; PD -> velocity command from the env's own dof_pos buffer
@@ -3519,7 +3568,7 @@ template <int EP, class real, class Src, class Mid> NM_FN void env_load2(ShW<rea
     stsv(ib, hoi + NM_IOFS(eplen_hi), (int)(ep >> 32), hl == 0);
     stsv(ib, hoi + NM_IOFS(ectr), (int)ctr_in, hl == 0);
 #endif
-    if constexpr (EP == 3) {
+    if constexpr (EP >= 3) {
       // delay d = k nsub + r, per half: substeps s < r aim at a_{t-k-1}, substeps s >= r at a_{t-k} (a_t itself where k = 0). Each
       // command comes from its own action by today's expression, so it has the bits an undelayed env would give that action.
       const V<int> ns = V<int>(A.nsub), one = V<int>(1), zero = V<int>(0);
@@ -3542,7 +3591,7 @@ template <int EP, class real, class Src, class Mid> NM_FN void env_load2(ShW<rea
   } else {
     wave_sync();
     stsv(rb, ho + (hl + NM_OFS(ctrl)), ((act - defp) - ldsv(rb, ho + (l18c + (7 + NM_OFS(qpos))))) * p_gain, l18);
-    if constexpr (EP == 3) stsv(lat_rows(w).rsw, h, V<int>(0), hl == V<int>(0));     // a physics-only launch ignores latency
+    if constexpr (EP >= 3) stsv(lat_rows(w).rsw, h, V<int>(0), hl == V<int>(0));     // a physics-only launch ignores latency
   }
   stsv(rb, ho + (hl + NM_OFS(eact)), act, l18); stsv(rb, ho + (hl + NM_OFS(epact)), prev_act, l18); stsv(rb, ho + (hl + NM_OFS(epdv)), prev_dofvel, l18);
   wave_sync();
@@ -3552,7 +3601,7 @@ template <int EP, class real, class Src, class Mid> NM_FN void env_load2(ShW<rea
 // the counters) is out: the kernel takes the wave's end-of-step ticket there, so the ticket's round trip is hidden under E7 / E8.
 // `published(1)` comes again after E7, a microsecond later: the group ticket is back by then, and the wave that turns out to be the last of
 // its group draws the top-level ticket there - under E8 and the buffer stores.
-template <class real, class Src, class Pub> NM_FN void env_finish2(ShW<real, 2>& w, const Model<real>& M, const Src& src, int wave, int dropped, Pub&& published) {
+template <int EP = 0, class real, class Src, class Pub> NM_FN void env_finish2(ShW<real, 2>& w, const Model<real>& M, const Src& src, int wave, int dropped, Pub&& published) {
   typedef V<real> vr;
   const Args<real>& A = launch_args(src);
   constexpr bool kS = ArgSrc<Src>::kScalarBase;
@@ -3630,6 +3679,11 @@ template <class real, class Src, class Pub> NM_FN void env_finish2(ShW<real, 2>&
   {
     vr lin[3] = {SHR(cvb, V<int>(3)), SHR(cvb, V<int>(4)), SHR(cvb, V<int>(5))}, ang[3] = {SHR(cvb, V<int>(0)), SHR(cvb, V<int>(1)), SHR(cvb, V<int>(2))};
     vr gv[3] = {vr(real(0)), vr(real(0)), vr(-M.grav)};
+    if constexpr (EP >= 4) {   // each half's env's own gravity_vec
+      const real* gr = grav_rows(w);
+      const V<int> go = h * kGravP + GP_VEC;
+      gv[0] = ldsv(gr, go); gv[1] = ldsv(gr, go + 1); gv[2] = ldsv(gr, go + 2);
+    }
     rot(blv, lin); rot(bav, ang); rot(pg, gv);
   }
   vr dofpos = SHR(qpos, l18c + 7), dofvel = SHR(qvel, l18c + 6);
@@ -3884,7 +3938,9 @@ NM_FN void wave_step(ShW<real, G>& w, const Model<real>& M, const Src& src, int 
       int env = wave * G + e;
       real* bp = nullptr;
       if constexpr (EP >= 2) bp = body_rows(w) + e * kBodyP;
-      if constexpr (EP == 3) env_load<EP>(w.e[e], M, A, env < A.N ? env : A.N - 1, bp, lat_rows(w).late + e * kNU, lat_rows(w).rsw + e, env < A.N);
+      if constexpr (EP >= 4) env_load<EP>(w.e[e], M, A, env < A.N ? env : A.N - 1, bp, lat_rows(w).late + e * kNU, lat_rows(w).rsw + e, env < A.N, grav_rows(w) + e * kGravP);
+      else
+      if constexpr (EP >= 3) env_load<EP>(w.e[e], M, A, env < A.N ? env : A.N - 1, bp, lat_rows(w).late + e * kNU, lat_rows(w).rsw + e, env < A.N);
       else
       env_load<EP>(w.e[e], M, A, env < A.N ? env : A.N - 1, bp);
     }
@@ -3894,15 +3950,19 @@ NM_FN void wave_step(ShW<real, G>& w, const Model<real>& M, const Src& src, int 
   if (NM_ABLATE(A.ablate) & 1024) return;   // measurement only: load stage alone
   if (!(NM_ABLATE(A.ablate) & 2048))
   for (int s = 0; s < A.nsub; s++) {
-    if constexpr (EP == 3) { if (s > 0) latency_switch(w, s); }
+    if constexpr (EP >= 3) { if (s > 0) latency_switch(w, s); }
     substep<EP>(w, M, s == A.nsub - 1, &dropped, NM_ABLATE(A.ablate));
   }
   if constexpr (G == 2) {
+    if constexpr (EP >= 4) env_finish2<EP>(w, M, src, wave, dropped, published);
+    else
     env_finish2(w, M, src, wave, dropped, published);
   } else {
 #pragma unroll
     for (int e = 0; e < G; e++) {
       int env = wave * G + e;
+      if constexpr (EP >= 4) env_finish<EP>(w.e[e], M, A, env, e == 0 ? dropped : 0, env < A.N, grav_rows(w) + e * kGravP);
+      else
       env_finish(w.e[e], M, A, env, e == 0 ? dropped : 0, env < A.N);
     }
   }

@@ -1,9 +1,9 @@
 // nm_env_rows.h - host side, plain C++17, no HIP header: the one owner of what the host decides about the per-env rows behind
-// nm::Args::envp (friction / gains, body rows, actuation latency) - layout, default rows, admission, which kinds are on and which level of
+// nm::Args::envp (friction / gains, body rows, actuation latency, gravity) - layout, default rows, admission, which kinds are on and which level of
 // the step a launch takes. Used by the env object (nm_hip.hip), the K-step launchers and the host emulation (tests/emul, -DNM_EMUL).
 //
 // The invariant every owner of a block keeps: ONCE THE BLOCK IS ALLOCATED, EVERY REGION WHOSE KIND IS OFF HOLDS THAT KIND'S DEFAULTS -
-// default friction / gain rows, default body rows, zero delays - so a transition writes or refills its own region and looks at no other
+// default friction / gain rows, default body rows, zero delays, default gravity rows - so a transition writes or refills its own region and looks at no other
 // kind's flag. The action history is exempt: it is state, not a parameter, and keeps what it holds.
 #pragma once
 #include <cmath>
@@ -16,16 +16,18 @@
 namespace nmrows {
 
 // ---- layout: one block of `real`s - N friction / gain rows, N body rows, then the latency words (4 bytes each in either dtype): N
-// delays, N action histories. The device finds the last two through nm::lat_delay / nm::lat_hist (nm_core.h), which tests/emul checks
-// against these.
-template <class real> constexpr size_t block_reals(size_t N) {
+// delays, N action histories; then, at the next multiple of sizeof(real), N gravity rows. The device finds the last three through
+// nm::lat_delay / nm::lat_hist / nm::grav_rows_of (nm_core.h), which tests/emul checks against these.
+template <class real> constexpr size_t grav_offset(size_t N) {
   return N * (nm::kEnvP + nm::kBodyP) + (N * nm::kLatP * 4 + sizeof(real) - 1) / sizeof(real);
 }
+template <class real> constexpr size_t block_reals(size_t N) { return grav_offset<real>(N) + N * nm::kGravP; }
 template <class real> inline real* fric_rows(real* base, int) { return base; }
 template <class real> inline real* body_rows(real* base, int N) { return base + (size_t)N * nm::kEnvP; }
 template <class real> inline int* delays(real* base, int N) { return reinterpret_cast<int*>(base + (size_t)N * (nm::kEnvP + nm::kBodyP)); }
 template <class real> inline float* histories(real* base, int N) { return reinterpret_cast<float*>(delays(base, N) + N); }
 constexpr size_t hist_words(size_t N) { return N * nm::kLatH * nm::kNU; }
+template <class real> inline real* grav_rows(real* base, int N) { return base + grav_offset<real>((size_t)N); }
 
 // ---- default rows: the model's own values (the fourth word of a friction / gain row is padding, zero)
 template <class real> inline void fric_default(const nm::Model<real>& M, real out[3]) {
@@ -37,6 +39,12 @@ template <class real> inline void body_default(const nm::Model<real>& M, real ou
   out[nm::BP_TOTAL] = M.total_mass;
   for (int g = 0; g < nm::kNCOL; g++) out[nm::BP_INVW + g] = M.colc[g * nm::kColN + 4];
   out[nm::BP_PGS] = M.pgs_scale;
+}
+
+// g and gravity_vec both the model's (0, 0, -gravity); the pads zero
+template <class real> inline void grav_default(const nm::Model<real>& M, real out[nm::kGravP]) {
+  for (int j = 0; j < nm::kGravP; j++) out[j] = real(0);
+  out[nm::GP_G + 2] = -M.grav; out[nm::GP_VEC + 2] = -M.grav;
 }
 
 // ---- admission: pure functions of the caller's rows; empty = admitted, otherwise what the entry point reports behind its own name
@@ -54,6 +62,17 @@ template <class real> inline std::string body_rows_fault(const real* rows, int N
   }
   return std::string();
 }
+// a zero g is admitted (free float); a zero gravity_vec is not: the termination divides by its norm
+template <class real> inline std::string grav_rows_fault(const real* rows, int N) {
+  for (int e = 0; e < N; e++) {
+    const real* r = rows + (size_t)e * nm::kGravP;
+    const char* why = nullptr;
+    for (int j = 0; j < nm::kGravP; j++) if (!std::isfinite((double)r[j])) why = "a non-finite value";
+    if (!why && r[nm::GP_VEC] == real(0) && r[nm::GP_VEC + 1] == real(0) && r[nm::GP_VEC + 2] == real(0)) why = "a zero gravity_vec";
+    if (why) return "row " + std::to_string(e) + ": " + why;
+  }
+  return std::string();
+}
 inline int delay_max(int nsub) { return nm::kLatH * nsub; }     // the history holds kLatH steps of nsub substeps
 inline std::string delays_fault(const int* d, int N, int nsub) {
   for (int e = 0; e < N; e++)
@@ -63,11 +82,14 @@ inline std::string delays_fault(const int* d, int N, int nsub) {
 }
 
 // ---- state: which kinds are on, and what follows from that for a launch
-enum Kind { kFric = 0, kBody = 1, kLat = 2 };
+enum Kind { kFric = 0, kBody = 1, kLat = 2, kGrav = 3 };
 struct State {
-  bool on[3] = {false, false, false};
-  // the level of the step a launch takes: the highest kind that is on; a physics-only launch ignores latency (level 2 on the rows level 3 reads)
-  int level(bool physics_only = false) const { return on[kLat] ? (physics_only ? 2 : 3) : (on[kBody] ? 2 : (on[kFric] ? 1 : 0)); }
+  bool on[4] = {false, false, false, false};
+  // the level of the step a launch takes: the highest kind that is on; a physics-only launch ignores latency (level 2 on the rows level 3
+  // reads; at level 4, which physics-only launches take too, the kernel skips it at run time: nm::Args::physics_only)
+  int level(bool physics_only = false) const {
+    return on[kGrav] ? 4 : (on[kLat] ? (physics_only ? 2 : 3) : (on[kBody] ? 2 : (on[kFric] ? 1 : 0)));
+  }
   // nm::Args::envp of a launch: the block while any kind is on, null (level 0 never looks) otherwise
   template <class real> real* envp(real* base) const { return level() ? base : nullptr; }
 };
@@ -75,6 +97,7 @@ struct State {
 // f(std::integral_constant<int, L>{}) for the level: the one place a run-time level becomes a template argument
 template <class F> inline auto with_level(int level, F&& f) {
   switch (level) {
+    case 4: return f(std::integral_constant<int, 4>{});
     case 3: return f(std::integral_constant<int, 3>{});
     case 2: return f(std::integral_constant<int, 2>{});
     case 1: return f(std::integral_constant<int, 1>{});

@@ -93,7 +93,7 @@ constexpr int kWG = NM_WG_WAVES;
 constexpr int kWG = 1;
 #endif
 // EP: level of per-env physics parameters (nm_core.h env_mu): 0 none, 1 friction / gain rows (nm::Args::envp), 2 those and body rows, 3 those
-// and actuation latency - the host launches a level above 0 only while its rows are set
+// and actuation latency, 4 those and gravity rows - the host launches a level above 0 only while its rows are set
 //
 // The launch arguments are read where they are used, by scalar loads from the kernel's own kernarg segment (nm::KernArgs): the wave's
 // first instructions are the loads of the base pointers and then the env rows' HBM reads, the epilogue fetches its pointers again from
@@ -316,6 +316,25 @@ __global__ void k_payload_draw(real* __restrict__ out, int N, uint64_t seed, int
   out[i] = envp_lerp(lo.v[col], u, hi.v[col] - lo.v[col]);
 }
 
+// Per-env gravity rows (nm::kGravP words per env). `fill`: the default row for every env (what nm_get_gravity reports while the feature
+// is off). `draw`: (three offsets, tilt, azimuth) per env by k_envp_draw's generator under its own key, lo + u (hi - lo) through envp_lerp.
+template <class real> struct GravRow { real v[nm::kGravP]; };
+template <class real> struct Grav5 { real v[5]; };
+template <class real>
+__global__ void k_grav_fill(real* __restrict__ rows, int N, GravRow<real> dflt) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nm::kGravP * N) return;
+  rows[i] = dflt.v[i % nm::kGravP];
+}
+template <class real>
+__global__ void k_gravity_draw(real* __restrict__ out, int N, uint64_t seed, int64_t env_offset, Grav5<real> lo, Grav5<real> hi) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= 5 * N) return;
+  const int env = i / 5, col = i - 5 * env;
+  const real u = (real)nm::rand_u24_bits(seed + nm::kGravityKey, (uint64_t)(env_offset + env), (uint32_t)col) * real(1.0 / 16777216.0);
+  out[i] = envp_lerp(lo.v[col], u, hi.v[col] - lo.v[col]);
+}
+
 // Per-env actuation latency (nm_core.h kLatP): delay[e] = lo + floor(u (hi - lo + 1)), u = bits * 2^-24 with bits =
 // rand_u24_bits(seed + kLatencyKey, global env id, 0): in integers, lo + ((bits * (hi - lo + 1)) >> 24) - exact, the same in either dtype.
 __global__ void k_latency_draw(int* __restrict__ delay, int N, uint64_t seed, int64_t env_offset, int lo, int hi) {
@@ -367,6 +386,9 @@ struct nm_env {
   virtual int draw_action_latency(int lo, int hi, hipStream_t s) = 0;
   virtual int set_action_history(const float* h, hipStream_t s) = 0;
   virtual int get_action_history(float* out, hipStream_t s) = 0;
+  virtual int set_gravity(const void* rows, hipStream_t s) = 0;
+  virtual int get_gravity(void* out, hipStream_t s) = 0;
+  virtual int draw_gravity(const double* lo, const double* hi, void* out, hipStream_t s) = 0;
   // push perturbations (nm_push.h): the setting and the push step index - full env steps taken, K per K-step launch; physics-only
   // launches and nm_reset leave it alone
   int push_interval = 0;
@@ -934,11 +956,17 @@ template <class real> struct Env : nm_env {
     HIPCHK(hipGetLastError());
     return 0;
   }
+  GravRow<real> grav_default() const { GravRow<real> r; nmrows::grav_default(M, r.v); return r; }
+  int grav_fill_default(real* dst, hipStream_t s) {
+    hipLaunchKernelGGL(k_grav_fill<real>, dim3((nm::kGravP * N + 255) / 256), dim3(256), 0, s, dst, N, grav_default());
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
   // at first use, from the slab (zeroed: the delays and the history start at zero); the fills are ordered on the first caller's stream
   int rows_alloc(hipStream_t s) {
     if (envp_dev) return 0;
     if (dalloc(&envp_dev, nmrows::block_reals<real>((size_t)N))) return 1;
-    return envp_write({}, s) || body_fill_default(nmrows::body_rows(envp_dev, N), s);
+    return envp_write({}, s) || body_fill_default(nmrows::body_rows(envp_dev, N), s) || grav_fill_default(nmrows::grav_rows(envp_dev, N), s);
   }
   int rows_turn(nmrows::Kind k, bool on) {
     rows.on[k] = on;
@@ -1047,6 +1075,38 @@ template <class real> struct Env : nm_env {
   }
   int get_action_history(float* out, hipStream_t s) override {
     return words_out(out, envp_dev ? nmrows::histories(envp_dev, N) : nullptr, nmrows::hist_words((size_t)N), s);
+  }
+  // ---- per-env gravity rows
+  int set_gravity(const void* rows_in, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (!rows_in) {       // off; nothing is freed
+      if (envp_dev && grav_fill_default(nmrows::grav_rows(envp_dev, N), s)) return 1;
+      return rows_turn(nmrows::kGrav, false);
+    }
+    // the rows are judged on the host before anything of the env changes
+    std::vector<real> h((size_t)N * nm::kGravP);
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpy(h.data(), rows_in, h.size() * sizeof(real), hipMemcpyDeviceToHost));
+    const std::string why = nmrows::grav_rows_fault(h.data(), N);
+    if (!why.empty()) return fail("nm_set_gravity: " + why);
+    if (rows_alloc(s)) return 1;
+    HIPCHK(hipMemcpyAsync(nmrows::grav_rows(envp_dev, N), rows_in, h.size() * sizeof(real), hipMemcpyDeviceToDevice, s));
+    return rows_turn(nmrows::kGrav, true);
+  }
+  int get_gravity(void* out, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (!out) return 0;
+    if (!envp_dev) return grav_fill_default((real*)out, s);
+    HIPCHK(hipMemcpyAsync(out, nmrows::grav_rows(envp_dev, N), (size_t)N * nm::kGravP * sizeof(real), hipMemcpyDeviceToDevice, s));
+    return 0;
+  }
+  int draw_gravity(const double* lo, const double* hi, void* out, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    Grav5<real> l, h;
+    for (int k = 0; k < 5; k++) { l.v[k] = (real)lo[k]; h.v[k] = (real)hi[k]; }
+    hipLaunchKernelGGL(k_gravity_draw<real>, dim3((5 * N + 255) / 256), dim3(256), 0, s, (real*)out, N, A.seed, A.env_offset, l, h);
+    HIPCHK(hipGetLastError());
+    return 0;
   }
   void set_dbg(void* p) override { A.dbg = (real*)p; }
   void set_ret_acc(float* p) override { A.ret_acc = p; }
@@ -1339,6 +1399,29 @@ int nm_set_action_history(nm_env* env, const float* hist_dev, void* stream) {
 int nm_get_action_history(nm_env* env, float* out_dev, void* stream) {
   NEED_ENV(env);
   return env->get_action_history(out_dev, (hipStream_t)stream);
+}
+int nm_set_gravity(nm_env* env, const void* rows_dev, void* stream) {
+  NEED_ENV(env);
+  return env->set_gravity(rows_dev, (hipStream_t)stream);
+}
+int nm_get_gravity(nm_env* env, void* out_dev, void* stream) {
+  NEED_ENV(env);
+  return env->get_gravity(out_dev, (hipStream_t)stream);
+}
+int nm_draw_gravity(nm_env* env, const double lo[5], const double hi[5], void* out_dev, void* stream) {
+  // every refusal comes before the first device call; the bounds are judged first, so a bad range is named whatever the handle is
+  if (!lo || !hi) return fail("nm_draw_gravity: lo / hi is NULL");
+  static const char* kCol[5] = {"offset x", "offset y", "offset z", "tilt", "azimuth"};
+  for (int k = 0; k < 5; k++) {
+    if (!std::isfinite(lo[k]) || !std::isfinite(hi[k])) return fail(std::string("nm_draw_gravity: the bounds of ") + kCol[k] + " must be finite");
+    if (lo[k] > hi[k]) return fail(std::string("nm_draw_gravity: lo > hi for ") + kCol[k]);
+  }
+  NEED_ENV(env);
+  if (!out_dev) return fail("nm_draw_gravity: out is NULL");
+  if (env->dtype == NM_DTYPE_F32)
+    for (int k = 0; k < 5; k++)
+      if (!std::isfinite((float)lo[k]) || !std::isfinite((float)hi[k])) return fail(std::string("nm_draw_gravity: the bounds of ") + kCol[k] + " must be finite in float32");
+  return env->draw_gravity(lo, hi, out_dev, (hipStream_t)stream);
 }
 int nm_step_tape(nm_env* env, const nm_tape_args* args, void* stream) {
   if (!env) return fail("nm_step_tape: env is NULL");

@@ -24,6 +24,8 @@ Differences a caller can observe (all documented in DESIGN.md):
   * and randomize_reset_state with reset_base_height_range / reset_dof_pos_range / reset_base_lin_vel_range / reset_base_ang_vel_range /
     reset_dof_vel_range: every reset draws the base height, the joint angles and all velocities afresh around qpos0 / zero
     (set_reset_noise), from the first reset() on
+  * and randomize_gravity / gravity_range, randomize_slope / slope_range, gravity_observed: a per-env gravity vector - a floor inclined
+    by theta is a level floor under a gravity tilted by theta - drawn once at construction (set_gravity, draw_gravity)
 """
 import ctypes as C
 import numpy as np
@@ -111,6 +113,33 @@ def latency_config(cfg):
     return _switched(getattr(cfg, "domain_rand", None), "randomize_action_latency", "action_latency_range", lowest=0, whole=True)
 
 
+GRAVITY = 9.81      # m/s^2: the model's gravity and upstream's gravity_vec (reference envs/nightmare_v3_env.py:46)
+
+
+def gravity_config(cfg):
+    """(offset_range, tilt_range, observed) of the optional cfg.domain_rand: what draw_gravity takes, both ranges None where nothing is
+    switched on. randomize_gravity needs gravity_range, (lo, hi) m/s^2 added to each component of g (legged_gym's names);
+    randomize_slope needs slope_range, (lo, hi) rad with 0 <= lo <= hi < pi/2, the floor's inclination; gravity_observed (default True):
+    whether the env layer sees g or keeps upstream's constant. Anything else is a ValueError."""
+    dr = getattr(cfg, "domain_rand", None)
+    off = _switched(dr, "randomize_gravity", "gravity_range")
+    tilt = _switched(dr, "randomize_slope", "slope_range", lowest=0.0)
+    if tilt is not None and not tilt[1] < np.pi / 2:
+        raise ValueError("cfg.domain_rand.slope_range must be finite with 0 <= lo <= hi < pi/2")
+    observed = getattr(dr, "gravity_observed", True)
+    if not isinstance(observed, (bool, np.bool_)):
+        raise ValueError("cfg.domain_rand.gravity_observed must be True or False")
+    return off, tilt, bool(observed)
+
+
+def gravity_from_draw(offset, theta, phi):
+    """g [n,3] in float64 of a floor inclined by theta towards azimuth phi, written in the floor's frame, plus a per-axis offset:
+    9.81 (sin theta cos phi, sin theta sin phi, -cos theta) + offset."""
+    offset, theta, phi = np.asarray(offset, np.float64), np.asarray(theta, np.float64), np.asarray(phi, np.float64)
+    s = np.sin(theta)
+    return GRAVITY * np.stack([s * np.cos(phi), s * np.sin(phi), -np.cos(theta)], axis=-1) + offset
+
+
 RESET_NOISE_RANGES = ("reset_base_height_range", "reset_dof_pos_range", "reset_base_lin_vel_range", "reset_base_ang_vel_range",
                       "reset_dof_vel_range")
 
@@ -168,6 +197,7 @@ class NightmareV3Env:
         envp_ranges = env_param_config(cfg)
         payload_ranges = payload_config(cfg)
         latency_range = latency_config(cfg)
+        gravity_ranges = gravity_config(cfg)
         reset_ranges = reset_noise_config(cfg)
         # reward table: zero scales dropped, the rest x dt (reference :123-128). Every name the reference has a _reward_ function
         # for (:399-497) is compiled; a name without one (`collision`, `feet_stumble`, config :95-96) fails like upstream's getattr.
@@ -248,6 +278,9 @@ class NightmareV3Env:
         # per-env actuation latency (optional cfg.domain_rand; no reference line): drawn once, here
         if latency_range is not None:
             self.draw_action_latency(*latency_range)
+        # per-env gravity vectors - slopes and gravity offsets (optional cfg.domain_rand; no reference line): drawn once, here
+        if gravity_ranges[0] is not None or gravity_ranges[1] is not None:
+            self.draw_gravity(*gravity_ranges)
         # randomised reset states (optional cfg.domain_rand; no reference line): on before the first reset(), whose reset_idx(all) is
         # draw 0 of every env
         if reset_ranges is not None:
@@ -468,6 +501,61 @@ class NightmareV3Env:
             raise ValueError("set_action_history: [num_envs, 3, 18]")
         self._ck(self._L.nm_set_action_history(self._h, C.c_void_p(t.data_ptr()), self._stream()))
         self._rows_keep["hist"] = t
+
+    def _vec3(self, v, err):
+        """[num_envs, 3] float64 numpy from one [3] for every env or a [num_envs, 3] array / tensor."""
+        v = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
+        v = np.tile(v, (self.num_envs, 1)) if v.ndim == 1 and v.size == 3 else v
+        if v.shape != (self.num_envs, 3):
+            raise ValueError(err)
+        return v
+
+    def set_gravity(self, g=None, gravity_vec=None):
+        """Per-env gravity vectors (nm_set_gravity; include/nightmare_hip.h states the semantics). g: the gravity the physics sees, m/s^2
+        in the frame of the floor - for an infinite plane a floor inclined by theta is a level floor under g = 9.81 (sin theta cos phi,
+        sin theta sin phi, -cos theta) - [num_envs, 3], one [3] for every env, or None = off. gravity_vec: what the env layer rotates into
+        the body frame (observation slots 6..8, the orientation reward, the 60 degree termination); None = equal to g, an IMU's view;
+        pass upstream's (0, 0, -9.81) to keep its env layer line for line. Honoured by step(), step_physics, policy_rollout, policy_play
+        and step_tape alike. The vectors hold until they are set again; no reset touches them. The attribute `gravity_vec` stays
+        upstream's constant. ValueError: a wrong shape; the library refuses non-finite values and a zero gravity_vec."""
+        if g is None:
+            if gravity_vec is not None:
+                raise ValueError("set_gravity: gravity_vec needs g")
+            self._rows_keep["grav"] = None
+            self._ck(self._L.nm_set_gravity(self._h, None, self._stream()))
+            return
+        err = "set_gravity: one [3] for every env or [num_envs, 3]"
+        rows = np.zeros((self.num_envs, 8))
+        rows[:, 0:3] = self._vec3(g, err)
+        rows[:, 4:7] = rows[:, 0:3] if gravity_vec is None else self._vec3(gravity_vec, err)
+        t = torch.from_numpy(rows).to(dtype=self._real).to(self.device).contiguous()
+        self._ck(self._L.nm_set_gravity(self._h, C.c_void_p(t.data_ptr()), self._stream()))
+        self._rows_keep["grav"] = t
+
+    def gravity(self):
+        """{'g', 'gravity_vec'}: [num_envs, 3] tensors in the env's dtype (nm_get_gravity); (0, 0, -9.81) twice while the feature is off."""
+        rows = torch.empty(self.num_envs, 8, dtype=self._real, device=self.device)
+        self._ck(self._L.nm_get_gravity(self._h, C.c_void_p(rows.data_ptr()), self._stream()))
+        return {"g": rows[:, 0:3].clone(), "gravity_vec": rows[:, 4:7].clone()}
+
+    def draw_gravity(self, offset_range=None, tilt_range=None, observed=True):
+        """Draw every env's gravity on the device (nm_draw_gravity: three offsets uniform in offset_range m/s^2, a tilt theta uniform in
+        tilt_range rad and, whenever a tilt range is given, an azimuth phi uniform in [0, 2 pi); None pins that part to 0), derive
+        g = 9.81 (sin theta cos phi, sin theta sin phi, -cos theta) + offset on the host in float64 and set the rows. observed: the env
+        layer sees g (True) or keeps upstream's (0, 0, -9.81). Keyed by the global env id: shards of one population draw what the whole
+        would. Returns what gravity() then reports."""
+        of = (0.0, 0.0) if offset_range is None else tuple(float(x) for x in offset_range)
+        ti = (0.0, 0.0) if tilt_range is None else tuple(float(x) for x in tilt_range)
+        if not (0.0 <= ti[0] <= ti[1] < np.pi / 2):
+            raise ValueError("draw_gravity: tilt_range must be (lo, hi) rad with 0 <= lo <= hi < pi/2")
+        az = 0.0 if tilt_range is None else 2.0 * np.pi
+        lo, hi = (C.c_double * 5)(of[0], of[0], of[0], ti[0], 0.0), (C.c_double * 5)(of[1], of[1], of[1], ti[1], az)
+        out = torch.empty(self.num_envs, 5, dtype=self._real, device=self.device)
+        self._ck(self._L.nm_draw_gravity(self._h, C.byref(lo), C.byref(hi), C.c_void_p(out.data_ptr()), self._stream()))
+        d = out.to(torch.float64).cpu().numpy()
+        g = gravity_from_draw(d[:, 0:3], d[:, 3], d[:, 4])
+        self.set_gravity(g, None if observed else np.array([0.0, 0.0, -GRAVITY]))
+        return self.gravity()
 
     def _record_state(self):
         # reference :261-272: when env 0 resets, dump what was logged so far, then log (time, qpos, qvel, act) of env 0

@@ -1,0 +1,134 @@
+"""ctypes binding of the host SIMT emulation with every kind of per-env row, the gravity rows of level 4 included (tests only; see
+nm_emul_grav.cpp). Layout, defaults, admission, state and level are the host object's own (nightmare_rl_amd/csrc/nm_env_rows.h)."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+LIB = os.path.join(HERE, "libnm_emul_grav.so")
+SRC = [os.path.join(HERE, "nm_emul_grav.cpp")] + [os.path.join(HERE, "..", "..", "nightmare_rl_amd", "csrc", f)
+                                                  for f in ("nm_core.h", "simt.h", "nm_host_model.h", "nm_env_rows.h", os.path.join("..", "model", "nm_model_data.h"))]
+FLAGS = ["-O1", "-std=c++17", "-ffp-contract=off", "-Wno-missing-braces"]     # tests/emul/emul.py's, so all shims round alike
+
+
+def build(force=False):
+    if force or not os.path.exists(LIB) or any(os.path.getmtime(s) > os.path.getmtime(LIB) for s in SRC):
+        subprocess.check_call(["g++"] + FLAGS + ["-fPIC", "-shared", "-o", LIB, SRC[0]])
+    return LIB
+
+
+_lib = None
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        build()
+        L = C.CDLL(LIB)
+        L.emug_create.restype = C.c_void_p
+        L.emug_create.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_int64, C.c_int]
+        L.emug_destroy.argtypes = [C.c_void_p]
+        L.emug_step.argtypes = [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_void_p]
+        L.emug_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.emug_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        for f in (L.emug_set_envp, L.emug_set_body, L.emug_set_latency, L.emug_set_gravity, L.emug_get_gravity, L.emug_default_body_row, L.emug_on_flags):
+            f.argtypes = [C.c_void_p, C.c_void_p]
+        L.emug_level.argtypes = [C.c_void_p, C.c_int]
+        L.emug_device_layout_agrees.argtypes = [C.c_void_p]
+        L.emug_hist.argtypes = [C.c_void_p]
+        L.emug_hist.restype = C.POINTER(C.c_float)
+        L.emug_eplen.argtypes = [C.c_void_p]
+        L.emug_eplen.restype = C.POINTER(C.c_int64)
+        L.emug_together_count.restype = C.c_long
+        assert L.emug_grav_p() == 8
+        _lib = L
+    return _lib
+
+
+def _p(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+WHAT = dict(qpos=(0, 25), qvel=(1, 24), qwarm=(2, 24), dofpos=(3, 18), dofvel=(4, 18), act=(5, 18), cmd=(6, 3), epsum=(7, 16))
+DBG_NTOG, DBG_NCON, DBG_NWARN = 156, 160, 161      # words of an env's debug row (nm_core.h env_debug)
+
+
+class EmulGrav:
+    def __init__(self, N, double=False, seed=0, env_off=0, envs_per_wave=2):
+        self.L = lib()
+        self.N = N
+        self.h = self.L.emug_create(N, int(double), seed, env_off, envs_per_wave)
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.L.emug_destroy(self.h)
+            self.h = None
+
+    def get(self, name):
+        w, k = WHAT[name]
+        out = np.empty((self.N, k))
+        self.L.emug_get(self.h, w, _p(out))
+        return out
+
+    def set(self, name, val):
+        w, k = WHAT[name]
+        v = np.ascontiguousarray(val, np.float64).reshape(self.N, k)
+        self.L.emug_set(self.h, w, _p(v))
+
+    def set_env_params(self, rows=None):
+        r = None if rows is None else np.ascontiguousarray(rows, np.float64).reshape(self.N, 3)
+        self.L.emug_set_envp(self.h, _p(r))
+
+    def set_body_params(self, rows=None):
+        r = None if rows is None else np.ascontiguousarray(rows, np.float64).reshape(self.N, 20)
+        self.L.emug_set_body(self.h, _p(r))
+
+    def set_action_latency(self, substeps=None):
+        d = None if substeps is None else np.ascontiguousarray(substeps, np.int32).reshape(self.N)
+        self.L.emug_set_latency(self.h, _p(d))
+
+    def set_gravity(self, rows=None):
+        """[N,8] rows (g[3], pad, gravity_vec[3], pad) or None: off. ValueError where the host's admission refuses them (nothing changes)."""
+        r = None if rows is None else np.ascontiguousarray(rows, np.float64).reshape(self.N, 8)
+        if self.L.emug_set_gravity(self.h, _p(r)):
+            raise ValueError("gravity rows refused")
+
+    def gravity(self):
+        """What the gravity region holds, whatever is on: the defaults while the kind is off."""
+        out = np.zeros((self.N, 8))
+        self.L.emug_get_gravity(self.h, _p(out))
+        return out
+
+    def default_body_row(self):
+        out = np.zeros(20)
+        self.L.emug_default_body_row(self.h, _p(out))
+        return out
+
+    def state(self, physics_only=False):
+        """(kinds that are on as a string of F, B, L, G; the level a launch takes)."""
+        on = np.zeros(4, np.int32)
+        self.L.emug_on_flags(self.h, _p(on))
+        return "".join(k for i, k in enumerate("FBLG") if on[i]), self.L.emug_level(self.h, int(physics_only))
+
+    def device_layout_agrees(self):
+        return bool(self.L.emug_device_layout_agrees(self.h))
+
+    @property
+    def history(self):
+        return np.ctypeslib.as_array(self.L.emug_hist(self.h), (self.N, 3, 18))
+
+    @property
+    def eplen(self):
+        return np.ctypeslib.as_array(self.L.emug_eplen(self.h), (self.N,))
+
+    def step(self, actions, cmd_u=None, nsub=2, physics_only=False, want_dbg=False):
+        N = self.N
+        a = np.ascontiguousarray(actions, np.float32).reshape(N, 18)
+        cu = None if cmd_u is None else np.ascontiguousarray(cmd_u, np.float64).reshape(N, 4)
+        obs, rew, done, to = np.zeros((N, 66), np.float32), np.zeros(N, np.float32), np.zeros(N, np.int64), np.zeros(N, np.float32)
+        dbg = np.zeros((N, 256)) if want_dbg else None
+        self.L.emug_step(self.h, _p(a), _p(cu), _p(obs), _p(rew), _p(done), _p(to), nsub, int(physics_only), _p(dbg))
+        self.dbg = dbg
+        return obs, rew, done, to

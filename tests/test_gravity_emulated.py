@@ -1,0 +1,272 @@
+"""Per-env gravity vectors (gravity rows, level 4 of the step) in the host emulation of the device source (tests/emul/nm_emul_grav.cpp):
+the fp64 emulation of a batch that mixes the four gravity sets over its envs against the fp64 fixture of the variant oracles
+(tests/golden/make_gravity_goldens.py: the unchanged oracle compiled against a header with another gravity; for the observed sets with the
+one line of its env layer that holds upstream's constant replaced), teacher-forced and free-running; the fp32 emulation inside the fp32
+bounds; default rows at level 4 against level 0 and level 3; mixed batches against uniform ones bit for bit; the bad-state paths under a
+tilted gravity; and the free-flight known answer that does not go through the oracle."""
+import numpy as np
+import pytest
+
+from conftest import load_golden
+
+POPS = ("drop", "stand", "belly")
+H = 0.008      # the model's timestep
+
+
+@pytest.fixture(scope="module")
+def G():
+    return load_golden("gravity.npz")
+
+
+@pytest.fixture(scope="module")
+def emul():
+    from emul import emul_grav
+    emul_grav.build()
+    return emul_grav
+
+
+def set_of(n, shift=0):
+    """Gravity set of env e: neighbours in a wave (2w, 2w + 1) always hold different sets, and every set meets every slot."""
+    e = np.arange(n)
+    return (e + e // 4 + shift) % 4
+
+
+def load_step(env, g, pop, t, sets):
+    """Start state of step t: env e takes env e % 8 of the trajectory of set sets[e]."""
+    ev = np.arange(len(sets)) % 8
+    pick = lambda k: g[f"{pop}_{k}"][sets, t, ev]
+    env.set("qpos", pick("qpos")); env.set("qvel", pick("qvel")); env.set("qwarm", pick("qw"))
+    env.set("dofpos", pick("dof_pos")); env.set("dofvel", pick("dof_vel")); env.set("act", pick("act")); env.set("cmd", pick("cmd"))
+    env.eplen[:] = pick("ep_len")
+
+
+def run(emul, g, pop, sets, double, rows, steps=None, envs_per_wave=2, forced=True, latency=None, envp=None, body=None):
+    """Single steps of one batch, teacher-forced (every step starts from the fixture's state) or free-running from the first state;
+    returns per-step (obs, rew, done, qpos, qvel), the error figures against the fixture, and what the debug rows counted."""
+    n = len(sets)
+    ev = np.arange(n) % 8
+    env = emul.EmulGrav(n, double=double, seed=5, envs_per_wave=envs_per_wave)
+    if envp is not None:
+        env.set_env_params(envp)
+    if body is not None:
+        env.set_body_params(body)
+    if latency is not None:
+        env.set_action_latency(latency)
+    if rows is not None:
+        env.set_gravity(rows)
+    out, oerrs, serr, ntog, nbig, flags = [], [], 0.0, 0, 0, 0
+    T = g[f"{pop}_actions"].shape[1] if steps is None else steps
+    for t in range(T):
+        if forced or t == 0:
+            load_step(env, g, pop, t, sets)
+        obs, rew, done, _ = env.step(g[f"{pop}_actions"][sets, t, ev], cmd_u=g[f"{pop}_cmd_u"][sets, t, ev].astype(np.float64), want_dbg=True)
+        oe = np.abs(obs.astype(np.float64) - g[f"{pop}_obs"][sets, t, ev]).max(axis=1)
+        re_ = np.abs(rew.astype(np.float64) - g[f"{pop}_rew"][sets, t, ev])
+        serr = max(serr, np.abs(env.get("qpos") - g[f"{pop}_qpos"][sets, t + 1, ev]).max(), np.abs(env.get("qvel") - g[f"{pop}_qvel"][sets, t + 1, ev]).max())
+        flags += int((done != g[f"{pop}_done"][sets, t, ev]).sum())
+        oerrs.append(np.maximum(oe, re_))
+        out.append((obs.copy(), rew.copy(), done.copy(), env.get("qpos"), env.get("qvel")))
+        ntog += int(env.dbg[0::2, emul.DBG_NTOG].sum())
+        nbig += int((env.dbg[:, emul.DBG_NCON] > 16).sum())      # ncon > kMaxCon (16) IS the dispatch to stage_constraint_big (nm_core.h stage_constraint)
+    return out, (np.stack(oerrs), flags), serr, ntog, nbig
+
+
+def same(a, b, mask=slice(None)):
+    for x, y in zip(a, b):
+        for u, v in zip(x, y):
+            np.testing.assert_array_equal(u[mask], v[mask])
+
+
+def test_layout_state_and_admission(G, emul):
+    """The gravity region lies behind the histories where the device looks for it and ends the block; while the kind is off it holds the
+    defaults; gravity on means level 4, for physics-only launches too; rows the admission refuses change nothing."""
+    for double in (False, True):
+        for n in (1, 3, 8):      # n * 55 latency words: odd counts leave the fp64 block a pad word in front of the gravity rows
+            env = emul.EmulGrav(n, double=double)
+            assert env.device_layout_agrees()
+            dflt = env.gravity()
+            np.testing.assert_array_equal(dflt, np.tile([0, 0, np.float32(-9.81) if not double else -9.81, 0] * 2, (n, 1)))
+            assert env.state() == ("", 0)
+            env.set_action_latency(np.zeros(n, int))
+            assert env.state() == ("L", 3) and env.state(physics_only=True) == ("L", 2)
+            rows = np.tile(G["rows"][1], (n, 1))
+            env.set_gravity(rows)
+            assert env.state() == ("LG", 4) and env.state(physics_only=True) == ("LG", 4)
+            np.testing.assert_allclose(env.gravity(), rows, rtol=1e-6 if not double else 0)
+            for bad in (np.nan, np.inf):
+                r = rows.copy(); r[n - 1, 1] = bad
+                with pytest.raises(ValueError):
+                    env.set_gravity(r)
+            r = rows.copy(); r[0, 4:7] = 0.0
+            with pytest.raises(ValueError):      # a zero gravity_vec: the termination divides by its norm
+                env.set_gravity(r)
+            np.testing.assert_allclose(env.gravity(), rows, rtol=1e-6 if not double else 0)
+            r = rows.copy(); r[:, 0:3] = 0.0      # a zero g is admitted: free float
+            env.set_gravity(r)
+            env.set_gravity(None)
+            np.testing.assert_array_equal(env.gravity(), dflt)
+            assert env.state() == ("L", 3)
+
+
+@pytest.mark.parametrize("envs_per_wave", [2, 1])
+@pytest.mark.parametrize("pop", POPS)
+def test_fp64_emulation_of_a_mixed_batch_matches_the_variant_oracles(G, emul, pop, envs_per_wave):
+    """Tolerances: the project's fp64 ones (tests/test_gpu_parity.py: obs / reward < 1e-6, state < 1e-8), no done flag differing.
+    Teacher-forced and free-running. Two envs per wave is the fp32 kernel's layout, one env per wave the fp64 kernel's."""
+    sets = set_of(16)
+    for forced in (True, False):
+        _, (err, flags), serr, ntog, nbig = run(emul, G, pop, sets, double=True, rows=G["rows"][sets], envs_per_wave=envs_per_wave, forced=forced)
+        print(f"{pop} {'forced' if forced else 'free'}: max obs/reward error {err.max():.2e}, max state error {serr:.2e}, two-env passes {ntog}, env-steps above 16 contacts {nbig}")
+        assert flags == 0
+        assert err.max() < 1e-6 and serr < 1e-8, (err.max(), serr)
+        if pop == "stand" and envs_per_wave == 2:
+            assert ntog > 0 and (sets[0::2] != sets[1::2]).all()
+        if pop == "belly":
+            assert nbig >= 4
+
+
+def test_fp32_emulation_is_inside_the_fp32_bounds(G, emul):
+    """median < 5e-6 and p99 < 1e-4 (tests/test_gpu_env_params.py), teacher-forced, the four sets mixed."""
+    sets, errs = set_of(16), []
+    for pop in POPS:
+        _, (err, flags), _, _, _ = run(emul, G, pop, sets, double=False, rows=G["rows"][sets])
+        print(f"{pop}: fp32 emulation vs fixture: median {np.median(err):.2e}, p99 {np.percentile(err, 99):.2e}, max {err.max():.2e}")
+        assert flags == 0
+        errs.append(err.ravel())
+    err = np.concatenate(errs)
+    assert np.median(err) < 5e-6 and np.percentile(err, 99) < 1e-4, (np.median(err), np.percentile(err, 99))
+
+
+@pytest.mark.parametrize("envs_per_wave", [1, 2])
+@pytest.mark.parametrize("double", [False, True], ids=["fp32", "fp64"])
+def test_default_rows_at_level_4_equal_level_0_and_level_3(G, emul, double, envs_per_wave):
+    """(0, 0, -9.81) twice in every env, set explicitly, against no rows at all (level 0) and against latency on with zero delays (level 3):
+    equal under == in every output. t + (-g) with g = (0, 0, -M.grav) is today's t[2] + M.grav, and adding an exact zero changes no
+    rounding."""
+    sets = np.zeros(8, int)
+    np.testing.assert_array_equal(G["sets"][0], [0, 0, 0, 0, 0, 1])
+    np.testing.assert_array_equal(G["rows"][0], [0, 0, -9.81, 0, 0, 0, -9.81, 0])
+    rows = np.tile(G["rows"][0], (8, 1))
+    for pop in POPS:
+        steps = 3 if pop != "belly" else G["belly_actions"].shape[1]
+        l0, _, _, _, _ = run(emul, G, pop, sets, double, None, steps, envs_per_wave)
+        l3, _, _, _, _ = run(emul, G, pop, sets, double, None, steps, envs_per_wave, latency=np.zeros(8, int))
+        l4, _, _, ntog, nbig = run(emul, G, pop, sets, double, rows, steps, envs_per_wave)
+        l4l, _, _, _, _ = run(emul, G, pop, sets, double, rows, steps, envs_per_wave, latency=np.zeros(8, int))
+        same(l0, l4); same(l3, l4); same(l3, l4l)
+        if pop == "belly":
+            assert nbig >= 1
+        if pop == "stand" and envs_per_wave == 2:
+            assert ntog > 0
+
+
+@pytest.mark.parametrize("pop", POPS)
+def test_fp32_mixed_batch_equals_uniform_batches_bit_for_bit(G, emul, pop):
+    """Env e of the mixed batch equals env e of the batch in which EVERY env holds e's gravity rows (two envs per wave): what differs
+    between the runs is only what the wave's other env carries."""
+    n, steps = 8, (4 if pop != "belly" else G["belly_actions"].shape[1])
+    sets = set_of(n)
+    mixed, _, _, ntog, nbig = run(emul, G, pop, sets, False, G["rows"][sets], steps)
+    for k in range(4):
+        uni, _, _, _, _ = run(emul, G, pop, sets, False, np.tile(G["rows"][k], (n, 1)), steps)
+        assert (sets == k).any()
+        same(mixed, uni, sets == k)
+    assert not np.array_equal(mixed[-1][4][sets == 1], run(emul, G, pop, sets, False, None, steps)[0][-1][4][sets == 1])      # the rows are not ignored
+    if pop == "stand":
+        assert ntog > 0
+    if pop == "belly":
+        assert nbig >= 1
+
+
+def test_gravity_with_every_other_kind_equals_the_uniform_runs(G, emul):
+    """All four kinds on, gravity mixed: env e equals the run in which every env holds e's gravity (fp32, bit for bit); and a physics-only
+    launch at level 4 ignores latency: equal to the same launch with latency off."""
+    n, steps = 8, 3
+    sets = set_of(n)
+    from nightmare_rl_amd.model import payload
+    body = payload.payload_rows(np.full(n, 0.5), np.tile([0.03, 0.0, 0.04], (n, 1)))
+    kw = dict(envp=np.tile([0.7, 26.0, 1.1], (n, 1)), body=body, latency=np.arange(n) % 7)
+    mixed, _, _, ntog, _ = run(emul, G, "stand", sets, False, G["rows"][sets], steps, **kw)
+    assert ntog > 0
+    for k in range(4):
+        uni, _, _, _, _ = run(emul, G, "stand", sets, False, np.tile(G["rows"][k], (n, 1)), steps, **kw)
+        same(mixed, uni, sets == k)
+
+    def physics(latency):
+        env = emul.EmulGrav(n, double=False, seed=5)
+        env.set_gravity(G["rows"][sets])
+        if latency is not None:
+            env.set_action_latency(latency)
+        load_step(env, G, "stand", 0, sets)
+        hist = env.history.copy()
+        for t in range(3):
+            env.step(G["stand_actions"][sets, t, np.arange(n)], physics_only=True)
+        np.testing.assert_array_equal(env.history, hist)
+        return env.get("qpos"), env.get("qvel"), env.get("qwarm")
+
+    for a, b in zip(physics(np.arange(n) % 7), physics(None)):
+        np.testing.assert_array_equal(a, b)
+
+
+@pytest.mark.parametrize("envs_per_wave", [1, 2])
+@pytest.mark.parametrize("double", [False, True], ids=["fp32", "fp64"])
+def test_bad_state_envs_fall_freely_under_their_own_gravity(G, emul, double, envs_per_wave):
+    """Set 1 (tilt 0.2 rad) in every env, one physics substep. Env 1: a non-finite qvel - mj_checkVel resets it to qpos0 and the substep
+    runs from there, in the air with ctrl = 0, where every body accelerates with g. Env 2: a joint velocity of 5e9 rad/s, below
+    mj_checkVel's 1e10 - the servo's damping alone makes qacc exceed 1e10, mj_checkAcc resets and takes the free-fall step itself:
+    qvel[0:3] = g h, qpos[0:3] = qpos0 + g h^2, qacc_warmstart[0:3] = g, exactly as the env's precision rounds them. Env 0, 3: untouched
+    neighbours, equal to the run without the planted values."""
+    n, sets = 4, np.ones(4, int)
+    rows = np.tile(G["rows"][1], (n, 1))
+    dt = np.float64 if double else np.float32
+
+    def go(plant):
+        env = emul.EmulGrav(n, double=double, seed=5, envs_per_wave=envs_per_wave)
+        env.set_gravity(rows)
+        load_step(env, G, "stand", 0, sets)
+        q0 = emul.EmulGrav(1, double=double).get("qpos")[0]
+        if plant:
+            v = env.get("qvel"); v[1, 7] = np.inf; v[2, 7] = 5e9; env.set("qvel", v)
+        env.step(np.zeros((n, 18), np.float32), nsub=1, physics_only=True, want_dbg=True)
+        return env.get("qpos"), env.get("qvel"), env.get("qwarm"), env.dbg[:, emul.DBG_NWARN].copy(), q0
+
+    qp, qv, qw, nwarn, q0 = go(True)
+    rp, rv, rw, nwarn0, _ = go(False)
+    np.testing.assert_array_equal(nwarn, [0, 1, 1, 0]); np.testing.assert_array_equal(nwarn0, 0)
+    for e in (0, 3):
+        np.testing.assert_array_equal(qp[e], rp[e]); np.testing.assert_array_equal(qv[e], rv[e])
+    g = rows[0, 0:3].astype(dt)
+    h = dt(H)
+    v = (g * h).astype(dt)
+    want_q = q0.copy(); want_q[0:3] = (q0[0:3].astype(dt) + (v * h).astype(dt)).astype(dt)
+    want_v = np.zeros(24); want_v[0:3] = v
+    want_w = np.zeros(24); want_w[0:3] = g
+    assert abs(g[0]) > 1.9 and g[1] == 0      # all three components matter: x is there, y is an exact zero
+    np.testing.assert_array_equal(qp[2], want_q); np.testing.assert_array_equal(qv[2], want_v); np.testing.assert_array_equal(qw[2], want_w)
+    tol = 1e-8 if double else 2e-5
+    assert np.abs(qp[1] - want_q).max() < tol and np.abs(qv[1] - want_v).max() < tol, (np.abs(qp[1] - want_q).max(), np.abs(qv[1] - want_v).max())
+
+
+def test_free_flight_known_answer_in_the_fp64_emulation(emul):
+    """The known answer of tests/test_gpu_gravity.py that does not go through the oracle, here first: two fp64 envs from the same state
+    (base at z = 5 m, random joint angles and joint / angular velocities), the same random actions, 10 physics-only steps without contact;
+    one under g = (1.3, -0.7, -6.0), one under g = 0. After n substeps qvel[0:3] differ by n h g and qpos[0:3] by h^2 g n (n + 1) / 2
+    (semi-implicit Euler); every other word agrees: a uniform field exerts no relative force. Tolerance: the fp64 state tolerance 1e-8."""
+    rng = np.random.default_rng(11)
+    g = np.array([1.3, -0.7, -6.0])
+    env = emul.EmulGrav(2, double=True, seed=5, envs_per_wave=1)
+    rows = np.zeros((2, 8)); rows[0, 0:3] = g; rows[:, 4:7] = [0, 0, -9.81]
+    env.set_gravity(rows)
+    q = env.get("qpos"); q[:, 2] = 5.0; q[:, 7:] += rng.uniform(-0.3, 0.3, 18); env.set("qpos", q)
+    v = np.zeros((2, 24)); v[:, 3:] = rng.uniform(-1, 1, 21); env.set("qvel", v)
+    nsub, n = 2, 0
+    for t in range(10):
+        env.step(np.tile(rng.uniform(-1, 1, 18).astype(np.float32), (2, 1)), nsub=nsub, physics_only=True, want_dbg=True)
+        assert (env.dbg[:, emul.DBG_NCON] == 0).all() and (env.dbg[:, emul.DBG_NWARN] == 0).all()
+        n += nsub
+        qp, qv = env.get("qpos"), env.get("qvel")
+        dv, dq = qv[0] - qv[1], qp[0] - qp[1]
+        ev = max(np.abs(dv[0:3] - n * H * g).max(), np.abs(dv[3:]).max())
+        eq = max(np.abs(dq[0:3] - H * H * g * n * (n + 1) / 2).max(), np.abs(dq[3:]).max())
+        assert ev < 1e-8 and eq < 1e-8, (t, ev, eq)
+    print(f"after {n} substeps: velocity error {ev:.2e}, position error {eq:.2e}")
