@@ -36,6 +36,8 @@ def lib():
         for f in (L.emug_set_envp, L.emug_set_body, L.emug_set_latency, L.emug_set_gravity, L.emug_get_gravity, L.emug_default_body_row, L.emug_on_flags):
             f.argtypes = [C.c_void_p, C.c_void_p]
         L.emug_level.argtypes = [C.c_void_p, C.c_int]
+        L.emug_get_rows.argtypes = [C.c_void_p] * 4
+        L.emug_carries_block.argtypes = [C.c_void_p]
         L.emug_device_layout_agrees.argtypes = [C.c_void_p]
         L.emug_hist.argtypes = [C.c_void_p]
         L.emug_hist.restype = C.POINTER(C.c_float)
@@ -51,7 +53,8 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-WHAT = dict(qpos=(0, 25), qvel=(1, 24), qwarm=(2, 24), dofpos=(3, 18), dofvel=(4, 18), act=(5, 18), cmd=(6, 3), epsum=(7, 16))
+WHAT = dict(qpos=(0, 25), qvel=(1, 24), qwarm=(2, 24), dofpos=(3, 18), dofvel=(4, 18), act=(5, 18), cmd=(6, 3), epsum=(7, 16),
+            feetair=(8, 6), feetflags=(9, 1), hcache=(10, 8), rngctr=(11, 1))      # the last four: what else a step carries over
 DBG_NTOG, DBG_NCON, DBG_NWARN = 156, 160, 161      # words of an env's debug row (nm_core.h env_debug)
 
 
@@ -100,6 +103,16 @@ class EmulGrav:
         out = np.zeros((self.N, 8))
         self.L.emug_get_gravity(self.h, _p(out))
         return out
+
+    def rows(self):
+        """What the block holds, whatever is on: ([N,3] friction / gains, [N,20] body rows, [N] delays, [N,8] gravity rows)."""
+        e, b, d = np.zeros((self.N, 3)), np.zeros((self.N, 20)), np.zeros(self.N, np.int32)
+        self.L.emug_get_rows(self.h, _p(e), _p(b), _p(d))
+        return e, b, d, self.gravity()
+
+    def carries_block(self):
+        """Whether a launch carries the block at all (nm::Args::envp non-null)."""
+        return bool(self.L.emug_carries_block(self.h))
 
     def default_body_row(self):
         out = np.zeros(20)

@@ -23,6 +23,8 @@ struct Base {
   virtual void set_latency(const int* d) = 0;
   virtual int set_gravity(const double* rows) = 0;
   virtual void get_gravity(double* rows8) = 0;
+  virtual void get_rows(double* envp3, double* body20, int* delays) = 0;
+  virtual int carries_block() = 0;
   virtual void default_body_row(double* out) = 0;
   virtual void on_flags(int* on4) = 0;
   virtual int level(int physics_only) = 0;
@@ -62,10 +64,13 @@ template <class real> struct EmuG : Base {
     switch (what) {
       case 0: return fn(qpos); case 1: return fn(qvel); case 2: return fn(qwarm); case 3: return fn(dofpos); case 4: return fn(dofvel);
       case 5: return fn(act); case 6: return fn(cmd); case 7: return fn(epsum);
+      case 8: return fn(feetair); case 9: return fn(feetflags); case 10: return fn(hcache); case 11: return fn(ctr);      // what else a step carries over
     }
   }
   void get(int what, double* out) override { array(what, [&](auto& a) { for (size_t i = 0; i < a.size(); i++) out[i] = (double)a[i]; }); }
-  void set(int what, const double* in) override { array(what, [&](auto& a) { for (size_t i = 0; i < a.size(); i++) a[i] = (real)in[i]; }); }
+  void set(int what, const double* in) override {
+    array(what, [&](auto& a) { for (size_t i = 0; i < a.size(); i++) a[i] = (typename std::decay_t<decltype(a)>::value_type)in[i]; });
+  }
   void set_envp(const double* in) override {
     rows.on[nmrows::kFric] = in != nullptr;
     real dflt[3];
@@ -101,6 +106,14 @@ template <class real> struct EmuG : Base {
     const real* g = nmrows::grav_rows(envp.data(), N);
     for (size_t i = 0; i < (size_t)N * nm::kGravP; i++) out[i] = (double)g[i];
   }
+  void get_rows(double* envp3, double* body20, int* d) override {      // what the first three regions hold, whatever is on
+    for (int i = 0; i < N; i++) {
+      for (int k = 0; k < 3; k++) envp3[i * 3 + k] = (double)nmrows::fric_rows(envp.data(), N)[i * nm::kEnvP + k];
+      for (int k = 0; k < nm::kBodyP; k++) body20[i * nm::kBodyP + k] = (double)nmrows::body_rows(envp.data(), N)[i * nm::kBodyP + k];
+      d[i] = nmrows::delays(envp.data(), N)[i];
+    }
+  }
+  int carries_block() override { return rows.envp(envp.data()) != nullptr; }
   void default_body_row(double* out) override {
     real r[nm::kBodyP];
     nmrows::body_default(M, r);
@@ -162,6 +175,8 @@ void emug_set_body(void* h, const double* rows20) { ((Base*)h)->set_body(rows20)
 void emug_set_latency(void* h, const int* d) { ((Base*)h)->set_latency(d); }
 int emug_set_gravity(void* h, const double* rows8) { return ((Base*)h)->set_gravity(rows8); }
 void emug_get_gravity(void* h, double* rows8) { ((Base*)h)->get_gravity(rows8); }
+void emug_get_rows(void* h, double* envp3, double* body20, int* delays) { ((Base*)h)->get_rows(envp3, body20, delays); }
+int emug_carries_block(void* h) { return ((Base*)h)->carries_block(); }
 void emug_default_body_row(void* h, double* out20) { ((Base*)h)->default_body_row(out20); }
 void emug_on_flags(void* h, int* on4) { ((Base*)h)->on_flags(on4); }
 int emug_level(void* h, int physics_only) { return ((Base*)h)->level(physics_only); }

@@ -208,11 +208,20 @@ def test_tape_with_gravity_equals_the_per_step_path(G, others):
         e.close()
 
 
+def _assert_rows_honoured(N, with_rows, cleared):
+    """Final observations of the launch with the gravity rows against the same launch with gravity cleared (every other kind as it
+    was): the envs of a non-default set differ, the envs of set 0 carry the nominal vectors and do not."""
+    m = torch.from_numpy(set_of(N) != 0).to(DEV)
+    assert not torch.equal(with_rows[m], cleared[m])
+    assert torch.equal(with_rows[~m], cleared[~m])
+
+
+@pytest.mark.parametrize("others", [False, True], ids=["alone", "every_other_kind_and_push"])
 @pytest.mark.parametrize("deterministic", [True, False])
-def test_play_with_gravity_equals_the_per_step_path(G, deterministic):
+def test_play_with_gravity_equals_the_per_step_path(G, deterministic, others):
     N, K = 16, 10
     ac, fu = _networks()
-    ea, eb = _mixed(G, N, 2, False)
+    ea, eb = _mixed(G, N, 2, others)
     it = torch.tensor([4], dtype=torch.int64, device=DEV)
     ep_idx = _ep_idx(ea)
     ba, bb = _books(N, ep_idx.numel()), _books(N, ep_idx.numel())
@@ -220,16 +229,24 @@ def test_play_with_gravity_equals_the_per_step_path(G, deterministic):
     ob, _ = _play_step_by_step(eb, fu, K, deterministic, 77, it, bb, ep_idx)
     _assert_same_env(ea, eb, oa, ob)
     _assert_same_books(ba, bb)
+    if others:
+        e0, = _mixed(G, N, 1, True)
+        e0.set_gravity(None)
+        o0 = e0.policy_play(K, fu.flat, deterministic=deterministic, seed=77, iter_dev=it)
+        torch.cuda.synchronize()
+        _assert_rows_honoured(N, oa, o0)
+        e0.close()
     for e in (ea, eb):
         e.close()
 
 
-def test_rollout_with_gravity_equals_the_per_step_path(G):
+@pytest.mark.parametrize("others", [False, True], ids=["alone", "every_other_kind_and_push"])
+def test_rollout_with_gravity_equals_the_per_step_path(G, others):
     from nightmare_rl_amd import _lib
     L = _lib.load()
     N, T, gamma = 16, 10, 0.99
     ac, fu = _networks()
-    ea, eb = _mixed(G, N, 2, False)
+    ea, eb = _mixed(G, N, 2, others)
     it = torch.tensor([3], dtype=torch.int64, device=DEV)
     ep_idx = _ep_idx(ea)
     ba, bb = _books(N, ep_idx.numel()), _books(N, ep_idx.numel())
@@ -245,6 +262,14 @@ def test_rollout_with_gravity_equals_the_per_step_path(G):
         assert torch.equal(getattr(sa, name), getattr(sb, name)), name
     _assert_same_env(ea, eb, oa, o)
     assert torch.equal(ba["cur_ret"], bb["cur_ret"]) and torch.equal(ba["cur_len"], bb["cur_len"])
+    if others:
+        e0, = _mixed(G, N, 1, True)
+        e0.set_gravity(None)
+        b0, s0 = _books(N, ep_idx.numel()), _storage(N, T)
+        o0 = e0.policy_rollout(T, fu.flat, 99, it, s0, gamma, b0["cur_ret"], b0["cur_len"], b0["fin"], ep=(ep_idx, b0["ep_acc"]))
+        torch.cuda.synchronize()
+        _assert_rows_honoured(N, oa, o0)
+        e0.close()
     for e in (ea, eb):
         e.close()
 

@@ -1,9 +1,9 @@
-"""The three kinds of per-env rows together on the device - friction / gains, body rows (base payload), actuation latency: the walk of
-tests/rows_walk.py over every single-kind on / off transition from every state of the other two kinds, through NightmareV3Env. After every
+"""The four kinds of per-env rows together on the device - friction / gains, body rows (base payload), actuation latency, gravity vectors:
+the walk of tests/rows_walk.py over every single-kind on / off transition from every state of the other three kinds, through NightmareV3Env. After every
 toggle the env that took the walk must be indistinguishable from a fresh env of the same seed put directly into that state: the same
 reported rows (the values set for the kinds that are on, what a never-touched env reports for the kinds that are off), and a step and a
 physics-only step from the same start that agree bit for bit. N = 3 in fp32 (one full wave and a half-empty one), N = 2 in fp64 (one env
-per wave). Exact comparisons; 25 small envs and 48 steps per dtype."""
+per wave). Exact comparisons; 65 small envs and 256 steps per dtype."""
 import numpy as np
 import pytest
 import torch
@@ -31,15 +31,18 @@ def toggle(env, kind, values):
     elif kind == "B":
         b = values.get("B")
         env.set_base_payload(*(() if b is None else (b[:, 0], b[:, 1:])))
-    else:
+    elif kind == "L":
         env.set_action_latency(values.get("L"))
+    else:
+        g = values.get("G")
+        env.set_gravity(*((None,) if g is None else (g[:, 0:3], g[:, 4:7])))
 
 
 def reported(env):
     torch.cuda.synchronize()
-    p = env.env_params()
+    p, g = env.env_params(), env.gravity()
     return (torch.stack([p["mu"], p["p_gain"], p["kv"]], dim=1).cpu().numpy(), env.base_payload()["rows"].cpu().numpy(),
-            env.action_latency().cpu().numpy())
+            env.action_latency().cpu().numpy(), torch.cat([g["g"], g["gravity_vec"]], dim=1).cpu().numpy())
 
 
 def two_steps(env, g):
@@ -69,7 +72,7 @@ def test_an_env_that_took_the_walk_equals_a_fresh_env_put_into_that_state(G, N, 
     walker = make_env(N, dtype=dtype, seed=SEED)
     dflt = reported(walker)      # what a never-touched env reports: the model's own rows, zero delays
     assert not dflt[2].any()
-    walk = Walk(N, ENVP_SETS, PAYLOADS)
+    walk = Walk(N, ENVP_SETS, PAYLOADS, load_golden("gravity.npz")["rows"])
     before, steps_that_differed = None, 0
     for i, kind, on in walk:
         toggle(walker, kind, walk.values)
@@ -84,6 +87,8 @@ def test_an_env_that_took_the_walk_equals_a_fresh_env_put_into_that_state(G, N, 
             want[1] = payload.payload_rows(walk.values["B"][:, 0], walk.values["B"][:, 1:]).astype(real)
         if "L" in walk.values:
             want[2] = walk.values["L"]
+        if "G" in walk.values:
+            want[3] = walk.values["G"][:, [0, 1, 2, 4, 5, 6]].astype(real)
         for w, x, y in zip(want, reported(walker), reported(fresh)):
             np.testing.assert_array_equal(x, y, err_msg=f"toggle {i} ({kind}): walker against fresh")
             np.testing.assert_array_equal(x, w, err_msg=f"toggle {i} ({kind}): walker against what was set")
@@ -97,6 +102,6 @@ def test_an_env_that_took_the_walk_equals_a_fresh_env_put_into_that_state(G, N, 
         fresh.close()
     for x, y in zip(reported(walker), dflt):      # the walk ends all-off
         np.testing.assert_array_equal(x, y)
-    # the toggles are not no-ops: each changes at least one env's servo gains, base inertia or delay, which two steps of a moving robot show
+    # the toggles are not no-ops: each changes at least one env's servo gains, base inertia, delay or gravity, which two steps of a moving robot show
     assert steps_that_differed == len(WALK) - 1
     walker.close()

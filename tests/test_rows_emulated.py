@@ -1,8 +1,9 @@
-"""The three kinds of per-env rows together - friction / gains, body rows, actuation latency - in the host emulation of the device source
-(tests/emul/nm_emul_rows.cpp), whose layout, default rows, on / off state and level are the host object's own
-(nightmare_rl_amd/csrc/nm_env_rows.h): the walk of tests/rows_walk.py over every single-kind transition from every state of the other two
-kinds. After every toggle the env that took the walk must be indistinguishable from a fresh env put directly into that state: the same
-rows, and bit-identical steps. N = 3 at two envs per wave: one full wave and one half-empty one. No tolerance anywhere."""
+"""The four kinds of per-env rows together - friction / gains, body rows, actuation latency, gravity vectors - in the host emulation of the
+device source (tests/emul/nm_emul_grav.cpp, the shim that has the gravity region), whose layout, default rows, on / off state and level
+are the host object's own (nightmare_rl_amd/csrc/nm_env_rows.h): the walk of tests/rows_walk.py over every single-kind transition from
+every state of the other three kinds. After every toggle the env that took the walk must be indistinguishable from a fresh env put
+directly into that state: the same rows, the same level for full and physics-only launches, and bit-identical steps. N = 3 at two envs
+per wave: one full wave and one half-empty one. No tolerance anywhere."""
 import numpy as np
 import pytest
 
@@ -15,6 +16,13 @@ ARRAYS = ("qpos", "qvel", "qwarm", "dofpos", "dofvel", "act", "cmd", "epsum", "f
 
 @pytest.fixture(scope="module")
 def emul():
+    from emul import emul_grav
+    emul_grav.build()
+    return emul_grav
+
+
+@pytest.fixture(scope="module")
+def emul3():
     from emul import emul_rows
     emul_rows.build()
     return emul_rows
@@ -27,10 +35,10 @@ def G():
 
 @pytest.fixture(scope="module")
 def SETS():
-    """(ENVP_SETS, PAYLOADS, body rows of the payloads): the value sets of the feature suites, from their fixtures."""
+    """(ENVP_SETS, PAYLOADS, body rows of the payloads, gravity rows): the value sets of the feature suites, from their fixtures."""
     from nightmare_rl_amd.model import payload
     envp, pay = load_golden("env_params.npz")["sets"], load_golden("payload.npz")["sets"]
-    return envp, pay, payload.payload_rows(pay[:, 0], pay[:, 1:])
+    return envp, pay, payload.payload_rows(pay[:, 0], pay[:, 1:]), load_golden("gravity.npz")["rows"]
 
 
 def test_the_walk_is_an_eulerian_circuit_of_the_cube():
@@ -38,10 +46,12 @@ def test_the_walk_is_an_eulerian_circuit_of_the_cube():
 
 
 @pytest.mark.parametrize("double", [False, True], ids=["fp32", "fp64"])
-def test_device_and_host_agree_on_where_the_latency_words_lie(emul, double):
-    """nm_core.h lat_delay / lat_hist (the device's way) against nm_env_rows.h (the host's), and the history ends inside the block."""
+def test_device_and_host_agree_on_where_the_latency_words_lie(emul, emul3, double):
+    """nm_core.h lat_delay / lat_hist (the device's way) against nm_env_rows.h (the host's), and the history ends inside the block; in
+    the shim of the walk the gravity rows behind it too."""
     for n in (1, 2, 3, 8, 9):
-        assert emul.EmulRows(n, double=double).device_layout_agrees(), n
+        assert emul3.EmulRows(n, double=double).device_layout_agrees(), n
+        assert emul.EmulGrav(n, double=double).device_layout_agrees(), n
 
 
 def put(env, values, body_of):
@@ -52,6 +62,8 @@ def put(env, values, body_of):
         env.set_body_params(body_of(values["B"]))
     if "L" in values:
         env.set_action_latency(values["L"])
+    if "G" in values:
+        env.set_gravity(values["G"])
 
 
 def load_start(env, g):
@@ -76,29 +88,35 @@ def two_steps(env, g):
 
 @pytest.mark.parametrize("double", [False, True], ids=["fp32", "fp64"])
 def test_an_env_that_took_the_walk_equals_a_fresh_env_put_into_that_state(emul, G, SETS, double):
-    envp_sets, payloads, body_rows = SETS
+    envp_sets, payloads, body_rows, grav_rows = SETS
     real = np.float64 if double else np.float32
     body_of = lambda _: body_rows[walk.idx["B"]]      # the body rows of the payloads that are set now
-    walker = emul.EmulRows(N, double=double, seed=5)
-    f_dflt, b_dflt = envp_sets[0].astype(real), walker.default_row()      # (1.0, 20.0, 0.8) are the model's own values: test_env_params_emulated.py
+    walker = emul.EmulGrav(N, double=double, seed=5)
+    f_dflt, b_dflt = envp_sets[0].astype(real), walker.default_body_row()      # (1.0, 20.0, 0.8) are the model's own values: test_env_params_emulated.py
+    g_dflt = grav_rows[0].astype(real)      # (0, 0, -9.81) twice: test_gravity_emulated.py
     steps_that_differed = 0
     before = None
-    walk = Walk(N, envp_sets, payloads)
+    walk = Walk(N, envp_sets, payloads, grav_rows)
     for i, kind, on in walk:
         # the toggle itself: the walker's one kind changes, the others are not touched
         if kind == "F":
             walker.set_env_params(walk.values.get("F"))
         elif kind == "B":
             walker.set_body_params(body_of(walk.values["B"]) if on else None)
-        else:
+        elif kind == "L":
             walker.set_action_latency(walk.values.get("L"))
-        fresh = emul.EmulRows(N, double=double, seed=5)
+        else:
+            walker.set_gravity(walk.values.get("G"))
+        fresh = emul.EmulGrav(N, double=double, seed=5)
         put(fresh, walk.values, body_of)
         # (a) the rows: walker = fresh = what was set for the kinds that are on, the defaults / zeros for the kinds that are off
-        assert walker.state() == fresh.state() == (walk.on(), walk.level(), walk.level() > 0), (i, kind)
+        for physics_only in (False, True):      # L on without G is 2 when physics-only, G on is 4 either way
+            assert walker.state(physics_only) == fresh.state(physics_only) == (walk.on(), walk.level(physics_only)), (i, kind, physics_only)
+        assert walker.carries_block() == fresh.carries_block() == (walk.level() > 0), (i, kind)
         want = (walk.values["F"].astype(real) if "F" in walk.values else np.tile(f_dflt, (N, 1)),
                 body_of(walk.values["B"]).astype(real) if "B" in walk.values else np.tile(b_dflt, (N, 1)),
-                walk.values.get("L", np.zeros(N, np.int32)))
+                walk.values.get("L", np.zeros(N, np.int32)),
+                walk.values["G"].astype(real) if "G" in walk.values else np.tile(g_dflt, (N, 1)))
         for w, x, y in zip(want, walker.rows(), fresh.rows()):
             np.testing.assert_array_equal(x, y, err_msg=f"toggle {i} ({kind})")
             np.testing.assert_array_equal(x, w.astype(np.float64) if w.dtype != np.int32 else w, err_msg=f"toggle {i} ({kind})")
@@ -109,6 +127,7 @@ def test_an_env_that_took_the_walk_equals_a_fresh_env_put_into_that_state(emul, 
         if before is not None:
             steps_that_differed += any((x != y).any() for x, y in zip(ow, before))
         before = ow
-    assert walker.state() == ("", 0, False)
-    # the toggles are not no-ops: each changes at least one env's servo gains, base inertia or delay, which two steps of a moving robot show
+    assert walker.state() == ("", 0) and not walker.carries_block()
+    assert (walk.level(True), walk.level()) == (0, 0)
+    # the toggles are not no-ops: each changes at least one env's servo gains, base inertia, delay or gravity, which two steps of a moving robot show
     assert steps_that_differed == len(WALK) - 1
