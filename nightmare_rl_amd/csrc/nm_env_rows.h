@@ -15,6 +15,8 @@
 
 namespace nmrows {
 
+enum Kind { kFric = 0, kBody = 1, kLat = 2, kGrav = 3 };
+
 // ---- layout: one block of `real`s - N friction / gain rows, N body rows, then the latency words (4 bytes each in either dtype): N
 // delays, N action histories; then, at the next multiple of sizeof(real), N gravity rows. The device finds the last three through
 // nm::lat_delay / nm::lat_hist / nm::grav_rows_of (nm_core.h), which tests/emul checks against these.
@@ -81,8 +83,29 @@ inline std::string delays_fault(const int* d, int N, int nsub) {
   return std::string();
 }
 
+// ---- descriptors: the kinds that are "N rows of W reals in the env's dtype, set whole, judged on the host" - body and gravity rows - differ
+// in nothing but this. Every owner of a block (the env object, the emulation) has ONE set / get / fill for them, written over a
+// descriptor D: D::kind, D::W, D::rows(base, N), D::dflt(M, out[W]), D::fault(rows, N). A new kind of that shape supplies its descriptor
+// (and its region in the layout above), its entry points, and the device's reads.
+template <Kind K> struct RowKind;
+template <> struct RowKind<kBody> {
+  static constexpr Kind kind = kBody;
+  static constexpr int W = nm::kBodyP;
+  template <class real> static real* rows(real* base, int N) { return body_rows(base, N); }
+  template <class real> static void dflt(const nm::Model<real>& M, real* out) { body_default(M, out); }
+  template <class real> static std::string fault(const real* r, int N) { return body_rows_fault(r, N); }
+};
+template <> struct RowKind<kGrav> {
+  static constexpr Kind kind = kGrav;
+  static constexpr int W = nm::kGravP;
+  template <class real> static real* rows(real* base, int N) { return grav_rows(base, N); }
+  template <class real> static void dflt(const nm::Model<real>& M, real* out) { grav_default(M, out); }
+  template <class real> static std::string fault(const real* r, int N) { return grav_rows_fault(r, N); }
+};
+typedef RowKind<kBody> BodyKind;
+typedef RowKind<kGrav> GravKind;
+
 // ---- state: which kinds are on, and what follows from that for a launch
-enum Kind { kFric = 0, kBody = 1, kLat = 2, kGrav = 3 };
 struct State {
   bool on[4] = {false, false, false, false};
   // the level of the step a launch takes: the highest kind that is on; a physics-only launch ignores latency (level 2 on the rows level 3

@@ -259,7 +259,8 @@ __global__ void k_finalize(int N, real* stat_sum, int* stat_cnt, float* ep_stats
 // caller's [N] array, or is the default where there is none. `get`: the columns of the rows, or the defaults where there are no rows.
 // `draw`: lo + u (hi - lo) in the env's precision, product and sum rounded separately (contraction switched off: a host restatement in
 // plain arithmetic gives the same bits), u = rand_u24_bits(seed + kEnvParamKey, global env id, column) * 2^-24.
-template <class real> struct EnvP3 { real v[3]; };
+template <class real, int L> struct Vals { real v[L]; };      // L values as one kernel argument
+template <class real> using EnvP3 = Vals<real, 3>;
 template <class real> struct EnvP3P { const real* p[3]; };
 template <class real> struct EnvP3W { real* p[3]; };
 template <class real>
@@ -284,55 +285,27 @@ template <class real> __device__ __forceinline__ real envp_lerp(real lo, real u,
   const real p = u * d;
   return lo + p;
 }
-template <class real>
-__global__ void k_envp_draw(real* __restrict__ rows, int N, uint64_t seed, int64_t env_offset, EnvP3<real> lo, EnvP3<real> hi) {
+// The uniform draw of every kind (friction / gains into the rows; payload and gravity parameters into the caller's buffer): C columns per
+// env at a stride of S words, the pad columns zero, under the kind's own `key`.
+template <class real, int C, int S>
+__global__ void k_uniform_draw(real* __restrict__ out, int N, uint64_t seed, uint64_t key, int64_t env_offset, Vals<real, C> lo, Vals<real, C> hi) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 4 * N) return;
-  const int env = i >> 2, col = i & 3;
+  if (i >= S * N) return;
+  const int env = i / S, col = i - S * env;
   real v = real(0);
-  if (col < 3) {
-    const real u = (real)nm::rand_u24_bits(seed + nm::kEnvParamKey, (uint64_t)(env_offset + env), (uint32_t)col) * real(1.0 / 16777216.0);
+  if (col < C) {
+    const real u = (real)nm::rand_u24_bits(seed + key, (uint64_t)(env_offset + env), (uint32_t)col) * real(1.0 / 16777216.0);
     v = envp_lerp(lo.v[col], u, hi.v[col] - lo.v[col]);
   }
-  rows[i] = v;
+  out[i] = v;
 }
-
-// Per-env body rows (base payload, nm::kBodyP words per env). `fill`: the default row for every env (what nm_get_body_params reports while
-// the feature is off). `draw`: (dm, rx, ry, rz) per env by k_envp_draw's generator under its own key, lo + u (hi - lo) through envp_lerp.
-template <class real> struct BodyRow { real v[nm::kBodyP]; };
-template <class real> struct Pay4 { real v[4]; };
-template <class real>
-__global__ void k_body_fill(real* __restrict__ rows, int N, BodyRow<real> dflt) {
+// `fill`: one row of W words for every env - a kind's default row, into its region or into the caller's buffer (what nm_get_body_params /
+// nm_get_gravity report while the block does not exist).
+template <class real, int W>
+__global__ void k_row_fill(real* __restrict__ rows, int N, Vals<real, W> row) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nm::kBodyP * N) return;
-  rows[i] = dflt.v[i % nm::kBodyP];
-}
-template <class real>
-__global__ void k_payload_draw(real* __restrict__ out, int N, uint64_t seed, int64_t env_offset, Pay4<real> lo, Pay4<real> hi) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 4 * N) return;
-  const int env = i >> 2, col = i & 3;
-  const real u = (real)nm::rand_u24_bits(seed + nm::kPayloadKey, (uint64_t)(env_offset + env), (uint32_t)col) * real(1.0 / 16777216.0);
-  out[i] = envp_lerp(lo.v[col], u, hi.v[col] - lo.v[col]);
-}
-
-// Per-env gravity rows (nm::kGravP words per env). `fill`: the default row for every env (what nm_get_gravity reports while the feature
-// is off). `draw`: (three offsets, tilt, azimuth) per env by k_envp_draw's generator under its own key, lo + u (hi - lo) through envp_lerp.
-template <class real> struct GravRow { real v[nm::kGravP]; };
-template <class real> struct Grav5 { real v[5]; };
-template <class real>
-__global__ void k_grav_fill(real* __restrict__ rows, int N, GravRow<real> dflt) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nm::kGravP * N) return;
-  rows[i] = dflt.v[i % nm::kGravP];
-}
-template <class real>
-__global__ void k_gravity_draw(real* __restrict__ out, int N, uint64_t seed, int64_t env_offset, Grav5<real> lo, Grav5<real> hi) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= 5 * N) return;
-  const int env = i / 5, col = i - 5 * env;
-  const real u = (real)nm::rand_u24_bits(seed + nm::kGravityKey, (uint64_t)(env_offset + env), (uint32_t)col) * real(1.0 / 16777216.0);
-  out[i] = envp_lerp(lo.v[col], u, hi.v[col] - lo.v[col]);
+  if (i >= W * N) return;
+  rows[i] = row.v[i % W];
 }
 
 // Per-env actuation latency (nm_core.h kLatP): delay[e] = lo + floor(u (hi - lo + 1)), u = bits * 2^-24 with bits =
@@ -832,6 +805,24 @@ template <class real> struct Env : nm_env {
     push_step += (uint64_t)K;
     return p;
   }
+  // what closes a K-step launch (k_rollout_tail), from the entry point's arguments `r`; the rollout alone bootstraps time-outs
+  template <class R> nmr::TailArgs kstep_tail(const R* r, int K, float gamma = -1.0f, const float* s_values = nullptr, float* s_rewards = nullptr) {
+    return {N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, gamma, s_values, s_rewards,
+            r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
+  }
+  // the books nmr::PlayArgs and nmr::TapeArgs share, from nm_play_args / nm_tape_args: play_scratch ([4 N + 4], allocated by the caller)
+  // stands in for the bookkeeping tensors the caller does not want; advances push_step by K
+  float* play_scratch = nullptr;
+  template <class P, class R> void kstep_books(P& p, const R* r, int K, real* log) {
+    const size_t n_ = (size_t)N;
+    p.cur_ret = r->cur_ret ? r->cur_ret : play_scratch; p.cur_len = r->cur_len ? r->cur_len : play_scratch + n_;
+    p.ret_sum = r->ret_sum ? r->ret_sum : play_scratch + 2 * n_; p.ret_cnt = r->ret_cnt ? r->ret_cnt : play_scratch + 3 * n_;
+    p.fin3 = r->fin3 ? r->fin3 : play_scratch + 4 * n_;
+    p.st_sum = roll_sum; p.st_cnt = roll_cnt; p.to_step = roll_to;
+    p.rec_log = log; p.rec_done = log ? rec_done : nullptr; p.rec_env = rec_env;
+    p.push = kstep_push(K); p.rnoise = kstep_rnoise();
+    rec_done_valid = log != nullptr;
+  }
   int rollout(const nm_rollout_args* r, int act, hipStream_t s) override {
     HIPCHK(hipSetDevice(device));
     if constexpr (sizeof(real) == 8 || NM_ENVS_PER_WAVE != 2) {
@@ -858,14 +849,12 @@ template <class real> struct Env : nm_env {
       R.rec_log = log;
       R.push = kstep_push(K); R.rnoise = kstep_rnoise();
       R.wave_clock = A.dbg ? reinterpret_cast<unsigned long long*>(A.dbg) : nullptr;   // measurement: the debug buffer ([N,256] reals) takes the waves' clocks instead
-      nmr::TailArgs ta{N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, r->bootstrap_time_outs ? r->gamma : -1.0f, r->s_values, r->s_rewards,
-                       r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
+      const nmr::TailArgs ta = kstep_tail(r, K, r->bootstrap_time_outs ? r->gamma : -1.0f, r->s_values, r->s_rewards);
       if (nmr::launch_rollout(M_dev, a, R, ta, act, rows.level(), s)) return fail("nm_rollout: launch failed");
       return 0;
     }
   }
   // ---- K x [policy, step] per launch with nothing collected (nm_play; reference play.py:118-132)
-  float* play_scratch = nullptr;       // [4 N + 4]: stand-ins for the bookkeeping tensors the caller does not want
   int play(const nm_play_args* r, int act, hipStream_t s) override {
     HIPCHK(hipSetDevice(device));
     if constexpr (sizeof(real) == 8 || NM_ENVS_PER_WAVE != 2) {
@@ -888,17 +877,8 @@ template <class real> struct Env : nm_env {
       P.wp = (const nmr::f32x4*)roll_wp; P.bp = roll_bp; P.stdv = r->params_flat_dev + RS::stdoff();
       P.seed = r->seed; P.iter_dev = r->iter_dev; P.step0 = r->step0;
       P.obs0 = r->obs0_dev; P.obs = r->obs_dev; P.actions = r->actions_dev;
-      const size_t n_ = (size_t)N;
-      P.cur_ret = r->cur_ret ? r->cur_ret : play_scratch; P.cur_len = r->cur_len ? r->cur_len : play_scratch + n_;
-      P.ret_sum = r->ret_sum ? r->ret_sum : play_scratch + 2 * n_; P.ret_cnt = r->ret_cnt ? r->ret_cnt : play_scratch + 3 * n_;
-      P.fin3 = r->fin3 ? r->fin3 : play_scratch + 4 * n_;
-      P.st_sum = roll_sum; P.st_cnt = roll_cnt; P.to_step = roll_to;
-      P.rec_log = log; P.rec_done = log ? rec_done : nullptr; P.rec_env = rec_env;
-      P.push = kstep_push(K); P.rnoise = kstep_rnoise();
-      rec_done_valid = log != nullptr;
-      nmr::TailArgs ta{N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, -1.0f, nullptr, nullptr,
-                       r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
-      if (nmr::launch_play(M_dev, a, P, ta, act, rows.level(), s)) return fail("nm_play: launch failed");
+      kstep_books(P, r, K, log);
+      if (nmr::launch_play(M_dev, a, P, kstep_tail(r, K), act, rows.level(), s)) return fail("nm_play: launch failed");
       return 0;
     }
   }
@@ -921,18 +901,10 @@ template <class real> struct Env : nm_env {
       nmr::TapeArgs T;
       T.K = K; T.tape = r->actions_dev;
       T.rec_obs = r->rec_obs_dev; T.rec_rew = r->rec_rew_dev; T.rec_dones = r->rec_done_dev;
-      const size_t n_ = (size_t)N;
-      T.cur_ret = r->cur_ret ? r->cur_ret : play_scratch; T.cur_len = r->cur_len ? r->cur_len : play_scratch + n_;
-      T.ret_sum = r->ret_sum ? r->ret_sum : play_scratch + 2 * n_; T.ret_cnt = r->ret_cnt ? r->ret_cnt : play_scratch + 3 * n_;
-      T.fin3 = r->fin3 ? r->fin3 : play_scratch + 4 * n_;
-      T.st_sum = roll_sum; T.st_cnt = roll_cnt; T.to_step = roll_to;
-      T.rec_log = log; T.rec_done = log ? rec_done : nullptr; T.rec_env = rec_env;
-      T.push = kstep_push(K); T.rnoise = kstep_rnoise();
-      rec_done_valid = log != nullptr;
-      nmr::TailArgs ta{N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, -1.0f, nullptr, nullptr,
-                       r->ep_idx_dev, r->n_ep, r->ep_acc_dev, A.to_owner};
-      if (nmr::launch_tape(M_dev, a, T, ta, rows.level(), s)) return fail("nm_step_tape: launch failed");
+      kstep_books(T, r, K, log);
+      if (nmr::launch_tape(M_dev, a, T, kstep_tail(r, K), rows.level(), s)) return fail("nm_step_tape: launch failed");
       // with an observation record every step filed its observation in its row: the env's own buffer receives the last one
+      const size_t n_ = (size_t)N;
       if (r->rec_obs_dev)
         HIPCHK(hipMemcpyAsync(r->obs_dev, r->rec_obs_dev + (size_t)(K - 1) * n_ * nm::kNOBS, n_ * nm::kNOBS * sizeof(float), hipMemcpyDeviceToDevice, s));
       return 0;
@@ -945,20 +917,8 @@ template <class real> struct Env : nm_env {
   real* envp_dev = nullptr;
   nmrows::State rows;
   EnvP3<real> envp_default() const { EnvP3<real> d; nmrows::fric_default(M, d.v); return d; }
-  BodyRow<real> body_default() const { BodyRow<real> r; nmrows::body_default(M, r.v); return r; }
   int envp_write(EnvP3P<real> src, hipStream_t s) {      // a null column = its default: all null refills the defaults
     hipLaunchKernelGGL(k_envp_set<real>, dim3((4 * N + 255) / 256), dim3(256), 0, s, envp_dev, N, src, envp_default());
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  int body_fill_default(real* dst, hipStream_t s) {
-    hipLaunchKernelGGL(k_body_fill<real>, dim3((nm::kBodyP * N + 255) / 256), dim3(256), 0, s, dst, N, body_default());
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
-  GravRow<real> grav_default() const { GravRow<real> r; nmrows::grav_default(M, r.v); return r; }
-  int grav_fill_default(real* dst, hipStream_t s) {
-    hipLaunchKernelGGL(k_grav_fill<real>, dim3((nm::kGravP * N + 255) / 256), dim3(256), 0, s, dst, N, grav_default());
     HIPCHK(hipGetLastError());
     return 0;
   }
@@ -966,11 +926,50 @@ template <class real> struct Env : nm_env {
   int rows_alloc(hipStream_t s) {
     if (envp_dev) return 0;
     if (dalloc(&envp_dev, nmrows::block_reals<real>((size_t)N))) return 1;
-    return envp_write({}, s) || body_fill_default(nmrows::body_rows(envp_dev, N), s) || grav_fill_default(nmrows::grav_rows(envp_dev, N), s);
+    return envp_write({}, s) || kind_fill<nmrows::BodyKind>(nmrows::body_rows(envp_dev, N), s) || kind_fill<nmrows::GravKind>(nmrows::grav_rows(envp_dev, N), s);
   }
   int rows_turn(nmrows::Kind k, bool on) {
     rows.on[k] = on;
     A.envp = rows.envp(envp_dev);
+    return 0;
+  }
+  // ---- the kinds with a descriptor D (nm_env_rows.h RowKind: body rows, gravity rows); `who`: the entry point's name
+  template <class D> int kind_fill(real* dst, hipStream_t s) {      // the default row for every env
+    Vals<real, D::W> r;
+    D::dflt(M, r.v);
+    hipLaunchKernelGGL((k_row_fill<real, D::W>), dim3((D::W * N + 255) / 256), dim3(256), 0, s, dst, N, r);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  template <class D> int kind_set(const char* who, const void* rows_in, hipStream_t s) {
+    HIPCHK(hipSetDevice(device));
+    if (!rows_in) {       // off; nothing is freed
+      if (envp_dev && kind_fill<D>(D::rows(envp_dev, N), s)) return 1;
+      return rows_turn(D::kind, false);
+    }
+    // the rows are judged on the host before anything of the env changes
+    std::vector<real> h((size_t)N * D::W);
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpy(h.data(), rows_in, h.size() * sizeof(real), hipMemcpyDeviceToHost));
+    const std::string why = D::fault(h.data(), N);
+    if (!why.empty()) return fail(std::string(who) + ": " + why);
+    if (rows_alloc(s)) return 1;
+    HIPCHK(hipMemcpyAsync(D::rows(envp_dev, N), rows_in, h.size() * sizeof(real), hipMemcpyDeviceToDevice, s));
+    return rows_turn(D::kind, true);
+  }
+  template <class D> int kind_get(void* out, hipStream_t s) {
+    HIPCHK(hipSetDevice(device));
+    if (!out) return 0;
+    if (!envp_dev) return kind_fill<D>((real*)out, s);
+    HIPCHK(hipMemcpyAsync(out, D::rows(envp_dev, N), (size_t)N * D::W * sizeof(real), hipMemcpyDeviceToDevice, s));
+    return 0;
+  }
+  // C uniform columns per env at a stride of S words under `key` (k_uniform_draw), into the rows or into the caller's buffer
+  template <int C, int S> int draw(real* out, uint64_t key, const double* lo, const double* hi, hipStream_t s) {
+    Vals<real, C> l, h;
+    for (int k = 0; k < C; k++) { l.v[k] = (real)lo[k]; h.v[k] = (real)hi[k]; }
+    hipLaunchKernelGGL((k_uniform_draw<real, C, S>), dim3((S * N + 255) / 256), dim3(256), 0, s, out, N, A.seed, key, A.env_offset, l, h);
+    HIPCHK(hipGetLastError());
     return 0;
   }
   int set_env_params(const void* mu, const void* p_gain, const void* kv, hipStream_t s) override {
@@ -992,44 +991,21 @@ template <class real> struct Env : nm_env {
   }
   int draw_env_params(const double* lo, const double* hi, hipStream_t s) override {
     HIPCHK(hipSetDevice(device));
-    if (rows_alloc(s)) return 1;
-    EnvP3<real> l, h;
-    for (int k = 0; k < 3; k++) { l.v[k] = (real)lo[k]; h.v[k] = (real)hi[k]; }
-    hipLaunchKernelGGL(k_envp_draw<real>, dim3((4 * N + 255) / 256), dim3(256), 0, s, envp_dev, N, A.seed, A.env_offset, l, h);
-    HIPCHK(hipGetLastError());
+    if (rows_alloc(s) || draw<3, nm::kEnvP>(envp_dev, nm::kEnvParamKey, lo, hi, s)) return 1;
     return rows_turn(nmrows::kFric, true);
   }
-  // ---- per-env body rows (base payload)
-  int set_body_params(const void* rows_in, hipStream_t s) override {
+  // ---- per-env body rows (base payload) and gravity rows: the descriptor kinds
+  int set_body_params(const void* rows_in, hipStream_t s) override { return kind_set<nmrows::BodyKind>("nm_set_body_params", rows_in, s); }
+  int get_body_params(void* out, hipStream_t s) override { return kind_get<nmrows::BodyKind>(out, s); }
+  int draw_payload(const double* lo, const double* hi, void* out, hipStream_t s) override {      // (dm, rx, ry, rz)
     HIPCHK(hipSetDevice(device));
-    if (!rows_in) {       // off; nothing is freed
-      if (envp_dev && body_fill_default(nmrows::body_rows(envp_dev, N), s)) return 1;
-      return rows_turn(nmrows::kBody, false);
-    }
-    // the rows are judged on the host before anything of the env changes
-    std::vector<real> h((size_t)N * nm::kBodyP);
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipMemcpy(h.data(), rows_in, h.size() * sizeof(real), hipMemcpyDeviceToHost));
-    const std::string why = nmrows::body_rows_fault(h.data(), N);
-    if (!why.empty()) return fail("nm_set_body_params: " + why);
-    if (rows_alloc(s)) return 1;
-    HIPCHK(hipMemcpyAsync(nmrows::body_rows(envp_dev, N), rows_in, h.size() * sizeof(real), hipMemcpyDeviceToDevice, s));
-    return rows_turn(nmrows::kBody, true);
+    return draw<4, 4>((real*)out, nm::kPayloadKey, lo, hi, s);
   }
-  int get_body_params(void* out, hipStream_t s) override {
+  int set_gravity(const void* rows_in, hipStream_t s) override { return kind_set<nmrows::GravKind>("nm_set_gravity", rows_in, s); }
+  int get_gravity(void* out, hipStream_t s) override { return kind_get<nmrows::GravKind>(out, s); }
+  int draw_gravity(const double* lo, const double* hi, void* out, hipStream_t s) override {      // (three offsets, tilt, azimuth)
     HIPCHK(hipSetDevice(device));
-    if (!out) return 0;
-    if (!envp_dev) return body_fill_default((real*)out, s);
-    HIPCHK(hipMemcpyAsync(out, nmrows::body_rows(envp_dev, N), (size_t)N * nm::kBodyP * sizeof(real), hipMemcpyDeviceToDevice, s));
-    return 0;
-  }
-  int draw_payload(const double* lo, const double* hi, void* out, hipStream_t s) override {
-    HIPCHK(hipSetDevice(device));
-    Pay4<real> l, h;
-    for (int k = 0; k < 4; k++) { l.v[k] = (real)lo[k]; h.v[k] = (real)hi[k]; }
-    hipLaunchKernelGGL(k_payload_draw<real>, dim3((4 * N + 255) / 256), dim3(256), 0, s, (real*)out, N, A.seed, A.env_offset, l, h);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return draw<5, 5>((real*)out, nm::kGravityKey, lo, hi, s);
   }
   // ---- per-env actuation latency
   int set_action_latency(const int* substeps, hipStream_t s) override {
@@ -1076,38 +1052,6 @@ template <class real> struct Env : nm_env {
   int get_action_history(float* out, hipStream_t s) override {
     return words_out(out, envp_dev ? nmrows::histories(envp_dev, N) : nullptr, nmrows::hist_words((size_t)N), s);
   }
-  // ---- per-env gravity rows
-  int set_gravity(const void* rows_in, hipStream_t s) override {
-    HIPCHK(hipSetDevice(device));
-    if (!rows_in) {       // off; nothing is freed
-      if (envp_dev && grav_fill_default(nmrows::grav_rows(envp_dev, N), s)) return 1;
-      return rows_turn(nmrows::kGrav, false);
-    }
-    // the rows are judged on the host before anything of the env changes
-    std::vector<real> h((size_t)N * nm::kGravP);
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipMemcpy(h.data(), rows_in, h.size() * sizeof(real), hipMemcpyDeviceToHost));
-    const std::string why = nmrows::grav_rows_fault(h.data(), N);
-    if (!why.empty()) return fail("nm_set_gravity: " + why);
-    if (rows_alloc(s)) return 1;
-    HIPCHK(hipMemcpyAsync(nmrows::grav_rows(envp_dev, N), rows_in, h.size() * sizeof(real), hipMemcpyDeviceToDevice, s));
-    return rows_turn(nmrows::kGrav, true);
-  }
-  int get_gravity(void* out, hipStream_t s) override {
-    HIPCHK(hipSetDevice(device));
-    if (!out) return 0;
-    if (!envp_dev) return grav_fill_default((real*)out, s);
-    HIPCHK(hipMemcpyAsync(out, nmrows::grav_rows(envp_dev, N), (size_t)N * nm::kGravP * sizeof(real), hipMemcpyDeviceToDevice, s));
-    return 0;
-  }
-  int draw_gravity(const double* lo, const double* hi, void* out, hipStream_t s) override {
-    HIPCHK(hipSetDevice(device));
-    Grav5<real> l, h;
-    for (int k = 0; k < 5; k++) { l.v[k] = (real)lo[k]; h.v[k] = (real)hi[k]; }
-    hipLaunchKernelGGL(k_gravity_draw<real>, dim3((5 * N + 255) / 256), dim3(256), 0, s, (real*)out, N, A.seed, A.env_offset, l, h);
-    HIPCHK(hipGetLastError());
-    return 0;
-  }
   void set_dbg(void* p) override { A.dbg = (real*)p; }
   void set_ret_acc(float* p) override { A.ret_acc = p; }
   int invalidate_time_outs(hipStream_t s) override {
@@ -1138,24 +1082,29 @@ static const char* kRewardNames[NM_NUM_REWARDS] = {"action_rate", "ang_vel_xy", 
                                                    "dof_vel", "feet_air_time", "feet_contact_forces", "lin_vel_z", "orientation", "stand_still",
                                                    "torques", "tracking_ang_vel", "tracking_lin_vel", "termination"};
 static_assert(NM_NUM_REWARDS == nm::kNREW, "reward table size");
+// nm_config (the ABI's) <-> nmhost::EnvConfig (the host model's): the same fields, in either direction; the reward table alone has two names
+static double* scales_of(nm_config& c) { return c.reward_scales; }
+static const double* scales_of(const nm_config& c) { return c.reward_scales; }
+static double* scales_of(nmhost::EnvConfig& c) { return c.rew_scales; }
+static const double* scales_of(const nmhost::EnvConfig& c) { return c.rew_scales; }
+template <class Dst, class Src> static void config_copy(Dst& d, const Src& s) {
+  d.decimation = s.decimation; d.p_gain = s.p_gain; d.action_scale = s.action_scale;
+  for (int i = 0; i < 3; i++) d.default_pos[i] = s.default_pos[i];
+  d.clip_actions = s.clip_actions; d.clip_observations = s.clip_observations;
+  d.obs_lin_vel = s.obs_lin_vel; d.obs_ang_vel = s.obs_ang_vel; d.obs_dof_pos = s.obs_dof_pos; d.obs_dof_vel = s.obs_dof_vel;
+  d.episode_length_s = s.episode_length_s; d.resampling_time = s.resampling_time;
+  d.max_lin_vel_x = s.max_lin_vel_x; d.max_ang_vel = s.max_ang_vel;
+  d.termination_contact_force = s.termination_contact_force; d.tracking_sigma = s.tracking_sigma;
+  for (int i = 0; i < NM_NUM_REWARDS; i++) scales_of(d)[i] = scales_of(s)[i];
+  d.tibia_contact_mode = s.tibia_contact_mode; d.tibia_max_contact_force = s.tibia_max_contact_force;
+  d.body_contact_mode = s.body_contact_mode; d.body_max_contact_force = s.body_max_contact_force;
+  d.base_height_target = s.base_height_target; d.max_contact_force = s.max_contact_force;
+}
 extern "C" {
 const char* nm_last_error(void) { return g_err.c_str(); }
 int nm_policy_set_error(const char* m) { return fail(m); }
 const char* nm_reward_name(int i) { return (i >= 0 && i < NM_NUM_REWARDS) ? kRewardNames[i] : ""; }
-void nm_default_config(nm_config* c) {
-  nmhost::EnvConfig d;
-  c->decimation = d.decimation; c->p_gain = d.p_gain; c->action_scale = d.action_scale;
-  for (int i = 0; i < 3; i++) c->default_pos[i] = d.default_pos[i];
-  c->clip_actions = d.clip_actions; c->clip_observations = d.clip_observations;
-  c->obs_lin_vel = d.obs_lin_vel; c->obs_ang_vel = d.obs_ang_vel; c->obs_dof_pos = d.obs_dof_pos; c->obs_dof_vel = d.obs_dof_vel;
-  c->episode_length_s = d.episode_length_s; c->resampling_time = d.resampling_time;
-  c->max_lin_vel_x = d.max_lin_vel_x; c->max_ang_vel = d.max_ang_vel;
-  c->termination_contact_force = d.termination_contact_force; c->tracking_sigma = d.tracking_sigma;
-  for (int i = 0; i < NM_NUM_REWARDS; i++) c->reward_scales[i] = d.rew_scales[i];
-  c->tibia_contact_mode = d.tibia_contact_mode; c->tibia_max_contact_force = d.tibia_max_contact_force;
-  c->body_contact_mode = d.body_contact_mode; c->body_max_contact_force = d.body_max_contact_force;
-  c->base_height_target = d.base_height_target; c->max_contact_force = d.max_contact_force;
-}
+void nm_default_config(nm_config* c) { config_copy(*c, nmhost::EnvConfig()); }
 int nm_create(const nm_config* cfg, int32_t num_envs, int32_t device, uint64_t seed, int64_t env_id_offset, int32_t dtype, nm_env** out) {
   if (!out) return fail("nm_create: out is NULL");
   *out = nullptr;
@@ -1172,17 +1121,7 @@ int nm_create(const nm_config* cfg, int32_t num_envs, int32_t device, uint64_t s
     if ((int)(cfg->resampling_time / (NM_TIMESTEP * cfg->decimation)) < 1) return fail("nm_create: resampling_time must be at least one env step (dt)");
     if (cfg->tibia_contact_mode < 0 || cfg->tibia_contact_mode > 2 || cfg->body_contact_mode < 0 || cfg->body_contact_mode > 2)
       return fail("nm_create: contact modes are 0 (ignore), 1 (penalise) or 2 (terminate)");
-    c.decimation = cfg->decimation; c.p_gain = cfg->p_gain; c.action_scale = cfg->action_scale;
-    for (int i = 0; i < 3; i++) c.default_pos[i] = cfg->default_pos[i];
-    c.clip_actions = cfg->clip_actions; c.clip_observations = cfg->clip_observations;
-    c.obs_lin_vel = cfg->obs_lin_vel; c.obs_ang_vel = cfg->obs_ang_vel; c.obs_dof_pos = cfg->obs_dof_pos; c.obs_dof_vel = cfg->obs_dof_vel;
-    c.episode_length_s = cfg->episode_length_s; c.resampling_time = cfg->resampling_time;
-    c.max_lin_vel_x = cfg->max_lin_vel_x; c.max_ang_vel = cfg->max_ang_vel;
-    c.termination_contact_force = cfg->termination_contact_force; c.tracking_sigma = cfg->tracking_sigma;
-    for (int i = 0; i < NM_NUM_REWARDS; i++) c.rew_scales[i] = cfg->reward_scales[i];
-    c.tibia_contact_mode = cfg->tibia_contact_mode; c.tibia_max_contact_force = cfg->tibia_max_contact_force;
-    c.body_contact_mode = cfg->body_contact_mode; c.body_max_contact_force = cfg->body_max_contact_force;
-    c.base_height_target = cfg->base_height_target; c.max_contact_force = cfg->max_contact_force;
+    config_copy(c, *cfg);
   }
   nm_env* e;
   int rc;
@@ -1338,20 +1277,32 @@ int nm_get_env_params(nm_env* env, void* mu_dev, void* p_gain_dev, void* kv_dev,
   NEED_ENV(env);
   return env->get_env_params(mu_dev, p_gain_dev, kv_dev, (hipStream_t)stream);
 }
-int nm_draw_env_params(nm_env* env, const double lo[3], const double hi[3], void* stream) {
-  // every refusal comes before the first device call; the bounds are judged first, so a bad range is named whatever the handle is
-  if (!lo || !hi) return fail("nm_draw_env_params: lo / hi is NULL");
-  static const char* kCol[3] = {"mu", "p_gain", "kv"};
-  for (int k = 0; k < 3; k++) {
-    if (!std::isfinite(lo[k]) || !std::isfinite(hi[k])) return fail(std::string("nm_draw_env_params: the bounds of ") + kCol[k] + " must be finite");
-    if (lo[k] > hi[k]) return fail(std::string("nm_draw_env_params: lo > hi for ") + kCol[k]);
-    if (k == 0 && !(lo[k] > 1e-5)) return fail("nm_draw_env_params: mu must be above 1e-5");
-    if (k != 0 && lo[k] < 0.0) return fail(std::string("nm_draw_env_params: ") + kCol[k] + " must not be negative");
+// What the draws that take lo[n] / hi[n] refuse before the first device call, in this order: null bounds; per column finite, lo <= hi and the
+// entry point's own `extra` check (null: none; it returns what is wrong with the column or null); the handle; `out` where there is one;
+// the bounds in float32 for an fp32 env. The bounds come first, so a bad range is named whatever the handle is. `who`: the entry point's name.
+static int draw_bounds_bad(const char* who, nm_env* env, const double* lo, const double* hi, const char* const* col, int n,
+                           const char* (*extra)(int k, double lo), bool has_out, const void* out) {
+  const std::string w = std::string(who) + ": ";
+  if (!lo || !hi) return fail(w + "lo / hi is NULL");
+  for (int k = 0; k < n; k++) {
+    if (!std::isfinite(lo[k]) || !std::isfinite(hi[k])) return fail(w + "the bounds of " + col[k] + " must be finite");
+    if (lo[k] > hi[k]) return fail(w + "lo > hi for " + col[k]);
+    if (const char* why = extra ? extra(k, lo[k]) : nullptr) return fail(w + why);
   }
-  NEED_ENV(env);
+  if (!env) return fail(w + "env is NULL");
+  if (has_out && !out) return fail(w + "out is NULL");
   if (env->dtype == NM_DTYPE_F32)
-    for (int k = 0; k < 3; k++)
-      if (!std::isfinite((float)hi[k])) return fail(std::string("nm_draw_env_params: the bounds of ") + kCol[k] + " must be finite in float32");
+    for (int k = 0; k < n; k++)
+      if (!std::isfinite((float)lo[k]) || !std::isfinite((float)hi[k])) return fail(w + "the bounds of " + col[k] + " must be finite in float32");
+  return 0;
+}
+int nm_draw_env_params(nm_env* env, const double lo[3], const double hi[3], void* stream) {
+  static const char* kCol[3] = {"mu", "p_gain", "kv"};
+  const auto extra = [](int k, double lo_k) -> const char* {
+    static const char* kNeg[3] = {nullptr, "p_gain must not be negative", "kv must not be negative"};
+    return k == 0 ? (lo_k > 1e-5 ? nullptr : "mu must be above 1e-5") : (lo_k < 0.0 ? kNeg[k] : nullptr);
+  };
+  if (draw_bounds_bad("nm_draw_env_params", env, lo, hi, kCol, 3, extra, false, nullptr)) return 1;
   return env->draw_env_params(lo, hi, (hipStream_t)stream);
 }
 int nm_set_body_params(nm_env* env, const void* rows_dev, void* stream) {
@@ -1363,18 +1314,8 @@ int nm_get_body_params(nm_env* env, void* out_dev, void* stream) {
   return env->get_body_params(out_dev, (hipStream_t)stream);
 }
 int nm_draw_payload(nm_env* env, const double lo[4], const double hi[4], void* out_dev, void* stream) {
-  // every refusal comes before the first device call; the bounds are judged first, so a bad range is named whatever the handle is
-  if (!lo || !hi) return fail("nm_draw_payload: lo / hi is NULL");
   static const char* kCol[4] = {"dm", "rx", "ry", "rz"};
-  for (int k = 0; k < 4; k++) {
-    if (!std::isfinite(lo[k]) || !std::isfinite(hi[k])) return fail(std::string("nm_draw_payload: the bounds of ") + kCol[k] + " must be finite");
-    if (lo[k] > hi[k]) return fail(std::string("nm_draw_payload: lo > hi for ") + kCol[k]);
-  }
-  NEED_ENV(env);
-  if (!out_dev) return fail("nm_draw_payload: out is NULL");
-  if (env->dtype == NM_DTYPE_F32)
-    for (int k = 0; k < 4; k++)
-      if (!std::isfinite((float)lo[k]) || !std::isfinite((float)hi[k])) return fail(std::string("nm_draw_payload: the bounds of ") + kCol[k] + " must be finite in float32");
+  if (draw_bounds_bad("nm_draw_payload", env, lo, hi, kCol, 4, nullptr, true, out_dev)) return 1;
   return env->draw_payload(lo, hi, out_dev, (hipStream_t)stream);
 }
 int nm_set_action_latency(nm_env* env, const int32_t* substeps_dev, void* stream) {
@@ -1409,18 +1350,8 @@ int nm_get_gravity(nm_env* env, void* out_dev, void* stream) {
   return env->get_gravity(out_dev, (hipStream_t)stream);
 }
 int nm_draw_gravity(nm_env* env, const double lo[5], const double hi[5], void* out_dev, void* stream) {
-  // every refusal comes before the first device call; the bounds are judged first, so a bad range is named whatever the handle is
-  if (!lo || !hi) return fail("nm_draw_gravity: lo / hi is NULL");
   static const char* kCol[5] = {"offset x", "offset y", "offset z", "tilt", "azimuth"};
-  for (int k = 0; k < 5; k++) {
-    if (!std::isfinite(lo[k]) || !std::isfinite(hi[k])) return fail(std::string("nm_draw_gravity: the bounds of ") + kCol[k] + " must be finite");
-    if (lo[k] > hi[k]) return fail(std::string("nm_draw_gravity: lo > hi for ") + kCol[k]);
-  }
-  NEED_ENV(env);
-  if (!out_dev) return fail("nm_draw_gravity: out is NULL");
-  if (env->dtype == NM_DTYPE_F32)
-    for (int k = 0; k < 5; k++)
-      if (!std::isfinite((float)lo[k]) || !std::isfinite((float)hi[k])) return fail(std::string("nm_draw_gravity: the bounds of ") + kCol[k] + " must be finite in float32");
+  if (draw_bounds_bad("nm_draw_gravity", env, lo, hi, kCol, 5, nullptr, true, out_dev)) return 1;
   return env->draw_gravity(lo, hi, out_dev, (hipStream_t)stream);
 }
 int nm_step_tape(nm_env* env, const nm_tape_args* args, void* stream) {

@@ -1,6 +1,6 @@
 """ctypes binding of the host SIMT emulation with the per-env rows of nm::Args::envp: friction / gains, body rows (base payload), actuation
-latency (tests only; see nm_emul_rows.cpp). One shim for the three kinds: layout, defaults, state and level are the host object's own
-(nightmare_rl_amd/csrc/nm_env_rows.h)."""
+latency, gravity vectors (tests only; see nm_emul_rows.cpp). One shim for the four kinds: layout, defaults, admission, state and level are
+the host object's own (nightmare_rl_amd/csrc/nm_env_rows.h)."""
 import ctypes as C
 import os
 import subprocess
@@ -43,17 +43,18 @@ def lib():
         L.emur_step.argtypes = [C.c_void_p] * 7 + [C.c_int, C.c_int, C.c_void_p]
         L.emur_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         L.emur_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        for f in (L.emur_set_envp, L.emur_set_body, L.emur_set_latency, L.emur_default_row):
+        for f in (L.emur_set_envp, L.emur_set_body, L.emur_set_latency, L.emur_set_gravity, L.emur_default_body_row, L.emur_on_flags):
             f.argtypes = [C.c_void_p, C.c_void_p]
-        L.emur_get_rows.argtypes = [C.c_void_p] * 4
-        L.emur_state.argtypes = [C.c_void_p]
+        L.emur_get_rows.argtypes = [C.c_void_p] * 5
+        L.emur_level.argtypes = [C.c_void_p, C.c_int]
+        L.emur_carries_block.argtypes = [C.c_void_p]
         L.emur_device_layout_agrees.argtypes = [C.c_void_p]
         L.emur_hist.argtypes = [C.c_void_p]
         L.emur_hist.restype = C.POINTER(C.c_float)
         L.emur_eplen.argtypes = [C.c_void_p]
         L.emur_eplen.restype = C.POINTER(C.c_int64)
         L.emur_together_count.restype = C.c_long
-        assert L.emur_lat_h() == H
+        assert L.emur_lat_h() == H and L.emur_grav_p() == 8
         _lib = L
     return _lib
 
@@ -64,7 +65,7 @@ def _p(a):
 
 WHAT = dict(qpos=(0, 25), qvel=(1, 24), qwarm=(2, 24), dofpos=(3, 18), dofvel=(4, 18), act=(5, 18), cmd=(6, 3), epsum=(7, 16),
             feetair=(8, 6), feetflags=(9, 1), hcache=(10, 8), rngctr=(11, 1))      # the last four: what else a step carries over
-DBG_NTOG, DBG_NCON = 156, 160      # words of an env's debug row (nm_core.h env_debug)
+DBG_NTOG, DBG_NCON, DBG_NWARN = 156, 160, 161      # words of an env's debug row (nm_core.h env_debug)
 
 
 class EmulRows:
@@ -95,31 +96,51 @@ class EmulRows:
         self.L.emur_set_envp(self.h, _p(r))
 
     def set_body_params(self, rows=None):
-        """[N,20] body rows (nightmare_rl_amd.model.payload.payload_rows), or None: off."""
+        """[N,20] body rows (nightmare_rl_amd.model.payload.payload_rows), or None: off. ValueError where the host's admission refuses
+        them (nothing changes)."""
         r = None if rows is None else np.ascontiguousarray(rows, np.float64).reshape(self.N, 20)
-        self.L.emur_set_body(self.h, _p(r))
+        if self.L.emur_set_body(self.h, _p(r)):
+            raise ValueError("body rows refused")
 
     def set_action_latency(self, substeps=None):
         """[N] delays in physics substeps, or None: off."""
         d = None if substeps is None else np.ascontiguousarray(substeps, np.int32).reshape(self.N)
         self.L.emur_set_latency(self.h, _p(d))
 
-    def default_row(self):
-        """The model's own row in the env's precision: what nm_get_body_params reports while the feature is off."""
+    def set_gravity(self, rows=None):
+        """[N,8] rows (g[3], pad, gravity_vec[3], pad) or None: off. ValueError where the host's admission refuses them (nothing changes)."""
+        r = None if rows is None else np.ascontiguousarray(rows, np.float64).reshape(self.N, 8)
+        if self.L.emur_set_gravity(self.h, _p(r)):
+            raise ValueError("gravity rows refused")
+
+    def default_body_row(self):
+        """The model's own body row in the env's precision: what nm_get_body_params reports while the feature is off."""
         out = np.zeros(20)
-        self.L.emur_default_row(self.h, _p(out))
+        self.L.emur_default_body_row(self.h, _p(out))
         return out
 
-    def rows(self):
-        """What the block holds, whatever is on: ([N,3] friction / gains, [N,20] body rows, [N] delays)."""
-        e, b, d = np.zeros((self.N, 3)), np.zeros((self.N, 20)), np.zeros(self.N, np.int32)
-        self.L.emur_get_rows(self.h, _p(e), _p(b), _p(d))
-        return e, b, d
+    default_row = default_body_row
 
-    def state(self):
-        """(kinds that are on as a string of F, B, L; level of a full step; whether a launch carries the block)."""
-        s = self.L.emur_state(self.h)
-        return "".join(k for i, k in enumerate("FBL") if s >> i & 1), s >> 4 & 3, bool(s >> 6 & 1)
+    def rows(self):
+        """What the block holds, whatever is on (the defaults of a kind that is off): ([N,3] friction / gains, [N,20] body rows, [N] delays,
+        [N,8] gravity rows)."""
+        e, b, d, g = np.zeros((self.N, 3)), np.zeros((self.N, 20)), np.zeros(self.N, np.int32), np.zeros((self.N, 8))
+        self.L.emur_get_rows(self.h, _p(e), _p(b), _p(d), _p(g))
+        return e, b, d, g
+
+    def gravity(self):
+        """What the gravity region holds, whatever is on: the defaults while the kind is off."""
+        return self.rows()[3]
+
+    def state(self, physics_only=False):
+        """(kinds that are on as a string of F, B, L, G; the level a launch takes)."""
+        on = np.zeros(4, np.int32)
+        self.L.emur_on_flags(self.h, _p(on))
+        return "".join(k for i, k in enumerate("FBLG") if on[i]), self.L.emur_level(self.h, int(physics_only))
+
+    def carries_block(self):
+        """Whether a launch carries the block at all (nm::Args::envp non-null)."""
+        return bool(self.L.emur_carries_block(self.h))
 
     def device_layout_agrees(self):
         return bool(self.L.emur_device_layout_agrees(self.h))

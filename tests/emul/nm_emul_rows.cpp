@@ -1,8 +1,8 @@
-// nm_emul_rows.cpp - TEST SCAFFOLDING: the host emulation of the device kernel source (see nm_emul.cpp) with the per-env rows of
-// nm::Args::envp exposed - friction / gain rows, the body rows of a base payload, actuation delays and the action history behind them.
-// Layout, default rows, the on / off state and the level of the step a launch takes are NOT restated here: they are the host object's
-// own (nightmare_rl_amd/csrc/nm_env_rows.h), so a suite that steps this shim tests the host's policy itself. Never linked into the
-// product library.
+// nm_emul_rows.cpp - TEST SCAFFOLDING: the host emulation of the device kernel source (see nm_emul.cpp) with ALL per-env rows of
+// nm::Args::envp exposed - friction / gain rows, the body rows of a base payload, actuation delays and the action history behind them,
+// gravity rows - and the level-4 LDS image (nm::ShWG), so every level of the step can run in it. Layout, default rows, admission, the
+// on / off state and the level of the step a launch takes are NOT restated here: they are the host object's own
+// (nightmare_rl_amd/csrc/nm_env_rows.h), so a suite that steps this shim tests the host's policy itself. Never linked into the product library.
 //
 // With -DNM_EMUL_ROWS_MAIN the file is a stand-alone program (for sanitizer builds, which must not be loaded into Python):
 // <program> envp|payload|latency <states file> steps one mixed batch of eight envs per population of that feature's fixture, from start
@@ -13,6 +13,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
 #include "../../nightmare_rl_amd/csrc/nm_host_model.h"
@@ -42,7 +43,7 @@ template <class real> struct EmuR {
     for (size_t i = 0; i < n_; i++)
       for (int j = 0; j < 25; j++) qpos[i * 25 + j] = T.qpos0[j];
     envp.assign(nmrows::block_reals<real>(n_), 0);      // the host allocates at first use; from then on, like here, every kind that is off holds its defaults
-    set_envp(nullptr); set_body(nullptr);
+    set_envp(nullptr); set_body(nullptr); set_gravity(nullptr);
   }
   int* delay() { return nmrows::delays(envp.data(), N); }
   float* hist() { return nmrows::histories(envp.data(), N); }
@@ -64,33 +65,43 @@ template <class real> struct EmuR {
       r[3] = real(0);
     }
   }
-  void set_body(const double* in) {   // [N,20] body rows or null = off
-    rows.on[nmrows::kBody] = in != nullptr;
-    real dflt[nm::kBodyP];
-    nmrows::body_default(M, dflt);
-    real* b = nmrows::body_rows(envp.data(), N);
-    for (size_t i = 0; i < (size_t)N * nm::kBodyP; i++) b[i] = in ? (real)in[i] : dflt[i % nm::kBodyP];
+  // the kinds with a descriptor D (nm_env_rows.h RowKind): [N, D::W] rows or null = off; judged by the host's admission before anything
+  // changes (1 = refused)
+  template <class D> int set_kind(const double* in) {
+    real dflt[D::W];
+    D::dflt(M, dflt);
+    std::vector<real> r((size_t)N * D::W);
+    for (size_t i = 0; i < r.size(); i++) r[i] = in ? (real)in[i] : dflt[i % D::W];
+    if (in && !D::fault(r.data(), N).empty()) return 1;
+    std::memcpy(D::rows(envp.data(), N), r.data(), r.size() * sizeof(real));
+    rows.on[D::kind] = in != nullptr;
+    return 0;
   }
+  int set_body(const double* in) { return set_kind<nmrows::BodyKind>(in); }      // [N,20] body rows
+  int set_gravity(const double* in) { return set_kind<nmrows::GravKind>(in); }      // [N,8] rows (g[3], pad, gravity_vec[3], pad)
   void set_latency(const int* d) {   // [N] substeps or null = off; the history keeps what it holds
     rows.on[nmrows::kLat] = d != nullptr;
     for (int i = 0; i < N; i++) delay()[i] = d ? d[i] : 0;
   }
-  void default_row(double* out) const {   // what nm_get_body_params reports while the feature is off
+  void default_body_row(double* out) const {   // what nm_get_body_params reports while the feature is off
     real r[nm::kBodyP];
     nmrows::body_default(M, r);
     for (int j = 0; j < nm::kBodyP; j++) out[j] = (double)r[j];
   }
-  // the device's own way to the latency words (nm_core.h lat_delay / lat_hist) ends where the host's layout says
+  // the device's own way to the words behind the body rows (nm_core.h lat_delay / lat_hist / grav_rows_of) ends where the host's layout
+  // says: the history ends in front of the gravity rows, and those end the block
   bool device_layout_agrees() {
     nm::Args<real> A{};
     A.N = N; A.envp = envp.data();
-    return nm::lat_delay(A) == delay() && nm::lat_hist(A) == hist() &&
-           reinterpret_cast<char*>(hist() + nmrows::hist_words((size_t)N)) <= reinterpret_cast<char*>(envp.data() + envp.size());
+    const real* g = nmrows::grav_rows(envp.data(), N);
+    return nm::lat_delay(A) == delay() && nm::lat_hist(A) == hist() && nm::grav_rows_of(A) == g &&
+           reinterpret_cast<const char*>(hist() + nmrows::hist_words((size_t)N)) <= reinterpret_cast<const char*>(g) &&
+           g + (size_t)N * nm::kGravP == envp.data() + envp.size();
   }
   template <int GG> void waves(const nm::Args<real>& A, int level) {
-    // the largest LDS image for every level: body_rows() / lat_rows() (nm_core.h) address by offset from the wave's images
-    static thread_local nm::ShWL<real, GG> sh;
-    nm::ShW<real, GG>& w = nm::ShWSel<real, GG, 3>::images(sh);
+    // the largest LDS image for every level: body_rows() / lat_rows() / grav_rows() (nm_core.h) address by offset from the wave's images
+    static thread_local nm::ShWG<real, GG> sh;
+    nm::ShW<real, GG>& w = nm::ShWSel<real, GG, 4>::images(sh);
     for (int wv = 0; wv * GG < N; wv++)
       nmrows::with_level(level, [&](auto L) { nm::wave_step<real, GG, decltype(L)::value>(w, M, A, wv); });
   }
@@ -120,11 +131,14 @@ struct Base {
   virtual void get(int what, double* out) = 0;
   virtual void set(int what, const double* in) = 0;
   virtual void set_envp(const double* rows) = 0;
-  virtual void set_body(const double* rows) = 0;
+  virtual int set_body(const double* rows) = 0;
   virtual void set_latency(const int* d) = 0;
-  virtual void default_row(double* out) = 0;
-  virtual void get_rows(double* envp3, double* body20, int* delays) = 0;
-  virtual int state() = 0;
+  virtual int set_gravity(const double* rows) = 0;
+  virtual void default_body_row(double* out) = 0;
+  virtual void get_rows(double* envp3, double* body20, int* delays, double* grav8) = 0;
+  virtual void on_flags(int* on4) = 0;
+  virtual int level(int physics_only) = 0;
+  virtual int carries_block() = 0;
   virtual bool device_layout_agrees() = 0;
   virtual float* hist() = 0;
   virtual int64_t* eplen() = 0;
@@ -138,19 +152,21 @@ template <class real> struct Impl : Base {
     e.array(what, [&](auto& a) { for (size_t i = 0; i < a.size(); i++) a[i] = (typename std::decay_t<decltype(a)>::value_type)in[i]; });
   }
   void set_envp(const double* rows) override { e.set_envp(rows); }
-  void set_body(const double* rows) override { e.set_body(rows); }
+  int set_body(const double* rows) override { return e.set_body(rows); }
   void set_latency(const int* d) override { e.set_latency(d); }
-  void default_row(double* out) override { e.default_row(out); }
-  void get_rows(double* envp3, double* body20, int* delays) override {      // what the block holds, whatever is on
+  int set_gravity(const double* rows) override { return e.set_gravity(rows); }
+  void default_body_row(double* out) override { e.default_body_row(out); }
+  void get_rows(double* envp3, double* body20, int* delays, double* grav8) override {      // what the block holds, whatever is on
     for (int i = 0; i < e.N; i++) {
       for (int k = 0; k < 3; k++) envp3[i * 3 + k] = (double)nmrows::fric_rows(e.envp.data(), e.N)[i * nm::kEnvP + k];
       for (int k = 0; k < nm::kBodyP; k++) body20[i * nm::kBodyP + k] = (double)nmrows::body_rows(e.envp.data(), e.N)[i * nm::kBodyP + k];
+      for (int k = 0; k < nm::kGravP; k++) grav8[i * nm::kGravP + k] = (double)nmrows::grav_rows(e.envp.data(), e.N)[i * nm::kGravP + k];
       delays[i] = e.delay()[i];
     }
   }
-  int state() override {      // bit k: kind k is on; bits 4..5: the level of a full step; bit 6: the launch carries the block
-    return (int)e.rows.on[0] | (int)e.rows.on[1] << 1 | (int)e.rows.on[2] << 2 | e.rows.level() << 4 | (e.rows.envp(e.envp.data()) != nullptr) << 6;
-  }
+  void on_flags(int* on4) override { for (int k = 0; k < 4; k++) on4[k] = e.rows.on[k]; }
+  int level(int physics_only) override { return e.rows.level(physics_only != 0); }
+  int carries_block() override { return e.rows.envp(e.envp.data()) != nullptr; }      // nm::Args::envp of a launch is not null
   bool device_layout_agrees() override { return e.device_layout_agrees(); }
   float* hist() override { return e.hist(); }
   int64_t* eplen() override { return e.ep.data(); }
@@ -172,17 +188,21 @@ void emur_step(void* h, const float* actions, const double* cmd_u, float* obs, f
 void emur_get(void* h, int what, double* out) { ((Base*)h)->get(what, out); }
 void emur_set(void* h, int what, const double* in) { ((Base*)h)->set(what, in); }
 void emur_set_envp(void* h, const double* rows3) { ((Base*)h)->set_envp(rows3); }
-void emur_set_body(void* h, const double* rows20) { ((Base*)h)->set_body(rows20); }
+int emur_set_body(void* h, const double* rows20) { return ((Base*)h)->set_body(rows20); }
 void emur_set_latency(void* h, const int* d) { ((Base*)h)->set_latency(d); }
-void emur_default_row(void* h, double* out20) { ((Base*)h)->default_row(out20); }
-void emur_get_rows(void* h, double* envp3, double* body20, int* delays) { ((Base*)h)->get_rows(envp3, body20, delays); }
-int emur_state(void* h) { return ((Base*)h)->state(); }
+int emur_set_gravity(void* h, const double* rows8) { return ((Base*)h)->set_gravity(rows8); }
+void emur_default_body_row(void* h, double* out20) { ((Base*)h)->default_body_row(out20); }
+void emur_get_rows(void* h, double* envp3, double* body20, int* delays, double* grav8) { ((Base*)h)->get_rows(envp3, body20, delays, grav8); }
+void emur_on_flags(void* h, int* on4) { ((Base*)h)->on_flags(on4); }
+int emur_level(void* h, int physics_only) { return ((Base*)h)->level(physics_only); }
+int emur_carries_block(void* h) { return ((Base*)h)->carries_block(); }
 int emur_device_layout_agrees(void* h) { return ((Base*)h)->device_layout_agrees(); }
 float* emur_hist(void* h) { return ((Base*)h)->hist(); }
 int64_t* emur_eplen(void* h) { return ((Base*)h)->eplen(); }
 long emur_together_count() { return nm::nm_emul_together(); }
 int emur_dbg_n() { return nm::kDbgN; }
 int emur_lat_h() { return nm::kLatH; }
+int emur_grav_p() { return nm::kGravP; }
 }
 #else
 // ---- the stand-alone program:  <program> envp|payload|latency <states file>

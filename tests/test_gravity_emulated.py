@@ -1,4 +1,4 @@
-"""Per-env gravity vectors (gravity rows, level 4 of the step) in the host emulation of the device source (tests/emul/nm_emul_grav.cpp):
+"""Per-env gravity vectors (gravity rows, level 4 of the step) in the host emulation of the device source (tests/emul/nm_emul_rows.cpp):
 the fp64 emulation of a batch that mixes the four gravity sets over its envs against the fp64 fixture of the variant oracles
 (tests/golden/make_gravity_goldens.py: the unchanged oracle compiled against a header with another gravity; for the observed sets with the
 one line of its env layer that holds upstream's constant replaced), teacher-forced and free-running; the fp32 emulation inside the fp32
@@ -20,9 +20,9 @@ def G():
 
 @pytest.fixture(scope="module")
 def emul():
-    from emul import emul_grav
-    emul_grav.build()
-    return emul_grav
+    from emul import emul_rows
+    emul_rows.build()
+    return emul_rows
 
 
 def set_of(n, shift=0):
@@ -45,7 +45,7 @@ def run(emul, g, pop, sets, double, rows, steps=None, envs_per_wave=2, forced=Tr
     returns per-step (obs, rew, done, qpos, qvel), the error figures against the fixture, and what the debug rows counted."""
     n = len(sets)
     ev = np.arange(n) % 8
-    env = emul.EmulGrav(n, double=double, seed=5, envs_per_wave=envs_per_wave)
+    env = emul.EmulRows(n, double=double, seed=5, envs_per_wave=envs_per_wave)
     if envp is not None:
         env.set_env_params(envp)
     if body is not None:
@@ -82,7 +82,7 @@ def test_layout_state_and_admission(G, emul):
     defaults; gravity on means level 4, for physics-only launches too; rows the admission refuses change nothing."""
     for double in (False, True):
         for n in (1, 3, 8):      # n * 55 latency words: odd counts leave the fp64 block a pad word in front of the gravity rows
-            env = emul.EmulGrav(n, double=double)
+            env = emul.EmulRows(n, double=double)
             assert env.device_layout_agrees()
             dflt = env.gravity()
             np.testing.assert_array_equal(dflt, np.tile([0, 0, np.float32(-9.81) if not double else -9.81, 0] * 2, (n, 1)))
@@ -193,7 +193,7 @@ def test_gravity_with_every_other_kind_equals_the_uniform_runs(G, emul):
         same(mixed, uni, sets == k)
 
     def physics(latency):
-        env = emul.EmulGrav(n, double=False, seed=5)
+        env = emul.EmulRows(n, double=False, seed=5)
         env.set_gravity(G["rows"][sets])
         if latency is not None:
             env.set_action_latency(latency)
@@ -221,10 +221,10 @@ def test_bad_state_envs_fall_freely_under_their_own_gravity(G, emul, double, env
     dt = np.float64 if double else np.float32
 
     def go(plant):
-        env = emul.EmulGrav(n, double=double, seed=5, envs_per_wave=envs_per_wave)
+        env = emul.EmulRows(n, double=double, seed=5, envs_per_wave=envs_per_wave)
         env.set_gravity(rows)
         load_step(env, G, "stand", 0, sets)
-        q0 = emul.EmulGrav(1, double=double).get("qpos")[0]
+        q0 = emul.EmulRows(1, double=double).get("qpos")[0]
         if plant:
             v = env.get("qvel"); v[1, 7] = np.inf; v[2, 7] = 5e9; env.set("qvel", v)
         env.step(np.zeros((n, 18), np.float32), nsub=1, physics_only=True, want_dbg=True)
@@ -254,7 +254,7 @@ def test_free_flight_known_answer_in_the_fp64_emulation(emul):
     (semi-implicit Euler); every other word agrees: a uniform field exerts no relative force. Tolerance: the fp64 state tolerance 1e-8."""
     rng = np.random.default_rng(11)
     g = np.array([1.3, -0.7, -6.0])
-    env = emul.EmulGrav(2, double=True, seed=5, envs_per_wave=1)
+    env = emul.EmulRows(2, double=True, seed=5, envs_per_wave=1)
     rows = np.zeros((2, 8)); rows[0, 0:3] = g; rows[:, 4:7] = [0, 0, -9.81]
     env.set_gravity(rows)
     q = env.get("qpos"); q[:, 2] = 5.0; q[:, 7:] += rng.uniform(-0.3, 0.3, 18); env.set("qpos", q)

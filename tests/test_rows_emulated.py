@@ -1,5 +1,5 @@
 """The four kinds of per-env rows together - friction / gains, body rows, actuation latency, gravity vectors - in the host emulation of the
-device source (tests/emul/nm_emul_grav.cpp, the shim that has the gravity region), whose layout, default rows, on / off state and level
+device source (tests/emul/nm_emul_rows.cpp, the one shim with all four regions), whose layout, default rows, on / off state and level
 are the host object's own (nightmare_rl_amd/csrc/nm_env_rows.h): the walk of tests/rows_walk.py over every single-kind transition from
 every state of the other three kinds. After every toggle the env that took the walk must be indistinguishable from a fresh env put
 directly into that state: the same rows, the same level for full and physics-only launches, and bit-identical steps. N = 3 at two envs
@@ -16,13 +16,6 @@ ARRAYS = ("qpos", "qvel", "qwarm", "dofpos", "dofvel", "act", "cmd", "epsum", "f
 
 @pytest.fixture(scope="module")
 def emul():
-    from emul import emul_grav
-    emul_grav.build()
-    return emul_grav
-
-
-@pytest.fixture(scope="module")
-def emul3():
     from emul import emul_rows
     emul_rows.build()
     return emul_rows
@@ -46,12 +39,11 @@ def test_the_walk_is_an_eulerian_circuit_of_the_cube():
 
 
 @pytest.mark.parametrize("double", [False, True], ids=["fp32", "fp64"])
-def test_device_and_host_agree_on_where_the_latency_words_lie(emul, emul3, double):
-    """nm_core.h lat_delay / lat_hist (the device's way) against nm_env_rows.h (the host's), and the history ends inside the block; in
-    the shim of the walk the gravity rows behind it too."""
+def test_device_and_host_agree_on_where_the_latency_words_lie(emul, double):
+    """nm_core.h lat_delay / lat_hist / grav_rows_of (the device's way) against nm_env_rows.h (the host's): the history ends inside the
+    block, in front of the gravity rows, and those end the block."""
     for n in (1, 2, 3, 8, 9):
-        assert emul3.EmulRows(n, double=double).device_layout_agrees(), n
-        assert emul.EmulGrav(n, double=double).device_layout_agrees(), n
+        assert emul.EmulRows(n, double=double).device_layout_agrees(), n
 
 
 def put(env, values, body_of):
@@ -91,7 +83,7 @@ def test_an_env_that_took_the_walk_equals_a_fresh_env_put_into_that_state(emul, 
     envp_sets, payloads, body_rows, grav_rows = SETS
     real = np.float64 if double else np.float32
     body_of = lambda _: body_rows[walk.idx["B"]]      # the body rows of the payloads that are set now
-    walker = emul.EmulGrav(N, double=double, seed=5)
+    walker = emul.EmulRows(N, double=double, seed=5)
     f_dflt, b_dflt = envp_sets[0].astype(real), walker.default_body_row()      # (1.0, 20.0, 0.8) are the model's own values: test_env_params_emulated.py
     g_dflt = grav_rows[0].astype(real)      # (0, 0, -9.81) twice: test_gravity_emulated.py
     steps_that_differed = 0
@@ -107,7 +99,7 @@ def test_an_env_that_took_the_walk_equals_a_fresh_env_put_into_that_state(emul, 
             walker.set_action_latency(walk.values.get("L"))
         else:
             walker.set_gravity(walk.values.get("G"))
-        fresh = emul.EmulGrav(N, double=double, seed=5)
+        fresh = emul.EmulRows(N, double=double, seed=5)
         put(fresh, walk.values, body_of)
         # (a) the rows: walker = fresh = what was set for the kinds that are on, the defaults / zeros for the kinds that are off
         for physics_only in (False, True):      # L on without G is 2 when physics-only, G on is 4 either way
