@@ -262,6 +262,42 @@ int nm_get_action_history(nm_env* env, float* out_dev, void* stream);
 int nm_set_gravity(nm_env* env, const void* rows_dev, void* stream);
 int nm_get_gravity(nm_env* env, void* out_dev, void* stream);
 int nm_draw_gravity(nm_env* env, const double lo[5], const double hi[5], void* out_dev, void* stream);
+/* Servo target model: a per-env slew-rate limit on the servo target and a damping term. It replaces what upstream keeps commented out:
+ * `limited_actions` (envs/nightmare_v3_env.py:97), the limiter line and the damping term (envs/nightmare_v3_env.py:187-188), and
+ * `d_gain = 0.05` / `action_rate_limit = 0.08` (envs/nightmare_v3_config.py:37-38).
+ * Each env carries one row of 4 words in the env's dtype: rate, d_gain, pad, pad. rate > 0 is the most the servo target may move per
+ * control step (rad; +inf = no limit), d_gain >= 0. Each env also carries the state L[18] in the env's dtype, upstream's limited_actions,
+ * zero at construction.
+ * Semantics: T = real(a) - default_pos, a the float32 action this step brings to the servo: a_t, or with nm_set_action_latency the late
+ * action a_{t-k} (the limiter sits behind the delay line; the action history keeps raw a_t). Once per full step
+ *   d = T - L;   L' = |d| <= rate ? T : L + copysign(rate, d)
+ * (upstream's limited += clip(d, -rate, rate) up to rounding; a select, so rate = +inf gives L' = T bit for bit), and
+ *   ctrl = (L_used - dof_pos buffer) p_gain - d_gain dof_vel buffer
+ * on the step-start snapshots of both buffers and the env's own p_gain. Substeps before the latency switch substep r use L (the state
+ * before the update), substeps from r on use L'; without latency r = 0 and every substep uses L'. Each command is computed from its own
+ * target. The physics clips to the +-8 ctrlrange as before. Everything else - observation slots 48..65, action_rate, default_position,
+ * the actions buffer, the transition and state-log records - keeps a_t: the policy meets the servo through the physics alone.
+ * L is state: every full step taken WHILE THE FEATURE IS ON updates it (the zero-action step of a reset sequence included); steps taken
+ * while it is off, resets (upstream's reset_idx touches neither actions nor limited_actions), physics-only launches (which ignore the
+ * whole servo row, as they ignore latency) and switching the feature on or off leave it alone. The MuJoCo bad-state path (ctrl = 0 for
+ * the rest of that substep) is unchanged. It works alike in nm_step, nm_rollout, nm_play and nm_step_tape, alone or with any other
+ * per-env kind. Off is the default, and off equals "on with (+inf, 0) in every env" under == in every output for a finite dof_vel buffer
+ * (the damping term is then an exact zero; a zero command may differ from today's in sign only). A non-finite dof_vel buffer makes the
+ * command NaN while the feature is on, even at d_gain = 0 (0 x inf); the physics meets it in its bad-state check like any bad control.
+ * nm_set_servo: `rows` is a DEVICE array [N,4] in the env's dtype, copied on `stream`; NULL switches the feature off (nothing is freed).
+ *   Refused, named by nm_last_error, before anything of the env changes (the rows are read back and judged on the host, which waits for
+ *   `stream`): rate not > 0 (NaN included; +inf is admitted), d_gain not finite or < 0.
+ * nm_get_servo: the rows into a DEVICE array [N,4] on `stream`; (+inf, 0, 0, 0) for every env while the feature is off.
+ * nm_draw_servo: row[e] = (rate, d_gain, 0, 0), value = lo[c] + u (hi[c] - lo[c]) in the env's precision, product and sum rounded
+ *   separately, u ~ U[0,1) from the counter RNG keyed by (seed + "SERVO", global env id, c): sharding changes nothing; lo == hi pins a
+ *   column; switches the feature on. Refused before any device call: non-finite bounds, lo > hi, rate lo <= 0, d_gain lo < 0.
+ * nm_get_servo_state / nm_set_servo_state: L as HOST doubles [N,18], in the style of nm_get_buffers (synchronous; zeros before the first
+ *   use of any per-env kind). */
+int nm_set_servo(nm_env* env, const void* rows_dev, void* stream);
+int nm_get_servo(nm_env* env, void* out_dev, void* stream);
+int nm_draw_servo(nm_env* env, const double lo[2], const double hi[2], void* stream);
+int nm_get_servo_state(nm_env* env, double* limited);
+int nm_set_servo_state(nm_env* env, const double* limited);
 /* State log (envs/nightmare_v3_env.py:261-272 records data[0]): env_index >= 0 makes every nm_step keep that env's
  * post-physics, pre-reset qpos/qvel; -1 = off. nm_get_state_record copies the last record to HOST qpos[25], qvel[24] and
  * the number of MuJoCo bad-state resets inside that step (data.time restarts there). Synchronous. */

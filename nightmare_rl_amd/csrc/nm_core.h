@@ -173,6 +173,25 @@ constexpr uint64_t kGravityKey = 0x47524156ull;   // nm_draw_gravity: rand_u24_b
 template <class real> NM_FN const real* grav_rows_of(const Args<real>& A) {
   return A.envp + ((size_t)A.N * (kEnvP + kBodyP) + ((size_t)A.N * kLatP * 4 + sizeof(real) - 1) / sizeof(real));
 }
+// The servo target model (nm_set_servo, level EP = 5 of the step; reference envs/nightmare_v3_env.py:97,187-188 and
+// envs/nightmare_v3_config.py:37-38, all commented out there): one row of kServoP words per env in the env's dtype - rate (the most the
+// servo target may move per control step, rad, > 0, +inf = no limit), d_gain (>= 0), two pads - and, behind the N rows, the state
+// real L[N][kNU]: the rate-limited target of the last full step (the reference's limited_actions), zero at construction. Both regions are
+// appended to the envp allocation behind the gravity rows: nothing in front of them moves. Per full step, with T = real(a) - default_pos
+// the target of the action this step brings to the servo (a_t, or the late action a_{t-k} of a delayed env):
+//   d = T - L;   L' = |d| <= rate ? T : L + copysign(rate, d)
+//   ctrl = (L_used - dof_pos) p_gain - d_gain dof_vel     (both buffers the step-start snapshots; L before the switch substep, L' from it on)
+// (rate, d_gain) = (+inf, 0) gives level 4's command for finite dof_vel. A non-finite dof_vel buffer makes the command NaN even at
+// d_gain = 0 (0 x inf); the physics then meets it as it meets any bad control, in its bad-state check.
+constexpr int kServoP = 4, SV_RATE = 0, SV_DGAIN = 1;
+constexpr uint64_t kServoKey = 0x534552564Full;   // nm_draw_servo: rand_u24_bits(seed + kServoKey, global env id, column)
+template <class real> NM_FN const real* servo_rows_of(const Args<real>& A) { return grav_rows_of(A) + (size_t)A.N * kGravP; }
+template <class real> NM_FN real* servo_state_of(const Args<real>& A) { return const_cast<real*>(servo_rows_of(A)) + (size_t)A.N * kServoP; }
+// the limiter of one step, per lane (= joint): `Lo` the state, `Tt` the target; returns L'. A select, so rate = +inf gives Tt bit for bit
+template <class VR, class R> NM_FN VR servo_limit(const VR& Lo, const VR& Tt, const R& rate) {
+  const VR d = Tt - Lo;
+  return sel(vabs(d) <= rate, Tt, sel(d < VR(0), Lo - rate, Lo + rate));
+}
 constexpr int kDbgN = 256;
 
 // Where a stage reads the launch arguments from: the stages that touch them (env_load*, env_finish*, wave_step) take the source as a
@@ -312,6 +331,8 @@ template <class real, int G> struct ShWSel<real, G, 4> {
   typedef ShWG<real, G> type;
   static NM_FN ShW<real, G>& images(type& s) { return s.l.b.w; }
 };
+// Level 5 (level 4 plus the servo target model) adds nothing to LDS: it parks its late command where level 3 does.
+template <class real, int G> struct ShWSel<real, G, 5> : ShWSel<real, G, 4> {};
 #define NM_OFS(field) ((int)(offsetof(Sh<real>, field) / sizeof(real)))
 #define NM_IOFS(field) ((int)(offsetof(Sh<real>, field) / sizeof(int)))
 
@@ -322,7 +343,9 @@ template <class real, int G> struct ShWSel<real, G, 4> {
 // rows when only a payload is set); 3, launched while actuation delays are set, is level 2 plus the delayed servo command (env_load*,
 // latency_switch; the host supplies default rows of both kinds where the caller set none); 4, launched while gravity rows are set, is
 // level 3 plus the env's own gravity in the base's bias acceleration, in the bad-state free-fall step and in the epilogue's projected
-// gravity (the host supplies defaults for every kind that is off: zero delays, so a level-4 launch without latency commands as level 2).
+// gravity (the host supplies defaults for every kind that is off: zero delays, so a level-4 launch without latency commands as level 2);
+// 5, launched while servo rows are set, is level 4 with the load stage's command formed from the env's rate-limited target and damped
+// by its d_gain (env_load*; no physics stage differs from level 4's).
 template <int EP, class real> NM_FN real env_mu(const Sh<real>& sh, const Model<real>& M) {
   if constexpr (EP != 0) return sh.envp[EP_MU]; else return M.mu;
 }
@@ -343,6 +366,11 @@ template <class real> struct BodyRef<3, real> {
   NM_FN explicit BodyRef(const real* q) : p(q) {}
 };
 template <class real> struct BodyRef<4, real> {
+  const real* p;
+  NM_FN BodyRef() : p(nullptr) {}
+  NM_FN explicit BodyRef(const real* q) : p(q) {}
+};
+template <class real> struct BodyRef<5, real> {
   const real* p;
   NM_FN BodyRef() : p(nullptr) {}
   NM_FN explicit BodyRef(const real* q) : p(q) {}
@@ -3098,6 +3126,13 @@ template <int EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real
       h1 = gldv(lat_hist(A), l18c + (env * (kLatH * kNU) + kNU));
       h2 = gldv(lat_hist(A), l18c + (env * (kLatH * kNU) + 2 * kNU));
     }
+  // level 5: the env's servo row (lanes 0..3) and its limited target (lane = joint), with the step's other reads
+  vr servo_in = vr(real(0)), lim_in = vr(real(0));
+  if constexpr (EP >= 5)
+    if (!A.physics_only) {
+      servo_in = gldv(servo_rows_of(A), sel(lane < kServoP, lane, V<int>(0)) + env * kServoP);
+      lim_in = gldv(servo_state_of(A), l18c + env * kNU);
+    }
   if (!A.physics_only) {   // what the epilogue needs from HBM is fetched now, under the physics, not when it is needed
     cmd_in = gldv(A.cmd, sel(lane < 3, lane, V<int>(0)) + env * 3);
     eps_in = gldv(A.epsum, sel(lane < kNREW, lane, V<int>(0)) + env * kNREW);
@@ -3149,8 +3184,19 @@ template <int EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real
       const int k = (dl >= nsub ? 1 : 0) + (dl >= 2 * nsub ? 1 : 0) + (dl >= 3 * nsub ? 1 : 0), r = dl - k * nsub;
       const V<float> fl = k == 0 ? af : (k == 1 ? h0 : (k == 2 ? h1 : h2));
       const V<float> fe = r > 0 ? (k == 0 ? h0 : (k == 1 ? h1 : h2)) : fl;
+      if constexpr (EP >= 5) {
+        // the limiter sits behind the delay line: it runs once, on the late action's target; the substeps before the switch keep the
+        // target the last step ended on. Each command comes from its own target, never as a difference from the other.
+        const real rate = rdlane(servo_in, SV_RATE), d_gain = rdlane(servo_in, SV_DGAIN);
+        const vr lim = servo_limit(lim_in, vcvt<real>(fl) - defp, vr(rate));
+        const vr damp = prev_dofvel * d_gain;
+        stsv(sh.ctrl, lane, ((r > 0 ? lim_in : lim) - dofpos_old) * p_gain - damp, l18);
+        stsv(late, lane, (lim - dofpos_old) * p_gain - damp, l18);
+        gstv(servo_state_of(A), lane + env * kNU, lim, l18 & VB(live));     // with the history: a launch runs whole or not at all
+      } else {
       stsv(sh.ctrl, lane, ((vcvt<real>(fe) - defp) - dofpos_old) * p_gain, l18);
       stsv(late, lane, ((vcvt<real>(fl) - defp) - dofpos_old) * p_gain, l18);
+      }
       *rsw = r;
       // the history takes this step's action now: all three rows are in registers here, and a launch runs whole or not at all
       float* hist = lat_hist(A);
@@ -3503,6 +3549,13 @@ template <int EP, class real, class Src, class Mid> NM_FN void env_load2(ShW<rea
       h1 = gldx<kS>(lat_hist(A), l18c + (env * (kLatH * kNU) + kNU));
       h2 = gldx<kS>(lat_hist(A), l18c + (env * (kLatH * kNU) + 2 * kNU));
     }
+  // level 5: each env's servo row (lanes 0..3 of its half) and its limited target (lane of the half = joint), with the step's other reads
+  vr servo_in = vr(real(0)), lim_in = vr(real(0));
+  if constexpr (EP >= 5)
+    if (!A.physics_only) {
+      servo_in = gldx<kS>(servo_rows_of(A), sel(hl < kServoP, hl, V<int>(0)) + env * kServoP);
+      lim_in = gldx<kS>(servo_state_of(A), l18c + env * kNU);
+    }
 #ifndef NM_EMUL
   int64_t ep = 0;
   uint32_t ctr_in = 0;
@@ -3576,8 +3629,20 @@ template <int EP, class real, class Src, class Mid> NM_FN void env_load2(ShW<rea
       const V<float> fl = sel(k == zero, af, sel(k == one, h0, sel(k == V<int>(2), h1, h2)));
       const V<float> fe = sel(r > zero, sel(k == zero, h0, sel(k == one, h1, h2)), fl);
       ShWL<real, 2>& L = lat_rows(w);
+      if constexpr (EP >= 5) {
+        // the limiter sits behind the delay line, per half: it runs once, on the late action's target; the substeps before the switch
+        // keep the target the last step ended on. Each command comes from its own target, never as a difference from the other.
+        const vr rate = sel(h != 0, vr(rdlane(servo_in, 32 + SV_RATE)), vr(rdlane(servo_in, SV_RATE)));
+        const vr d_gain = sel(h != 0, vr(rdlane(servo_in, 32 + SV_DGAIN)), vr(rdlane(servo_in, SV_DGAIN)));
+        const vr lim = servo_limit(lim_in, vcvt<real>(fl) - defp, rate);
+        const vr damp = prev_dofvel * d_gain;
+        stsv(rb, ho + (hl + NM_OFS(ctrl)), (sel(r > zero, lim_in, lim) - dofpos_old) * p_gain - damp, l18);
+        stsv(L.late, h * kNU + hl, (lim - dofpos_old) * p_gain - damp, l18);
+        gstx<kS>(servo_state_of(A), hl + env * kNU, lim, l18 & (env0 < V<int>(A.N)));     // a padded slot stores nothing
+      } else {
       stsv(rb, ho + (hl + NM_OFS(ctrl)), ((vcvt<real>(fe) - defp) - dofpos_old) * p_gain, l18);
       stsv(L.late, h * kNU + hl, ((vcvt<real>(fl) - defp) - dofpos_old) * p_gain, l18);
+      }
       stsv(L.rsw, h, r, hl == zero);
       // the history takes this step's action now: all three rows are in registers here, and a launch runs whole or not at all. A
       // padded slot (it recomputes the last env) stores nothing

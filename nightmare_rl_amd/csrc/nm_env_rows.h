@@ -1,10 +1,10 @@
 // nm_env_rows.h - host side, plain C++17, no HIP header: the one owner of what the host decides about the per-env rows behind
-// nm::Args::envp (friction / gains, body rows, actuation latency, gravity) - layout, default rows, admission, which kinds are on and which level of
+// nm::Args::envp (friction / gains, body rows, actuation latency, gravity, the servo target model) - layout, default rows, admission, which kinds are on and which level of
 // the step a launch takes. Used by the env object (nm_hip.hip), the K-step launchers and the host emulation (tests/emul, -DNM_EMUL).
 //
 // The invariant every owner of a block keeps: ONCE THE BLOCK IS ALLOCATED, EVERY REGION WHOSE KIND IS OFF HOLDS THAT KIND'S DEFAULTS -
-// default friction / gain rows, default body rows, zero delays, default gravity rows - so a transition writes or refills its own region and looks at no other
-// kind's flag. The action history is exempt: it is state, not a parameter, and keeps what it holds.
+// default friction / gain rows, default body rows, zero delays, default gravity rows, default servo rows - so a transition writes or refills its own region and
+// looks at no other kind's flag. The action history and the servo's limited targets are exempt: they are state, not parameters, and keep what they hold.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -15,7 +15,7 @@
 
 namespace nmrows {
 
-enum Kind { kFric = 0, kBody = 1, kLat = 2, kGrav = 3 };
+enum Kind { kFric = 0, kBody = 1, kLat = 2, kGrav = 3, kServo = 4 };
 
 // ---- layout: one block of `real`s - N friction / gain rows, N body rows, then the latency words (4 bytes each in either dtype): N
 // delays, N action histories; then, at the next multiple of sizeof(real), N gravity rows. The device finds the last three through
@@ -30,6 +30,12 @@ template <class real> inline int* delays(real* base, int N) { return reinterpret
 template <class real> inline float* histories(real* base, int N) { return reinterpret_cast<float*>(delays(base, N) + N); }
 constexpr size_t hist_words(size_t N) { return N * nm::kLatH * nm::kNU; }
 template <class real> inline real* grav_rows(real* base, int N) { return base + grav_offset<real>((size_t)N); }
+// The servo target model is appended behind the gravity rows: N rows of kServoP reals, then the state, N x kNU limited targets. block_reals
+// stays the block through the gravity rows (what a holder of levels 0..4 alone allocates); an owner that can launch level 5 allocates
+// servo_block_reals. The device's way there: nm::servo_rows_of / nm::servo_state_of.
+template <class real> constexpr size_t servo_block_reals(size_t N) { return block_reals<real>(N) + N * (nm::kServoP + nm::kNU); }
+template <class real> inline real* servo_rows(real* base, int N) { return base + block_reals<real>((size_t)N); }
+template <class real> inline real* servo_state(real* base, int N) { return servo_rows(base, N) + (size_t)N * nm::kServoP; }
 
 // ---- default rows: the model's own values (the fourth word of a friction / gain row is padding, zero)
 template <class real> inline void fric_default(const nm::Model<real>& M, real out[3]) {
@@ -47,6 +53,12 @@ template <class real> inline void body_default(const nm::Model<real>& M, real ou
 template <class real> inline void grav_default(const nm::Model<real>& M, real out[nm::kGravP]) {
   for (int j = 0; j < nm::kGravP; j++) out[j] = real(0);
   out[nm::GP_G + 2] = -M.grav; out[nm::GP_VEC + 2] = -M.grav;
+}
+
+// no limit, no damping: level 5 then commands as level 4 does
+template <class real> inline void servo_default(const nm::Model<real>&, real out[nm::kServoP]) {
+  for (int j = 0; j < nm::kServoP; j++) out[j] = real(0);
+  out[nm::SV_RATE] = (real)INFINITY;
 }
 
 // ---- admission: pure functions of the caller's rows; empty = admitted, otherwise what the entry point reports behind its own name
@@ -71,6 +83,17 @@ template <class real> inline std::string grav_rows_fault(const real* rows, int N
     const char* why = nullptr;
     for (int j = 0; j < nm::kGravP; j++) if (!std::isfinite((double)r[j])) why = "a non-finite value";
     if (!why && r[nm::GP_VEC] == real(0) && r[nm::GP_VEC + 1] == real(0) && r[nm::GP_VEC + 2] == real(0)) why = "a zero gravity_vec";
+    if (why) return "row " + std::to_string(e) + ": " + why;
+  }
+  return std::string();
+}
+// rate > 0 (+inf = no limit) and not NaN; d_gain finite and >= 0
+template <class real> inline std::string servo_rows_fault(const real* rows, int N) {
+  for (int e = 0; e < N; e++) {
+    const real* r = rows + (size_t)e * nm::kServoP;
+    const char* why = nullptr;
+    if (!(r[nm::SV_RATE] > 0)) why = "rate not > 0";
+    if (!why && !(std::isfinite((double)r[nm::SV_DGAIN]) && r[nm::SV_DGAIN] >= 0)) why = "d_gain not finite and >= 0";
     if (why) return "row " + std::to_string(e) + ": " + why;
   }
   return std::string();
@@ -102,16 +125,25 @@ template <> struct RowKind<kGrav> {
   template <class real> static void dflt(const nm::Model<real>& M, real* out) { grav_default(M, out); }
   template <class real> static std::string fault(const real* r, int N) { return grav_rows_fault(r, N); }
 };
+template <> struct RowKind<kServo> {
+  static constexpr Kind kind = kServo;
+  static constexpr int W = nm::kServoP;
+  template <class real> static real* rows(real* base, int N) { return servo_rows(base, N); }
+  template <class real> static void dflt(const nm::Model<real>& M, real* out) { servo_default(M, out); }
+  template <class real> static std::string fault(const real* r, int N) { return servo_rows_fault(r, N); }
+};
 typedef RowKind<kBody> BodyKind;
 typedef RowKind<kGrav> GravKind;
+typedef RowKind<kServo> ServoKind;
 
 // ---- state: which kinds are on, and what follows from that for a launch
 struct State {
-  bool on[4] = {false, false, false, false};
+  bool on[5] = {false, false, false, false, false};
   // the level of the step a launch takes: the highest kind that is on; a physics-only launch ignores latency (level 2 on the rows level 3
-  // reads; at level 4, which physics-only launches take too, the kernel skips it at run time: nm::Args::physics_only)
+  // reads; at level 4, which physics-only launches take too, the kernel skips it at run time: nm::Args::physics_only; at level 5 it skips
+  // the servo row and its state the same way)
   int level(bool physics_only = false) const {
-    return on[kGrav] ? 4 : (on[kLat] ? (physics_only ? 2 : 3) : (on[kBody] ? 2 : (on[kFric] ? 1 : 0)));
+    return on[kServo] ? 5 : on[kGrav] ? 4 : (on[kLat] ? (physics_only ? 2 : 3) : (on[kBody] ? 2 : (on[kFric] ? 1 : 0)));
   }
   // nm::Args::envp of a launch: the block while any kind is on, null (level 0 never looks) otherwise
   template <class real> real* envp(real* base) const { return level() ? base : nullptr; }
@@ -126,6 +158,13 @@ template <class F> inline auto with_level(int level, F&& f) {
     case 1: return f(std::integral_constant<int, 1>{});
     default: return f(std::integral_constant<int, 0>{});
   }
+}
+
+// the same for an owner that can launch level 5. with_level keeps the cases it had, so a holder of levels 0..4 alone (tests/emul's rows
+// shim) instantiates what it did and nothing more
+template <class F> inline auto with_level5(int level, F&& f) {
+  if (level == 5) return f(std::integral_constant<int, 5>{});
+  return with_level(level, f);
 }
 
 }  // namespace nmrows

@@ -93,7 +93,8 @@ constexpr int kWG = NM_WG_WAVES;
 constexpr int kWG = 1;
 #endif
 // EP: level of per-env physics parameters (nm_core.h env_mu): 0 none, 1 friction / gain rows (nm::Args::envp), 2 those and body rows, 3 those
-// and actuation latency, 4 those and gravity rows - the host launches a level above 0 only while its rows are set
+// and actuation latency, 4 those and gravity rows, 5 those and the servo target model - the host launches a level above 0 only while its
+// rows are set
 //
 // The launch arguments are read where they are used, by scalar loads from the kernel's own kernarg segment (nm::KernArgs): the wave's
 // first instructions are the loads of the base pointers and then the env rows' HBM reads, the epilogue fetches its pointers again from
@@ -362,6 +363,11 @@ struct nm_env {
   virtual int set_gravity(const void* rows, hipStream_t s) = 0;
   virtual int get_gravity(void* out, hipStream_t s) = 0;
   virtual int draw_gravity(const double* lo, const double* hi, void* out, hipStream_t s) = 0;
+  virtual int set_servo(const void* rows, hipStream_t s) = 0;
+  virtual int get_servo(void* out, hipStream_t s) = 0;
+  virtual int draw_servo(const double* lo, const double* hi, hipStream_t s) = 0;
+  virtual int get_servo_state(double* L) = 0;
+  virtual int set_servo_state(const double* L) = 0;
   // push perturbations (nm_push.h): the setting and the push step index - full env steps taken, K per K-step launch; physics-only
   // launches and nm_reset leave it alone
   int push_interval = 0;
@@ -538,7 +544,7 @@ template <class real> struct Env : nm_env {
     }
     constexpr int G = sizeof(real) == 8 ? 1 : NM_ENVS_PER_WAVE;  // the fp64 verification build keeps one env per wave (LDS)
     constexpr int W = sizeof(real) == 8 ? 1 : kWG;
-    nmrows::with_level(rows.level(physics_only), [&](auto L) {
+    nmrows::with_level5(rows.level(physics_only), [&](auto L) {
       hipLaunchKernelGGL((k_env_step<real, G, decltype(L)::value>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
     });
     HIPCHK(hipGetLastError());
@@ -910,7 +916,7 @@ template <class real> struct Env : nm_env {
       return 0;
     }
   }
-  // ---- per-env rows (friction / gains, body rows, actuation latency): ONE lazily allocated block behind A.envp, which every launch copies
+  // ---- per-env rows (friction / gains, body rows, actuation latency, gravity, servo target model): ONE lazily allocated block behind A.envp, which every launch copies
   // with the rest of A. Where each kind lies in it, what an unset kind holds, which rows are admitted and which level of the step a launch
   // takes: nm_env_rows.h, and its invariant - once the block exists, every region whose kind is off holds that kind's defaults - is what
   // the functions below keep: each writes or refills its own region and looks at no other kind.
@@ -922,18 +928,19 @@ template <class real> struct Env : nm_env {
     HIPCHK(hipGetLastError());
     return 0;
   }
-  // at first use, from the slab (zeroed: the delays and the history start at zero); the fills are ordered on the first caller's stream
+  // at first use, from the slab (zeroed: the delays, the history and the servo's limited targets start at zero); the fills are ordered on the first caller's stream
   int rows_alloc(hipStream_t s) {
     if (envp_dev) return 0;
-    if (dalloc(&envp_dev, nmrows::block_reals<real>((size_t)N))) return 1;
-    return envp_write({}, s) || kind_fill<nmrows::BodyKind>(nmrows::body_rows(envp_dev, N), s) || kind_fill<nmrows::GravKind>(nmrows::grav_rows(envp_dev, N), s);
+    if (dalloc(&envp_dev, nmrows::servo_block_reals<real>((size_t)N))) return 1;
+    return envp_write({}, s) || kind_fill<nmrows::BodyKind>(nmrows::body_rows(envp_dev, N), s) || kind_fill<nmrows::GravKind>(nmrows::grav_rows(envp_dev, N), s) ||
+           kind_fill<nmrows::ServoKind>(nmrows::servo_rows(envp_dev, N), s);
   }
   int rows_turn(nmrows::Kind k, bool on) {
     rows.on[k] = on;
     A.envp = rows.envp(envp_dev);
     return 0;
   }
-  // ---- the kinds with a descriptor D (nm_env_rows.h RowKind: body rows, gravity rows); `who`: the entry point's name
+  // ---- the kinds with a descriptor D (nm_env_rows.h RowKind: body rows, gravity rows, servo rows); `who`: the entry point's name
   template <class D> int kind_fill(real* dst, hipStream_t s) {      // the default row for every env
     Vals<real, D::W> r;
     D::dflt(M, r.v);
@@ -1006,6 +1013,29 @@ template <class real> struct Env : nm_env {
   int draw_gravity(const double* lo, const double* hi, void* out, hipStream_t s) override {      // (three offsets, tilt, azimuth)
     HIPCHK(hipSetDevice(device));
     return draw<5, 5>((real*)out, nm::kGravityKey, lo, hi, s);
+  }
+  // ---- the servo target model: rows (rate, d_gain, pad, pad) through the descriptor; the limited targets are state (like the history)
+  int set_servo(const void* rows_in, hipStream_t s) override { return kind_set<nmrows::ServoKind>("nm_set_servo", rows_in, s); }
+  int get_servo(void* out, hipStream_t s) override { return kind_get<nmrows::ServoKind>(out, s); }
+  int draw_servo(const double* lo, const double* hi, hipStream_t s) override {      // (rate, d_gain) into the rows
+    HIPCHK(hipSetDevice(device));
+    if (rows_alloc(s) || draw<2, nm::kServoP>(nmrows::servo_rows(envp_dev, N), nm::kServoKey, lo, hi, s)) return 1;
+    return rows_turn(nmrows::kServo, true);
+  }
+  int get_servo_state(double* L) override {
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipDeviceSynchronize());
+    if (!L) return 0;
+    if (!envp_dev) { for (size_t i = 0; i < (size_t)N * nm::kNU; i++) L[i] = 0.0; return 0; }      // never allocated: zero, as at construction
+    return d2h(nmrows::servo_state(envp_dev, N), L, (size_t)N * nm::kNU);
+  }
+  int set_servo_state(const double* L) override {
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipDeviceSynchronize());
+    if (!L) return fail("nm_set_servo_state: the state is NULL");
+    if (rows_alloc(nullptr)) return 1;
+    HIPCHK(hipDeviceSynchronize());
+    return h2d(nmrows::servo_state(envp_dev, N), L, (size_t)N * nm::kNU);
   }
   // ---- per-env actuation latency
   int set_action_latency(const int* substeps, hipStream_t s) override {
@@ -1353,6 +1383,31 @@ int nm_draw_gravity(nm_env* env, const double lo[5], const double hi[5], void* o
   static const char* kCol[5] = {"offset x", "offset y", "offset z", "tilt", "azimuth"};
   if (draw_bounds_bad("nm_draw_gravity", env, lo, hi, kCol, 5, nullptr, true, out_dev)) return 1;
   return env->draw_gravity(lo, hi, out_dev, (hipStream_t)stream);
+}
+int nm_set_servo(nm_env* env, const void* rows_dev, void* stream) {
+  NEED_ENV(env);
+  return env->set_servo(rows_dev, (hipStream_t)stream);
+}
+int nm_get_servo(nm_env* env, void* out_dev, void* stream) {
+  NEED_ENV(env);
+  return env->get_servo(out_dev, (hipStream_t)stream);
+}
+int nm_draw_servo(nm_env* env, const double lo[2], const double hi[2], void* stream) {
+  static const char* kCol[2] = {"rate", "d_gain"};
+  const auto extra = [](int k, double lo_k) -> const char* {
+    return k == 0 ? (lo_k > 0.0 ? nullptr : "rate must be above 0") : (lo_k < 0.0 ? "d_gain must not be negative" : nullptr);
+  };
+  if (draw_bounds_bad("nm_draw_servo", env, lo, hi, kCol, 2, extra, false, nullptr)) return 1;
+  if (env->dtype == NM_DTYPE_F32 && !((float)lo[0] > 0.0f)) return fail("nm_draw_servo: rate must be above 0 in float32");
+  return env->draw_servo(lo, hi, (hipStream_t)stream);
+}
+int nm_get_servo_state(nm_env* env, double* limited) {
+  NEED_ENV(env);
+  return env->get_servo_state(limited);
+}
+int nm_set_servo_state(nm_env* env, const double* limited) {
+  NEED_ENV(env);
+  return env->set_servo_state(limited);
 }
 int nm_step_tape(nm_env* env, const nm_tape_args* args, void* stream) {
   if (!env) return fail("nm_step_tape: env is NULL");

@@ -26,6 +26,10 @@ Differences a caller can observe (all documented in DESIGN.md):
     (set_reset_noise), from the first reset() on
   * and randomize_gravity / gravity_range, randomize_slope / slope_range, gravity_observed: a per-env gravity vector - a floor inclined
     by theta is a level floor under a gravity tilted by theta - drawn once at construction (set_gravity, draw_gravity)
+  * an OPTIONAL `cfg.control.action_rate_limit` / `cfg.control.d_gain` - the two lines upstream's config keeps commented out
+    (reference envs/nightmare_v3_config.py:37-38) - switch on the servo target model: a slew-rate limit on the servo target and a
+    damping term (set_servo; reference envs/nightmare_v3_env.py:97,187-188, commented out as well). cfg.domain_rand may carry
+    randomize_action_rate_limit / action_rate_limit_range and randomize_d_gain / d_gain_range, drawn once at construction (draw_servo)
 """
 import ctypes as C
 import numpy as np
@@ -111,6 +115,37 @@ def latency_config(cfg):
     randomize_action_latency needs action_latency_range; a range that is not two integers 0 <= lo <= hi is a ValueError (the upper limit,
     three env steps, is the library's to judge: it depends on the decimation)."""
     return _switched(getattr(cfg, "domain_rand", None), "randomize_action_latency", "action_latency_range", lowest=0, whole=True)
+
+
+def servo_config(cfg):
+    """(rate_range, d_gain_range) of the servo target model, each a (lo, hi) pair or None (= the default: no limit, no damping): what
+    draw_servo takes. The optional cfg.control.action_rate_limit (rad per control step, > 0, inf = no limit) and cfg.control.d_gain
+    (finite, >= 0) - upstream's own names, reference envs/nightmare_v3_config.py:37-38 - give every env that value, as the pair (v, v);
+    cfg.domain_rand.randomize_action_rate_limit needs action_rate_limit_range (finite, 0 < lo <= hi), randomize_d_gain needs d_gain_range
+    (finite, 0 <= lo <= hi), and a range takes the place of the value of cfg.control. Anything else is a ValueError."""
+    ctl, dr = getattr(cfg, "control", None), getattr(cfg, "domain_rand", None)
+
+    def value(name, ok, what):
+        v = getattr(ctl, name, None)
+        if v is None:
+            return None
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"cfg.control.{name} must be a number") from None
+        if not ok(v):
+            raise ValueError(f"cfg.control.{name} must be {what}")
+        return v
+
+    rate = value("action_rate_limit", lambda v: v > 0, "above 0 (inf = no limit)")
+    d_gain = value("d_gain", lambda v: np.isfinite(v) and v >= 0, "finite and >= 0")
+    rr = _switched(dr, "randomize_action_rate_limit", "action_rate_limit_range", lowest=0.0, strict=True)
+    dg = _switched(dr, "randomize_d_gain", "d_gain_range", lowest=0.0)
+    if rr is None and rate is not None and np.isfinite(rate):
+        rr = (rate, rate)
+    if dg is None and d_gain is not None:
+        dg = (d_gain, d_gain)
+    return rr, dg
 
 
 GRAVITY = 9.81      # m/s^2: the model's gravity and upstream's gravity_vec (reference envs/nightmare_v3_env.py:46)
@@ -199,6 +234,7 @@ class NightmareV3Env:
         latency_range = latency_config(cfg)
         gravity_ranges = gravity_config(cfg)
         reset_ranges = reset_noise_config(cfg)
+        servo_ranges = servo_config(cfg)
         # reward table: zero scales dropped, the rest x dt (reference :123-128). Every name the reference has a _reward_ function
         # for (:399-497) is compiled; a name without one (`collision`, `feet_stumble`, config :95-96) fails like upstream's getattr.
         names = [L.nm_reward_name(i).decode() for i in range(_lib.NUM_REWARDS)]
@@ -281,6 +317,10 @@ class NightmareV3Env:
         # per-env gravity vectors - slopes and gravity offsets (optional cfg.domain_rand; no reference line): drawn once, here
         if gravity_ranges[0] is not None or gravity_ranges[1] is not None:
             self.draw_gravity(*gravity_ranges)
+        # the servo target model (optional cfg.control.action_rate_limit / d_gain, reference config :37-38; optional cfg.domain_rand ranges):
+        # set once, here, before the first reset()
+        if servo_ranges[0] is not None or servo_ranges[1] is not None:
+            self.draw_servo(*servo_ranges)
         # randomised reset states (optional cfg.domain_rand; no reference line): on before the first reset(), whose reset_idx(all) is
         # draw 0 of every env
         if reset_ranges is not None:
@@ -556,6 +596,59 @@ class NightmareV3Env:
         g = gravity_from_draw(d[:, 0:3], d[:, 3], d[:, 4])
         self.set_gravity(g, None if observed else np.array([0.0, 0.0, -GRAVITY]))
         return self.gravity()
+
+    def set_servo(self, rate_limit=None, d_gain=None):
+        """The servo target model (nm_set_servo; include/nightmare_hip.h states the semantics; reference envs/nightmare_v3_env.py:97,187-188
+        and envs/nightmare_v3_config.py:37-38, commented out upstream). rate_limit: the most an env's servo target may move per control
+        step, rad, > 0, inf = no limit; d_gain: the damping on the joint velocity buffer, >= 0. Each: num_envs values, a scalar for every
+        env, or None = its default (inf, 0). Both None switch the feature off. The observation, the rewards, the actions buffer and the
+        logs keep a_t: the policy meets the servo through the physics alone. Honoured by step(), policy_rollout, policy_play and
+        step_tape alike; step_physics ignores it. The rows hold until they are set again; no reset touches them, nor the limited targets
+        (servo_state()). The library refuses a rate that is not > 0 and a d_gain that is not finite and >= 0."""
+        if rate_limit is None and d_gain is None:
+            self._rows_keep["servo"] = None
+            self._ck(self._L.nm_set_servo(self._h, None, self._stream()))
+            return
+        err = "set_servo: one value per env (or a scalar)"
+        rows = torch.zeros(self.num_envs, 4, dtype=self._real, device=self.device)
+        rows[:, 0] = float("inf") if rate_limit is None else self._per_env(rate_limit, self._real, err)
+        if d_gain is not None:
+            rows[:, 1] = self._per_env(d_gain, self._real, err)
+        self._ck(self._L.nm_set_servo(self._h, C.c_void_p(rows.data_ptr()), self._stream()))
+        self._rows_keep["servo"] = rows
+
+    def servo(self):
+        """{'rate_limit', 'd_gain'}: [num_envs] tensors in the env's dtype (nm_get_servo); (inf, 0) while the feature is off."""
+        rows = torch.empty(self.num_envs, 4, dtype=self._real, device=self.device)
+        self._ck(self._L.nm_get_servo(self._h, C.c_void_p(rows.data_ptr()), self._stream()))
+        return {"rate_limit": rows[:, 0].clone(), "d_gain": rows[:, 1].clone()}
+
+    def draw_servo(self, rate_range=None, d_gain_range=None):
+        """Draw every env's servo row on the device (nm_draw_servo: rate uniform in rate_range, rad per control step, 0 < lo <= hi finite;
+        d_gain uniform in d_gain_range, 0 <= lo <= hi finite) and switch the feature on. None pins that column to its default (no limit /
+        no damping). Keyed by the global env id: shards of one population draw what the whole would. Returns what servo() then reports."""
+        rr = None if rate_range is None else tuple(float(x) for x in rate_range)
+        dg = (0.0, 0.0) if d_gain_range is None else tuple(float(x) for x in d_gain_range)
+        lo, hi = (C.c_double * 2)(1.0 if rr is None else rr[0], dg[0]), (C.c_double * 2)(1.0 if rr is None else rr[1], dg[1])
+        self._ck(self._L.nm_draw_servo(self._h, C.byref(lo), C.byref(hi), self._stream()))
+        if rr is None:      # the draw takes finite bounds: "no limit" goes in as a column of its own
+            self.set_servo(None, self.servo()["d_gain"])
+        return self.servo()
+
+    def servo_state(self):
+        """[num_envs, 18] float64 numpy: every env's rate-limited servo target L, upstream's limited_actions (nm_get_servo_state), in the
+        env's precision. Zero at construction; it follows the steps taken while the servo model is on. reset_idx() leaves it alone;
+        reset() is reset_idx() and one step under zero actions, which updates it like any other step."""
+        out = np.empty((self.num_envs, 18))
+        self._ck(self._L.nm_get_servo_state(self._h, out.ctypes.data))
+        return out
+
+    def set_servo_state(self, limited):
+        """Overwrite the limited targets ([num_envs, 18]): checkpoints and tests."""
+        a = np.ascontiguousarray(limited, np.float64)
+        if a.shape != (self.num_envs, 18):
+            raise ValueError("set_servo_state: [num_envs, 18]")
+        self._ck(self._L.nm_set_servo_state(self._h, a.ctypes.data))
 
     def _record_state(self):
         # reference :261-272: when env 0 resets, dump what was logged so far, then log (time, qpos, qvel, act) of env 0

@@ -113,6 +113,10 @@ def main():
                     help="per-env actuation latency in physics substeps, drawn once from the integers LO..HI, at most 3 x decimation (default: none)")
     ap.add_argument("--gain-range", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                     help="per-env multipliers of the servo stiffness and damping, each drawn once from U[LO, HI) (default: 1.0)")
+    ap.add_argument("--action-rate-limit", type=float, default=None, metavar="R", dest="action_rate_limit",
+                    help="the servo target may move at most R rad per control step (upstream's commented-out control.action_rate_limit = 0.08; default: no limit)")
+    ap.add_argument("--d-gain", type=float, default=None, metavar="D", dest="d_gain",
+                    help="damping D on the joint velocity in the servo command (upstream's commented-out control.d_gain = 0.05; default: 0)")
     a = ap.parse_args()
     path = a.checkpoint or get_load_path(a.log_root)
     dev = torch.device("cuda", 0)
@@ -133,6 +137,10 @@ def main():
             com_displacement_range = None if a.com_range is None else (-a.com_range, a.com_range)
             randomize_action_latency, action_latency_range = a.latency_range is not None, a.latency_range
         cfg.domain_rand = domain_rand
+    if a.action_rate_limit is not None:      # upstream's own names (reference envs/nightmare_v3_config.py:37-38)
+        cfg.control.action_rate_limit = a.action_rate_limit
+    if a.d_gain is not None:
+        cfg.control.d_gain = a.d_gain
     env = NightmareV3Env(cfg, device=dev, seed=a.seed, **({"log_dir": a.record_states} if a.record_states is not None else {}))
     print(f"push perturbations: every {env.push_interval} steps, |v| < {env.max_push_vel_xy} m/s" if env.push_interval else "push perturbations: off")
     if a.friction_range or a.gain_range:

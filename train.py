@@ -45,6 +45,10 @@ def main():
                          "velocities (rad/s) from U[-V, V) (0 = off, the default)")
     ap.add_argument("--gain-range", type=float, nargs=2, default=None, metavar=("LO", "HI"), dest="gain_range",
                     help="per-env multipliers of the servo stiffness (p_gain) and damping (kv), each drawn once from U[LO, HI) (default: 1.0)")
+    ap.add_argument("--action-rate-limit", type=float, default=None, metavar="R", dest="action_rate_limit",
+                    help="the servo target may move at most R rad per control step (upstream's commented-out control.action_rate_limit = 0.08; default: no limit)")
+    ap.add_argument("--d-gain", type=float, default=None, metavar="D", dest="d_gain",
+                    help="damping D on the joint velocity in the servo command (upstream's commented-out control.d_gain = 0.05; default: 0)")
     ap.add_argument("--gpus", type=int, default=None, help="ranks (one per GPU); without torch.distributed.run, train.py starts them itself")
     args = ap.parse_args()
 
@@ -95,6 +99,10 @@ def main():
             reset_dof_pos_range = (-args.reset_dof_pos, args.reset_dof_pos)
             reset_base_lin_vel_range = reset_base_ang_vel_range = reset_dof_vel_range = (-args.reset_vel, args.reset_vel)
         cfg.domain_rand = domain_rand
+    if args.action_rate_limit is not None:      # upstream's own names (reference envs/nightmare_v3_config.py:37-38)
+        cfg.control.action_rate_limit = args.action_rate_limit
+    if args.d_gain is not None:
+        cfg.control.d_gain = args.d_gain
     lo, hi = shard_range(args.num_envs, rank, world)
     cfg.env.num_envs = hi - lo
     train_cfg.runner.resume = args.resume
