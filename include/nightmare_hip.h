@@ -316,6 +316,15 @@ int nm_get_state_log_dones(nm_env* env, int32_t first_step, int32_t count, unsig
  * kernel with HIP events on the launch stream. Each call synchronises, returns the summed kernel time and the
  * launch count since the previous call, clears them, and sets the new enable state. */
 int nm_profile(nm_env* env, int32_t enable, double* sum_ms, int64_t* count);
+/* Which instantiation of the step kernel nm_step launches. The library holds two for fp32 envs without per-env rows: the generic one,
+ * which asks the configuration at run time, and a lean one compiled for the shipped default configuration (the model's link frames,
+ * solimp power 2, tibia / body contact mode 1, no reward term beyond the default table, no debug buffer, state record, observation
+ * noise or injected command uniforms). Both compute the same bits. mode 0 (the default): the lean one whenever a launch qualifies,
+ * decided per launch; mode 1: always the generic one. nm_get_step_variant returns what the last nm_step / nm_step_physics of this env
+ * launched: 0 generic, 1 lean (0 before the first step). Every other launch (fp64, per-env rows set, nm_step_physics, the K-step
+ * entry points) is generic. */
+int nm_set_step_variant(nm_env* env, int32_t mode);
+int nm_get_step_variant(nm_env* env);
 /* Stage-skipping measurement switches are NOT part of this ABI: they exist only in the -DNM_MEASURE build
  * (libnightmare_hip_measure.so, include/nightmare_hip_measure.h). */
 

@@ -33,7 +33,8 @@ EXPORTS = ["nm_default_config", "nm_reward_name", "nm_last_error", "nm_create", 
            "nm_set_action_latency", "nm_get_action_latency", "nm_draw_action_latency", "nm_set_action_history", "nm_get_action_history",
            "nm_set_reset_noise", "nm_get_reset_noise", "nm_reset_noise_offsets",
            "nm_set_gravity", "nm_get_gravity", "nm_draw_gravity",
-           "nm_set_servo", "nm_get_servo", "nm_draw_servo", "nm_get_servo_state", "nm_set_servo_state"]
+           "nm_set_servo", "nm_get_servo", "nm_draw_servo", "nm_get_servo_state", "nm_set_servo_state",
+           "nm_set_step_variant", "nm_get_step_variant"]
 
 
 class NmConfig(C.Structure):
@@ -200,6 +201,9 @@ def _bind(L, full):
         L.nm_draw_servo.argtypes = [vp, C.POINTER(C.c_double * 2), C.POINTER(C.c_double * 2), vp]
         L.nm_get_servo_state.argtypes = [vp, vp]
         L.nm_set_servo_state.argtypes = [vp, vp]
+    if hasattr(L, "nm_set_step_variant"):
+        L.nm_set_step_variant.argtypes = [vp, C.c_int32]
+        L.nm_get_step_variant.argtypes = [vp]
     if not full:        # the measurement build holds the env entry points only
         return L
     L.nm_gae.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_float, vp, vp]

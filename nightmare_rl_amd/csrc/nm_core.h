@@ -55,7 +55,10 @@ enum { R_ACTION_RATE, R_ANG_VEL_XY, R_BASE_HEIGHT, R_BODY_CONTACT, R_DEFAULT_POS
        R_LIN_VEL_Z, R_ORIENTATION, R_STAND_STILL, R_TORQUES, R_TRACK_ANG, R_TRACK_LIN, R_TERMINATION };
 
 // model + config constants, converted once to `real` by the host. The device kernel copies the struct (3 KB in fp32) into LDS
-// when a wave starts, so every M.x below is an LDS broadcast read, not a scalar load through a pointer.
+// when a wave starts, so every M.x below is an LDS broadcast read, not a scalar load through a pointer - and a flag among them
+// (link_rot_id, si_power, the contact modes, rew_extra, collide_batch_min) costs an LDS round trip, a v_readfirstlane and a scalar
+// branch where a stage tests it. Those tests go through the configuration traits below (CfgAsk / CfgLean): the lean step kernel
+// answers them at compile time. The values themselves (kv, h, colc[...], rew_scale[...]) are still LDS reads in every kernel.
 template <class real> struct Model {
   const real* hullv;    // [nhull][4] xyz0, body frame (HBM/L2: 27 KB)
   const real* hullnv;   // [nhull][maxnbr+1][4]: per vertex, its hull neighbours as (x, y, z, local id or -1) and, last, itself:
@@ -235,6 +238,53 @@ template <class real, int OFS> NM_FN KernArgs<real, OFS> scalar_src(const KernAr
   return KernArgs<real, OFS>{(kernarg_ptr)(((uint64_t)hi << 32) | lo)};
 }
 #endif
+
+// Questions about the env's configuration whose answer can change only when the host reconfigures the env object: the stages put them
+// to a traits type `Cfg`, handed down from wave_step as an empty tag argument.
+//   CfgAsk (the default of every stage): ask at run time - the model's flags in LDS, the optional pointers of the launch arguments.
+//   CfgLean: the shipped default configuration, answered at compile time - the model's link frames (link 0 of a leg rotated against
+//     its parent, links 1 and 2 not), solimp power 2, tibia and body contact mode 1, no reward term beyond the default table, the floor
+//     batch from three touching meshes on, and none of the optional inputs / outputs (debug buffer, state record, observation noise,
+//     injected command uniforms), no physics-only launch. The host launches a kernel built on it only while all of that holds
+//     (lean_config() below is the one place that says what "all of that" is).
+struct CfgAsk { static constexpr bool kLean = false; };
+struct CfgLean {
+  static constexpr bool kLean = true;
+  static constexpr int kTibiaMode = 1, kBodyMode = 1, kBatchMin = 3;
+  static constexpr bool link_rot_id(int k) { return k != 0; }
+};
+template <class Cfg, class real> NM_FN bool cfg_link_rot_id(const Model<real>& M, int k) {
+  if constexpr (Cfg::kLean) return Cfg::link_rot_id(k); else return uniform(M.link_rot_id[k]);
+}
+template <class Cfg, class real> NM_FN bool cfg_si_square(const Model<real>& M) {
+  if constexpr (Cfg::kLean) return true; else return M.si_power == real(2);
+}
+template <class Cfg, class real> NM_FN int cfg_tibia_mode(const Model<real>& M) {
+  if constexpr (Cfg::kLean) return Cfg::kTibiaMode; else return M.tibia_mode;
+}
+template <class Cfg, class real> NM_FN int cfg_body_mode(const Model<real>& M) {
+  if constexpr (Cfg::kLean) return Cfg::kBodyMode; else return M.body_mode;
+}
+template <class Cfg, class real> NM_FN int cfg_rew_extra(const Model<real>& M) {
+  if constexpr (Cfg::kLean) return 0; else return M.rew_extra;
+}
+template <class Cfg, class real> NM_FN int cfg_batch_min(const Model<real>& M) {
+  if constexpr (Cfg::kLean) return Cfg::kBatchMin; else return M.collide_batch_min;
+}
+// an optional pointer of the launch arguments (null = the feature is off), a flag of them
+template <class Cfg, class T> NM_FN T* cfg_opt(T* p) {
+  if constexpr (Cfg::kLean) return nullptr; else return p;
+}
+template <class Cfg> NM_FN int cfg_flag(int f) {
+  if constexpr (Cfg::kLean) return 0; else return f;
+}
+// what CfgLean assumes, for the host's choice of kernel (per launch: `A` as the launch will see it)
+template <class real> inline bool lean_config(const Model<real>& M, const Args<real>& A) {
+  for (int k = 0; k < 3; k++)
+    if ((M.link_rot_id[k] != 0) != CfgLean::link_rot_id(k)) return false;
+  return M.si_power == real(2) && M.tibia_mode == CfgLean::kTibiaMode && M.body_mode == CfgLean::kBodyMode && M.rew_extra == 0 &&
+         M.collide_batch_min == CfgLean::kBatchMin && !A.dbg && !A.rec && !A.noise_vec && !A.cmd_u && !A.physics_only && !A.ablate;
+}
 
 // ----------------------------------------------------------------------------------------- LDS image of one env
 template <class real> struct Sh {
@@ -576,7 +626,7 @@ template <class real> NM_FN V<real> legsum(const V<real>& x, const VB& isleg) { 
   return gsum8(sel(isleg, x, V<real>(real(0))));
 }
 
-template <int EP, class real, int G> NM_FN void stage_smooth(ShW<real, G>& w, const Model<real>& M, bool last) {
+template <int EP, class real, int G, class Cfg = CfgAsk> NM_FN void stage_smooth(ShW<real, G>& w, const Model<real>& M, bool last, Cfg = Cfg()) {
   typedef V<real> vr;
   real* lds = reinterpret_cast<real*>(&w.e[0]);
   // Lane groups of 8: group g works on env g % G; groups [0, G) factor M, groups [G, 2G) factor M + h*kv*I (implicitfast) - the two
@@ -688,7 +738,7 @@ template <int EP, class real, int G> NM_FN void stage_smooth(ShW<real, G>& w, co
         vr ax[3] = {ldsv(M.legc, cb + 12), ldsv(M.legc, cb + 13), ldsv(M.legc, cb + 14)};
         vr R0[9];
         {
-          if (uniform(M.link_rot_id[k])) {   // the link frame is not rotated against its parent's (femur, tibia): Rp * 1
+          if (cfg_link_rot_id<Cfg>(M, k)) {   // the link frame is not rotated against its parent's (femur, tibia): Rp * 1
 #pragma unroll
             for (int j = 0; j < 9; j++) R0[j] = Rp[j];
           } else {
@@ -1421,7 +1471,7 @@ template <class real> NM_FN void collide_rings(const Sh<real>& sh, const Model<r
     hull_ring(M, vadr + r.cur[g], r.nb[g], r.vv[g]);
   }
 }
-template <class real> NM_FN void stage_collide(Sh<real>& sh, const Model<real>& M, int* dropped, Rings<real>& rg, bool pairs = true) {
+template <class real, class Cfg = CfgAsk> NM_FN void stage_collide(Sh<real>& sh, const Model<real>& M, int* dropped, Rings<real>& rg, bool pairs = true, Cfg = Cfg()) {
   typedef V<real> vr;
   const V<int> lane = lane_id();
   const real bz = sh.qpos[2];
@@ -1513,7 +1563,7 @@ template <class real> NM_FN void stage_collide(Sh<real>& sh, const Model<real>& 
   // The standing / walking robot: several feet on the floor, each a lone contact at its support vertex (certified from the table, above).
   // Those go out together, mesh g on lane kBatchLane0 + g: one pass of per-lane frames instead of one pass per mesh.
   bool batch = false;
-  if (nhit >= M.collide_batch_min) {
+  if (nhit >= cfg_batch_min<Cfg>(M)) {
     const uint64_t hitm = (uint64_t)hitbits << kBatchLane0;
     vr X[3] = {vv[kNCOL - 1][0], vv[kNCOL - 1][1], vv[kNCOL - 1][2]}, svl = val[kNCOL - 1];
     V<int> slackl = nb[kNCOL - 1];
@@ -1680,7 +1730,7 @@ template <class X> NM_FN X noslip_pair_cost(const X& d, const X& hK1, const X& d
 template <class real, class X> NM_FN auto noslip_pair_bad(const X& change) { return change > X(real(1e-10)); }   // costChange: revert an update that does not decrease the cost
 
 // Contact rows on lanes: build, project (A = J M^-1 J'), warm start, PGS, NoSlip, map back, sensors.
-template <class real, bool PAIR, int EP> NM_FN void stage_constraint_body(Sh<real>& sh, real* jrow, const Model<real>& M, bool last, bool nosweep, BodyRef<EP, real> br) {
+template <class real, bool PAIR, int EP, class Cfg = CfgAsk> NM_FN void stage_constraint_body(Sh<real>& sh, real* jrow, const Model<real>& M, bool last, bool nosweep, BodyRef<EP, real> br) {
   typedef V<real> vr;
   const V<int> lane = lane_id();
   const int ncon = uniform(sh.ncon), nefc = 4 * ncon;
@@ -1811,10 +1861,10 @@ template <class real, bool PAIR, int EP> NM_FN void stage_constraint_body(Sh<rea
   {
     vr x = vabs(dist) * vrcp(M.si_width);
     vr ylo, yhi;
-    if (M.si_power == real(2)) {  // the model's solimp (mjmodel.xml defaults): pow(x, 2) = x*x and pow(mid, 1) = mid, both exact
-      vr omx = vmax(vr(real(1)) - x, vr(real(0)));
+    if (cfg_si_square<Cfg>(M)) {  // the model's solimp (mjmodel.xml defaults): pow(x, 2) = x*x and pow(mid, 1) = mid, both exact
+      vr omx = vmax(vsub_rn(vr(real(1)), x), vr(real(0)));     // (x keeps its own rounding: the lean and the generic instantiation agree)
       ylo = (x * x) * vrcp(M.si_mid);
-      yhi = vr(real(1)) - (omx * omx) * vrcp(real(1) - M.si_mid);
+      yhi = vsub_rn(vr(real(1)), (omx * omx) * vrcp(real(1) - M.si_mid));
     } else {
       ylo = vpow(x, vr(M.si_power)) / vpow(vr(M.si_mid), vr(M.si_power - real(1)));
       yhi = vr(real(1)) - vpow(vmax(vr(real(1)) - x, vr(real(0))), vr(M.si_power)) / vpow(vr(real(1) - M.si_mid), vr(M.si_power - real(1)));
@@ -2098,8 +2148,8 @@ template <class real, bool PAIR, int EP> NM_FN void stage_constraint_body(Sh<rea
   wave_sync();
 }
 
-template <class real, int EP> NM_COLD void stage_constraint_pairs(Sh<real>& sh, real* jrow, const Model<real>& M, bool last, bool nosweep, BodyRef<EP, real> br) {
-  stage_constraint_body<real, true, EP>(sh, jrow, M, last, nosweep, br);
+template <class real, int EP, class Cfg = CfgAsk> NM_COLD void stage_constraint_pairs(Sh<real>& sh, real* jrow, const Model<real>& M, bool last, bool nosweep, BodyRef<EP, real> br) {
+  stage_constraint_body<real, true, EP, Cfg>(sh, jrow, M, last, nosweep, br);
 }
 
 // =========================================================================================  stage C, two envs at once
@@ -2113,7 +2163,7 @@ constexpr int kMaxCon2 = 8, kMaxRow2 = 4 * kMaxCon2;
 #ifdef NM_EMUL
 inline long& nm_emul_together() { static long n = 0; return n; }   // host emulation only: how often the two-env pass ran (tests assert it did)
 #endif
-template <int EP, class real> NM_FN void stage_constraint2(ShW<real, 2>& w, const Model<real>& M, bool last, bool nosweep) {
+template <int EP, class real, class Cfg = CfgAsk> NM_FN void stage_constraint2(ShW<real, 2>& w, const Model<real>& M, bool last, bool nosweep, Cfg = Cfg()) {
   typedef V<real> vr;
   constexpr int kSR = (int)(sizeof(Sh<real>) / sizeof(real)), kSI = (int)(sizeof(Sh<real>) / sizeof(int));
   const V<int> lane = lane_id();
@@ -2212,10 +2262,10 @@ template <int EP, class real> NM_FN void stage_constraint2(ShW<real, 2>& w, cons
   {
     vr x = vabs(dist) * vrcp(M.si_width);
     vr ylo, yhi;
-    if (M.si_power == real(2)) {
-      vr omx = vmax(vr(real(1)) - x, vr(real(0)));
+    if (cfg_si_square<Cfg>(M)) {
+      vr omx = vmax(vsub_rn(vr(real(1)), x), vr(real(0)));     // (x keeps its own rounding: the lean and the generic instantiation agree)
       ylo = (x * x) * vrcp(M.si_mid);
-      yhi = vr(real(1)) - (omx * omx) * vrcp(real(1) - M.si_mid);
+      yhi = vsub_rn(vr(real(1)), (omx * omx) * vrcp(real(1) - M.si_mid));
     } else {
       ylo = vpow(x, vr(M.si_power)) / vpow(vr(M.si_mid), vr(M.si_power - real(1)));
       yhi = vr(real(1)) - vpow(vmax(vr(real(1)) - x, vr(real(0))), vr(M.si_power)) / vpow(vr(real(1) - M.si_mid), vr(M.si_power - real(1)));
@@ -2840,10 +2890,10 @@ template <class real> NM_COLD void floor_frames(Sh<real>& sh) {
   stsv(sh.cnrm(), c * 3 + 2, V<real>(real(1)), on);
   wave_sync();
 }
-template <class real, int EP> NM_FN void stage_constraint(Sh<real>& sh, real* jrow, const Model<real>& M, bool last, bool nosweep, BodyRef<EP, real> br) {
+template <class real, int EP, class Cfg = CfgAsk> NM_FN void stage_constraint(Sh<real>& sh, real* jrow, const Model<real>& M, bool last, bool nosweep, BodyRef<EP, real> br) {
   if (uniform(sh.ncon) > kMaxCon) { floor_frames(sh); stage_constraint_big<real, EP>(sh, M, last, nosweep, br); }
-  else if (uniform(sh.anypair) != 0) { floor_frames(sh); stage_constraint_pairs<real, EP>(sh, jrow, M, last, nosweep, br); }
-  else stage_constraint_body<real, false, EP>(sh, jrow, M, last, nosweep, br);
+  else if (uniform(sh.anypair) != 0) { floor_frames(sh); stage_constraint_pairs<real, EP, Cfg>(sh, jrow, M, last, nosweep, br); }
+  else stage_constraint_body<real, false, EP, Cfg>(sh, jrow, M, last, nosweep, br);
 }
 
 // =========================================================================================  stage D
@@ -3020,7 +3070,7 @@ inline void nm_set_priority(int) {}
 #endif
 
 // mj_step(model, data, 1) for the G envs of the wave
-template <int EP, class real, int G> NM_FN void substep(ShW<real, G>& w, const Model<real>& M, bool last, int* dropped, int ablate) {
+template <int EP, class real, int G, class Cfg = CfgAsk> NM_FN void substep(ShW<real, G>& w, const Model<real>& M, bool last, int* dropped, int ablate, Cfg cfg = Cfg()) {
   const V<int> lane = opaque_lane();
   if constexpr (G == 2) {   // both envs at once on half-waves (lanes 0..31 | 32..63), as in env_load2
     constexpr int kSR = (int)(sizeof(Sh<real>) / sizeof(real));
@@ -3049,13 +3099,13 @@ template <int EP, class real, int G> NM_FN void substep(ShW<real, G>& w, const M
   }
   wave_sync();
   nm_stamp(1);
-  if (!(ablate & 8)) stage_smooth<EP>(w, M, last);
+  if (!(ablate & 8)) stage_smooth<EP>(w, M, last, cfg);
   nm_stamp(2);
   // collision of every env of the wave, then the constraint stage: both envs in one pass when each has 1..kMaxCon2 floor contacts
   // (stage_constraint2), else one after the other
   for (int e = 0; e < G; e++) {
     Sh<real>& sh = w.e[e];
-    if (!(ablate & 1)) { Rings<real> rg; collide_rings(sh, M, rg); stage_collide(sh, M, dropped, rg, G != 2 && !(ablate & 16)); }
+    if (!(ablate & 1)) { Rings<real> rg; collide_rings(sh, M, rg); stage_collide(sh, M, dropped, rg, G != 2 && !(ablate & 16), cfg); }
     else { sh.ncon = 0; sh.anypair = 0; wave_sync(); }
   }
   if constexpr (G == 2) {
@@ -3074,7 +3124,7 @@ template <int EP, class real, int G> NM_FN void substep(ShW<real, G>& w, const M
       nm_emul_together() += 1;
 #endif
       w.e[0].ntog += 1;
-      stage_constraint2<EP>(w, M, last, (ablate & 2) != 0);
+      stage_constraint2<EP>(w, M, last, (ablate & 2) != 0, cfg);
       nm_stamp(8);
     }
   }
@@ -3082,7 +3132,7 @@ template <int EP, class real, int G> NM_FN void substep(ShW<real, G>& w, const M
     for (int e = 0; e < G; e++) {
       BodyRef<EP, real> br;
       if constexpr (EP >= 2) br = BodyRef<EP, real>(body_rows(w) + e * kBodyP);
-      stage_constraint<real, EP>(w.e[e], w.jrow, M, last, (ablate & 2) != 0, br);
+      stage_constraint<real, EP, Cfg>(w.e[e], w.jrow, M, last, (ablate & 2) != 0, br);
       nm_stamp(8);
     }
   if constexpr (EP >= 4) stage_integrate<real, G, EP>(w, M);
@@ -3513,7 +3563,7 @@ template <int EP = 0, class real> NM_FN void env_finish(Sh<real>& sh, const Mode
 // `mid()` runs after every HBM read has been issued and before the first of them is waited for: the kernel copies the model constants
 // (L2 -> LDS, `M` is that copy) there, so the two round trips of a wave's start-up overlap instead of following each other.
 struct NoMid { NM_FN void operator()() const {} NM_FN void operator()(int) const {} };
-template <int EP, class real, class Src, class Mid> NM_FN void env_load2(ShW<real, 2>& w, const Model<real>& M, const Src& src, int wave, Mid&& mid) {
+template <int EP, class real, class Src, class Mid, class Cfg = CfgAsk> NM_FN void env_load2(ShW<real, 2>& w, const Model<real>& M, const Src& src, int wave, Mid&& mid, Cfg = Cfg()) {
   typedef V<real> vr;
   const Args<real>& A = launch_args(src);
   constexpr bool kS = ArgSrc<Src>::kScalarBase;
@@ -3543,7 +3593,7 @@ template <int EP, class real, class Src, class Mid> NM_FN void env_load2(ShW<rea
   V<int> dl = V<int>(0);
   V<float> h0 = V<float>(0.0f), h1 = V<float>(0.0f), h2 = V<float>(0.0f);
   if constexpr (EP >= 3)
-    if (!A.physics_only) {
+    if (!cfg_flag<Cfg>(A.physics_only)) {
       dl = gldx<kS>(lat_delay(A), env);
       h0 = gldx<kS>(lat_hist(A), l18c + env * (kLatH * kNU));
       h1 = gldx<kS>(lat_hist(A), l18c + (env * (kLatH * kNU) + kNU));
@@ -3552,7 +3602,7 @@ template <int EP, class real, class Src, class Mid> NM_FN void env_load2(ShW<rea
   // level 5: each env's servo row (lanes 0..3 of its half) and its limited target (lane of the half = joint), with the step's other reads
   vr servo_in = vr(real(0)), lim_in = vr(real(0));
   if constexpr (EP >= 5)
-    if (!A.physics_only) {
+    if (!cfg_flag<Cfg>(A.physics_only)) {
       servo_in = gldx<kS>(servo_rows_of(A), sel(hl < kServoP, hl, V<int>(0)) + env * kServoP);
       lim_in = gldx<kS>(servo_state_of(A), l18c + env * kNU);
     }
@@ -3560,7 +3610,7 @@ template <int EP, class real, class Src, class Mid> NM_FN void env_load2(ShW<rea
   int64_t ep = 0;
   uint32_t ctr_in = 0;
 #endif
-  if (!A.physics_only) {
+  if (!cfg_flag<Cfg>(A.physics_only)) {
     cmd_in = gldx<kS>(A.cmd, sel(hl < 3, hl, V<int>(0)) + env * 3);
     eps_in = gldx<kS>(A.epsum, sel(hl < kNREW, hl, V<int>(0)) + env * kNREW);
 #ifndef NM_EMUL
@@ -3605,7 +3655,7 @@ template <int EP, class real, class Src, class Mid> NM_FN void env_load2(ShW<rea
 #else
   act = (real)af;
 #endif
-  if (!A.physics_only) {
+  if (!cfg_flag<Cfg>(A.physics_only)) {
     stsv(rb, ho + (hl + NM_OFS(ecmd)), cmd_in, hl < 3);
     stsv(rb, ho + (hl + NM_OFS(eepsum)), eps_in, hl < kNREW);
 #ifdef NM_EMUL
@@ -3666,7 +3716,7 @@ template <int EP, class real, class Src, class Mid> NM_FN void env_load2(ShW<rea
 // the counters) is out: the kernel takes the wave's end-of-step ticket there, so the ticket's round trip is hidden under E7 / E8.
 // `published(1)` comes again after E7, a microsecond later: the group ticket is back by then, and the wave that turns out to be the last of
 // its group draws the top-level ticket there - under E8 and the buffer stores.
-template <int EP = 0, class real, class Src, class Pub> NM_FN void env_finish2(ShW<real, 2>& w, const Model<real>& M, const Src& src, int wave, int dropped, Pub&& published) {
+template <int EP = 0, class real, class Src, class Pub, class Cfg = CfgAsk> NM_FN void env_finish2(ShW<real, 2>& w, const Model<real>& M, const Src& src, int wave, int dropped, Pub&& published, Cfg = Cfg()) {
   typedef V<real> vr;
   const Args<real>& A = launch_args(src);
   constexpr bool kS = ArgSrc<Src>::kScalarBase;
@@ -3701,14 +3751,14 @@ template <int EP = 0, class real, class Src, class Pub> NM_FN void env_finish2(S
     gstx<kS>(A.qpos, hl + env * kNQ, q, live & (hl < kNQ));
     gstx<kS>(A.qvel, hl + env * kNV, v, live & (hl < kNV));
     gstx<kS>(A.qwarm, hl + env * kNV, wq, live & (hl < kNV));
-    if (A.rec) {
+    if (cfg_opt<Cfg>(A.rec)) {
       const VB r = live & (env == V<int>(A.rec_env));
       gstx<kS>(A.rec, hl, q, r & (hl < kNQ));
       gstx<kS>(A.rec, hl + kNQ, v, r & (hl < kNV));
       gstx<kS>(A.rec, V<int>(kNQ + kNV), to_real<real>(nwarn), r & (hl == 0));
     }
   }
-  if (A.dbg) {
+  if (cfg_opt<Cfg>(A.dbg)) {
     if (lives[0]) env_debug(w.e[0], A, wave * 2, dropped);
     if (lives[1]) env_debug(w.e[1], A, wave * 2 + 1, 0);
   }
@@ -3721,7 +3771,7 @@ template <int EP = 0, class real, class Src, class Pub> NM_FN void env_finish2(S
     if (hl == 0 && live && nwarn) nm_consume(atomicAdd(A.stat_cnt + 2, nwarn));
 #endif
   }
-  if (A.physics_only) return;
+  if (cfg_flag<Cfg>(A.physics_only)) return;
   if (NM_ABLATE(A.ablate) & 128) return;   // measurement only: epilogue inputs were loaded, nothing of E3-E8 runs
   NM_ESTAMP(11);
 
@@ -3763,7 +3813,7 @@ template <int EP = 0, class real, class Src, class Pub> NM_FN void env_finish2(S
   auto resample = [&](int hh, int which) {
     const int e = wave * 2 + hh;
     real ux, uy;
-    if (A.cmd_u) { ux = gld1(A.cmd_u, (size_t)(e * 4 + 2 * which)); uy = gld1(A.cmd_u, (size_t)(e * 4 + 2 * which + 1)); }
+    if (cfg_opt<Cfg>(A.cmd_u)) { ux = gld1(A.cmd_u, (size_t)(e * 4 + 2 * which)); uy = gld1(A.cmd_u, (size_t)(e * 4 + 2 * which + 1)); }
     else {
       ux = (real)rand_u24_bits(A.seed, (uint64_t)(A.env_offset + e), ctr[hh]) * real(1.0 / 16777216.0);
       uy = (real)rand_u24_bits(A.seed, (uint64_t)(A.env_offset + e), ctr[hh] + 1) * real(1.0 / 16777216.0);
@@ -3796,12 +3846,12 @@ template <int EP = 0, class real, class Src, class Pub> NM_FN void env_finish2(S
 #pragma unroll
     for (int l = 1; l < 6; l++) fm = vmax(fm, feet[l]);
     reset = reset | (fm > vr(M.term_force));
-    if ((M.tibia_mode == 2) | (M.body_mode == 2)) {   // env.py:248-251
+    if ((cfg_tibia_mode<Cfg>(M) == 2) | (cfg_body_mode<Cfg>(M) == 2)) {   // env.py:248-251
       vr tm = tib[0];
 #pragma unroll
       for (int l = 1; l < 6; l++) tm = vmax(tm, tib[l]);
-      if (M.tibia_mode == 2) reset = reset | (tm > vr(M.tibia_max));
-      if (M.body_mode == 2) reset = reset | (body > vr(M.body_max));
+      if (cfg_tibia_mode<Cfg>(M) == 2) reset = reset | (tm > vr(M.tibia_max));
+      if (cfg_body_mode<Cfg>(M) == 2) reset = reset | (body > vr(M.body_max));
     }
     vr nrm = vsqrt(pg[0] * pg[0] + pg[1] * pg[1] + pg[2] * pg[2]);
     if (sizeof(real) == 8) reset = reset | (vacos(-pg[2] / nrm) > vr(real(1.0471975511965976)));
@@ -3843,9 +3893,9 @@ template <int EP = 0, class real, class Src, class Pub> NM_FN void env_finish2(S
     vr da = prev_act - act;
     rt[R_ACTION_RATE] = hsum32(sel(l18, da * da, vr(real(0)))) * M.rew_scale[R_ACTION_RATE];
     vr sumt = ((tib[0] + tib[1]) + (tib[2] + tib[3])) + (tib[4] + tib[5]);
-    if ((M.tibia_mode != 1) | (M.body_mode != 1)) {   // env.py:479-485: each part counts only in mode 1
-      sumt = M.tibia_mode == 1 ? sumt : vr(real(0));
-      body = M.body_mode == 1 ? body : vr(real(0));
+    if ((cfg_tibia_mode<Cfg>(M) != 1) | (cfg_body_mode<Cfg>(M) != 1)) {   // env.py:479-485: each part counts only in mode 1
+      sumt = cfg_tibia_mode<Cfg>(M) == 1 ? sumt : vr(real(0));
+      body = cfg_body_mode<Cfg>(M) == 1 ? body : vr(real(0));
     }
     rt[R_BODY_CONTACT] = (sumt + body) * M.rew_scale[R_BODY_CONTACT];
     vr dp = dofpos - defp;
@@ -3858,7 +3908,7 @@ template <int EP = 0, class real, class Src, class Pub> NM_FN void env_finish2(S
     vr el = (cmd[0] - blv[0]) * (cmd[0] - blv[0]) + (cmd[1] - blv[1]) * (cmd[1] - blv[1]);
     rt[R_TRACK_LIN] = vexp(-el / M.sigma) * M.rew_scale[R_TRACK_LIN];
     rt[R_TERMINATION] = sel(reset & !time_out, vr(M.rew_scale[R_TERMINATION]), vr(real(0)));
-    if (M.rew_extra) {   // the terms config.py:88-95 ships with scale 0: one uniform branch in the default configuration
+    if (cfg_rew_extra<Cfg>(M)) {   // the terms config.py:88-95 ships with scale 0: one uniform branch in the default configuration
       rt[R_ANG_VEL_XY] = (bav[0] * bav[0] + bav[1] * bav[1]) * M.rew_scale[R_ANG_VEL_XY];                  // env.py:403-405
       vr dh = SHR(bh, V<int>(0)) - M.base_h_target;
       rt[R_BASE_HEIGHT] = dh * dh * M.rew_scale[R_BASE_HEIGHT];                                            // env.py:411-413
@@ -3910,7 +3960,7 @@ template <int EP = 0, class real, class Src, class Pub> NM_FN void env_finish2(S
     auto put = [&](const vr& x0, const V<int>& idx, const VB& m0) {
       const VB m = m0 & live;
       vr x = x0;
-      if (A.noise_vec) {  // env.py:304-305: + (2 U[0,1) - 1) * noise_scale_vec before the clip
+      if (cfg_opt<Cfg>(A.noise_vec)) {  // env.py:304-305: + (2 U[0,1) - 1) * noise_scale_vec before the clip
         auto nz = [&](int k, int e) {
           real u = A.noise_u ? gld1(A.noise_u, (size_t)e * kNOBS + k)
                              : (real)rand_u24_bits(A.seed + kNoiseKey, (uint64_t)(A.env_offset + e), (uint32_t)(A.noise_step * kNOBS + k)) * real(1.0 / 16777216.0);
@@ -3990,12 +4040,14 @@ template <class real, int G> NM_FN void latency_switch(ShW<real, G>& w, int s) {
 
 // `src`: where the launch arguments are read from (ArgSrc above). The two-env stages fetch what they need where they begin; what the
 // substep loop itself reads (nsub, and the ablation mask of a measurement build) is fetched once here and stays in a scalar register.
-template <class real, int G, int EP = 0, class Mid = NoMid, class Pub = NoMid, class Src = Args<real>>
-NM_FN void wave_step(ShW<real, G>& w, const Model<real>& M, const Src& src, int wave, Mid&& mid = Mid(), Pub&& published = Pub()) {
+// `cfg`: who answers the stages' questions about the configuration (CfgAsk / CfgLean above); the lean answers exist for two envs per wave.
+template <class real, int G, int EP = 0, class Mid = NoMid, class Pub = NoMid, class Src = Args<real>, class Cfg = CfgAsk>
+NM_FN void wave_step(ShW<real, G>& w, const Model<real>& M, const Src& src, int wave, Mid&& mid = Mid(), Pub&& published = Pub(), Cfg cfg = Cfg()) {
+  static_assert(!Cfg::kLean || G == 2, "CfgLean: the one-env stages (env_load, env_finish) ask at run time");
   const Args<real>& A = launch_args(src);
   nm_stamp(-1);
   if constexpr (G == 2) {
-    env_load2<EP>(w, M, src, wave, mid);
+    env_load2<EP>(w, M, src, wave, mid, cfg);
   } else {
     mid();
 #pragma unroll
@@ -4016,12 +4068,12 @@ NM_FN void wave_step(ShW<real, G>& w, const Model<real>& M, const Src& src, int 
   if (!(NM_ABLATE(A.ablate) & 2048))
   for (int s = 0; s < A.nsub; s++) {
     if constexpr (EP >= 3) { if (s > 0) latency_switch(w, s); }
-    substep<EP>(w, M, s == A.nsub - 1, &dropped, NM_ABLATE(A.ablate));
+    substep<EP>(w, M, s == A.nsub - 1, &dropped, NM_ABLATE(A.ablate), cfg);
   }
   if constexpr (G == 2) {
-    if constexpr (EP >= 4) env_finish2<EP>(w, M, src, wave, dropped, published);
+    if constexpr (EP >= 4) env_finish2<EP>(w, M, src, wave, dropped, published, cfg);
     else
-    env_finish2(w, M, src, wave, dropped, published);
+    env_finish2(w, M, src, wave, dropped, published, cfg);
   } else {
 #pragma unroll
     for (int e = 0; e < G; e++) {

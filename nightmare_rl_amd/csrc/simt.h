@@ -83,6 +83,17 @@ NM_FN double vrcp(double x) { return 1.0 / x; }
 // row layout: the contraction is not left to the compiler's mood)
 NM_FN float vfma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 NM_FN double vfma(double a, double b, double c) { return __builtin_fma(a, b, c); }
+// a - b with `b` rounded as the value it is, never as the product inside a fused multiply-add. Where the compiler is free to contract it
+// fuses a product with a subtraction of the same basic block, and which blocks there are differs between two instantiations of one
+// stage (a branch one of them answers at compile time): where both must give the same bits, the subtraction says so itself.
+NM_FN float vsub_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+NM_FN double vsub_rn(double a, double b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
 // a in the lanes of the wave-uniform 64-bit lane mask m (an SGPR pair), b elsewhere: ONE v_cndmask. The sweeps walk their rows in lane
 // order, so the mask of row i + 1 is the mask of row i shifted by one (s_lshl_b64): two instructions per kept value instead of three.
 NM_FN float sel_mask(uint64_t m, float a, float b) {
@@ -341,6 +352,7 @@ NM_FN double vrcp(double x) { return 1.0 / x; }
 template <class T, class S> NM_FN V<T> vcvt(const V<S>& a) { V<T> r; for (int i = 0; i < NM_WAVE; i++) r.v[i] = (T)a.v[i]; return r; }
 
 template <class T> NM_FN V<T> vfma(const V<T>& a, const V<T>& b, const V<T>& c) { return a * b + c; }      // (the host build is compiled with -ffp-contract=off: two roundings, everywhere)
+template <class A, class B> NM_FN auto vsub_rn(const A& a, const B& b) { return a - b; }     // (no contraction anywhere in the host build)
 NM_FN float vfma(float a, float b, float c) { return a * b + c; }
 NM_FN double vfma(double a, double b, double c) { return a * b + c; }
 template <class T> NM_FN V<T> sel_mask(uint64_t m, const V<T>& a, const V<T>& b) {

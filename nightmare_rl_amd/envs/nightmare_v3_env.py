@@ -1026,6 +1026,15 @@ class NightmareV3Env:
         self._ret_acc = t
         self._ck(self._L.nm_set_return_accumulator(self._h, None if t is None else t.data_ptr()))
 
+    def set_step_variant(self, generic):
+        """generic=True: step() always launches the generic step kernel; False (the default of a new env): the lean instantiation for the
+        shipped default configuration whenever a launch qualifies (include/nightmare_hip.h nm_set_step_variant). Same bits either way."""
+        self._ck(self._L.nm_set_step_variant(self._h, 1 if generic else 0))
+
+    def step_variant(self):
+        """'lean' or 'generic': what the last step() / step_physics() launched."""
+        return "lean" if self._L.nm_get_step_variant(self._h) == 1 else "generic"
+
     def profile(self, enable):
         """(sum_ms, count) of step-kernel HIP-event times since the last call; sets event recording on/off."""
         ms, cnt = C.c_double(0), C.c_int64(0)
