@@ -298,6 +298,32 @@ int nm_get_servo(nm_env* env, void* out_dev, void* stream);
 int nm_draw_servo(nm_env* env, const double lo[2], const double hi[2], void* stream);
 int nm_get_servo_state(nm_env* env, double* limited);
 int nm_set_servo_state(nm_env* env, const double* limited);
+/* Servo torque limit: MuJoCo 3.1.2's actuator `forcerange`, per env. The reference's servos are ideal (no forcerange in mjmodel.xml);
+ * the semantics are stated from the upstream source of mj_fwdActuation and mjd_actuator_vel.
+ * Each env carries one row of 4 words in the env's dtype: fmax_coxa, fmax_femur, fmax_tibia, pad. Word k limits joint 3 leg + k of all
+ * six legs; each value > 0, +inf = no limit; the range is symmetric, [-fmax, +fmax].
+ * Force (mj_fwdActuation), in every forward pass of every substep, with the env's own kv (nm_set_env_params):
+ *   f = kv clip(ctrl, +-8) - kv qvel;   qfrc_actuator = f > fmax ? fmax : (f < -fmax ? -fmax : f)
+ * (compares and selects: a NaN force stays NaN and meets the bad-state check as it does without a limit).
+ * Implicit factor (mjd_actuator_vel inside mj_implicit, implicitfast): an actuator whose force sits on its bound contributes no velocity
+ * derivative, so the step's second factor is that of M + h kv D, D = diag(d_j), d_j = 1 where |f_j| < fmax_j and 0 otherwise (the 6 base
+ * dofs 0 as before), decided on the same f as the clamp, in the same forward pass.
+ * It is physics, like friction, kv, payload and gravity: nm_step, nm_step_physics, nm_rollout, nm_play and nm_step_tape honour it alike,
+ * alone or with any other per-env kind; resets, pushes, latency and the servo target model meet it through the ctrl they produce alone.
+ * No observation slot, reward term, record or state-log field changes. Off is the default, and off equals "on with (+inf, +inf, +inf)
+ * in every env" under == in every output.
+ * nm_set_torque_limit (mj_fwdActuation's clamp, mjd_actuator_vel's mask): `rows` is a DEVICE array [N,4] in the env's dtype, copied on
+ *   `stream`; NULL switches the feature off (nothing is freed). Refused, named by nm_last_error, before anything of the env changes (the
+ *   rows are read back and judged on the host, which waits for `stream`): a limit that is not > 0 (NaN included; +inf is admitted).
+ * nm_get_torque_limit (the forcerange the stages read): the rows into a DEVICE array [N,4] on `stream`; (+inf, +inf, +inf, 0) for every
+ *   env while the feature is off.
+ * nm_draw_torque_limit (forcerange randomisation): row[e] = (f0, f1, f2, 0), f_c = lo[c] + u (hi[c] - lo[c]) in the env's precision,
+ *   product and sum rounded separately, u ~ U[0,1) from the counter RNG keyed by (seed + "TORQUE", global env id, c) - three independent
+ *   draws per env; sharding changes nothing; lo == hi pins a column; switches the feature on. Refused before any device call: non-finite
+ *   bounds, lo > hi, lo <= 0. */
+int nm_set_torque_limit(nm_env* env, const void* rows_dev, void* stream);
+int nm_get_torque_limit(nm_env* env, void* out_dev, void* stream);
+int nm_draw_torque_limit(nm_env* env, const double lo[3], const double hi[3], void* stream);
 /* State log (envs/nightmare_v3_env.py:261-272 records data[0]): env_index >= 0 makes every nm_step keep that env's
  * post-physics, pre-reset qpos/qvel; -1 = off. nm_get_state_record copies the last record to HOST qpos[25], qvel[24] and
  * the number of MuJoCo bad-state resets inside that step (data.time restarts there). Synchronous. */

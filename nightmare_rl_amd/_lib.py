@@ -34,6 +34,7 @@ EXPORTS = ["nm_default_config", "nm_reward_name", "nm_last_error", "nm_create", 
            "nm_set_reset_noise", "nm_get_reset_noise", "nm_reset_noise_offsets",
            "nm_set_gravity", "nm_get_gravity", "nm_draw_gravity",
            "nm_set_servo", "nm_get_servo", "nm_draw_servo", "nm_get_servo_state", "nm_set_servo_state",
+           "nm_set_torque_limit", "nm_get_torque_limit", "nm_draw_torque_limit",
            "nm_set_step_variant", "nm_get_step_variant"]
 
 
@@ -204,6 +205,10 @@ def _bind(L, full):
     if hasattr(L, "nm_set_step_variant"):
         L.nm_set_step_variant.argtypes = [vp, C.c_int32]
         L.nm_get_step_variant.argtypes = [vp]
+    if hasattr(L, "nm_set_torque_limit"):
+        L.nm_set_torque_limit.argtypes = [vp, vp, vp]
+        L.nm_get_torque_limit.argtypes = [vp, vp, vp]
+        L.nm_draw_torque_limit.argtypes = [vp, C.POINTER(C.c_double * 3), C.POINTER(C.c_double * 3), vp]
     if not full:        # the measurement build holds the env entry points only
         return L
     L.nm_gae.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_float, vp, vp]

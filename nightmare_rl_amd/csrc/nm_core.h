@@ -195,6 +195,15 @@ template <class VR, class R> NM_FN VR servo_limit(const VR& Lo, const VR& Tt, co
   const VR d = Tt - Lo;
   return sel(vabs(d) <= rate, Tt, sel(d < VR(0), Lo - rate, Lo + rate));
 }
+// The servo torque limit (nm_set_torque_limit, level EP = 6 of the step; MuJoCo's actuator forcerange): one row of kTorqueP words per env
+// in the env's dtype - fmax of the coxa, femur and tibia servos (word k limits joint 3 leg + k of all six legs; > 0, +inf = no limit), a
+// pad. The rows are appended to the envp allocation behind the servo state: nothing in front of them moves. In every forward pass
+// (stage A), per joint, with f = kv ctrl - kv qvel:
+//   qfrc_actuator = f > fmax ? fmax : (f < -fmax ? -fmax : f)        (mj_fwdActuation; compares and selects: a NaN force stays NaN)
+//   the joint enters the implicit factor M + h kv D with d = 1 where |f| < fmax, 0 otherwise        (mjd_actuator_vel in mj_implicit)
+constexpr int kTorqueP = 4;
+constexpr uint64_t kTorqueKey = 0x544F52515545ull;   // nm_draw_torque_limit: rand_u24_bits(seed + kTorqueKey, global env id, column)
+template <class real> NM_FN const real* torque_rows_of(const Args<real>& A) { return servo_state_of(A) + (size_t)A.N * kNU; }
 constexpr int kDbgN = 256;
 
 // Where a stage reads the launch arguments from: the stages that touch them (env_load*, env_finish*, wave_step) take the source as a
@@ -383,6 +392,17 @@ template <class real, int G> struct ShWSel<real, G, 4> {
 };
 // Level 5 (level 4 plus the servo target model) adds nothing to LDS: it parks its late command where level 3 does.
 template <class real, int G> struct ShWSel<real, G, 5> : ShWSel<real, G, 4> {};
+// Level 6 (level 5 plus the servo torque limit) keeps the G torque rows of the wave's envs behind level 4's block: stage A reads them in
+// every forward pass.
+template <class real, int G> struct ShWT {
+  ShWG<real, G> g;
+  real torque[G * kTorqueP];
+};
+template <class real, int G> NM_FN real* torque_rows(ShW<real, G>& w) { return reinterpret_cast<ShWT<real, G>*>(&w)->torque; }
+template <class real, int G> struct ShWSel<real, G, 6> {
+  typedef ShWT<real, G> type;
+  static NM_FN ShW<real, G>& images(type& s) { return s.g.l.b.w; }
+};
 #define NM_OFS(field) ((int)(offsetof(Sh<real>, field) / sizeof(real)))
 #define NM_IOFS(field) ((int)(offsetof(Sh<real>, field) / sizeof(int)))
 
@@ -395,7 +415,9 @@ template <class real, int G> struct ShWSel<real, G, 5> : ShWSel<real, G, 4> {};
 // level 3 plus the env's own gravity in the base's bias acceleration, in the bad-state free-fall step and in the epilogue's projected
 // gravity (the host supplies defaults for every kind that is off: zero delays, so a level-4 launch without latency commands as level 2);
 // 5, launched while servo rows are set, is level 4 with the load stage's command formed from the env's rate-limited target and damped
-// by its d_gain (env_load*; no physics stage differs from level 4's).
+// by its d_gain (env_load*; no physics stage differs from level 4's); 6, launched while torque rows are set, is level 5 with stage A's
+// servo force clamped to the env's limits and the saturated joints left out of the implicit factor (the first level that changes a
+// physics stage: its statements stand under EP >= 6 alone).
 template <int EP, class real> NM_FN real env_mu(const Sh<real>& sh, const Model<real>& M) {
   if constexpr (EP != 0) return sh.envp[EP_MU]; else return M.mu;
 }
@@ -421,6 +443,11 @@ template <class real> struct BodyRef<4, real> {
   NM_FN explicit BodyRef(const real* q) : p(q) {}
 };
 template <class real> struct BodyRef<5, real> {
+  const real* p;
+  NM_FN BodyRef() : p(nullptr) {}
+  NM_FN explicit BodyRef(const real* q) : p(q) {}
+};
+template <class real> struct BodyRef<6, real> {
   const real* p;
   NM_FN BodyRef() : p(nullptr) {}
   NM_FN explicit BodyRef(const real* q) : p(q) {}
@@ -960,10 +987,32 @@ template <int EP, class real, int G, class Cfg = CfgAsk> NM_FN void stage_smooth
     const V<int> eoQ = eo + sel(pass1, V<int>(NM_OFS(legtmp) + 36), V<int>(NM_OFS(qfs)));
     const V<int> eoA = eo + sel(pass1, V<int>(NM_OFS(legtmp) + 60), V<int>(NM_OFS(qas)));
     vr Mh[6];
+    vr fa[3];      // level 6 only: the clamped servo forces of the lane's leg (mj_fwdActuation with forcerange)
+    if constexpr (EP >= 6) {
+      // the env's torque row lies behind level 4's block (torque_rows). The force, the clamp and the mask of the lane's three joints come
+      // first: a joint whose force sits on its bound has no velocity derivative (mjd_actuator_vel), so it stays out of M + h kv D. Both
+      // are decided on the same f; compares and selects, so a NaN force stays NaN and masks its joint out.
+      typedef ShWT<real, G> WT;
+      const V<int> to = (grp & (G - 1)) * kTorqueP + (int)(offsetof(WT, torque) / sizeof(real));
+      const vr kv = LDG(envp, EP_KV);
+      const vr hkv = M.h * kv;
+      vr dgk[3];
+#pragma unroll
+      for (int k = 0; k < 3; k++) {
+        vr ctrl = LDL(ctrl, leg * 3 + k), qd = LDL(qvel, leg * 3 + (6 + k));
+        ctrl = vmin(vmax(ctrl, vr(-M.ctrl_max)), vr(M.ctrl_max));
+        // (the contraction the compiler gives the lower levels' kv ctrl - kv qd - cl, written down: default rows then give their bits)
+        const vr f = vfma(kv, ctrl, -(kv * qd)), fmax = ldsv(lds, to + k);
+        fa[k] = sel(f > fmax, fmax, sel(f < -fmax, -fmax, f));
+        dgk[k] = sel(pass1 & (vabs(f) < fmax), hkv, vr(real(0)));
+      }
+      Mh[0] = Ml[0] + dgk[0]; Mh[1] = Ml[1]; Mh[2] = Ml[2]; Mh[3] = Ml[3] + dgk[1]; Mh[4] = Ml[4]; Mh[5] = Ml[5] + dgk[2];
+    } else {
     vr dg;
     if constexpr (EP != 0) dg = sel(pass1, M.h * LDG(envp, EP_KV), vr(real(0)));   // the env's own kv: lanes 8g..8g+7 are env g % G
     else dg = sel(pass1, vr(M.h * M.kv), vr(real(0)));
     Mh[0] = Ml[0] + dg; Mh[1] = Ml[1]; Mh[2] = Ml[2]; Mh[3] = Ml[3] + dg; Mh[4] = Ml[4]; Mh[5] = Ml[5] + dg;
+    }
     vr Mi[6], W[3][6];
     ldl3(Mi, Mh, real(1));
 #pragma unroll
@@ -999,12 +1048,15 @@ template <int EP, class real, int G, class Cfg = CfgAsk> NM_FN void stage_smooth
       vr y[3], t[3];
 #pragma unroll
       for (int k = 0; k < 3; k++) {
+        if constexpr (EP >= 6) y[k] = fa[k] - cl[k];      // the clamped force, formed in front of the factorisation
+        else {
         vr ctrl = LDL(ctrl, leg * 3 + k), qd = LDL(qvel, leg * 3 + (6 + k));
         ctrl = vmin(vmax(ctrl, vr(-M.ctrl_max)), vr(M.ctrl_max));
         if constexpr (EP != 0) {
           const vr kv = LDG(envp, EP_KV);
           y[k] = kv * ctrl - kv * qd - cl[k];
         } else y[k] = M.kv * ctrl - M.kv * qd - cl[k];
+        }
         stsv(lds, eoQ + leg * 3 + (6 + k), y[k], st_leg);
       }
       ldl3_solve(t, Mi, y);
@@ -3145,7 +3197,7 @@ template <int EP, class real, int G, class Cfg = CfgAsk> NM_FN void substep(ShW<
 
 // load one env's state into its LDS image, action -> servo command (E1)
 template <int EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real>& M, const Args<real>& A, int env, real* bp = nullptr,
-                                                real* late = nullptr, int* rsw = nullptr, bool live = true, real* gp = nullptr) {
+                                                real* late = nullptr, int* rsw = nullptr, bool live = true, real* gp = nullptr, real* tq = nullptr) {
   typedef V<real> vr;
   const V<int> lane = opaque_lane();   // index math stays local to this function (not kept live across the physics)
   const VB l18 = lane < kNU;
@@ -3163,6 +3215,8 @@ template <int EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real
   if constexpr (EP >= 2) body_in = gldv(A.envp, sel(lane < kBodyP, lane, V<int>(0)) + (A.N * kEnvP + env * kBodyP));   // the env's body row, behind the N envp rows
   vr grav_in = vr(real(0));
   if constexpr (EP >= 4) grav_in = gldv(grav_rows_of(A), sel(lane < kGravP, lane, V<int>(0)) + env * kGravP);   // the env's gravity row, behind the histories
+  vr torque_in = vr(real(0));
+  if constexpr (EP >= 6) torque_in = gldv(torque_rows_of(A), sel(lane < kTorqueP, lane, V<int>(0)) + env * kTorqueP);   // the env's torque row, behind the servo state: physics, so a physics-only launch reads it too
   vr cmd_in = vr(real(0)), eps_in = vr(real(0)), prev_act = vr(real(0)), prev_dofvel = vr(real(0)), dofpos_old = vr(real(0));
   int64_t ep = 0;
   uint32_t ctr_in = 0;
@@ -3205,6 +3259,7 @@ template <int EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real
     stsv(sh.envp, lane, envp_in, lane < kEnvPS);
     if constexpr (EP >= 2) stsv(bp, lane, body_in, lane < kBodyP);
     if constexpr (EP >= 4) stsv(gp, lane, grav_in, lane < kGravP);
+    if constexpr (EP >= 6) stsv(tq, lane, torque_in, lane < kTorqueP);
     p_gain = rdlane(envp_in, EP_PGAIN);
   }
   // ---- E1 (env.py:152-156,181-192): float32 scale + clip; PD -> velocity command from the env's own dof_pos buffer
@@ -3588,6 +3643,8 @@ template <int EP, class real, class Src, class Mid, class Cfg = CfgAsk> NM_FN vo
   if constexpr (EP >= 2) body_in = gldx<kS>(A.envp, sel(hl < kBodyP, hl, V<int>(0)) + (env * kBodyP + A.N * kEnvP));   // each env's body row (behind the N envp rows), lanes 0..19 of its half
   vr grav_in = vr(real(0));
   if constexpr (EP >= 4) grav_in = gldx<kS>(grav_rows_of(A), sel(hl < kGravP, hl, V<int>(0)) + env * kGravP);   // each env's gravity row (behind the histories), lanes 0..7 of its half
+  vr torque_in = vr(real(0));
+  if constexpr (EP >= 6) torque_in = gldx<kS>(torque_rows_of(A), sel(hl < kTorqueP, hl, V<int>(0)) + env * kTorqueP);   // each env's torque row (behind the servo state), lanes 0..3 of its half: physics, so a physics-only launch reads it too
   vr cmd_in = vr(real(0)), eps_in = vr(real(0)), prev_act = vr(real(0)), prev_dofvel = vr(real(0)), dofpos_old = vr(real(0));
   // level 3: each env's delay and its whole action history (three rows, lane of the half = joint) with the step's other reads
   V<int> dl = V<int>(0);
@@ -3639,6 +3696,7 @@ template <int EP, class real, class Src, class Mid, class Cfg = CfgAsk> NM_FN vo
     stsv(rb, ho + (hl + NM_OFS(envp)), envp_in, hl < kEnvPS);
     if constexpr (EP >= 2) stsv(body_rows(w), h * kBodyP + hl, body_in, hl < kBodyP);
     if constexpr (EP >= 4) stsv(grav_rows(w), h * kGravP + hl, grav_in, hl < kGravP);
+    if constexpr (EP >= 6) stsv(torque_rows(w), h * kTorqueP + hl, torque_in, hl < kTorqueP);
     p_gain = sel(h != 0, vr(rdlane(envp_in, 32 + EP_PGAIN)), vr(rdlane(envp_in, EP_PGAIN)));
   }
   // ---- E1 (env.py:152-156,181-192): float32 scale + clip; PD -> velocity command from the env's own dof_pos buffer
@@ -4055,6 +4113,8 @@ NM_FN void wave_step(ShW<real, G>& w, const Model<real>& M, const Src& src, int 
       int env = wave * G + e;
       real* bp = nullptr;
       if constexpr (EP >= 2) bp = body_rows(w) + e * kBodyP;
+      if constexpr (EP >= 6) env_load<EP>(w.e[e], M, A, env < A.N ? env : A.N - 1, bp, lat_rows(w).late + e * kNU, lat_rows(w).rsw + e, env < A.N, grav_rows(w) + e * kGravP, torque_rows(w) + e * kTorqueP);
+      else
       if constexpr (EP >= 4) env_load<EP>(w.e[e], M, A, env < A.N ? env : A.N - 1, bp, lat_rows(w).late + e * kNU, lat_rows(w).rsw + e, env < A.N, grav_rows(w) + e * kGravP);
       else
       if constexpr (EP >= 3) env_load<EP>(w.e[e], M, A, env < A.N ? env : A.N - 1, bp, lat_rows(w).late + e * kNU, lat_rows(w).rsw + e, env < A.N);

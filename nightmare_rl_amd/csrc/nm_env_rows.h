@@ -1,9 +1,9 @@
 // nm_env_rows.h - host side, plain C++17, no HIP header: the one owner of what the host decides about the per-env rows behind
-// nm::Args::envp (friction / gains, body rows, actuation latency, gravity, the servo target model) - layout, default rows, admission, which kinds are on and which level of
+// nm::Args::envp (friction / gains, body rows, actuation latency, gravity, the servo target model, the servo torque limit) - layout, default rows, admission, which kinds are on and which level of
 // the step a launch takes. Used by the env object (nm_hip.hip), the K-step launchers and the host emulation (tests/emul, -DNM_EMUL).
 //
 // The invariant every owner of a block keeps: ONCE THE BLOCK IS ALLOCATED, EVERY REGION WHOSE KIND IS OFF HOLDS THAT KIND'S DEFAULTS -
-// default friction / gain rows, default body rows, zero delays, default gravity rows, default servo rows - so a transition writes or refills its own region and
+// default friction / gain rows, default body rows, zero delays, default gravity rows, default servo rows, default torque rows - so a transition writes or refills its own region and
 // looks at no other kind's flag. The action history and the servo's limited targets are exempt: they are state, not parameters, and keep what they hold.
 #pragma once
 #include <cmath>
@@ -15,7 +15,7 @@
 
 namespace nmrows {
 
-enum Kind { kFric = 0, kBody = 1, kLat = 2, kGrav = 3, kServo = 4 };
+enum Kind { kFric = 0, kBody = 1, kLat = 2, kGrav = 3, kServo = 4, kTorque = 5 };
 
 // ---- layout: one block of `real`s - N friction / gain rows, N body rows, then the latency words (4 bytes each in either dtype): N
 // delays, N action histories; then, at the next multiple of sizeof(real), N gravity rows. The device finds the last three through
@@ -36,6 +36,10 @@ template <class real> inline real* grav_rows(real* base, int N) { return base + 
 template <class real> constexpr size_t servo_block_reals(size_t N) { return block_reals<real>(N) + N * (nm::kServoP + nm::kNU); }
 template <class real> inline real* servo_rows(real* base, int N) { return base + block_reals<real>((size_t)N); }
 template <class real> inline real* servo_state(real* base, int N) { return servo_rows(base, N) + (size_t)N * nm::kServoP; }
+// The servo torque limit is appended behind the servo state: N rows of kTorqueP reals. servo_block_reals stays what a holder of levels
+// 0..5 alone allocates; an owner that can launch level 6 allocates torque_block_reals. The device's way there: nm::torque_rows_of.
+template <class real> constexpr size_t torque_block_reals(size_t N) { return servo_block_reals<real>(N) + N * nm::kTorqueP; }
+template <class real> inline real* torque_rows(real* base, int N) { return base + servo_block_reals<real>((size_t)N); }
 
 // ---- default rows: the model's own values (the fourth word of a friction / gain row is padding, zero)
 template <class real> inline void fric_default(const nm::Model<real>& M, real out[3]) {
@@ -59,6 +63,12 @@ template <class real> inline void grav_default(const nm::Model<real>& M, real ou
 template <class real> inline void servo_default(const nm::Model<real>&, real out[nm::kServoP]) {
   for (int j = 0; j < nm::kServoP; j++) out[j] = real(0);
   out[nm::SV_RATE] = (real)INFINITY;
+}
+
+// no limit on any joint: level 6 then computes what level 5 does
+template <class real> inline void torque_default(const nm::Model<real>&, real out[nm::kTorqueP]) {
+  for (int j = 0; j < 3; j++) out[j] = (real)INFINITY;
+  out[3] = real(0);
 }
 
 // ---- admission: pure functions of the caller's rows; empty = admitted, otherwise what the entry point reports behind its own name
@@ -98,6 +108,15 @@ template <class real> inline std::string servo_rows_fault(const real* rows, int 
   }
   return std::string();
 }
+// each of the three limits > 0 (+inf = no limit) and not NaN; the pad is not judged
+template <class real> inline std::string torque_rows_fault(const real* rows, int N) {
+  for (int e = 0; e < N; e++) {
+    const real* r = rows + (size_t)e * nm::kTorqueP;
+    for (int j = 0; j < 3; j++)
+      if (!(r[j] > 0)) return "row " + std::to_string(e) + ": limit " + std::to_string(j) + " not > 0";
+  }
+  return std::string();
+}
 inline int delay_max(int nsub) { return nm::kLatH * nsub; }     // the history holds kLatH steps of nsub substeps
 inline std::string delays_fault(const int* d, int N, int nsub) {
   for (int e = 0; e < N; e++)
@@ -132,18 +151,27 @@ template <> struct RowKind<kServo> {
   template <class real> static void dflt(const nm::Model<real>& M, real* out) { servo_default(M, out); }
   template <class real> static std::string fault(const real* r, int N) { return servo_rows_fault(r, N); }
 };
+template <> struct RowKind<kTorque> {
+  static constexpr Kind kind = kTorque;
+  static constexpr int W = nm::kTorqueP;
+  template <class real> static real* rows(real* base, int N) { return torque_rows(base, N); }
+  template <class real> static void dflt(const nm::Model<real>& M, real* out) { torque_default(M, out); }
+  template <class real> static std::string fault(const real* r, int N) { return torque_rows_fault(r, N); }
+};
 typedef RowKind<kBody> BodyKind;
 typedef RowKind<kGrav> GravKind;
 typedef RowKind<kServo> ServoKind;
+typedef RowKind<kTorque> TorqueKind;
 
 // ---- state: which kinds are on, and what follows from that for a launch
 struct State {
-  bool on[5] = {false, false, false, false, false};
+  bool on[6] = {false, false, false, false, false, false};
   // the level of the step a launch takes: the highest kind that is on; a physics-only launch ignores latency (level 2 on the rows level 3
   // reads; at level 4, which physics-only launches take too, the kernel skips it at run time: nm::Args::physics_only; at level 5 it skips
-  // the servo row and its state the same way)
+  // the servo row and its state the same way; the torque limit is physics: level 6 whenever it is on, physics-only launches included,
+  // and the kernel skips latency and the servo row at run time there as levels 4 and 5 do)
   int level(bool physics_only = false) const {
-    return on[kServo] ? 5 : on[kGrav] ? 4 : (on[kLat] ? (physics_only ? 2 : 3) : (on[kBody] ? 2 : (on[kFric] ? 1 : 0)));
+    return on[kTorque] ? 6 : on[kServo] ? 5 : on[kGrav] ? 4 : (on[kLat] ? (physics_only ? 2 : 3) : (on[kBody] ? 2 : (on[kFric] ? 1 : 0)));
   }
   // nm::Args::envp of a launch: the block while any kind is on, null (level 0 never looks) otherwise
   template <class real> real* envp(real* base) const { return level() ? base : nullptr; }
@@ -165,6 +193,12 @@ template <class F> inline auto with_level(int level, F&& f) {
 template <class F> inline auto with_level5(int level, F&& f) {
   if (level == 5) return f(std::integral_constant<int, 5>{});
   return with_level(level, f);
+}
+
+// and for an owner that can launch level 6; with_level and with_level5 keep their cases
+template <class F> inline auto with_level6(int level, F&& f) {
+  if (level == 6) return f(std::integral_constant<int, 6>{});
+  return with_level5(level, f);
 }
 
 }  // namespace nmrows

@@ -193,6 +193,9 @@ struct nm_env {
   virtual int draw_servo(const double* lo, const double* hi, hipStream_t s) = 0;
   virtual int get_servo_state(double* L) = 0;
   virtual int set_servo_state(const double* L) = 0;
+  virtual int set_torque_limit(const void* rows, hipStream_t s) = 0;
+  virtual int get_torque_limit(void* out, hipStream_t s) = 0;
+  virtual int draw_torque_limit(const double* lo, const double* hi, hipStream_t s) = 0;
   // push perturbations (nm_push.h): the setting and the push step index - full env steps taken, K per K-step launch; physics-only
   // launches and nm_reset leave it alone
   int push_interval = 0;
@@ -383,7 +386,7 @@ template <class real> struct Env : nm_env {
       if constexpr (sizeof(real) == 4 && G == 2) HIPCHK(nm_launch_step_lean(N, s, (const nm::Model<float>*)M_dev, a));
 #endif
     } else {
-      nmrows::with_level5(rows.level(physics_only), [&](auto L) {
+      nmrows::with_level6(rows.level(physics_only), [&](auto L) {
         hipLaunchKernelGGL((k_env_step<real, G, decltype(L)::value>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
       });
       HIPCHK(hipGetLastError());
@@ -756,7 +759,7 @@ template <class real> struct Env : nm_env {
       return 0;
     }
   }
-  // ---- per-env rows (friction / gains, body rows, actuation latency, gravity, servo target model): ONE lazily allocated block behind A.envp, which every launch copies
+  // ---- per-env rows (friction / gains, body rows, actuation latency, gravity, servo target model, servo torque limit): ONE lazily allocated block behind A.envp, which every launch copies
   // with the rest of A. Where each kind lies in it, what an unset kind holds, which rows are admitted and which level of the step a launch
   // takes: nm_env_rows.h, and its invariant - once the block exists, every region whose kind is off holds that kind's defaults - is what
   // the functions below keep: each writes or refills its own region and looks at no other kind.
@@ -771,16 +774,16 @@ template <class real> struct Env : nm_env {
   // at first use, from the slab (zeroed: the delays, the history and the servo's limited targets start at zero); the fills are ordered on the first caller's stream
   int rows_alloc(hipStream_t s) {
     if (envp_dev) return 0;
-    if (dalloc(&envp_dev, nmrows::servo_block_reals<real>((size_t)N))) return 1;
+    if (dalloc(&envp_dev, nmrows::torque_block_reals<real>((size_t)N))) return 1;
     return envp_write({}, s) || kind_fill<nmrows::BodyKind>(nmrows::body_rows(envp_dev, N), s) || kind_fill<nmrows::GravKind>(nmrows::grav_rows(envp_dev, N), s) ||
-           kind_fill<nmrows::ServoKind>(nmrows::servo_rows(envp_dev, N), s);
+           kind_fill<nmrows::ServoKind>(nmrows::servo_rows(envp_dev, N), s) || kind_fill<nmrows::TorqueKind>(nmrows::torque_rows(envp_dev, N), s);
   }
   int rows_turn(nmrows::Kind k, bool on) {
     rows.on[k] = on;
     A.envp = rows.envp(envp_dev);
     return 0;
   }
-  // ---- the kinds with a descriptor D (nm_env_rows.h RowKind: body rows, gravity rows, servo rows); `who`: the entry point's name
+  // ---- the kinds with a descriptor D (nm_env_rows.h RowKind: body rows, gravity rows, servo rows, torque rows); `who`: the entry point's name
   template <class D> int kind_fill(real* dst, hipStream_t s) {      // the default row for every env
     Vals<real, D::W> r;
     D::dflt(M, r.v);
@@ -876,6 +879,14 @@ template <class real> struct Env : nm_env {
     if (rows_alloc(nullptr)) return 1;
     HIPCHK(hipDeviceSynchronize());
     return h2d(nmrows::servo_state(envp_dev, N), L, (size_t)N * nm::kNU);
+  }
+  // ---- the servo torque limit: rows (fmax coxa, femur, tibia, pad) through the descriptor
+  int set_torque_limit(const void* rows_in, hipStream_t s) override { return kind_set<nmrows::TorqueKind>("nm_set_torque_limit", rows_in, s); }
+  int get_torque_limit(void* out, hipStream_t s) override { return kind_get<nmrows::TorqueKind>(out, s); }
+  int draw_torque_limit(const double* lo, const double* hi, hipStream_t s) override {      // three independent limits into the rows
+    HIPCHK(hipSetDevice(device));
+    if (rows_alloc(s) || draw<3, nm::kTorqueP>(nmrows::torque_rows(envp_dev, N), nm::kTorqueKey, lo, hi, s)) return 1;
+    return rows_turn(nmrows::kTorque, true);
   }
   // ---- per-env actuation latency
   int set_action_latency(const int* substeps, hipStream_t s) override {
@@ -1248,6 +1259,25 @@ int nm_get_servo_state(nm_env* env, double* limited) {
 int nm_set_servo_state(nm_env* env, const double* limited) {
   NEED_ENV(env);
   return env->set_servo_state(limited);
+}
+// The servo torque limit stands for MuJoCo's actuator forcerange: the clamp of mj_fwdActuation and, in mj_implicit (implicitfast), the
+// velocity derivative mjd_actuator_vel leaves out for an actuator whose force sits on its bound (level 6 of the step, nm_core.h stage A)
+int nm_set_torque_limit(nm_env* env, const void* rows_dev, void* stream) {      // mj_fwdActuation's clamp + mjd_actuator_vel's mask, per env
+  NEED_ENV(env);
+  return env->set_torque_limit(rows_dev, (hipStream_t)stream);
+}
+int nm_get_torque_limit(nm_env* env, void* out_dev, void* stream) {      // the forcerange rows as the stages read them
+  NEED_ENV(env);
+  return env->get_torque_limit(out_dev, (hipStream_t)stream);
+}
+int nm_draw_torque_limit(nm_env* env, const double lo[3], const double hi[3], void* stream) {      // forcerange drawn per env and joint type
+  static const char* kCol[3] = {"the coxa limit", "the femur limit", "the tibia limit"};
+  const auto extra = [](int, double lo_k) -> const char* { return lo_k > 0.0 ? nullptr : "a limit must be above 0"; };
+  if (draw_bounds_bad("nm_draw_torque_limit", env, lo, hi, kCol, 3, extra, false, nullptr)) return 1;
+  if (env->dtype == NM_DTYPE_F32)
+    for (int k = 0; k < 3; k++)
+      if (!((float)lo[k] > 0.0f)) return fail("nm_draw_torque_limit: a limit must be above 0 in float32");
+  return env->draw_torque_limit(lo, hi, (hipStream_t)stream);
 }
 int nm_step_tape(nm_env* env, const nm_tape_args* args, void* stream) {
   if (!env) return fail("nm_step_tape: env is NULL");

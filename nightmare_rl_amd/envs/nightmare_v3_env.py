@@ -30,6 +30,9 @@ Differences a caller can observe (all documented in DESIGN.md):
     (reference envs/nightmare_v3_config.py:37-38) - switch on the servo target model: a slew-rate limit on the servo target and a
     damping term (set_servo; reference envs/nightmare_v3_env.py:97,187-188, commented out as well). cfg.domain_rand may carry
     randomize_action_rate_limit / action_rate_limit_range and randomize_d_gain / d_gain_range, drawn once at construction (draw_servo)
+  * an OPTIONAL `cfg.control.torque_limit` (N m; a scalar or one value each for the coxa, femur and tibia servos) bounds the servo
+    torque as MuJoCo's actuator forcerange does (set_torque_limit); cfg.domain_rand may carry randomize_torque_limit /
+    torque_limit_range, drawn once at construction (draw_torque_limit). The reference has neither: its servos are ideal
 """
 import ctypes as C
 import numpy as np
@@ -148,6 +151,43 @@ def servo_config(cfg):
     return rr, dg
 
 
+def torque_config(cfg):
+    """(limit, limit_range) of the servo torque limit: `limit` three values (coxa, femur, tibia; N m, > 0, inf = no limit) from the
+    optional cfg.control.torque_limit - a scalar gives all three - or None; `limit_range` a [3, 2] list of (lo, hi) pairs from the optional
+    cfg.domain_rand.randomize_torque_limit / torque_limit_range - one pair (lo, hi) for all three joint types or three pairs, finite,
+    0 < lo <= hi - or None; a range takes the place of the value. Anything else is a ValueError."""
+    ctl, dr = getattr(cfg, "control", None), getattr(cfg, "domain_rand", None)
+    limit = None
+    v = getattr(ctl, "torque_limit", None)
+    if v is not None:
+        try:
+            a = np.asarray(v, np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            raise ValueError("cfg.control.torque_limit must be a number or three numbers") from None
+        if a.size not in (1, 3):
+            raise ValueError("cfg.control.torque_limit must be a number or three numbers (coxa, femur, tibia)")
+        if not (a > 0).all():
+            raise ValueError("cfg.control.torque_limit must be above 0 (inf = no limit)")
+        limit = [float(x) for x in np.broadcast_to(a, (3,))]
+    rng = None
+    if getattr(dr, "randomize_torque_limit", False):
+        r = getattr(dr, "torque_limit_range", None)
+        if r is None:
+            raise ValueError("cfg.domain_rand.randomize_torque_limit needs torque_limit_range")
+        try:
+            a = np.asarray(r, np.float64)
+        except (TypeError, ValueError):
+            raise ValueError("cfg.domain_rand.torque_limit_range must be a pair (lo, hi) or three pairs") from None
+        if a.shape == (2,):
+            a = np.tile(a, (3, 1))
+        if a.shape != (3, 2):
+            raise ValueError("cfg.domain_rand.torque_limit_range must be a pair (lo, hi) or three pairs")
+        if not (np.isfinite(a).all() and (a[:, 0] > 0).all() and (a[:, 0] <= a[:, 1]).all()):
+            raise ValueError("cfg.domain_rand.torque_limit_range must be finite with 0 < lo <= hi")
+        rng = a.tolist()
+    return limit, rng
+
+
 GRAVITY = 9.81      # m/s^2: the model's gravity and upstream's gravity_vec (reference envs/nightmare_v3_env.py:46)
 
 
@@ -235,6 +275,7 @@ class NightmareV3Env:
         gravity_ranges = gravity_config(cfg)
         reset_ranges = reset_noise_config(cfg)
         servo_ranges = servo_config(cfg)
+        torque_limit, torque_range = torque_config(cfg)
         # reward table: zero scales dropped, the rest x dt (reference :123-128). Every name the reference has a _reward_ function
         # for (:399-497) is compiled; a name without one (`collision`, `feet_stumble`, config :95-96) fails like upstream's getattr.
         names = [L.nm_reward_name(i).decode() for i in range(_lib.NUM_REWARDS)]
@@ -321,6 +362,12 @@ class NightmareV3Env:
         # set once, here, before the first reset()
         if servo_ranges[0] is not None or servo_ranges[1] is not None:
             self.draw_servo(*servo_ranges)
+        # the servo torque limit (optional cfg.control.torque_limit / cfg.domain_rand.torque_limit_range; no reference line): set once,
+        # here, before the first reset()
+        if torque_range is not None:
+            self.draw_torque_limit(torque_range)
+        elif torque_limit is not None and np.isfinite(torque_limit).any():
+            self.set_torque_limit(torque_limit)
         # randomised reset states (optional cfg.domain_rand; no reference line): on before the first reset(), whose reset_idx(all) is
         # draw 0 of every env
         if reset_ranges is not None:
@@ -634,6 +681,49 @@ class NightmareV3Env:
         if rr is None:      # the draw takes finite bounds: "no limit" goes in as a column of its own
             self.set_servo(None, self.servo()["d_gain"])
         return self.servo()
+
+    def set_torque_limit(self, limit=None):
+        """The servo torque limit (nm_set_torque_limit; include/nightmare_hip.h states the semantics: MuJoCo's actuator forcerange - the
+        clamp of mj_fwdActuation and the saturated joints left out of implicitfast's velocity derivative). limit: N m, > 0, inf = no
+        limit; a scalar (every joint of every env), 3 values (coxa, femur, tibia of every env), [num_envs] (one value per env) or
+        [num_envs, 3]. None switches the feature off. It is physics: step(), step_physics, policy_rollout, policy_play and step_tape
+        honour it alike; no observation, reward or log field changes. The rows hold until they are set again; no reset touches them.
+        The library refuses a limit that is not > 0."""
+        if limit is None:
+            self._rows_keep["torque"] = None
+            self._ck(self._L.nm_set_torque_limit(self._h, None, self._stream()))
+            return
+        t = torch.as_tensor(limit, dtype=self._real).detach().to(self.device)
+        n = self.num_envs
+        if t.dim() == 0 or (t.dim() == 1 and t.numel() == 3):      # (with num_envs == 3, three values are read as coxa, femur, tibia)
+            t = t.expand(n, 3)
+        elif t.dim() == 1 and t.numel() == n:
+            t = t.reshape(n, 1).expand(n, 3)
+        elif tuple(t.shape) != (n, 3):
+            raise ValueError("set_torque_limit: a scalar, 3 values, [num_envs] or [num_envs, 3]")
+        rows = torch.zeros(n, 4, dtype=self._real, device=self.device)
+        rows[:, :3] = t
+        self._ck(self._L.nm_set_torque_limit(self._h, C.c_void_p(rows.data_ptr()), self._stream()))
+        self._rows_keep["torque"] = rows
+
+    def torque_limit(self):
+        """[num_envs, 3] in the env's dtype: every env's (coxa, femur, tibia) limit (nm_get_torque_limit); inf while the feature is off."""
+        rows = torch.empty(self.num_envs, 4, dtype=self._real, device=self.device)
+        self._ck(self._L.nm_get_torque_limit(self._h, C.c_void_p(rows.data_ptr()), self._stream()))
+        return rows[:, :3].clone()
+
+    def draw_torque_limit(self, limit_range):
+        """Draw every env's three limits on the device (nm_draw_torque_limit: three independent uniform draws per env) and switch the
+        feature on. limit_range: (lo, hi) for all three joint types, or [3, 2]; finite, 0 < lo <= hi. Keyed by the global env id: shards of
+        one population draw what the whole would. Returns what torque_limit() then reports."""
+        a = np.asarray(limit_range, np.float64)
+        if a.shape == (2,):
+            a = np.tile(a, (3, 1))
+        if a.shape != (3, 2):
+            raise ValueError("draw_torque_limit: (lo, hi) or [3, 2]")
+        lo, hi = (C.c_double * 3)(*a[:, 0]), (C.c_double * 3)(*a[:, 1])
+        self._ck(self._L.nm_draw_torque_limit(self._h, C.byref(lo), C.byref(hi), self._stream()))
+        return self.torque_limit()
 
     def servo_state(self):
         """[num_envs, 18] float64 numpy: every env's rate-limited servo target L, upstream's limited_actions (nm_get_servo_state), in the

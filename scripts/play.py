@@ -117,6 +117,8 @@ def main():
                     help="the servo target may move at most R rad per control step (upstream's commented-out control.action_rate_limit = 0.08; default: no limit)")
     ap.add_argument("--d-gain", type=float, default=None, metavar="D", dest="d_gain",
                     help="damping D on the joint velocity in the servo command (upstream's commented-out control.d_gain = 0.05; default: 0)")
+    ap.add_argument("--torque-limit", type=float, default=None, metavar="F", dest="torque_limit",
+                    help="every servo delivers at most F N m (MuJoCo's actuator forcerange; default: no limit)")
     a = ap.parse_args()
     path = a.checkpoint or get_load_path(a.log_root)
     dev = torch.device("cuda", 0)
@@ -141,6 +143,8 @@ def main():
         cfg.control.action_rate_limit = a.action_rate_limit
     if a.d_gain is not None:
         cfg.control.d_gain = a.d_gain
+    if a.torque_limit is not None:
+        cfg.control.torque_limit = a.torque_limit
     env = NightmareV3Env(cfg, device=dev, seed=a.seed, **({"log_dir": a.record_states} if a.record_states is not None else {}))
     print(f"push perturbations: every {env.push_interval} steps, |v| < {env.max_push_vel_xy} m/s" if env.push_interval else "push perturbations: off")
     if a.friction_range or a.gain_range:

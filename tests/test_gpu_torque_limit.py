@@ -1,0 +1,398 @@
+"""The servo torque limit (nm_set_torque_limit and friends, level 6 of the step) on the device, in every stepping path. References: the
+fp64 fixture of the patched oracle (tests/golden/torque.npz, make_torque_goldens.py) for what the rows mean - the mixed batch gives env e
+set e % 5, its kv included, so the two envs of a wave always differ; uniform batches for what a mixed batch must give and the per-step path
+for the K-step launches (bit for bit); a numpy restatement over oracle.rand_u24 for the draw. N = 8 (four two-env waves) and N = 7 (a
+half-empty last wave) against the fixture; N = 63 and 1 where only bits are compared; at most 10 steps per run."""
+import types
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import load_golden
+from test_gpu_parity import make_env
+from test_gpu_play import _assert_same_books, _books, _ep_idx, _networks, _stats, _storage
+from test_gpu_play import _step_by_step as _play_step_by_step
+from test_gpu_push import _actions, _assert_same_step
+from test_gpu_rollout import _record
+from test_gpu_tape import _assert_same_env, _records
+from test_gpu_tape import _step_by_step as _tape_step_by_step
+from test_torque_limit_host import draw_restated
+from torque_tools import POPS, mixed, mixed_rows, set_of
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+SEED = 5
+INF = float("inf")
+ENVP_SETS = np.array([[1.0, 20.0, 0.8], [0.4, 20.0, 0.5], [1.6, 14.0, 0.8], [0.7, 26.0, 1.1]])
+PAYLOADS = np.array([[0.0, 0.0, 0.0, 0.0], [0.5, 0.03, 0.0, 0.04], [-0.3, 0.0, 0.0, 0.0], [1.0, -0.05, 0.02, 0.05]])
+DELAYS = np.array([0, 1, 2, 3, 4, 5, 6, 0])
+RATE = np.array([INF, 0.03, 0.02, 0.08, 0.04, INF, 0.02, 0.08])
+D_GAIN = np.array([0.0, 0.0, 0.05, 0.05, 0.2, 0.2, 0.0, 0.1])
+
+
+@pytest.fixture(scope="module")
+def G():
+    return load_golden("torque.npz")
+
+
+def set_rows(env, g, limits=True):
+    lim, kv = mixed_rows(g, env.num_envs)
+    env.set_env_params(kv=kv)
+    env.set_torque_limit(lim if limits else None)
+
+
+def load_state(env, g, pop, t):
+    """Start state of step t of the mixed batch; returns the step's (actions, command uniforms)."""
+    n = env.num_envs
+    pick = lambda k: mixed(g, f"{pop}_{k}", t, n)
+    env.set_state(pick("qpos"), pick("qvel"), pick("qw"))
+    env.set_buffers(dof_pos=pick("dof_pos"), dof_vel=pick("dof_vel"), actions=pick("act"), commands=pick("cmd"))
+    env.episode_length_buf = torch.from_numpy(np.asarray(pick("ep_len"), np.int64)).to(DEV)
+    return pick("actions"), pick("cmd_u").astype(np.float64)
+
+
+def step_errors(env, g, pop, t, out):
+    n = env.num_envs
+    obs, rew, done = out[0].cpu().numpy(), out[2].cpu().numpy(), out[3].cpu().numpy()
+    oerr = np.abs(obs.astype(np.float64) - mixed(g, f"{pop}_obs", t, n)).max(axis=1)
+    rerr = np.abs(rew.astype(np.float64) - mixed(g, f"{pop}_rew", t, n))
+    q, v, _ = env.get_state()
+    serr = np.maximum(np.abs(q - mixed(g, f"{pop}_qpos", t + 1, n)).max(axis=1), np.abs(v - mixed(g, f"{pop}_qvel", t + 1, n)).max(axis=1))
+    return np.maximum(oerr, rerr), serr, int((done != mixed(g, f"{pop}_done", t, n)).sum())
+
+
+def forced(env, g, pop, steps):
+    errs, serrs, flags = [], [], 0
+    for t in range(steps):
+        a, cu = load_state(env, g, pop, t)
+        env.set_command_uniforms(cu)
+        e, s, f = step_errors(env, g, pop, t, env.step(torch.from_numpy(a)))
+        errs.append(e); serrs.append(s); flags += f
+    return np.stack(errs), np.stack(serrs), flags
+
+
+def free(env, g, pop, steps, compare=True):
+    """Free-running from the recording's first state; returns the errors and every step's (obs, rew, done, qpos, qvel, qwarm)."""
+    errs, serrs, flags, out = [], [], 0, []
+    n = env.num_envs
+    load_state(env, g, pop, 0)
+    for t in range(steps):
+        env.set_command_uniforms(mixed(g, f"{pop}_cmd_u", t, n).astype(np.float64))
+        r = env.step(torch.from_numpy(mixed(g, f"{pop}_actions", t, n)))
+        if compare:
+            e, s, f = step_errors(env, g, pop, t, r)
+            errs.append(e); serrs.append(s); flags += f
+        out.append((r[0].cpu().numpy().copy(), r[2].cpu().numpy().copy(), r[3].cpu().numpy().copy()) + tuple(env.get_state()))
+    return (np.stack(errs), np.stack(serrs), flags, out) if compare else out
+
+
+# ------------------------------------------------------------------------------------------------ 1. the kernels vs the patched oracle
+@pytest.mark.parametrize("N", [8, 7])
+def test_fp64_kernel_matches_the_patched_oracle(G, N):
+    """Teacher-forced single steps and the free-running trajectories of both populations: obs / reward < 1e-6, state < 1e-8 (the
+    project's fp64 bounds, tests/test_gpu_parity.py), no done flag differing. N = 7: the last wave's second slot is padding."""
+    env = make_env(N, dtype=torch.float64, seed=SEED)
+    set_rows(env, G)
+    T = G["drop_actions"].shape[1]
+    for pop in POPS:
+        err, serr, flags = forced(env, G, pop, T)
+        print(f"N={N} {pop} forced: max obs/reward error {err.max():.2e}, state {serr.max():.2e}")
+        assert flags == 0 and err.max() < 1e-6 and serr.max() < 1e-8, (pop, err.max(), serr.max())
+        err, serr, flags, _ = free(env, G, pop, T)
+        print(f"N={N} {pop} free {T} steps: max obs/reward error {err.max():.2e}, state {serr.max():.2e}")
+        assert flags == 0 and err.max() < 1e-6 and serr.max() < 1e-8, (pop, "free", err.max(), serr.max())
+    assert env.step_variant() == "generic"
+    env.close()
+
+
+@pytest.mark.parametrize("N", [8, 7])
+def test_fp32_kernel_is_within_the_fp32_bounds(G, N):
+    """Teacher-forced single steps: median < 5e-6, p99 < 1e-4. The generator's condition f keeps every recorded force
+    more than 1e-5 N m off its bound - hundreds of float32 ulps of a force of a few N m - so no clamp decision flips."""
+    env = make_env(N, dtype=torch.float32, seed=SEED)
+    set_rows(env, G)
+    errs = []
+    for pop in POPS:
+        err, _, flags = forced(env, G, pop, G[f"{pop}_actions"].shape[1])
+        print(f"N={N} {pop}: median {np.median(err):.2e}, p99 {np.percentile(err, 99):.2e}, max {err.max():.2e}, done flags differing {flags}")
+        assert flags == 0
+        errs.append(err.ravel())
+    err = np.concatenate(errs)
+    assert np.median(err) < 5e-6 and np.percentile(err, 99) < 1e-4, (np.median(err), np.percentile(err, 99), err.max())
+    assert env.step_variant() == "generic"      # the lean kernel is level 0 only
+    env.close()
+
+
+# ------------------------------------------------------------------------------------------------ 2. sensitivity
+def test_without_the_rows_the_kernel_misses_the_fixture_exactly_where_a_limit_is_set(G):
+    """The comparison of test 1 can fail: with the torque rows cleared (each env keeps its kv) the fp64 kernel leaves the state bound in
+    every env of sets 1..4 and stays inside both bounds in those of set 0. In `stand` only set 3 saturates inside the recorded window
+    (the generator prints 0 saturated joint-steps for sets 1, 2, 4), so there the miss is required of set 3 and the match of the rest."""
+    env = make_env(8, dtype=torch.float64, seed=SEED)
+    set_rows(env, G, limits=False)
+    for pop in POPS:
+        err, serr, _ = forced(env, G, pop, G[f"{pop}_actions"].shape[1])
+        e, s = err.max(axis=0), serr.max(axis=0)
+        limited = set_of(8) != 0 if pop == "drop" else set_of(8) == 3
+        assert (s[limited] > 1e-8).all() and (s[~limited] < 1e-8).all() and (e[~limited] < 1e-6).all(), (pop, e, s)
+    env.close()
+
+
+# ------------------------------------------------------------------------------------------------ 3. off = defaults; mixed = uniform
+@pytest.mark.parametrize("N", [8, 7])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["fp32", "fp64"])
+def test_never_set_defaults_set_and_set_then_cleared_are_identical(G, dtype, N):
+    from nightmare_rl_amd import _lib
+    npdt = np.float32 if dtype == torch.float32 else np.float64
+    envs = [make_env(N, dtype=dtype, seed=SEED) for _ in range(3)]
+    for e in envs:
+        e.reset()
+        assert torch.isinf(e.torque_limit()).all()
+    envs[1].set_torque_limit(INF)
+    lim, _ = mixed_rows(G, N)
+    envs[2].set_torque_limit(lim)
+    np.testing.assert_array_equal(envs[2].torque_limit().cpu().numpy(), lim.astype(npdt))
+    # rows the library refuses, before anything of the env changes
+    for bad in (0.0, -1.0, float("nan"), [1.0, 0.0, 1.0], -INF):
+        with pytest.raises(_lib.NightmareHipError, match="nm_set_torque_limit"):
+            envs[2].set_torque_limit(bad)
+    with pytest.raises(_lib.NightmareHipError, match="nm_draw_torque_limit"):
+        envs[2].draw_torque_limit((0.0, 1.0))
+    with pytest.raises(ValueError):
+        envs[2].set_torque_limit(np.ones(N + 1))
+    np.testing.assert_array_equal(envs[2].torque_limit().cpu().numpy(), lim.astype(npdt))
+    envs[2].set_torque_limit()                                # off again
+    assert torch.isinf(envs[2].torque_limit()).all()
+    acts = _actions(6, N)
+    for s in range(6):
+        r = [e.step(acts[s]) for e in envs]
+        _assert_same_step(envs[0], envs[1], r[0], r[1], f"default rows, step {s}")
+        _assert_same_step(envs[0], envs[2], r[0], r[2], f"set then cleared, step {s}")
+    assert envs[1].step_variant() == "generic"      # level 6, even under default rows
+    # the other shapes set_torque_limit takes
+    envs[1].set_torque_limit([6.4, 0.3, 2.4])
+    assert envs[1].torque_limit().cpu().numpy().tolist() == np.tile(np.array([6.4, 0.3, 2.4]).astype(npdt), (N, 1)).tolist()
+    envs[1].set_torque_limit(np.arange(1, N + 1))
+    assert envs[1].torque_limit().cpu().numpy().tolist() == np.tile(np.arange(1, N + 1).astype(npdt)[:, None], (1, 3)).tolist()
+    for e in envs:
+        e.close()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["fp32", "fp64"])
+def test_mixed_batch_equals_the_uniform_batches_bit_for_bit(G, dtype):
+    """Env e of the mixed batch (N = 63: 31 full waves and a half-empty one) equals env e of the batch whose envs ALL hold e's row and
+    kv, from the same states: 4 free-running steps of `drop`. And a batch of ONE env equals env 0 of the uniform batch under every set."""
+    N = 63
+    env, one = make_env(N, dtype=dtype, seed=SEED), make_env(1, dtype=dtype, seed=SEED)
+    set_rows(env, G)
+    mx = free(env, G, "drop", 4, compare=False)
+    for k in range(5):
+        env.set_env_params(kv=float(G["kv"][k]))
+        env.set_torque_limit(G["sets"][k])
+        uni = free(env, G, "drop", 4, compare=False)
+        one.set_env_params(kv=float(G["kv"][k]))
+        one.set_torque_limit(G["sets"][k])
+        single = free(one, G, "drop", 4, compare=False)
+        m = set_of(N) == k
+        for t, (x, y, z) in enumerate(zip(mx, uni, single)):
+            for i, (u, v, w) in enumerate(zip(x, y, z)):
+                np.testing.assert_array_equal(u[m], v[m], err_msg=f"set {k} step {t} item {i}")
+                np.testing.assert_array_equal(w[0], v[0], err_msg=f"one env, set {k} step {t} item {i}")
+    env.close(); one.close()
+
+
+# ------------------------------------------------------------------------------------------------ 4. every stepping path
+def _pair(G, N, n=2, everything=False):
+    """n envs with the mixed batch's torque rows (and, with everything, friction / gains, payloads, latency, gravity, servo rows and
+    pushes as well), reset."""
+    envs = [make_env(N, seed=SEED) for _ in range(n)]
+    e8 = np.arange(N)
+    lim, kv = mixed_rows(G, N)
+    for e in envs:
+        e.reset()
+        e.set_torque_limit(lim)
+        if everything:
+            r = ENVP_SETS[(e8 + 1) % 4]
+            e.set_env_params(mu=r[:, 0], p_gain=r[:, 1], kv=r[:, 2])
+            p = PAYLOADS[(e8 // 2 + e8) % 4]
+            e.set_base_payload(p[:, 0], p[:, 1:])
+            e.set_action_latency(DELAYS[e8 % 8])
+            tilt = 0.05 * (1 + e8 % 3)
+            e.set_gravity(np.stack([9.81 * np.sin(tilt), np.zeros(N), -9.81 * np.cos(tilt)], axis=1))
+            e.set_servo(RATE[e8 % 8], D_GAIN[e8 % 8])
+            e.set_push(3, 0.5)
+    return envs
+
+
+@pytest.mark.parametrize("everything", [False, True], ids=["torque", "torque+friction+gains+payload+latency+gravity+servo+pushes"])
+@pytest.mark.parametrize("N", [8, 63])
+def test_tape_equals_the_per_step_path(G, N, everything):
+    K = 6
+    ea, eb, e0 = _pair(G, N, 3, everything)
+    e0.set_torque_limit()
+    acts = _actions(K, N)
+    ep_idx = _ep_idx(ea)
+    ba, bb = _books(N, ep_idx.numel()), _books(N, ep_idx.numel())
+    rec, rec0 = _records(K, N), _records(K, N)
+    oa = ea.step_tape(acts, record=rec, stats=_stats(ba, ep_idx))
+    ob, _, per_step = _tape_step_by_step(eb, acts, bb, ep_idx)
+    e0.step_tape(acts, record=rec0)
+    torch.cuda.synchronize()
+    for k in ("obs", "rew", "done"):
+        assert torch.equal(rec[k], per_step[k]), k
+    _assert_same_env(ea, eb, oa, ob)
+    _assert_same_books(ba, bb)
+    # the rows were honoured, and by no env without a finite limit (set 3's femur limit of 0.3 N m is below what holding a leg up takes:
+    # its envs must differ; whether 3.2 N m is reached inside six steps from a reset is not asserted)
+    differs = (rec["obs"] != rec0["obs"]).any(dim=2).any(dim=0).cpu().numpy()
+    assert differs[set_of(N) == 3].all() and not differs[set_of(N) == 0].any()
+    for e in (ea, eb, e0):
+        e.close()
+
+
+@pytest.mark.parametrize("everything", [False, True], ids=["torque", "everything"])
+@pytest.mark.parametrize("N", [8, 63])
+@pytest.mark.parametrize("deterministic", [True, False])
+def test_play_equals_the_per_step_path(G, deterministic, N, everything):
+    K = 6
+    ac, fu = _networks()
+    ea, eb = _pair(G, N, 2, everything)
+    it = torch.tensor([4], dtype=torch.int64, device=DEV)
+    ep_idx = _ep_idx(ea)
+    ba, bb = _books(N, ep_idx.numel()), _books(N, ep_idx.numel())
+    oa = ea.policy_play(K, fu.flat, deterministic=deterministic, seed=77, iter_dev=it, stats=_stats(ba, ep_idx))
+    ob, _ = _play_step_by_step(eb, fu, K, deterministic, 77, it, bb, ep_idx)
+    _assert_same_env(ea, eb, oa, ob)
+    _assert_same_books(ba, bb)
+    for e in (ea, eb):
+        e.close()
+
+
+@pytest.mark.parametrize("everything", [False, True], ids=["torque", "everything"])
+@pytest.mark.parametrize("N", [8, 63])
+def test_rollout_equals_the_per_step_path(G, N, everything):
+    from nightmare_rl_amd import _lib
+    L = _lib.load()
+    T, gamma = 6, 0.99
+    ac, fu = _networks()
+    ea, eb = _pair(G, N, 2, everything)
+    it = torch.tensor([3], dtype=torch.int64, device=DEV)
+    ep_idx = _ep_idx(ea)
+    ba, bb = _books(N, ep_idx.numel()), _books(N, ep_idx.numel())
+    sa, sb = _storage(N, T), _storage(N, T)
+    oa = ea.policy_rollout(T, fu.flat, 99, it, sa, gamma, ba["cur_ret"], ba["cur_len"], ba["fin"], ep=(ep_idx, ba["ep_acc"]))
+    o = eb.get_observations()
+    for s in range(T):
+        act = eb.policy_act(fu.flat, o, 99, it, s, sb)
+        o, _, rew, done, infos = eb.step(act)
+        _record(L, eb, sb, s, gamma, bb["cur_ret"], bb["cur_len"], bb["fin"], ep_idx, bb["ep_acc"])
+    torch.cuda.synchronize()
+    for name in ("observations", "actions", "values", "actions_log_prob", "mu", "sigma", "rewards", "dones"):
+        assert torch.equal(getattr(sa, name), getattr(sb, name)), name
+    _assert_same_env(ea, eb, oa, o)
+    assert torch.equal(ba["cur_ret"], bb["cur_ret"]) and torch.equal(ba["cur_len"], bb["cur_len"])
+    for e in (ea, eb):
+        e.close()
+
+
+def test_physics_only_launches_honour_the_limit(G):
+    """nm_step_physics is physics: under a 0.3 N m femur limit it leaves the state a launch without the limit reaches, and equals a
+    second env under the same rows bit for bit (level 6 with the run-time skip of latency and the servo row)."""
+    ea, eb, e0 = (make_env(8, seed=SEED) for _ in range(3))
+    acts = _actions(3, 8)
+    for e in (ea, eb, e0):
+        e.reset()
+    ea.set_torque_limit([6.4, 0.3, 2.4]); eb.set_torque_limit([6.4, 0.3, 2.4])
+    eb.set_servo(0.05, 0.1); eb.set_action_latency(3)      # ignored by a physics-only launch
+    for t in range(3):
+        for e in (ea, eb, e0):
+            e.step_physics(acts[t])
+    qa, qb, q0 = ea.get_state()[0], eb.get_state()[0], e0.get_state()[0]
+    np.testing.assert_array_equal(qa, qb)
+    assert (np.abs(qa - q0).max(axis=1) > 1e-6).all()
+    for e in (ea, eb, e0):
+        e.close()
+
+
+# ------------------------------------------------------------------------------------------------ 5. resets
+def test_resets_inside_a_k_step_launch_leave_the_rows_alone(G):
+    """4-step episodes (cfg.env.episode_length_s = 0.064) with the episode lengths of tests/test_gpu_reset_noise.py: within 10 steps every
+    env resets twice, env 6 at the last step of each 5-step launch. The rows after the launches are the rows set, and the two tape
+    launches end where ten single steps end."""
+    from nightmare_rl_amd.envs.nightmare_v3_config import NightmareV3Config
+    from nightmare_rl_amd.envs.nightmare_v3_env import NightmareV3Env
+    N, K = 8, 10
+    eplen = (4, 4, 3, 1, 1, 3, 0, 2)
+    lim, _ = mixed_rows(G, N)
+
+    def build():
+        cfg = NightmareV3Config()
+        cfg.env.num_envs, cfg.env.episode_length_s = N, 0.064
+        env = NightmareV3Env(cfg, device=DEV, seed=SEED)
+        assert int(env.max_episode_length) == 4
+        env.reset_idx(None)
+        env.episode_length_buf = torch.tensor(eplen, dtype=torch.int64, device=DEV)
+        env.set_torque_limit(lim)
+        return env
+
+    ea, eb = build(), build()
+    acts = _actions(K, N)
+    resets = np.zeros(N, int)
+    for t in range(K):
+        resets += ea.step(acts[t])[3].cpu().numpy()
+    assert (resets == 2).all()
+    for half in (acts[:5], acts[5:]):
+        eb.step_tape(half)
+    for x, y in zip(ea.get_state(), eb.get_state()):
+        np.testing.assert_array_equal(x, y)
+    for e in (ea, eb):
+        e.reset_idx([1, 6])
+        np.testing.assert_array_equal(e.torque_limit().cpu().numpy(), lim.astype(np.float32))
+    ea.close(); eb.close()
+
+
+# ------------------------------------------------------------------------------------------------ 6. the config and the draw
+def test_the_config_names_switch_the_limit_on():
+    from nightmare_rl_amd.envs.nightmare_v3_config import NightmareV3Config
+    from nightmare_rl_amd.envs.nightmare_v3_env import NightmareV3Env
+    cfg = NightmareV3Config()
+    cfg.env.num_envs = 8
+    cfg.control.torque_limit = 3.2
+    env = NightmareV3Env(cfg, device=DEV, seed=SEED)
+    assert (env.torque_limit() == np.float32(3.2)).all()
+    env.reset()
+    assert env.step_variant() == "generic"
+    env.close()
+    cfg = NightmareV3Config()
+    cfg.env.num_envs = 8
+    cfg.control.torque_limit = [6.4, 0.3, 2.4]
+    env = NightmareV3Env(cfg, device=DEV, seed=SEED)
+    assert env.torque_limit().cpu().numpy().tolist() == np.tile(np.float32([6.4, 0.3, 2.4]), (8, 1)).tolist()
+    env.close()
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["fp32", "fp64"])
+def test_the_draw_is_its_numpy_restatement_and_a_shard_is_a_slice(dtype):
+    from nightmare_rl_amd.envs.nightmare_v3_config import NightmareV3Config
+    from nightmare_rl_amd.envs.nightmare_v3_env import NightmareV3Env
+    npdt = np.float64 if dtype == torch.float64 else np.float32
+    rng = [[2.0, 4.0], [0.5, 0.5], [1.0, 3.0]]
+    lo, hi = [r[0] for r in rng], [r[1] for r in rng]
+
+    def build(n, offset):
+        cfg = NightmareV3Config()
+        cfg.env.num_envs = n
+        cfg.domain_rand = types.SimpleNamespace(randomize_torque_limit=True, torque_limit_range=rng)
+        return NightmareV3Env(cfg, device=DEV, seed=SEED, env_id_offset=offset, dtype=dtype)
+
+    whole, shard = build(16, 0), build(8, 8)
+    want = draw_restated(SEED, np.arange(16), lo, hi, npdt)
+    np.testing.assert_array_equal(whole.torque_limit().cpu().numpy(), want)
+    np.testing.assert_array_equal(shard.torque_limit().cpu().numpy(), want[8:])      # a shard with env_offset = 8 draws what envs 8.. of the whole got
+    whole.reset()
+    whole.step(torch.zeros(16, 18, device=DEV))
+    np.testing.assert_array_equal(whole.torque_limit().cpu().numpy(), want)      # drawn once: resets and steps leave the rows alone
+    got = whole.draw_torque_limit((1.5, 1.5)).cpu().numpy()
+    assert (got == npdt(1.5)).all()
+    whole.close(); shard.close()

@@ -49,6 +49,8 @@ def main():
                     help="the servo target may move at most R rad per control step (upstream's commented-out control.action_rate_limit = 0.08; default: no limit)")
     ap.add_argument("--d-gain", type=float, default=None, metavar="D", dest="d_gain",
                     help="damping D on the joint velocity in the servo command (upstream's commented-out control.d_gain = 0.05; default: 0)")
+    ap.add_argument("--torque-limit", type=float, default=None, metavar="F", dest="torque_limit",
+                    help="every servo delivers at most F N m (MuJoCo's actuator forcerange; default: no limit)")
     ap.add_argument("--gpus", type=int, default=None, help="ranks (one per GPU); without torch.distributed.run, train.py starts them itself")
     args = ap.parse_args()
 
@@ -103,6 +105,8 @@ def main():
         cfg.control.action_rate_limit = args.action_rate_limit
     if args.d_gain is not None:
         cfg.control.d_gain = args.d_gain
+    if args.torque_limit is not None:
+        cfg.control.torque_limit = args.torque_limit
     lo, hi = shard_range(args.num_envs, rank, world)
     cfg.env.num_envs = hi - lo
     train_cfg.runner.resume = args.resume
