@@ -324,6 +324,37 @@ int nm_set_servo_state(nm_env* env, const double* limited);
 int nm_set_torque_limit(nm_env* env, const void* rows_dev, void* stream);
 int nm_get_torque_limit(nm_env* env, void* out_dev, void* stream);
 int nm_draw_torque_limit(nm_env* env, const double lo[3], const double hi[3], void* stream);
+/* Per-env rows re-drawn at every reset, from pools - the `mode="reset"` events of Isaac Lab, legged_gym's per-reset payload; it replaces
+ * nothing upstream (the reference has one robot, one floor and ideal servos, and its reset_idx touches no model constant).
+ * kind: 0 friction / gains [4] (mu, p_gain, kv, pad), 1 body rows [20], 2 actuation latency [1] (a 4-byte int in either dtype), 3 gravity
+ * rows [8], 4 servo rows [4], 5 torque-limit rows [4]: the rows of nm_set_env_params, nm_set_body_params, nm_set_action_latency,
+ * nm_set_gravity, nm_set_servo and nm_set_torque_limit, 41 words in all. Each kind may own a pool of P such rows, 1 <= P <= 65536, in the
+ * env's dtype. While a kind has a pool, an env's reset - time-out, termination or nm_reset; not the bad-state reset inside the physics,
+ * and nm_step_physics never resets - overwrites that kind's row of that env with pool row
+ *   i = (rand_u24_bits(seed + "RESAMP", global env id, 8 k + kind) * P) >> 24        (64-bit integers, the counter in 32 bits)
+ * k is the env's reset-row count, a buffer of its own (not the reset count of nm_set_reset_noise), read for all six kinds and then
+ * incremented by one. A pool has no arithmetic: fp32 and fp64, host and device agree bit for bit, and correlated parameters are
+ * expressible. The new rows hold from the first step of the new episode; the resetting step ran on the old rows and returns the terminal
+ * observation, as before. The action history and the servo's limited targets are state and keep what they hold. It works alike in
+ * nm_step, nm_reset (distinct ids), nm_rollout, nm_play and nm_step_tape, and the state after any step of any path equals the per-step
+ * path's. The key is the global env id: sharding changes nothing. A pool of one row equal to the rows every env holds is the feature
+ * off, bit for bit.
+ * nm_set_reset_rows: rows_dev is a DEVICE array [P, width] in the env's dtype ([P] int32 for kind 2), copied into memory of the env's
+ *   own on `stream`; it switches the kind on, and the rows the envs hold stay until each env's next reset (nm_reset right after it
+ *   draws k = 0 for every env). rows_dev NULL drops the pool: the rows stay what they are. Switching a kind off (its nm_set_* with NULL)
+ *   drops its pool as well; setting rows by hand while a pool is installed holds until that env's next reset. Refused, named by
+ *   nm_last_error, before anything of the env changes: a kind outside 0..5, P outside 1..65536, a NULL env (in this order, before the
+ *   first device call), then a pool row that the kind's own setter would refuse (read back and judged on the host, which waits for
+ *   `stream`; friction / gains: finite, mu > 1e-5, gains >= 0).
+ * nm_get_reset_rows: P (0 = no pool) and, if out_dev is not NULL, the pool into a DEVICE array [P, width] on `stream`.
+ * nm_set_reset_row_counts / nm_get_reset_row_counts: the HOST [N] reset-row counts (zeros at first use): a checkpoint's content.
+ * nm_reset_rows_pick: i of all six kinds for reset k of the env with global id `global_env` and the pool sizes sizes[6] (size 0 -> 0),
+ *   computed on the host by the function the kernels call; no env, no device. */
+int nm_set_reset_rows(nm_env* env, int32_t kind, const void* rows_dev, int32_t P, void* stream);
+int nm_get_reset_rows(nm_env* env, int32_t kind, int32_t* P, void* out_dev, void* stream);
+int nm_set_reset_row_counts(nm_env* env, const uint32_t* counts_host);
+int nm_get_reset_row_counts(nm_env* env, uint32_t* counts_host);
+int nm_reset_rows_pick(uint64_t seed, int64_t global_env, uint32_t k, const uint32_t sizes[6], uint32_t out[6]);
 /* State log (envs/nightmare_v3_env.py:261-272 records data[0]): env_index >= 0 makes every nm_step keep that env's
  * post-physics, pre-reset qpos/qvel; -1 = off. nm_get_state_record copies the last record to HOST qpos[25], qvel[24] and
  * the number of MuJoCo bad-state resets inside that step (data.time restarts there). Synchronous. */

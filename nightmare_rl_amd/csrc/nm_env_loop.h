@@ -1,6 +1,6 @@
 // nm_env_loop.h - what the K-step launches k_env_rollout (nm_rollout_kernels.h), k_env_play (nm_play_kernels.h) and k_env_tape
 // (nm_tape_kernels.h) share: the wave index, the launch prologue, the episode books of the wave's two envs, the per-step update of the
-// env step's launch arguments, the push perturbation of a step (nm_push.h) and the reset draw of a step (nm_reset_noise.h). X below is the launch's own argument struct, RollArgs, PlayArgs or TapeArgs (nm_rollout.h): the helpers read
+// env step's launch arguments, the push perturbation of a step (nm_push.h), the reset draw of a step (nm_reset_noise.h) and the re-draw of its per-env rows (nm_reset_rows.h). X below is the launch's own argument struct, RollArgs, PlayArgs or TapeArgs (nm_rollout.h): the helpers read
 // the fields all carry (cur_ret, cur_len, fin3, to_step, st_sum, st_cnt, rec_log) and `if constexpr` on the struct's traits (kPlayBooks,
 // kStepRecord) decides what only some of them file.
 #pragma once
@@ -12,6 +12,7 @@
 #include "nm_env_rows.h"     // with_level6: the launchers of the three K-step kernels pick the step's level through it
 #include "nm_push.h"
 #include "nm_reset_noise.h"
+#include "nm_reset_rows.h"
 #include "nm_rollout.h"
 
 namespace nmr {
@@ -129,6 +130,34 @@ __device__ __forceinline__ void step_reset_noise(const X* Xs, const nm::Args<flo
   const int mask = (int)(__builtin_amdgcn_ballot_w64(d > 0) & 3ull);
   if (mask) reset_noise_store(Xs, As, mask, wave);
 }
+// The re-draw of the per-env rows of the step whose books were just filed (nm_reset_rows.h; X::rrows), for the envs of this wave that the
+// step reset, called right behind step_reset_noise with the same done word and the same wave-uniform test. Lanes 0..40 own the 41 words
+// of one env at a time, lane 0 its reset-row count; the pools and their sizes are read from the env object's descriptor in device memory.
+// The load stage of wave_step reads every row with vector loads (gldv / gldx), once per step, through the same L1 these vector stores
+// write through: the wait at the head of the step function (or of books_last) is behind the previous step's loads of the same rows, the
+// body ends with a wait of its own, and step_close's wait puts the stores in L2 before the load stage asks for the rows. The resetting
+// step itself ran on the old rows. Out of line, like reset_noise_store: taken once per episode, and its registers are nobody else's.
+template <class X>
+__device__ __noinline__ void reset_rows_store(const X* Xs, const nm::Args<float>* As, int mask, int wave) {
+  const int lane = threadIdx.x;
+  mask = __builtin_amdgcn_readfirstlane(mask);
+#pragma unroll 1
+  for (int hh = 0; hh < 2; hh++) {
+    const int env = wave * 2 + hh;
+    if (!((mask >> hh) & 1) || env >= As->N) continue;
+    const uint32_t k = simt::gld1((const uint32_t*)Xs->rrows.count, (size_t)env);
+    if (lane < nm::kResetRowWords)
+      nm::reset_rows_apply<float>(*As, Xs->rrows.desc, As->seed, (uint64_t)(As->env_offset + env), (size_t)env, k, lane);
+    if (lane == 0) simt::gst1(Xs->rrows.count, (size_t)env, k + 1u);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+template <class X>
+__device__ __forceinline__ void step_reset_rows(const X* Xs, const nm::Args<float>* As, long long d, int wave) {
+  if (__builtin_amdgcn_readfirstlane(Xs->rrows.on) == 0) return;
+  const int mask = (int)(__builtin_amdgcn_ballot_w64(d > 0) & 3ull);
+  if (mask) reset_rows_store(Xs, As, mask, wave);
+}
 // the books of the launch's last step (no policy step follows it)
 template <class X>
 __device__ __noinline__ void books_last(const X* Xs, const nm::Args<float>* As, int t, int wave) {
@@ -137,6 +166,7 @@ __device__ __noinline__ void books_last(const X* Xs, const nm::Args<float>* As, 
   books_load(rec, Xs, As, wave);
   books_file(rec, Xs, As, t, wave);
   step_reset_noise(Xs, As, rec.d, wave);             // a reset at the launch's last step
+  step_reset_rows(Xs, As, rec.d, wave);
 }
 
 // The launch arguments of env step t that every K-step launch sets (lane 0, after the policy of step t), and what closes the policy step.

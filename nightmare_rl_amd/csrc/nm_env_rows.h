@@ -125,6 +125,20 @@ inline std::string delays_fault(const int* d, int N, int nsub) {
   return std::string();
 }
 
+// friction / gain rows as envp_write and nm_draw_env_params admit them: finite, mu > 1e-5, gains >= 0; the pad is not judged
+template <class real> inline std::string fric_rows_fault(const real* rows, int N) {
+  for (int e = 0; e < N; e++) {
+    const real* r = rows + (size_t)e * nm::kEnvP;
+    const char* why = nullptr;
+    for (int j = 0; j < nm::kEnvPS; j++) if (!std::isfinite((double)r[j])) why = "a non-finite value";
+    if (!why && !(r[nm::EP_MU] > real(1e-5))) why = "mu must be above 1e-5";
+    if (!why && r[nm::EP_PGAIN] < 0) why = "p_gain must not be negative";
+    if (!why && r[nm::EP_KV] < 0) why = "kv must not be negative";
+    if (why) return "row " + std::to_string(e) + ": " + why;
+  }
+  return std::string();
+}
+
 // ---- descriptors: the kinds that are "N rows of W reals in the env's dtype, set whole, judged on the host" - body and gravity rows - differ
 // in nothing but this. Every owner of a block (the env object, the emulation) has ONE set / get / fill for them, written over a
 // descriptor D: D::kind, D::W, D::rows(base, N), D::dflt(M, out[W]), D::fault(rows, N). A new kind of that shape supplies its descriptor
@@ -162,6 +176,24 @@ typedef RowKind<kBody> BodyKind;
 typedef RowKind<kGrav> GravKind;
 typedef RowKind<kServo> ServoKind;
 typedef RowKind<kTorque> TorqueKind;
+
+// the rows of a reset pool (nm_reset_rows.h) of P rows of `kind`, judged by the rule the kind's own setter applies: `rows` holds P rows of
+// the kind's width in `real` - for kLat, P ints
+constexpr int kKinds = 6;
+constexpr int kind_width(int kind) {
+  return kind == kFric ? nm::kEnvP : kind == kBody ? nm::kBodyP : kind == kLat ? 1 : kind == kGrav ? nm::kGravP : kind == kServo ? nm::kServoP : nm::kTorqueP;
+}
+template <class real> inline std::string pool_rows_fault(int kind, const void* rows, int P, int nsub) {
+  const real* r = static_cast<const real*>(rows);
+  switch (kind) {
+    case kFric: return fric_rows_fault<real>(r, P);
+    case kBody: return BodyKind::fault<real>(r, P);
+    case kLat: return delays_fault(static_cast<const int*>(rows), P, nsub);
+    case kGrav: return GravKind::fault<real>(r, P);
+    case kServo: return ServoKind::fault<real>(r, P);
+    default: return TorqueKind::fault<real>(r, P);
+  }
+}
 
 // ---- state: which kinds are on, and what follows from that for a launch
 struct State {

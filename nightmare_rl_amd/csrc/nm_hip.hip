@@ -14,6 +14,7 @@
 #include "nm_env_rows.h"
 #include "nm_push.h"
 #include "nm_reset_noise.h"
+#include "nm_reset_rows.h"
 #include "nm_rollout.h"
 
 static thread_local std::string g_err;
@@ -209,6 +210,12 @@ struct nm_env {
   int step_variant_mode = 0, step_variant_last = 0;
   virtual int set_reset_counts(const uint32_t* counts_host) = 0;
   virtual int get_reset_counts(uint32_t* counts_host) = 0;
+  // per-env rows re-drawn at reset (nm_reset_rows.h): the pools' sizes as the device descriptor holds them (0 = no pool)
+  uint32_t rrows_size[nm::kResetRowKinds] = {};
+  virtual int set_reset_rows(int kind, const void* rows_dev, uint32_t P, hipStream_t s) = 0;
+  virtual int get_reset_rows(int kind, uint32_t* P, void* out_dev, hipStream_t s) = 0;
+  virtual int set_reset_row_counts(const uint32_t* counts_host) = 0;
+  virtual int get_reset_row_counts(uint32_t* counts_host) = 0;
 };
 
 template <class real> struct Env : nm_env {
@@ -336,6 +343,7 @@ template <class real> struct Env : nm_env {
     hipLaunchKernelGGL(k_reset<real>, dim3((n + 255) / 256), dim3(256), 0, s, M, a, idp, n);
     HIPCHK(hipGetLastError());
     if (rnoise_on && launch_reset_noise(nullptr, idp, n, s)) return 1;     // the same envs' reset draw (nm_reset_noise.h)
+    if (rrows_any() && launch_reset_rows(nullptr, idp, n, s)) return 1;    // and the re-draw of their per-env rows (nm_reset_rows.h)
     return finalize(ep_stats, nullptr, s);
   }
   int step(const float* actions, int64_t* eplen, float* obs, float* rew, int64_t* done, float* time_outs, float* ep_stats, int physics_only,
@@ -394,6 +402,8 @@ template <class real> struct Env : nm_env {
     if (prof_on) HIPCHK(hipEventRecord(e1, s));
     // randomised reset states: the draw of the envs this step reset, decided on the device from done[] (nm_reset_noise.h)
     if (!physics_only && rnoise_on && launch_reset_noise(done, nullptr, N, s)) return 1;
+    // per-env rows re-drawn at reset: the same decision on the device, for the kinds that have a pool (nm_reset_rows.h)
+    if (!physics_only && rrows_any() && launch_reset_rows(done, nullptr, N, s)) return 1;
     return 0;
   }
   int d2h(const real* dev, double* host, size_t n) {
@@ -641,6 +651,100 @@ template <class real> struct Env : nm_env {
     }
     return r;
   }
+  // ---- per-env rows re-drawn at reset (nm_reset_rows.h): the pools are copies in device memory of this object, the descriptor the
+  // kernels read lies in device memory too and is rewritten stream-ordered after synchronising; the reset-row counts are allocated
+  // (zeroed) at first use
+  nm::ResetRowsDesc* rrows_desc_dev = nullptr;
+  nm::ResetRowsDesc rrows_desc = {};
+  uint32_t rrows_cap[nm::kResetRowKinds] = {};      // rows the kind's device buffer holds
+  uint32_t* rrows_count = nullptr;
+  bool rrows_any() const {
+    for (int k = 0; k < nm::kResetRowKinds; k++) if (rrows_size[k]) return true;
+    return false;
+  }
+  int rrows_reserve() {
+    if (rrows_count) return 0;
+    if (dalloc(&rrows_count, (size_t)N) || dalloc(&rrows_desc_dev, 1)) return 1;
+    HIPCHK(hipMemset(rrows_count, 0, (size_t)N * sizeof(uint32_t)));
+    HIPCHK(hipMemset(rrows_desc_dev, 0, sizeof(nm::ResetRowsDesc)));
+    HIPCHK(hipDeviceSynchronize());
+    return 0;
+  }
+  static size_t rrows_word(int kind) { return kind == nmrows::kLat ? sizeof(int) : sizeof(real); }
+  // the descriptor as the host holds it -> device, behind everything `s` carries (a launch in flight may be reading the old one)
+  int rrows_publish(hipStream_t s) {
+    for (int k = 0; k < nm::kResetRowKinds; k++) rrows_desc.size[k] = rrows_size[k];
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpyAsync(rrows_desc_dev, &rrows_desc, sizeof rrows_desc, hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+  }
+  // what switching a kind off does to its pool (nm_set_* with null): dropped; the buffer stays for the next pool
+  int rrows_drop(int kind, hipStream_t s) {
+    if (!rrows_size[kind]) return 0;
+    rrows_size[kind] = 0;
+    return rrows_publish(s);
+  }
+  int set_reset_rows(int kind, const void* rows_in, uint32_t P, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (!rows_in) return rrows_drop(kind, s);       // the kind stays on or off as it is, its rows keep what they hold
+    // the pool is judged on the host before anything of the env changes
+    const size_t bytes = (size_t)P * nmrows::kind_width(kind) * rrows_word(kind);
+    std::vector<char> h(bytes);
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpy(h.data(), rows_in, bytes, hipMemcpyDeviceToHost));
+    const std::string why = nmrows::pool_rows_fault<real>(kind, h.data(), (int)P, A.nsub);
+    if (!why.empty()) return fail("nm_set_reset_rows: " + why);
+    if (rows_alloc(s) || rrows_reserve()) return 1;
+    if (P > rrows_cap[kind]) {       // a buffer of its own per kind; an outgrown one stays allocated until the env goes (a launch may hold it)
+      char* buf = nullptr;
+      HIPCHK(hipMalloc((void**)&buf, bytes));
+      allocs.push_back(buf);
+      rrows_desc.pool[kind] = (uint64_t)(uintptr_t)buf;
+      rrows_cap[kind] = P;
+    }
+    HIPCHK(hipMemcpyAsync((void*)(uintptr_t)rrows_desc.pool[kind], rows_in, bytes, hipMemcpyDeviceToDevice, s));
+    rrows_size[kind] = P;
+    if (rrows_publish(s)) return 1;
+    return rows_turn((nmrows::Kind)kind, true);      // the current rows stay until each env's next reset
+  }
+  int get_reset_rows(int kind, uint32_t* P, void* out, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (P) *P = rrows_size[kind];
+    if (out && rrows_size[kind])
+      HIPCHK(hipMemcpyAsync(out, (const void*)(uintptr_t)rrows_desc.pool[kind], (size_t)rrows_size[kind] * nmrows::kind_width(kind) * rrows_word(kind),
+                            hipMemcpyDeviceToDevice, s));
+    return 0;
+  }
+  int set_reset_row_counts(const uint32_t* counts_host) override {
+    HIPCHK(hipSetDevice(device));
+    if (!counts_host) return fail("nm_set_reset_row_counts: counts_host is NULL");
+    if (rrows_reserve()) return 1;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(rrows_count, counts_host, (size_t)N * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return 0;
+  }
+  int get_reset_row_counts(uint32_t* counts_host) override {
+    if (!counts_host) return 0;
+    if (!rrows_count) { memset(counts_host, 0, (size_t)N * sizeof(uint32_t)); return 0; }
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(counts_host, rrows_count, (size_t)N * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+  }
+  // the re-draw behind a step (done: the step's reset flags) or behind k_reset (done = null: the n listed envs); on the same stream
+  int launch_reset_rows(const int64_t* done, const int32_t* ids, int n, hipStream_t s) {
+    hipLaunchKernelGGL(nm::k_reset_rows<real>, dim3((unsigned)(((size_t)n * 64 + 255) / 256)), dim3(256), 0, s, A, (const nm::ResetRowsDesc*)rrows_desc_dev,
+                       rrows_count, done, ids, n);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  // the reset-rows arguments of a K-step launch
+  nmr::ResetRowsArgs kstep_rrows() {
+    nmr::ResetRowsArgs r{};
+    if (rrows_any()) { r.on = 1; r.desc = rrows_desc_dev; r.count = rrows_count; }
+    return r;
+  }
   // the push arguments of a K-step launch (nmr::PushArgs says how the step index travels); advances push_step by K
   nmr::PushArgs kstep_push(int K) {
     nmr::PushArgs p{};
@@ -669,7 +773,7 @@ template <class real> struct Env : nm_env {
     p.fin3 = r->fin3 ? r->fin3 : play_scratch + 4 * n_;
     p.st_sum = roll_sum; p.st_cnt = roll_cnt; p.to_step = roll_to;
     p.rec_log = log; p.rec_done = log ? rec_done : nullptr; p.rec_env = rec_env;
-    p.push = kstep_push(K); p.rnoise = kstep_rnoise();
+    p.push = kstep_push(K); p.rnoise = kstep_rnoise(); p.rrows = kstep_rrows();
     rec_done_valid = log != nullptr;
   }
   int rollout(const nm_rollout_args* r, int act, hipStream_t s) override {
@@ -696,7 +800,7 @@ template <class real> struct Env : nm_env {
       R.st_sum = roll_sum; R.st_cnt = roll_cnt; R.to_step = roll_to;
       R.last_values = r->last_values_dev;
       R.rec_log = log;
-      R.push = kstep_push(K); R.rnoise = kstep_rnoise();
+      R.push = kstep_push(K); R.rnoise = kstep_rnoise(); R.rrows = kstep_rrows();
       R.wave_clock = A.dbg ? reinterpret_cast<unsigned long long*>(A.dbg) : nullptr;   // measurement: the debug buffer ([N,256] reals) takes the waves' clocks instead
       const nmr::TailArgs ta = kstep_tail(r, K, r->bootstrap_time_outs ? r->gamma : -1.0f, r->s_values, r->s_rewards);
       if (nmr::launch_rollout(M_dev, a, R, ta, act, rows.level(), s)) return fail("nm_rollout: launch failed");
@@ -795,6 +899,7 @@ template <class real> struct Env : nm_env {
     HIPCHK(hipSetDevice(device));
     if (!rows_in) {       // off; nothing is freed
       if (envp_dev && kind_fill<D>(D::rows(envp_dev, N), s)) return 1;
+      if (rrows_drop(D::kind, s)) return 1;         // off also drops the kind's reset pool (nm_reset_rows.h)
       return rows_turn(D::kind, false);
     }
     // the rows are judged on the host before anything of the env changes
@@ -826,6 +931,7 @@ template <class real> struct Env : nm_env {
     HIPCHK(hipSetDevice(device));
     if (!mu && !p_gain && !kv) {     // off; the rows stay allocated (a launch in flight may read them)
       if (envp_dev && envp_write({}, s)) return 1;
+      if (rrows_drop(nmrows::kFric, s)) return 1;
       return rows_turn(nmrows::kFric, false);
     }
     if (rows_alloc(s) || envp_write({{(const real*)mu, (const real*)p_gain, (const real*)kv}}, s)) return 1;
@@ -893,6 +999,7 @@ template <class real> struct Env : nm_env {
     HIPCHK(hipSetDevice(device));
     if (!substeps) {       // off; nothing is freed, the history keeps what it holds
       if (envp_dev) HIPCHK(hipMemsetAsync(nmrows::delays(envp_dev, N), 0, (size_t)N * sizeof(int), s));
+      if (rrows_drop(nmrows::kLat, s)) return 1;
       return rows_turn(nmrows::kLat, false);
     }
     // the delays are judged on the host before anything of the env changes
@@ -1148,6 +1255,37 @@ int nm_reset_noise_offsets(const double* ranges10, uint64_t seed, int64_t global
     const nm::ResetNoise<double> p = nm::reset_noise_params<double>(ranges10);
     for (int c = 0; c < nm::kResetCols; c++) out43[c] = nm::reset_noise_draw<double>(p, seed, (uint64_t)global_env, k, c);
   }
+  return 0;
+}
+// per-env rows re-drawn at reset, from pools (nm_reset_rows.h). Every refusal that needs no look at the pool comes before the first device
+// call, the kind and the size first, so a bad pool is named whatever the handle is
+int nm_set_reset_rows(nm_env* env, int32_t kind, const void* rows_dev, int32_t P, void* stream) {
+  if (kind < 0 || kind >= nm::kResetRowKinds) return fail("nm_set_reset_rows: kind must be 0..5 (friction / gains, body, latency, gravity, servo, torque limit)");
+  if (rows_dev && (P < 1 || (uint32_t)P > nm::kResetRowsMaxPool)) return fail("nm_set_reset_rows: a pool holds 1..65536 rows");
+  NEED_ENV(env);
+  return env->set_reset_rows(kind, rows_dev, (uint32_t)P, (hipStream_t)stream);
+}
+int nm_get_reset_rows(nm_env* env, int32_t kind, int32_t* P, void* out_dev, void* stream) {
+  if (kind < 0 || kind >= nm::kResetRowKinds) return fail("nm_get_reset_rows: kind must be 0..5");
+  NEED_ENV(env);
+  uint32_t p = 0;
+  if (env->get_reset_rows(kind, &p, out_dev, (hipStream_t)stream)) return 1;
+  if (P) *P = (int32_t)p;
+  return 0;
+}
+int nm_set_reset_row_counts(nm_env* env, const uint32_t* counts_host) {
+  NEED_ENV(env);
+  return env->set_reset_row_counts(counts_host);
+}
+int nm_get_reset_row_counts(nm_env* env, uint32_t* counts_host) {
+  NEED_ENV(env);
+  return env->get_reset_row_counts(counts_host);
+}
+int nm_reset_rows_pick(uint64_t seed, int64_t global_env, uint32_t k, const uint32_t sizes[6], uint32_t out[6]) {
+  if (!sizes || !out) return fail("nm_reset_rows_pick: sizes / out is NULL");
+  for (int i = 0; i < nm::kResetRowKinds; i++)
+    if (sizes[i] > nm::kResetRowsMaxPool) return fail("nm_reset_rows_pick: a pool holds at most 65536 rows");
+  nm::nm_reset_rows_pick(seed, (uint64_t)global_env, k, sizes, out);
   return 0;
 }
 int nm_set_env_params(nm_env* env, const void* mu_dev, const void* p_gain_dev, const void* kv_dev, void* stream) {

@@ -35,7 +35,7 @@ __device__ __noinline__ void play_step(float* xb, const PlayArgs* Ps, nm::Args<f
   ActOut o{Ps->actions, nullptr, nullptr, nullptr, nullptr, nullptr};
   policy_wave<S, ACT, kPolicyPlay>(xb, Ps->wp, Ps->bp, Ps->stdv, t == 0 ? Ps->obs0 : (const float*)Ps->obs, As->N, wave, Ps->seed,
                                    (uint64_t)simt::gld1(Ps->iter_dev, 0) * 4096ull + Ps->step0 + (uint64_t)t, o, Ps->deterministic != 0);
-  if (t > 0) { books_file(rec, Ps, As, t - 1, wave); step_reset_noise(Ps, As, rec.d, wave); }   // the reset draw of step t - 1, before the push of step t
+  if (t > 0) { books_file(rec, Ps, As, t - 1, wave); step_reset_noise(Ps, As, rec.d, wave); step_reset_rows(Ps, As, rec.d, wave); }   // the reset draw of step t - 1, before the push of step t
   if (threadIdx.x == 0) step_args(As, Ps, t, noise0);
   step_push(Ps, As, t, wave);
   step_close();

@@ -24,6 +24,7 @@
 
 #include "nm_act.h"
 #include "nm_reset_noise.h"
+#include "nm_reset_rows.h"
 #include "nm_sample.h"
 #include "nm_sfor.h"
 
@@ -258,6 +259,16 @@ struct ResetNoiseArgs {
   const float* qpos0;           // [kNQ]
   uint32_t* count;              // [N]
 };
+// Per-env rows re-drawn at reset inside a K-step launch (nm_reset_rows.h; step_reset_rows of nm_env_loop.h). The six pools live in a
+// descriptor in device memory of the env object - the argument structs sit in LDS, which has no room for them - and the out-of-line body
+// reads it there, with the envs' reset-row counts, which the owning wave reads and advances itself.
+struct ResetRowsArgs {
+  const nm::ResetRowsDesc* desc;
+  uint32_t* count;              // [N]
+  int on;                       // 0 = no pool is installed: nothing above is read
+  int pad;
+};
+static_assert(sizeof(ResetRowsArgs) == 24, "one small member of the K-step argument structs");
 // ---- the K-step launch (kernels in nm_rollout.hip - a translation unit of its own, so that the code generation of k_env_step in
 // nm_hip.hip is not touched by a second kernel around the same physics; host launchers below)
 struct RollArgs {
@@ -275,6 +286,7 @@ struct RollArgs {
   float* rec_log;                                              // [K,kRecRow] or null: the state log (Args::rec of step t = row t; env.py:261-272)
   PushArgs push;
   ResetNoiseArgs rnoise;
+  ResetRowsArgs rrows;
   // what the episode books of nm_env_loop.h file for this launch: kPlayBooks = per-env return sums + the logged env's reset flag (else the
   // rollout's storage rows), kStepRecord = optional [K,N] reward / done rows
   static constexpr bool kPlayBooks = false, kStepRecord = false;
@@ -295,6 +307,7 @@ struct PlayArgs {
   unsigned char* rec_done; int rec_env;                        // [K] or null: the logged env's reset flag per step (the log's reader dumps a file there)
   PushArgs push;
   ResetNoiseArgs rnoise;
+  ResetRowsArgs rrows;
   static constexpr bool kPlayBooks = true, kStepRecord = false;
 };
 // k_env_tape (nm_tape_kernels.h): K x env.step with the actions of step t read from row t of a [K,N,18] tape - no policy, no sampling
@@ -312,6 +325,7 @@ struct TapeArgs {
   unsigned char* rec_done; int rec_env;
   PushArgs push;
   ResetNoiseArgs rnoise;
+  ResetRowsArgs rrows;
   static constexpr bool kPlayBooks = true, kStepRecord = true;
 };
 struct TailArgs {

@@ -32,7 +32,7 @@ __device__ __noinline__ void policy_step(float* xb, const RollArgs* Rs, nm::Args
   ActOut o{Rs->s_actions + so * nm::kNU, Rs->s_logp + so, Rs->s_values + so, Rs->s_mu + so * nm::kNU, Rs->s_sigma + so * nm::kNU, t == 0 ? Rs->s_obs : nullptr};
   // the observation is the one this wave's previous step wrote into the storage row of step t
   policy_wave<S, ACT>(xb, Rs->wp, Rs->bp, Rs->stdv, t == 0 ? Rs->obs0 : Rs->s_obs + so * nm::kNOBS, N, wave, Rs->seed, (uint64_t)simt::gld1(Rs->iter_dev, 0) * 4096ull + (uint64_t)t, o);
-  if (t > 0) { books_file(rec, Rs, As, t - 1, wave); step_reset_noise(Rs, As, rec.d, wave); }   // the reset draw of step t - 1, before the push of step t
+  if (t > 0) { books_file(rec, Rs, As, t - 1, wave); step_reset_noise(Rs, As, rec.d, wave); step_reset_rows(Rs, As, rec.d, wave); }   // the reset draw of step t - 1, before the push of step t
   if (threadIdx.x == 0) {
     As->actions = o.actions;
     As->obs = t + 1 < Rs->K ? Rs->s_obs + (so + N) * nm::kNOBS : Rs->obs_final;     // the step files its observation where the next act reads it

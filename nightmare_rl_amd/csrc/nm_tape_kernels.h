@@ -28,6 +28,7 @@ __device__ __noinline__ void tape_step(const TapeArgs* Ts, nm::Args<float>* As, 
     books_load(rec, Ts, As, wave);
     books_file(rec, Ts, As, t - 1, wave);
     step_reset_noise(Ts, As, rec.d, wave);           // the reset draw of step t - 1, before the push of step t
+    step_reset_rows(Ts, As, rec.d, wave);            // and the re-draw of its per-env rows
   }
   if (threadIdx.x == 0) {
     const size_t so = (size_t)t * As->N;

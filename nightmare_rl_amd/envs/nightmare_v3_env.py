@@ -33,6 +33,9 @@ Differences a caller can observe (all documented in DESIGN.md):
   * an OPTIONAL `cfg.control.torque_limit` (N m; a scalar or one value each for the coxa, femur and tibia servos) bounds the servo
     torque as MuJoCo's actuator forcerange does (set_torque_limit); cfg.domain_rand may carry randomize_torque_limit /
     torque_limit_range, drawn once at construction (draw_torque_limit). The reference has neither: its servos are ideal
+  * and cfg.domain_rand.resample_on_reset / resample_pool_size: every per-env kind whose randomize_* switch is on is then re-drawn at
+    every reset of an env - in step(), reset_idx, policy_rollout, policy_play and step_tape alike - from a pool of rows filled from the
+    same ranges (set_reset_pool), instead of being drawn once
 """
 import ctypes as C
 import numpy as np
@@ -231,6 +234,155 @@ def reset_noise_config(cfg):
     return tuple(_range(dr, n) or (0.0, 0.0) for n in RESET_NOISE_RANGES)
 
 
+RESET_POOL_KINDS = ("env_params", "base_payload", "action_latency", "gravity", "servo", "torque_limit")   # nmrows::Kind order
+RESET_POOL_WIDTH = (4, 20, 1, 8, 4, 4)
+RESET_POOL_MAX = 65536
+
+
+def resample_config(cfg):
+    """The pool size of the optional cfg.domain_rand.resample_on_reset, or None where the class is missing or the switch is false:
+    every kind whose randomize_* switch is on is then re-drawn at every reset from a pool of resample_pool_size rows (default 1024,
+    1..65536). A switch that is not True / False or a size that is not a whole number in that range is a ValueError."""
+    dr = getattr(cfg, "domain_rand", None)
+    on = getattr(dr, "resample_on_reset", False)
+    if not isinstance(on, (bool, np.bool_)):
+        raise ValueError("cfg.domain_rand.resample_on_reset must be True or False")
+    if not on:
+        return None
+    size = getattr(dr, "resample_pool_size", 1024)
+    if isinstance(size, (bool, np.bool_)) or not isinstance(size, (int, np.integer)) or not 1 <= int(size) <= RESET_POOL_MAX:
+        raise ValueError(f"cfg.domain_rand.resample_pool_size must be a whole number in 1..{RESET_POOL_MAX}")
+    return int(size)
+
+
+# ---- values -> rows: what the row setters and the reset pools (set_reset_pool) share. n: the number of rows (num_envs, or a pool's size);
+# err: the caller's ValueError text for a wrong count
+def per_row_values(x, n, dtype, err, device):
+    """n values, or one scalar for every row, as a contiguous [n] tensor of `dtype` on `device`."""
+    t = torch.as_tensor(x, dtype=dtype).detach().to(device)
+    t = t.expand(n) if t.dim() == 0 else t.reshape(-1)
+    if t.numel() != n:
+        raise ValueError(err)
+    return t.contiguous()
+
+
+def env_param_columns(n, real, device, mu, p_gain, kv, err):
+    """The three columns (mu, p_gain, kv) nm_set_env_params takes: [n] tensors, None = the default."""
+    return [None if x is None else per_row_values(x, n, real, err, device) for x in (mu, p_gain, kv)]
+
+
+def env_param_rows(cols, defaults, n, real, device):
+    """[n, 4] rows (mu, p_gain, kv, pad) as the library forms them from the columns: a missing column holds its default."""
+    rows = torch.zeros(n, 4, dtype=real, device=device)
+    for j, (c, d) in enumerate(zip(cols, defaults)):
+        rows[:, j] = d if c is None else c
+    return rows
+
+
+def vec3_rows(v, n, err):
+    """[n, 3] float64 numpy from one [3] for every row or an [n, 3] array / tensor."""
+    v = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
+    v = np.tile(v, (n, 1)) if v.ndim == 1 and v.size == 3 else v
+    if v.shape != (n, 3):
+        raise ValueError(err)
+    return v
+
+
+def payload_values(n, dm, r, err):
+    """(dm [n], r [n, 3]) float64 numpy of a point mass per row: dm n values or a scalar, r [n, 3], one [3] for all or None = the origin."""
+    dm = per_row_values(dm, n, torch.float64, err, "cpu").numpy()
+    r = np.zeros(3) if r is None else np.asarray(r.detach().cpu().numpy() if isinstance(r, torch.Tensor) else r, dtype=np.float64)
+    r = np.tile(r, (n, 1)) if r.ndim == 1 else r.reshape(-1, 3)
+    if r.shape != (n, 3):
+        raise ValueError(err)
+    return dm, r
+
+
+def payload_body_rows(dm, r):
+    """[n, 20] float64 body rows of the payloads (model/payload.py derives them; ValueError for what MuJoCo's compiler refuses)."""
+    from ..model import payload
+    return payload.payload_rows(dm, r)
+
+
+def gravity_rows(n, g, gravity_vec, err):
+    """[n, 8] float64 gravity rows: g[3], pad, gravity_vec[3] (None = g), pad."""
+    rows = np.zeros((n, 8))
+    rows[:, 0:3] = vec3_rows(g, n, err)
+    rows[:, 4:7] = rows[:, 0:3] if gravity_vec is None else vec3_rows(gravity_vec, n, err)
+    return rows
+
+
+def servo_rows(n, real, device, rate_limit, d_gain, err):
+    """[n, 4] servo rows (rate, d_gain, pad, pad): None = the column's default (inf, 0)."""
+    rows = torch.zeros(n, 4, dtype=real, device=device)
+    rows[:, 0] = float("inf") if rate_limit is None else per_row_values(rate_limit, n, real, err, device)
+    if d_gain is not None:
+        rows[:, 1] = per_row_values(d_gain, n, real, err, device)
+    return rows
+
+
+def torque_rows(n, real, device, limit, err):
+    """[n, 4] torque-limit rows (coxa, femur, tibia, pad) from a scalar, 3 values, [n] or [n, 3]."""
+    t = torch.as_tensor(limit, dtype=real).detach().to(device)
+    if t.dim() == 0 or (t.dim() == 1 and t.numel() == 3):      # (with n == 3, three values are read as coxa, femur, tibia)
+        t = t.expand(n, 3)
+    elif t.dim() == 1 and t.numel() == n:
+        t = t.reshape(n, 1).expand(n, 3)
+    elif tuple(t.shape) != (n, 3):
+        raise ValueError(err)
+    rows = torch.zeros(n, 4, dtype=real, device=device)
+    rows[:, :3] = t
+    return rows
+
+
+def latency_values(n, device, substeps, who):
+    """[n] int32 delays from n integers or one integer for every row."""
+    t = torch.as_tensor(substeps)
+    if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
+        raise ValueError(f"{who}: whole substeps (an integer per env)")
+    return per_row_values(t, n, torch.int32, f"{who}: one delay per env (or one for all)", device)
+
+
+def config_pools(cfg, seed, size, envp_default):
+    """The reset pools of a config whose resample_on_reset is on: {kind: the keyword values set_reset_pool takes}, `size` rows each, for
+    every kind whose randomize_* switch is on. Filled on the host in float64 from the ranges the *_config parsers return, with
+    np.random.default_rng([seed, kind index]): no env id enters, so every rank of a sharded population builds the same pools.
+    envp_default: (mu, p_gain, kv) the library runs with while friction / gains are off."""
+    dr = getattr(cfg, "domain_rand", None)
+    P = int(size)
+    rng = [np.random.default_rng([int(seed), k]) for k in range(len(RESET_POOL_KINDS))]
+
+    def uni(k, r, shape=None):
+        return rng[k].uniform(r[0], r[1], P if shape is None else shape)
+
+    pools = {}
+    fr, st, da = env_param_config(cfg)
+    if fr is not None or st is not None or da is not None:
+        mu0, pg, kv0 = envp_default
+        pools["env_params"] = dict(mu=None if fr is None else uni(0, fr), p_gain=None if st is None else uni(0, (pg * st[0], pg * st[1])),
+                                   kv=None if da is None else uni(0, (kv0 * da[0], kv0 * da[1])))
+    ma, co = payload_config(cfg)
+    if ma is not None or co is not None:
+        pools["base_payload"] = dict(dm=np.zeros(P) if ma is None else uni(1, ma), r=np.zeros((P, 3)) if co is None else uni(1, co, (P, 3)))
+    lat = latency_config(cfg)
+    if lat is not None:
+        pools["action_latency"] = dict(substeps=rng[2].integers(lat[0], lat[1] + 1, P).astype(np.int32))
+    off, tilt, observed = gravity_config(cfg)
+    if off is not None or tilt is not None:
+        o = np.zeros((P, 3)) if off is None else uni(3, off, (P, 3))
+        theta = np.zeros(P) if tilt is None else uni(3, tilt)
+        phi = np.zeros(P) if tilt is None else uni(3, (0.0, 2.0 * np.pi))
+        pools["gravity"] = dict(g=gravity_from_draw(o, theta, phi), gravity_vec=None if observed else np.array([0.0, 0.0, -GRAVITY]))
+    rr, dg = servo_config(cfg)
+    if getattr(dr, "randomize_action_rate_limit", False) or getattr(dr, "randomize_d_gain", False):
+        pools["servo"] = dict(rate_limit=None if rr is None else uni(4, rr), d_gain=None if dg is None else uni(4, dg))
+    _, trange = torque_config(cfg)
+    if trange is not None:
+        a = np.asarray(trange, np.float64)
+        pools["torque_limit"] = dict(limit=rng[5].uniform(a[:, 0], a[:, 1], (P, 3)))
+    return pools
+
+
 class NightmareV3Env:
     def __init__(self, cfg: NightmareV3Config, log_dir="/tmp/nightmare_v3/logs", num_threads=1, *, device=None, seed=0,
                  env_id_offset=0, dtype=torch.float32, lib=None):
@@ -276,6 +428,7 @@ class NightmareV3Env:
         reset_ranges = reset_noise_config(cfg)
         servo_ranges = servo_config(cfg)
         torque_limit, torque_range = torque_config(cfg)
+        resample_size = resample_config(cfg)
         # reward table: zero scales dropped, the rest x dt (reference :123-128). Every name the reference has a _reward_ function
         # for (:399-497) is compiled; a name without one (`collision`, `feet_stumble`, config :95-96) fails like upstream's getattr.
         names = [L.nm_reward_name(i).decode() for i in range(_lib.NUM_REWARDS)]
@@ -346,28 +499,35 @@ class NightmareV3Env:
         self._rows_keep = {}
         # the library's own defaults (the model's mu and kv, the config's p_gain): what it reports while the feature is off, read once here
         self._envp_default = tuple(float(v[0]) for v in self.env_params().values()) if hasattr(L, "nm_get_env_params") else None
-        if any(r is not None for r in envp_ranges):
+        # re-drawn at every reset instead (cfg.domain_rand.resample_on_reset): the kinds whose randomize_* switch is on get a pool each,
+        # installed before the first reset(), in place of their once-only draw below
+        pools = config_pools(cfg, seed, resample_size, self._envp_default) if resample_size is not None else {}
+        if "env_params" not in pools and any(r is not None for r in envp_ranges):
             self.draw_env_params(*envp_ranges)
         # per-env base payload (optional cfg.domain_rand; no reference line): drawn once, here
         self._payload = None
-        if any(r is not None for r in payload_ranges):
+        if "base_payload" not in pools and any(r is not None for r in payload_ranges):
             self.draw_base_payload(*payload_ranges)
         # per-env actuation latency (optional cfg.domain_rand; no reference line): drawn once, here
-        if latency_range is not None:
+        if "action_latency" not in pools and latency_range is not None:
             self.draw_action_latency(*latency_range)
         # per-env gravity vectors - slopes and gravity offsets (optional cfg.domain_rand; no reference line): drawn once, here
-        if gravity_ranges[0] is not None or gravity_ranges[1] is not None:
+        if "gravity" not in pools and (gravity_ranges[0] is not None or gravity_ranges[1] is not None):
             self.draw_gravity(*gravity_ranges)
         # the servo target model (optional cfg.control.action_rate_limit / d_gain, reference config :37-38; optional cfg.domain_rand ranges):
         # set once, here, before the first reset()
-        if servo_ranges[0] is not None or servo_ranges[1] is not None:
+        if "servo" not in pools and (servo_ranges[0] is not None or servo_ranges[1] is not None):
             self.draw_servo(*servo_ranges)
         # the servo torque limit (optional cfg.control.torque_limit / cfg.domain_rand.torque_limit_range; no reference line): set once,
         # here, before the first reset()
-        if torque_range is not None:
+        if "torque_limit" in pools:
+            pass
+        elif torque_range is not None:
             self.draw_torque_limit(torque_range)
         elif torque_limit is not None and np.isfinite(torque_limit).any():
             self.set_torque_limit(torque_limit)
+        for kind, values in pools.items():
+            self.set_reset_pool(kind, **values)
         # randomised reset states (optional cfg.domain_rand; no reference line): on before the first reset(), whose reset_idx(all) is
         # draw 0 of every env
         if reset_ranges is not None:
@@ -459,18 +619,14 @@ class NightmareV3Env:
     def _per_env(self, x, dtype, err, device=None):
         """num_envs values, or one scalar for every env, as a contiguous [num_envs] tensor of `dtype` on the env's device (or `device`);
         err: the caller's ValueError text for any other count."""
-        t = torch.as_tensor(x, dtype=dtype).detach().to(self.device if device is None else device)
-        t = t.expand(self.num_envs) if t.dim() == 0 else t.reshape(-1)
-        if t.numel() != self.num_envs:
-            raise ValueError(err)
-        return t.contiguous()
+        return per_row_values(x, self.num_envs, dtype, err, self.device if device is None else device)
 
     def set_env_params(self, mu=None, p_gain=None, kv=None):
         """Per-env sliding friction, servo stiffness (in place of cfg.control.p_gain) and servo damping (in place of kv = 0.8), honoured by
         step(), step_physics, policy_rollout, policy_play and step_tape alike (nm_set_env_params). Each: a tensor / array of num_envs values, a
         scalar for every env, or None = the default. All three None switch the feature off. The values hold until they are set again (no reset
         resamples them) and are not validated: mu <= 1e-5 or a negative gain is the caller's responsibility."""
-        cols = [None if x is None else self._per_env(x, self._real, "set_env_params: one value per env (or a scalar)") for x in (mu, p_gain, kv)]
+        cols = env_param_columns(self.num_envs, self._real, self.device, mu, p_gain, kv, "set_env_params: one value per env (or a scalar)")
         self._rows_keep["envp"] = cols
         p = [C.c_void_p(t.data_ptr()) if t is not None else None for t in cols]
         self._ck(self._L.nm_set_env_params(self._h, p[0], p[1], p[2], self._stream()))
@@ -505,14 +661,8 @@ class NightmareV3Env:
             self._payload = self._rows_keep["body"] = None
             self._ck(self._L.nm_set_body_params(self._h, None, self._stream()))
             return
-        from ..model import payload
-        err = "set_base_payload: one dm per env (or a scalar) and one r[3] per env (or one for all)"
-        dm = self._per_env(dm, torch.float64, err, device="cpu").numpy()
-        r = np.zeros(3) if r is None else np.asarray(r.detach().cpu().numpy() if isinstance(r, torch.Tensor) else r, dtype=np.float64)
-        r = np.tile(r, (self.num_envs, 1)) if r.ndim == 1 else r.reshape(-1, 3)
-        if r.shape != (self.num_envs, 3):
-            raise ValueError(err)
-        rows = payload.payload_rows(dm, r)
+        dm, r = payload_values(self.num_envs, dm, r, "set_base_payload: one dm per env (or a scalar) and one r[3] per env (or one for all)")
+        rows = payload_body_rows(dm, r)
         t = torch.from_numpy(rows).to(dtype=self._real).to(self.device).contiguous()
         self._ck(self._L.nm_set_body_params(self._h, C.c_void_p(t.data_ptr()), self._stream()))
         self._rows_keep["body"] = t
@@ -552,10 +702,7 @@ class NightmareV3Env:
             self._rows_keep["lat"] = None
             self._ck(self._L.nm_set_action_latency(self._h, None, self._stream()))
             return
-        t = torch.as_tensor(substeps)
-        if t.is_floating_point() or t.is_complex() or t.dtype == torch.bool:
-            raise ValueError("set_action_latency: whole substeps (an integer per env)")
-        t = self._per_env(t, torch.int32, "set_action_latency: one delay per env (or one for all)")
+        t = latency_values(self.num_envs, self.device, substeps, "set_action_latency")
         self._ck(self._L.nm_set_action_latency(self._h, C.c_void_p(t.data_ptr()), self._stream()))
         self._rows_keep["lat"] = t
 
@@ -591,11 +738,7 @@ class NightmareV3Env:
 
     def _vec3(self, v, err):
         """[num_envs, 3] float64 numpy from one [3] for every env or a [num_envs, 3] array / tensor."""
-        v = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float64)
-        v = np.tile(v, (self.num_envs, 1)) if v.ndim == 1 and v.size == 3 else v
-        if v.shape != (self.num_envs, 3):
-            raise ValueError(err)
-        return v
+        return vec3_rows(v, self.num_envs, err)
 
     def set_gravity(self, g=None, gravity_vec=None):
         """Per-env gravity vectors (nm_set_gravity; include/nightmare_hip.h states the semantics). g: the gravity the physics sees, m/s^2
@@ -611,10 +754,7 @@ class NightmareV3Env:
             self._rows_keep["grav"] = None
             self._ck(self._L.nm_set_gravity(self._h, None, self._stream()))
             return
-        err = "set_gravity: one [3] for every env or [num_envs, 3]"
-        rows = np.zeros((self.num_envs, 8))
-        rows[:, 0:3] = self._vec3(g, err)
-        rows[:, 4:7] = rows[:, 0:3] if gravity_vec is None else self._vec3(gravity_vec, err)
+        rows = gravity_rows(self.num_envs, g, gravity_vec, "set_gravity: one [3] for every env or [num_envs, 3]")
         t = torch.from_numpy(rows).to(dtype=self._real).to(self.device).contiguous()
         self._ck(self._L.nm_set_gravity(self._h, C.c_void_p(t.data_ptr()), self._stream()))
         self._rows_keep["grav"] = t
@@ -656,11 +796,7 @@ class NightmareV3Env:
             self._rows_keep["servo"] = None
             self._ck(self._L.nm_set_servo(self._h, None, self._stream()))
             return
-        err = "set_servo: one value per env (or a scalar)"
-        rows = torch.zeros(self.num_envs, 4, dtype=self._real, device=self.device)
-        rows[:, 0] = float("inf") if rate_limit is None else self._per_env(rate_limit, self._real, err)
-        if d_gain is not None:
-            rows[:, 1] = self._per_env(d_gain, self._real, err)
+        rows = servo_rows(self.num_envs, self._real, self.device, rate_limit, d_gain, "set_servo: one value per env (or a scalar)")
         self._ck(self._L.nm_set_servo(self._h, C.c_void_p(rows.data_ptr()), self._stream()))
         self._rows_keep["servo"] = rows
 
@@ -693,16 +829,7 @@ class NightmareV3Env:
             self._rows_keep["torque"] = None
             self._ck(self._L.nm_set_torque_limit(self._h, None, self._stream()))
             return
-        t = torch.as_tensor(limit, dtype=self._real).detach().to(self.device)
-        n = self.num_envs
-        if t.dim() == 0 or (t.dim() == 1 and t.numel() == 3):      # (with num_envs == 3, three values are read as coxa, femur, tibia)
-            t = t.expand(n, 3)
-        elif t.dim() == 1 and t.numel() == n:
-            t = t.reshape(n, 1).expand(n, 3)
-        elif tuple(t.shape) != (n, 3):
-            raise ValueError("set_torque_limit: a scalar, 3 values, [num_envs] or [num_envs, 3]")
-        rows = torch.zeros(n, 4, dtype=self._real, device=self.device)
-        rows[:, :3] = t
+        rows = torque_rows(self.num_envs, self._real, self.device, limit, "set_torque_limit: a scalar, 3 values, [num_envs] or [num_envs, 3]")
         self._ck(self._L.nm_set_torque_limit(self._h, C.c_void_p(rows.data_ptr()), self._stream()))
         self._rows_keep["torque"] = rows
 
@@ -724,6 +851,106 @@ class NightmareV3Env:
         lo, hi = (C.c_double * 3)(*a[:, 0]), (C.c_double * 3)(*a[:, 1])
         self._ck(self._L.nm_draw_torque_limit(self._h, C.byref(lo), C.byref(hi), self._stream()))
         return self.torque_limit()
+
+    # ------------------------------------------------------------------ per-env rows re-drawn at reset, from pools
+    @staticmethod
+    def _pool_len(*vals, row=None):
+        """The pool size the values imply: the leading length of the first value with a row dimension (row: the length of ONE row's
+        value - 3 for a vector - or None for a scalar per row); 1 where every value is one row's."""
+        for v in vals:
+            if v is None:
+                continue
+            a = v if isinstance(v, torch.Tensor) else np.asarray(v)
+            nd = a.dim() if isinstance(a, torch.Tensor) else a.ndim
+            if nd > (0 if row is None else 1):
+                return int(a.shape[0])
+        return 1
+
+    def set_reset_pool(self, kind, size=None, **values):
+        """Give one kind of per-env rows a POOL that every reset of an env re-draws its row from (nm_set_reset_rows; include/nightmare_hip.h
+        states the semantics): a time-out, a termination or reset_idx - in step(), policy_rollout, policy_play and step_tape alike -
+        overwrites that env's row with pool row i, i drawn from (seed, global env id, the env's reset-row count). kind: one of
+        RESET_POOL_KINDS; values: what the kind's own setter takes - env_params: mu, p_gain, kv; base_payload: dm, r; action_latency:
+        substeps; gravity: g, gravity_vec; servo: rate_limit, d_gain; torque_limit: limit - with a leading pool dimension P in place of
+        num_envs (1 <= P <= 65536; `size` states P where every value is a single row's, and three torque limits are one row). It
+        switches the kind on; the rows the envs hold stay until each env's next reset. No values: the pool is dropped and the rows stay.
+        Switching the kind off through its own setter drops the pool too. The library refuses a pool row the kind's setter would refuse."""
+        if kind not in RESET_POOL_KINDS:
+            raise ValueError(f"set_reset_pool: kind must be one of {RESET_POOL_KINDS}")
+        ki = RESET_POOL_KINDS.index(kind)
+        if all(v is None for v in values.values()):
+            self._rows_keep["pool_" + kind] = None
+            self._ck(self._L.nm_set_reset_rows(self._h, ki, None, 0, self._stream()))
+            return
+        who, real, dev = f"set_reset_pool({kind!r})", self._real, self.device
+
+        def take(*names):
+            extra = set(values) - set(names)
+            if extra:
+                raise ValueError(f"{who}: takes {', '.join(names)}, not {', '.join(sorted(extra))}")
+            return [values.get(n) for n in names]
+
+        err = f"{who}: one value per pool row (or one for all)"
+        if kind == "env_params":
+            v = take("mu", "p_gain", "kv")
+            P = self._pool_len(*v) if size is None else int(size)
+            rows = env_param_rows(env_param_columns(P, real, dev, *v, err), self._envp_default, P, real, dev)
+        elif kind == "base_payload":
+            dm, r = take("dm", "r")
+            P = (self._pool_len(dm) if self._pool_len(dm) > 1 else self._pool_len(r, row=3)) if size is None else int(size)
+            rows = torch.from_numpy(payload_body_rows(*payload_values(P, 0.0 if dm is None else dm, r, err))).to(dtype=real)
+        elif kind == "action_latency":
+            (d,) = take("substeps")
+            P = self._pool_len(d) if size is None else int(size)
+            rows = latency_values(P, dev, d, who)
+        elif kind == "gravity":
+            g, gv = take("g", "gravity_vec")
+            if g is None:
+                raise ValueError(f"{who}: gravity_vec needs g")
+            P = (self._pool_len(g, row=3) if self._pool_len(g, row=3) > 1 else self._pool_len(gv, row=3)) if size is None else int(size)
+            rows = torch.from_numpy(gravity_rows(P, g, gv, f"{who}: one [3] for every pool row or [P, 3]")).to(dtype=real)
+        elif kind == "servo":
+            v = take("rate_limit", "d_gain")
+            P = self._pool_len(*v) if size is None else int(size)
+            rows = servo_rows(P, real, dev, *v, err)
+        else:
+            (lim,) = take("limit")
+            a = torch.as_tensor(lim)
+            P = (1 if a.dim() == 0 or (a.dim() == 1 and a.numel() == 3) else int(a.shape[0])) if size is None else int(size)
+            rows = torque_rows(P, real, dev, lim, f"{who}: a scalar, 3 values, [P] or [P, 3]")
+        if not 1 <= P <= RESET_POOL_MAX:
+            raise ValueError(f"{who}: a pool holds 1..{RESET_POOL_MAX} rows")
+        rows = rows.to(dev).contiguous()
+        self._ck(self._L.nm_set_reset_rows(self._h, ki, C.c_void_p(rows.data_ptr()), P, self._stream()))
+        self._rows_keep["pool_" + kind] = rows
+
+    def reset_pool(self, kind):
+        """(rows, P) of the kind's pool - rows a [P, width] tensor in the env's dtype as the kernels read it (nm_get_reset_rows; [P] int32
+        for action_latency) - or None while the kind has no pool."""
+        if kind not in RESET_POOL_KINDS:
+            raise ValueError(f"reset_pool: kind must be one of {RESET_POOL_KINDS}")
+        ki = RESET_POOL_KINDS.index(kind)
+        P = C.c_int32(0)
+        self._ck(self._L.nm_get_reset_rows(self._h, ki, C.byref(P), None, self._stream()))
+        if P.value == 0:
+            return None
+        rows = (torch.empty(P.value, dtype=torch.int32, device=self.device) if kind == "action_latency"
+                else torch.empty(P.value, RESET_POOL_WIDTH[ki], dtype=self._real, device=self.device))
+        self._ck(self._L.nm_get_reset_rows(self._h, ki, None, C.c_void_p(rows.data_ptr()), self._stream()))
+        return rows, P.value
+
+    def reset_row_counts(self):
+        """[num_envs] uint32 numpy: how often each env's rows have been re-drawn (nm_get_reset_row_counts); a checkpoint's content."""
+        k = np.zeros(self.num_envs, np.uint32)
+        self._ck(self._L.nm_get_reset_row_counts(self._h, k.ctypes.data_as(C.c_void_p)))
+        return k
+
+    def set_reset_row_counts(self, counts):
+        """Install [num_envs] reset-row counts (a checkpoint's): the next reset of env e draws with counts[e]."""
+        k = np.ascontiguousarray(counts, np.uint32).reshape(-1)
+        if k.size != self.num_envs:
+            raise ValueError("set_reset_row_counts: counts must hold num_envs values")
+        self._ck(self._L.nm_set_reset_row_counts(self._h, k.ctypes.data_as(C.c_void_p)))
 
     def servo_state(self):
         """[num_envs, 18] float64 numpy: every env's rate-limited servo target L, upstream's limited_actions (nm_get_servo_state), in the

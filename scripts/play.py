@@ -119,6 +119,8 @@ def main():
                     help="damping D on the joint velocity in the servo command (upstream's commented-out control.d_gain = 0.05; default: 0)")
     ap.add_argument("--torque-limit", type=float, default=None, metavar="F", dest="torque_limit",
                     help="every servo delivers at most F N m (MuJoCo's actuator forcerange; default: no limit)")
+    ap.add_argument("--resample-on-reset", type=int, nargs="?", const=1024, default=None, metavar="P", dest="resample_on_reset",
+                    help="re-draw every per-env range above at every reset of an env, from a pool of P rows per kind (default P: 1024), instead of once")
     a = ap.parse_args()
     path = a.checkpoint or get_load_path(a.log_root)
     dev = torch.device("cuda", 0)
@@ -138,6 +140,8 @@ def main():
             randomize_com_displacement = a.com_range is not None
             com_displacement_range = None if a.com_range is None else (-a.com_range, a.com_range)
             randomize_action_latency, action_latency_range = a.latency_range is not None, a.latency_range
+            resample_on_reset = a.resample_on_reset is not None
+            resample_pool_size = a.resample_on_reset if a.resample_on_reset is not None else 1024
         cfg.domain_rand = domain_rand
     if a.action_rate_limit is not None:      # upstream's own names (reference envs/nightmare_v3_config.py:37-38)
         cfg.control.action_rate_limit = a.action_rate_limit

@@ -51,6 +51,8 @@ def main():
                     help="damping D on the joint velocity in the servo command (upstream's commented-out control.d_gain = 0.05; default: 0)")
     ap.add_argument("--torque-limit", type=float, default=None, metavar="F", dest="torque_limit",
                     help="every servo delivers at most F N m (MuJoCo's actuator forcerange; default: no limit)")
+    ap.add_argument("--resample-on-reset", type=int, nargs="?", const=1024, default=None, metavar="P", dest="resample_on_reset",
+                    help="re-draw every per-env range above at every reset of an env, from a pool of P rows per kind (default P: 1024), instead of once")
     ap.add_argument("--gpus", type=int, default=None, help="ranks (one per GPU); without torch.distributed.run, train.py starts them itself")
     args = ap.parse_args()
 
@@ -100,6 +102,8 @@ def main():
             randomize_reset_state = reset_noise
             reset_dof_pos_range = (-args.reset_dof_pos, args.reset_dof_pos)
             reset_base_lin_vel_range = reset_base_ang_vel_range = reset_dof_vel_range = (-args.reset_vel, args.reset_vel)
+            resample_on_reset = args.resample_on_reset is not None
+            resample_pool_size = args.resample_on_reset if args.resample_on_reset is not None else 1024
         cfg.domain_rand = domain_rand
     if args.action_rate_limit is not None:      # upstream's own names (reference envs/nightmare_v3_config.py:37-38)
         cfg.control.action_rate_limit = args.action_rate_limit
