@@ -324,6 +324,42 @@ int nm_set_servo_state(nm_env* env, const double* limited);
 int nm_set_torque_limit(nm_env* env, const void* rows_dev, void* stream);
 int nm_get_torque_limit(nm_env* env, void* out_dev, void* stream);
 int nm_draw_torque_limit(nm_env* env, const double lo[3], const double hi[3], void* stream);
+/* External wrench on the base: MuJoCo 3.1.2's `xfrc_applied` on the base body, per env - the "external force / torque on the base" of
+ * legged_gym-shaped trainers. The reference applies none; the semantics are stated from the upstream source of mj_fwdAcceleration /
+ * mj_xfrcAccumulate (mj_applyFT on the body's xipos).
+ * Each env carries one row of 8 words in the env's dtype: F[3] (N), pad, tau[3] (N m), pad - both in the world frame (the floor's frame
+ * when gravity rows tilt it), F applied at the base body's centre of mass xipos. In every forward pass of every substep the wrench enters
+ * qfrc_smooth as J'[F; tau] and nowhere else; for the free joint (translations in the world frame, rotations about the body axes)
+ *   qfrc_smooth[0:3] += F;   qfrc_smooth[3:6] += Rb' tau + ipos x (Rb' F)
+ * with Rb the base's rotation and ipos its COM offset in its own frame (the env's own body row while a payload is set). It has no velocity
+ * derivative: the implicit factor M + h kv D does not change. Unlike a push it goes through the contact solver. The bad-state step
+ * (mj_resetData inside mj_step) applies none, as upstream clears xfrc_applied there. It is physics: nm_step, nm_step_physics, nm_rollout,
+ * nm_play and nm_step_tape honour it alike, alone or with any other per-env kind. No observation slot, reward term (the `torques` reward
+ * reads the joint part, which stays zero), record or state-log field changes; no reset touches the rows, and the rows re-drawn at reset
+ * (nm_set_reset_rows) do not include this kind. Off is the default, and off equals "on with zero rows" under == in every output.
+ * nm_set_base_wrench (xfrc_applied, constant until set again): `rows` is a DEVICE array [N,8] in the env's dtype, copied on `stream`;
+ *   NULL switches the feature off, ends a schedule and refills zero rows (nothing is freed). Refused, named by nm_last_error, before
+ *   anything of the env changes (the rows are read back and judged on the host, which waits for `stream`): a non-finite force or torque;
+ *   rows while a schedule is on.
+ * nm_get_base_wrench (the rows the stages read): into a DEVICE array [N,8] on `stream`; zero for every env while the feature is off.
+ * nm_set_wrench_schedule (random wrenches over time windows): switches the feature on and lets the env write its own rows. The env counts
+ *   its full env steps in a wrench step index s (K per K-step launch; nm_step_physics and nm_reset leave it alone), and the call sets
+ *   s = start_step. With 1 <= duration_steps <= interval_steps, at the start of step s every env's row is
+ *     a fresh draw   if s >= interval_steps && s % interval_steps == 0          (window q = s / interval_steps)
+ *     set to zero    if s >= interval_steps && s % interval_steps == duration_steps   (only when duration_steps < interval_steps)
+ *     unchanged      otherwise,
+ *   the draw per axis (0..2 = F, 3..5 = tau) v = (2u - 1) * max[axis] in the env's precision (fp32: max rounded to float first),
+ *   u ~ U[0,1) from the counter RNG keyed by (seed + "WRENCH", global env id, 6 q + axis): sharding changes nothing. The call installs
+ *   the rows that hold once step start_step has begun - the draw of window start_step / interval_steps if start_step lies inside a window,
+ *   zero otherwise - so a checkpoint's numbers continue a run exactly. interval_steps == 0 switches the schedule off and the rows to zero
+ *   (the feature stays as it is; the maxima may be NULL). Synchronous. Refused before the handle is looked at: a negative or non-finite
+ *   maximum, duration_steps < 1 or > interval_steps, a negative interval or one of 2^31 steps or more.
+ * nm_get_wrench_schedule: the setting and the current s (any pointer may be NULL): a checkpoint's numbers. */
+int nm_set_base_wrench(nm_env* env, const void* rows_dev, void* stream);
+int nm_get_base_wrench(nm_env* env, void* out_dev, void* stream);
+int nm_set_wrench_schedule(nm_env* env, int64_t interval_steps, int64_t duration_steps, const double max_force[3], const double max_torque[3],
+                           uint64_t start_step);
+int nm_get_wrench_schedule(nm_env* env, int64_t* interval_steps, int64_t* duration_steps, double max_force[3], double max_torque[3], uint64_t* step);
 /* Per-env rows re-drawn at every reset, from pools - the `mode="reset"` events of Isaac Lab, legged_gym's per-reset payload; it replaces
  * nothing upstream (the reference has one robot, one floor and ideal servos, and its reset_idx touches no model constant).
  * kind: 0 friction / gains [4] (mu, p_gain, kv, pad), 1 body rows [20], 2 actuation latency [1] (a 4-byte int in either dtype), 3 gravity

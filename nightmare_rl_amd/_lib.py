@@ -35,6 +35,7 @@ EXPORTS = ["nm_default_config", "nm_reward_name", "nm_last_error", "nm_create", 
            "nm_set_gravity", "nm_get_gravity", "nm_draw_gravity",
            "nm_set_servo", "nm_get_servo", "nm_draw_servo", "nm_get_servo_state", "nm_set_servo_state",
            "nm_set_torque_limit", "nm_get_torque_limit", "nm_draw_torque_limit",
+           "nm_set_base_wrench", "nm_get_base_wrench", "nm_set_wrench_schedule", "nm_get_wrench_schedule",
            "nm_set_step_variant", "nm_get_step_variant",
            "nm_set_reset_rows", "nm_get_reset_rows", "nm_set_reset_row_counts", "nm_get_reset_row_counts", "nm_reset_rows_pick"]
 
@@ -216,6 +217,12 @@ def _bind(L, full):
         L.nm_set_reset_row_counts.argtypes = [vp, vp]
         L.nm_get_reset_row_counts.argtypes = [vp, vp]
         L.nm_reset_rows_pick.argtypes = [C.c_uint64, C.c_int64, C.c_uint32, C.POINTER(C.c_uint32 * 6), C.POINTER(C.c_uint32 * 6)]
+    if hasattr(L, "nm_set_base_wrench"):
+        L.nm_set_base_wrench.argtypes = [vp, vp, vp]
+        L.nm_get_base_wrench.argtypes = [vp, vp, vp]
+        L.nm_set_wrench_schedule.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(C.c_double * 3), C.POINTER(C.c_double * 3), C.c_uint64]
+        L.nm_get_wrench_schedule.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double * 3), C.POINTER(C.c_double * 3),
+                                             C.POINTER(C.c_uint64)]
     if not full:        # the measurement build holds the env entry points only
         return L
     L.nm_gae.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_float, vp, vp]

@@ -204,6 +204,23 @@ template <class VR, class R> NM_FN VR servo_limit(const VR& Lo, const VR& Tt, co
 constexpr int kTorqueP = 4;
 constexpr uint64_t kTorqueKey = 0x544F52515545ull;   // nm_draw_torque_limit: rand_u24_bits(seed + kTorqueKey, global env id, column)
 template <class real> NM_FN const real* torque_rows_of(const Args<real>& A) { return servo_state_of(A) + (size_t)A.N * kNU; }
+// The external wrench on the base (nm_set_base_wrench / nm_set_wrench_schedule, level EP = 7 of the step; MuJoCo's xfrc_applied on the
+// base body): one row of kWrenchP words per env in the env's dtype - the force F[3] (N), a pad, the torque tau[3] (N m), a pad, both in
+// the world frame (the floor's frame when slopes are on), F applied at the base body's centre of mass. The rows are appended to the envp
+// allocation behind the torque rows: nothing in front of them moves. In every forward pass (stage A) the six base dofs of qfrc_smooth
+// receive J'[F; tau], which for the free joint (translations in the world frame, rotations about the body axes) is
+//   qfrc[0:3] += F;   qfrc[3:6] += Rb' tau + ipos x (Rb' F)        (ipos: the base's COM offset in its own frame, BP_IPOS of the body row)
+// and nothing else changes: no velocity derivative, so the implicit factor M + h kv D is level 6's. The bad-state free-fall step applies
+// no wrench (mj_resetData clears xfrc_applied, and the closed form stands for "reset, forward, integrate"); the substeps after it read the
+// row again, as an env layer that writes xfrc_applied before every mj_step would have it.
+constexpr int kWrenchP = 8, WP_F = 0, WP_T = 4;
+constexpr uint64_t kWrenchKey = 0x5752454E4348ull;   // the wrench schedule: rand_u24_bits(seed + kWrenchKey, global env id, 6 * window + axis)
+template <class real> NM_FN const real* wrench_rows_of(const Args<real>& A) { return torque_rows_of(A) + (size_t)A.N * kTorqueP; }
+// Behind the N wrench rows, kWrenchArgBytes that end the allocation: the schedule parameters of a K-step launch (nmr::WrenchArgs,
+// nm_rollout.h), which its level-7 kernels read there - the argument structs of the K-step launches keep their size, and with it the LDS
+// and kernarg figures of every lower level.
+constexpr int kWrenchArgBytes = 48;
+template <class real> NM_FN const void* wrench_args_of(const Args<real>& A) { return wrench_rows_of(A) + (size_t)A.N * kWrenchP; }
 constexpr int kDbgN = 256;
 
 // Where a stage reads the launch arguments from: the stages that touch them (env_load*, env_finish*, wave_step) take the source as a
@@ -403,6 +420,17 @@ template <class real, int G> struct ShWSel<real, G, 6> {
   typedef ShWT<real, G> type;
   static NM_FN ShW<real, G>& images(type& s) { return s.g.l.b.w; }
 };
+// Level 7 (level 6 plus the external wrench on the base) keeps the G wrench rows of the wave's envs behind level 6's block: stage A reads
+// them in every forward pass.
+template <class real, int G> struct ShWX {
+  ShWT<real, G> t;
+  real wrench[G * kWrenchP];
+};
+template <class real, int G> NM_FN real* wrench_rows(ShW<real, G>& w) { return reinterpret_cast<ShWX<real, G>*>(&w)->wrench; }
+template <class real, int G> struct ShWSel<real, G, 7> {
+  typedef ShWX<real, G> type;
+  static NM_FN ShW<real, G>& images(type& s) { return s.t.g.l.b.w; }
+};
 #define NM_OFS(field) ((int)(offsetof(Sh<real>, field) / sizeof(real)))
 #define NM_IOFS(field) ((int)(offsetof(Sh<real>, field) / sizeof(int)))
 
@@ -417,7 +445,8 @@ template <class real, int G> struct ShWSel<real, G, 6> {
 // 5, launched while servo rows are set, is level 4 with the load stage's command formed from the env's rate-limited target and damped
 // by its d_gain (env_load*; no physics stage differs from level 4's); 6, launched while torque rows are set, is level 5 with stage A's
 // servo force clamped to the env's limits and the saturated joints left out of the implicit factor (the first level that changes a
-// physics stage: its statements stand under EP >= 6 alone).
+// physics stage: its statements stand under EP >= 6 alone); 7, launched while the base wrench is on, is level 6 with J'[F; tau] of the
+// env's wrench row added to the six base dofs of qfrc_smooth in stage A (its statements stand under EP >= 7 alone).
 template <int EP, class real> NM_FN real env_mu(const Sh<real>& sh, const Model<real>& M) {
   if constexpr (EP != 0) return sh.envp[EP_MU]; else return M.mu;
 }
@@ -448,6 +477,11 @@ template <class real> struct BodyRef<5, real> {
   NM_FN explicit BodyRef(const real* q) : p(q) {}
 };
 template <class real> struct BodyRef<6, real> {
+  const real* p;
+  NM_FN BodyRef() : p(nullptr) {}
+  NM_FN explicit BodyRef(const real* q) : p(q) {}
+};
+template <class real> struct BodyRef<7, real> {
   const real* p;
   NM_FN BodyRef() : p(nullptr) {}
   NM_FN explicit BodyRef(const real* q) : p(q) {}
@@ -1061,11 +1095,38 @@ template <int EP, class real, int G, class Cfg = CfgAsk> NM_FN void stage_smooth
       }
       ldl3_solve(t, Mi, y);
       vr xb[6];
+      if constexpr (EP >= 7) {
+        // the env's wrench row lies behind level 6's block (wrench_rows): J'[F; tau] on the six base dofs, F at the base body's COM -
+        // translations in the world frame, rotations about the body axes, so qfrc[0:3] += F and qfrc[3:6] += Rb' tau + ipos x (Rb' F).
+        // Formed as -(cbias - wr): a zero row (+0 in every word, as the host fills it) then leaves -cbias's bits, a zero cbias included.
+        typedef ShWX<real, G> WX;
+        const V<int> xo = (grp & (G - 1)) * kWrenchP + (int)(offsetof(WX, wrench) / sizeof(real));
+        const vr F[3] = {ldsv(lds, xo + WP_F), ldsv(lds, xo + (WP_F + 1)), ldsv(lds, xo + (WP_F + 2))};
+        const vr Tq[3] = {ldsv(lds, xo + WP_T), ldsv(lds, xo + (WP_T + 1)), ldsv(lds, xo + (WP_T + 2))};
+        const vr ipos[3] = {LDB(BP_IPOS), LDB(BP_IPOS + 1), LDB(BP_IPOS + 2)};
+        vr Fl[3], wr[6];
+#pragma unroll
+        for (int j = 0; j < 3; j++) Fl[j] = Rb[j] * F[0] + Rb[3 + j] * F[1] + Rb[6 + j] * F[2];
+        cross3(wr + 3, ipos, Fl);
+#pragma unroll
+        for (int j = 0; j < 3; j++) {
+          wr[j] = F[j];
+          wr[3 + j] = (Rb[j] * Tq[0] + Rb[3 + j] * Tq[1] + Rb[6 + j] * Tq[2]) + wr[3 + j];
+        }
+#pragma unroll
+        for (int j = 0; j < 6; j++) {
+          vr wy = W[0][j] * y[0] + W[1][j] * y[1] + W[2][j] * y[2];
+          const vr qb = -(cbias[j] - wr[j]);
+          xb[j] = qb - legsum<real>(wy, isleg);
+          stsv(lds, eoQ + j, qb, st_all);
+        }
+      } else {
 #pragma unroll
       for (int j = 0; j < 6; j++) {
         vr wy = W[0][j] * y[0] + W[1][j] * y[1] + W[2][j] * y[2];
         xb[j] = -cbias[j] - legsum<real>(wy, isleg);
         stsv(lds, eoQ + j, -cbias[j], st_all);
+      }
       }
       ldl6_solve(L, Di, xb);
 #pragma unroll
@@ -3197,7 +3258,7 @@ template <int EP, class real, int G, class Cfg = CfgAsk> NM_FN void substep(ShW<
 
 // load one env's state into its LDS image, action -> servo command (E1)
 template <int EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real>& M, const Args<real>& A, int env, real* bp = nullptr,
-                                                real* late = nullptr, int* rsw = nullptr, bool live = true, real* gp = nullptr, real* tq = nullptr) {
+                                                real* late = nullptr, int* rsw = nullptr, bool live = true, real* gp = nullptr, real* tq = nullptr, real* wx = nullptr) {
   typedef V<real> vr;
   const V<int> lane = opaque_lane();   // index math stays local to this function (not kept live across the physics)
   const VB l18 = lane < kNU;
@@ -3217,6 +3278,8 @@ template <int EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real
   if constexpr (EP >= 4) grav_in = gldv(grav_rows_of(A), sel(lane < kGravP, lane, V<int>(0)) + env * kGravP);   // the env's gravity row, behind the histories
   vr torque_in = vr(real(0));
   if constexpr (EP >= 6) torque_in = gldv(torque_rows_of(A), sel(lane < kTorqueP, lane, V<int>(0)) + env * kTorqueP);   // the env's torque row, behind the servo state: physics, so a physics-only launch reads it too
+  vr wrench_in = vr(real(0));
+  if constexpr (EP >= 7) wrench_in = gldv(wrench_rows_of(A), sel(lane < kWrenchP, lane, V<int>(0)) + env * kWrenchP);   // the env's wrench row, behind the torque rows: physics, so a physics-only launch reads it too
   vr cmd_in = vr(real(0)), eps_in = vr(real(0)), prev_act = vr(real(0)), prev_dofvel = vr(real(0)), dofpos_old = vr(real(0));
   int64_t ep = 0;
   uint32_t ctr_in = 0;
@@ -3260,6 +3323,7 @@ template <int EP, class real> NM_FN void env_load(Sh<real>& sh, const Model<real
     if constexpr (EP >= 2) stsv(bp, lane, body_in, lane < kBodyP);
     if constexpr (EP >= 4) stsv(gp, lane, grav_in, lane < kGravP);
     if constexpr (EP >= 6) stsv(tq, lane, torque_in, lane < kTorqueP);
+    if constexpr (EP >= 7) stsv(wx, lane, wrench_in, lane < kWrenchP);
     p_gain = rdlane(envp_in, EP_PGAIN);
   }
   // ---- E1 (env.py:152-156,181-192): float32 scale + clip; PD -> velocity command from the env's own dof_pos buffer
@@ -3645,6 +3709,8 @@ template <int EP, class real, class Src, class Mid, class Cfg = CfgAsk> NM_FN vo
   if constexpr (EP >= 4) grav_in = gldx<kS>(grav_rows_of(A), sel(hl < kGravP, hl, V<int>(0)) + env * kGravP);   // each env's gravity row (behind the histories), lanes 0..7 of its half
   vr torque_in = vr(real(0));
   if constexpr (EP >= 6) torque_in = gldx<kS>(torque_rows_of(A), sel(hl < kTorqueP, hl, V<int>(0)) + env * kTorqueP);   // each env's torque row (behind the servo state), lanes 0..3 of its half: physics, so a physics-only launch reads it too
+  vr wrench_in = vr(real(0));
+  if constexpr (EP >= 7) wrench_in = gldx<kS>(wrench_rows_of(A), sel(hl < kWrenchP, hl, V<int>(0)) + env * kWrenchP);   // each env's wrench row (behind the torque rows), lanes 0..7 of its half: physics, so a physics-only launch reads it too
   vr cmd_in = vr(real(0)), eps_in = vr(real(0)), prev_act = vr(real(0)), prev_dofvel = vr(real(0)), dofpos_old = vr(real(0));
   // level 3: each env's delay and its whole action history (three rows, lane of the half = joint) with the step's other reads
   V<int> dl = V<int>(0);
@@ -3697,6 +3763,7 @@ template <int EP, class real, class Src, class Mid, class Cfg = CfgAsk> NM_FN vo
     if constexpr (EP >= 2) stsv(body_rows(w), h * kBodyP + hl, body_in, hl < kBodyP);
     if constexpr (EP >= 4) stsv(grav_rows(w), h * kGravP + hl, grav_in, hl < kGravP);
     if constexpr (EP >= 6) stsv(torque_rows(w), h * kTorqueP + hl, torque_in, hl < kTorqueP);
+    if constexpr (EP >= 7) stsv(wrench_rows(w), h * kWrenchP + hl, wrench_in, hl < kWrenchP);
     p_gain = sel(h != 0, vr(rdlane(envp_in, 32 + EP_PGAIN)), vr(rdlane(envp_in, EP_PGAIN)));
   }
   // ---- E1 (env.py:152-156,181-192): float32 scale + clip; PD -> velocity command from the env's own dof_pos buffer
@@ -4113,6 +4180,8 @@ NM_FN void wave_step(ShW<real, G>& w, const Model<real>& M, const Src& src, int 
       int env = wave * G + e;
       real* bp = nullptr;
       if constexpr (EP >= 2) bp = body_rows(w) + e * kBodyP;
+      if constexpr (EP >= 7) env_load<EP>(w.e[e], M, A, env < A.N ? env : A.N - 1, bp, lat_rows(w).late + e * kNU, lat_rows(w).rsw + e, env < A.N, grav_rows(w) + e * kGravP, torque_rows(w) + e * kTorqueP, wrench_rows(w) + e * kWrenchP);
+      else
       if constexpr (EP >= 6) env_load<EP>(w.e[e], M, A, env < A.N ? env : A.N - 1, bp, lat_rows(w).late + e * kNU, lat_rows(w).rsw + e, env < A.N, grav_rows(w) + e * kGravP, torque_rows(w) + e * kTorqueP);
       else
       if constexpr (EP >= 4) env_load<EP>(w.e[e], M, A, env < A.N ? env : A.N - 1, bp, lat_rows(w).late + e * kNU, lat_rows(w).rsw + e, env < A.N, grav_rows(w) + e * kGravP);

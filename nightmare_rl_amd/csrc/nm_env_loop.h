@@ -1,6 +1,6 @@
 // nm_env_loop.h - what the K-step launches k_env_rollout (nm_rollout_kernels.h), k_env_play (nm_play_kernels.h) and k_env_tape
 // (nm_tape_kernels.h) share: the wave index, the launch prologue, the episode books of the wave's two envs, the per-step update of the
-// env step's launch arguments, the push perturbation of a step (nm_push.h), the reset draw of a step (nm_reset_noise.h) and the re-draw of its per-env rows (nm_reset_rows.h). X below is the launch's own argument struct, RollArgs, PlayArgs or TapeArgs (nm_rollout.h): the helpers read
+// env step's launch arguments, the push perturbation of a step (nm_push.h), the wrench schedule of a step (nm_wrench.h), the reset draw of a step (nm_reset_noise.h) and the re-draw of its per-env rows (nm_reset_rows.h). X below is the launch's own argument struct, RollArgs, PlayArgs or TapeArgs (nm_rollout.h): the helpers read
 // the fields all carry (cur_ret, cur_len, fin3, to_step, st_sum, st_cnt, rec_log) and `if constexpr` on the struct's traits (kPlayBooks,
 // kStepRecord) decides what only some of them file.
 #pragma once
@@ -9,11 +9,12 @@
 #include <type_traits>
 
 #include "nm_core.h"
-#include "nm_env_rows.h"     // with_level6: the launchers of the three K-step kernels pick the step's level through it
+#include "nm_env_rows.h"     // with_level7: the launchers of the three K-step kernels pick the step's level through it
 #include "nm_push.h"
 #include "nm_reset_noise.h"
 #include "nm_reset_rows.h"
 #include "nm_rollout.h"
+#include "nm_wrench.h"
 
 namespace nmr {
 
@@ -195,6 +196,30 @@ __device__ __forceinline__ void step_push(const X* Xs, const nm::Args<float>* As
   if (iv == 0) return;
   const uint32_t p = (uint32_t)__builtin_amdgcn_readfirstlane((int)Xs->push.phase) + (uint32_t)t, q = p / iv;
   if (q * iv == p && (t > 0 || __builtin_amdgcn_readfirstlane(Xs->push.past0) != 0)) push_store(Xs, As, q, wave);
+}
+// The wrench schedule of env step t, if the step opens or closes a window (nm_wrench.h; the WrenchArgs behind the env's wrench rows say
+// when - written by the launcher in front of this launch, read here through the scalar-uniform gld1): lanes 0..11 of the wave own
+// (env 2 wave + lane / 6, axis lane % 6) and store their draw, or zero, into the env's wrench row. Called next to step_push, after the
+// wait at the head of the policy step: the load stage of the step before read the row with vector loads (gldx) whose values it has long
+// consumed, through the same L1 these vector stores write through, and step_close's wait puts the stores in L2 before the load stage of
+// this step asks for the row; at t = 0 stream order covers the previous launch. Only the level-7 kernels call it, and the host writes
+// interval = 0 unless the schedule is on. The branch is wave-uniform. Out of line, like push_store: taken twice per `interval`
+// steps at most, and its registers are nobody else's.
+static __device__ __noinline__ void wrench_store(const WrenchArgs* W, const nm::Args<float>* As, uint32_t q, int draw, int wave) {
+  const int lane = threadIdx.x, half = lane >= 6 ? 1 : 0, axis = lane - 6 * half, env = wave * 2 + half;
+  if (lane < 12 && env < As->N) {
+    float v = 0.0f;
+    if (draw) v = nm::wrench_value<float>(As->seed, (uint64_t)(As->env_offset + env), simt::gld1(&W->q0, 0) + q, axis, simt::gld1(W->maxv, (size_t)axis));
+    simt::gst1(const_cast<float*>(nm::wrench_rows_of(*As)), (size_t)env * nm::kWrenchP + nm::wrench_word(axis), v);
+  }
+}
+__device__ __forceinline__ void step_wrench(const nm::Args<float>* As, int t, int wave) {
+  const WrenchArgs* W = static_cast<const WrenchArgs*>(nm::wrench_args_of(*As));
+  const uint32_t iv = (uint32_t)__builtin_amdgcn_readfirstlane(simt::gld1(&W->interval, 0));
+  if (iv == 0) return;
+  const uint32_t p = (uint32_t)__builtin_amdgcn_readfirstlane((int)simt::gld1(&W->phase, 0)) + (uint32_t)t, dq = p / iv, r = p - dq * iv;
+  const uint32_t du = (uint32_t)__builtin_amdgcn_readfirstlane(simt::gld1(&W->duration, 0));
+  if ((r == 0 || (du < iv && r == du)) && (dq > 0 || __builtin_amdgcn_readfirstlane(simt::gld1(&W->past0, 0)) != 0)) wrench_store(W, As, dq, r == 0, wave);
 }
 __device__ __forceinline__ void step_close() {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the actions are in L2 before the load stage asks for them (other lanes of this wave)

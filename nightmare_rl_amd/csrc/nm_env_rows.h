@@ -1,9 +1,9 @@
 // nm_env_rows.h - host side, plain C++17, no HIP header: the one owner of what the host decides about the per-env rows behind
-// nm::Args::envp (friction / gains, body rows, actuation latency, gravity, the servo target model, the servo torque limit) - layout, default rows, admission, which kinds are on and which level of
+// nm::Args::envp (friction / gains, body rows, actuation latency, gravity, the servo target model, the servo torque limit, the base wrench) - layout, default rows, admission, which kinds are on and which level of
 // the step a launch takes. Used by the env object (nm_hip.hip), the K-step launchers and the host emulation (tests/emul, -DNM_EMUL).
 //
 // The invariant every owner of a block keeps: ONCE THE BLOCK IS ALLOCATED, EVERY REGION WHOSE KIND IS OFF HOLDS THAT KIND'S DEFAULTS -
-// default friction / gain rows, default body rows, zero delays, default gravity rows, default servo rows, default torque rows - so a transition writes or refills its own region and
+// default friction / gain rows, default body rows, zero delays, default gravity rows, default servo rows, default torque rows, zero wrench rows - so a transition writes or refills its own region and
 // looks at no other kind's flag. The action history and the servo's limited targets are exempt: they are state, not parameters, and keep what they hold.
 #pragma once
 #include <cmath>
@@ -15,7 +15,7 @@
 
 namespace nmrows {
 
-enum Kind { kFric = 0, kBody = 1, kLat = 2, kGrav = 3, kServo = 4, kTorque = 5 };
+enum Kind { kFric = 0, kBody = 1, kLat = 2, kGrav = 3, kServo = 4, kTorque = 5, kWrench = 6 };      // kWrench lies outside the pooled range [0, kKinds)
 
 // ---- layout: one block of `real`s - N friction / gain rows, N body rows, then the latency words (4 bytes each in either dtype): N
 // delays, N action histories; then, at the next multiple of sizeof(real), N gravity rows. The device finds the last three through
@@ -40,6 +40,12 @@ template <class real> inline real* servo_state(real* base, int N) { return servo
 // 0..5 alone allocates; an owner that can launch level 6 allocates torque_block_reals. The device's way there: nm::torque_rows_of.
 template <class real> constexpr size_t torque_block_reals(size_t N) { return servo_block_reals<real>(N) + N * nm::kTorqueP; }
 template <class real> inline real* torque_rows(real* base, int N) { return base + servo_block_reals<real>((size_t)N); }
+// The external wrench on the base is appended behind the torque rows: N rows of kWrenchP reals, then kWrenchArgBytes for the schedule
+// parameters of a K-step launch (zero = no schedule). torque_block_reals stays what a holder of levels 0..6 alone allocates; an owner
+// that can launch level 7 allocates wrench_block_reals. The device's way there: nm::wrench_rows_of / nm::wrench_args_of.
+template <class real> constexpr size_t wrench_block_reals(size_t N) { return torque_block_reals<real>(N) + N * nm::kWrenchP + nm::kWrenchArgBytes / sizeof(real); }
+template <class real> inline real* wrench_rows(real* base, int N) { return base + torque_block_reals<real>((size_t)N); }
+template <class real> inline void* wrench_args(real* base, int N) { return wrench_rows(base, N) + (size_t)N * nm::kWrenchP; }
 
 // ---- default rows: the model's own values (the fourth word of a friction / gain row is padding, zero)
 template <class real> inline void fric_default(const nm::Model<real>& M, real out[3]) {
@@ -69,6 +75,11 @@ template <class real> inline void servo_default(const nm::Model<real>&, real out
 template <class real> inline void torque_default(const nm::Model<real>&, real out[nm::kTorqueP]) {
   for (int j = 0; j < 3; j++) out[j] = (real)INFINITY;
   out[3] = real(0);
+}
+
+// no force, no torque: level 7 then computes what level 6 does
+template <class real> inline void wrench_default(const nm::Model<real>&, real out[nm::kWrenchP]) {
+  for (int j = 0; j < nm::kWrenchP; j++) out[j] = real(0);
 }
 
 // ---- admission: pure functions of the caller's rows; empty = admitted, otherwise what the entry point reports behind its own name
@@ -114,6 +125,15 @@ template <class real> inline std::string torque_rows_fault(const real* rows, int
     const real* r = rows + (size_t)e * nm::kTorqueP;
     for (int j = 0; j < 3; j++)
       if (!(r[j] > 0)) return "row " + std::to_string(e) + ": limit " + std::to_string(j) + " not > 0";
+  }
+  return std::string();
+}
+// the force and the torque finite; the pads are not judged
+template <class real> inline std::string wrench_rows_fault(const real* rows, int N) {
+  for (int e = 0; e < N; e++) {
+    const real* r = rows + (size_t)e * nm::kWrenchP;
+    for (int j = 0; j < 3; j++)
+      if (!std::isfinite((double)r[nm::WP_F + j]) || !std::isfinite((double)r[nm::WP_T + j])) return "row " + std::to_string(e) + ": a non-finite value";
   }
   return std::string();
 }
@@ -172,13 +192,21 @@ template <> struct RowKind<kTorque> {
   template <class real> static void dflt(const nm::Model<real>& M, real* out) { torque_default(M, out); }
   template <class real> static std::string fault(const real* r, int N) { return torque_rows_fault(r, N); }
 };
+template <> struct RowKind<kWrench> {
+  static constexpr Kind kind = kWrench;
+  static constexpr int W = nm::kWrenchP;
+  template <class real> static real* rows(real* base, int N) { return wrench_rows(base, N); }
+  template <class real> static void dflt(const nm::Model<real>& M, real* out) { wrench_default(M, out); }
+  template <class real> static std::string fault(const real* r, int N) { return wrench_rows_fault(r, N); }
+};
 typedef RowKind<kBody> BodyKind;
 typedef RowKind<kGrav> GravKind;
 typedef RowKind<kServo> ServoKind;
 typedef RowKind<kTorque> TorqueKind;
+typedef RowKind<kWrench> WrenchKind;
 
 // the rows of a reset pool (nm_reset_rows.h) of P rows of `kind`, judged by the rule the kind's own setter applies: `rows` holds P rows of
-// the kind's width in `real` - for kLat, P ints
+// the kind's width in `real` - for kLat, P ints. The pooled kinds are the first six: the base wrench (kWrench) has no pool
 constexpr int kKinds = 6;
 constexpr int kind_width(int kind) {
   return kind == kFric ? nm::kEnvP : kind == kBody ? nm::kBodyP : kind == kLat ? 1 : kind == kGrav ? nm::kGravP : kind == kServo ? nm::kServoP : nm::kTorqueP;
@@ -197,13 +225,14 @@ template <class real> inline std::string pool_rows_fault(int kind, const void* r
 
 // ---- state: which kinds are on, and what follows from that for a launch
 struct State {
-  bool on[6] = {false, false, false, false, false, false};
+  bool on[7] = {false, false, false, false, false, false, false};
   // the level of the step a launch takes: the highest kind that is on; a physics-only launch ignores latency (level 2 on the rows level 3
   // reads; at level 4, which physics-only launches take too, the kernel skips it at run time: nm::Args::physics_only; at level 5 it skips
   // the servo row and its state the same way; the torque limit is physics: level 6 whenever it is on, physics-only launches included,
-  // and the kernel skips latency and the servo row at run time there as levels 4 and 5 do)
+  // and the kernel skips latency and the servo row at run time there as levels 4 and 5 do; the base wrench is physics as well: level 7
+  // whenever it is on)
   int level(bool physics_only = false) const {
-    return on[kTorque] ? 6 : on[kServo] ? 5 : on[kGrav] ? 4 : (on[kLat] ? (physics_only ? 2 : 3) : (on[kBody] ? 2 : (on[kFric] ? 1 : 0)));
+    return on[kWrench] ? 7 : on[kTorque] ? 6 : on[kServo] ? 5 : on[kGrav] ? 4 : (on[kLat] ? (physics_only ? 2 : 3) : (on[kBody] ? 2 : (on[kFric] ? 1 : 0)));
   }
   // nm::Args::envp of a launch: the block while any kind is on, null (level 0 never looks) otherwise
   template <class real> real* envp(real* base) const { return level() ? base : nullptr; }
@@ -231,6 +260,12 @@ template <class F> inline auto with_level5(int level, F&& f) {
 template <class F> inline auto with_level6(int level, F&& f) {
   if (level == 6) return f(std::integral_constant<int, 6>{});
   return with_level5(level, f);
+}
+
+// and for an owner that can launch level 7; with_level, with_level5 and with_level6 keep their cases
+template <class F> inline auto with_level7(int level, F&& f) {
+  if (level == 7) return f(std::integral_constant<int, 7>{});
+  return with_level6(level, f);
 }
 
 }  // namespace nmrows

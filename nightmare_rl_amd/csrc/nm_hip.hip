@@ -16,6 +16,7 @@
 #include "nm_reset_noise.h"
 #include "nm_reset_rows.h"
 #include "nm_rollout.h"
+#include "nm_wrench.h"
 
 static thread_local std::string g_err;
 static int fail(const std::string& m) { g_err = m; return 1; }
@@ -197,6 +198,13 @@ struct nm_env {
   virtual int set_torque_limit(const void* rows, hipStream_t s) = 0;
   virtual int get_torque_limit(void* out, hipStream_t s) = 0;
   virtual int draw_torque_limit(const double* lo, const double* hi, hipStream_t s) = 0;
+  virtual int set_base_wrench(const void* rows, hipStream_t s) = 0;
+  virtual int get_base_wrench(void* out, hipStream_t s) = 0;
+  virtual int install_wrench_schedule() = 0;
+  // the wrench schedule (nm_wrench.h): the setting and the wrench step index, counted like the push step index
+  int wrench_interval = 0, wrench_duration = 0;
+  double wrench_max[6] = {};
+  uint64_t wrench_step = 0;
   // push perturbations (nm_push.h): the setting and the push step index - full env steps taken, K per K-step launch; physics-only
   // launches and nm_reset leave it alone
   int push_interval = 0;
@@ -217,6 +225,11 @@ struct nm_env {
   virtual int set_reset_row_counts(const uint32_t* counts_host) = 0;
   virtual int get_reset_row_counts(uint32_t* counts_host) = 0;
 };
+
+// what puts a K-step launch's nmr::WrenchArgs behind the wrench rows (nm::wrench_args_of), on the launch's stream
+__global__ void k_wrench_args(nmr::WrenchArgs* dst, nmr::WrenchArgs w) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) *dst = w;
+}
 
 template <class real> struct Env : nm_env {
   nmhost::Tables<real> T;
@@ -369,6 +382,9 @@ template <class real> struct Env : nm_env {
                            nm::push_counter(push_interval, ps), (real)push_max);
         HIPCHK(hipGetLastError());
       }
+      const uint64_t ws = wrench_step++;
+      if (const int due = nm::wrench_due(wrench_interval, wrench_duration, ws))      // as the push: a launch of its own on the steps that open or close a window
+        if (launch_wrench(nm::wrench_window(wrench_interval, ws), due == 1, s)) return 1;
     }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (prof_on) {  // HIP events on the launch stream around the dominant kernel only (bench.py's roofline leg)
@@ -394,7 +410,7 @@ template <class real> struct Env : nm_env {
       if constexpr (sizeof(real) == 4 && G == 2) HIPCHK(nm_launch_step_lean(N, s, (const nm::Model<float>*)M_dev, a));
 #endif
     } else {
-      nmrows::with_level6(rows.level(physics_only), [&](auto L) {
+      nmrows::with_level7(rows.level(physics_only), [&](auto L) {
         hipLaunchKernelGGL((k_env_step<real, G, decltype(L)::value>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
       });
       HIPCHK(hipGetLastError());
@@ -758,6 +774,31 @@ template <class real> struct Env : nm_env {
     push_step += (uint64_t)K;
     return p;
   }
+  // the rows of the wrench schedule on the device: the draw of window q for every env, or zero (nm::k_wrench)
+  int launch_wrench(uint32_t q, bool draw, hipStream_t s) {
+    nm::WrenchMax<real> mx;
+    for (int k = 0; k < 6; k++) mx.v[k] = (real)wrench_max[k];
+    hipLaunchKernelGGL(nm::k_wrench<real>, dim3((6 * N + 255) / 256), dim3(256), 0, s, nmrows::wrench_rows(envp_dev, N), N, A.seed, A.env_offset, q, draw ? 1 : 0, mx);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
+  // the wrench arguments of a K-step launch (nmr::WrenchArgs says how the step index travels), written behind the wrench rows on the
+  // launch's stream while the kind is on (the level-7 kernels alone read them); advances wrench_step by K
+  int kstep_wrench(int K, hipStream_t s) {
+    nmr::WrenchArgs w{};
+    if (wrench_interval > 0) {
+      w.interval = wrench_interval; w.duration = wrench_duration;
+      w.phase = (uint32_t)(wrench_step % (uint64_t)wrench_interval);
+      w.q0 = nm::wrench_window(wrench_interval, wrench_step);
+      w.past0 = wrench_step >= (uint64_t)wrench_interval;
+      for (int k = 0; k < 6; k++) w.maxv[k] = (float)wrench_max[k];
+    }
+    wrench_step += (uint64_t)K;
+    if (!rows.on[nmrows::kWrench]) return 0;
+    hipLaunchKernelGGL(k_wrench_args, dim3(1), dim3(64), 0, s, static_cast<nmr::WrenchArgs*>(nmrows::wrench_args(envp_dev, N)), w);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
   // what closes a K-step launch (k_rollout_tail), from the entry point's arguments `r`; the rollout alone bootstraps time-outs
   template <class R> nmr::TailArgs kstep_tail(const R* r, int K, float gamma = -1.0f, const float* s_values = nullptr, float* s_rewards = nullptr) {
     return {N, K, roll_sum, roll_cnt, roll_to, r->ep_stats_dev, r->time_outs_dev, M.ep_len_s, counters_dev, gamma, s_values, s_rewards,
@@ -803,6 +844,7 @@ template <class real> struct Env : nm_env {
       R.push = kstep_push(K); R.rnoise = kstep_rnoise(); R.rrows = kstep_rrows();
       R.wave_clock = A.dbg ? reinterpret_cast<unsigned long long*>(A.dbg) : nullptr;   // measurement: the debug buffer ([N,256] reals) takes the waves' clocks instead
       const nmr::TailArgs ta = kstep_tail(r, K, r->bootstrap_time_outs ? r->gamma : -1.0f, r->s_values, r->s_rewards);
+      if (kstep_wrench(K, s)) return 1;
       if (nmr::launch_rollout(M_dev, a, R, ta, act, rows.level(), s)) return fail("nm_rollout: launch failed");
       return 0;
     }
@@ -831,6 +873,7 @@ template <class real> struct Env : nm_env {
       P.seed = r->seed; P.iter_dev = r->iter_dev; P.step0 = r->step0;
       P.obs0 = r->obs0_dev; P.obs = r->obs_dev; P.actions = r->actions_dev;
       kstep_books(P, r, K, log);
+      if (kstep_wrench(K, s)) return 1;
       if (nmr::launch_play(M_dev, a, P, kstep_tail(r, K), act, rows.level(), s)) return fail("nm_play: launch failed");
       return 0;
     }
@@ -855,6 +898,7 @@ template <class real> struct Env : nm_env {
       T.K = K; T.tape = r->actions_dev;
       T.rec_obs = r->rec_obs_dev; T.rec_rew = r->rec_rew_dev; T.rec_dones = r->rec_done_dev;
       kstep_books(T, r, K, log);
+      if (kstep_wrench(K, s)) return 1;
       if (nmr::launch_tape(M_dev, a, T, kstep_tail(r, K), rows.level(), s)) return fail("nm_step_tape: launch failed");
       // with an observation record every step filed its observation in its row: the env's own buffer receives the last one
       const size_t n_ = (size_t)N;
@@ -863,7 +907,7 @@ template <class real> struct Env : nm_env {
       return 0;
     }
   }
-  // ---- per-env rows (friction / gains, body rows, actuation latency, gravity, servo target model, servo torque limit): ONE lazily allocated block behind A.envp, which every launch copies
+  // ---- per-env rows (friction / gains, body rows, actuation latency, gravity, servo target model, servo torque limit, base wrench): ONE lazily allocated block behind A.envp, which every launch copies
   // with the rest of A. Where each kind lies in it, what an unset kind holds, which rows are admitted and which level of the step a launch
   // takes: nm_env_rows.h, and its invariant - once the block exists, every region whose kind is off holds that kind's defaults - is what
   // the functions below keep: each writes or refills its own region and looks at no other kind.
@@ -878,16 +922,17 @@ template <class real> struct Env : nm_env {
   // at first use, from the slab (zeroed: the delays, the history and the servo's limited targets start at zero); the fills are ordered on the first caller's stream
   int rows_alloc(hipStream_t s) {
     if (envp_dev) return 0;
-    if (dalloc(&envp_dev, nmrows::torque_block_reals<real>((size_t)N))) return 1;
+    if (dalloc(&envp_dev, nmrows::wrench_block_reals<real>((size_t)N))) return 1;
     return envp_write({}, s) || kind_fill<nmrows::BodyKind>(nmrows::body_rows(envp_dev, N), s) || kind_fill<nmrows::GravKind>(nmrows::grav_rows(envp_dev, N), s) ||
-           kind_fill<nmrows::ServoKind>(nmrows::servo_rows(envp_dev, N), s) || kind_fill<nmrows::TorqueKind>(nmrows::torque_rows(envp_dev, N), s);
+           kind_fill<nmrows::ServoKind>(nmrows::servo_rows(envp_dev, N), s) || kind_fill<nmrows::TorqueKind>(nmrows::torque_rows(envp_dev, N), s) ||
+           kind_fill<nmrows::WrenchKind>(nmrows::wrench_rows(envp_dev, N), s);
   }
   int rows_turn(nmrows::Kind k, bool on) {
     rows.on[k] = on;
     A.envp = rows.envp(envp_dev);
     return 0;
   }
-  // ---- the kinds with a descriptor D (nm_env_rows.h RowKind: body rows, gravity rows, servo rows, torque rows); `who`: the entry point's name
+  // ---- the kinds with a descriptor D (nm_env_rows.h RowKind: body rows, gravity rows, servo rows, torque rows, wrench rows); `who`: the entry point's name
   template <class D> int kind_fill(real* dst, hipStream_t s) {      // the default row for every env
     Vals<real, D::W> r;
     D::dflt(M, r.v);
@@ -899,7 +944,8 @@ template <class real> struct Env : nm_env {
     HIPCHK(hipSetDevice(device));
     if (!rows_in) {       // off; nothing is freed
       if (envp_dev && kind_fill<D>(D::rows(envp_dev, N), s)) return 1;
-      if (rrows_drop(D::kind, s)) return 1;         // off also drops the kind's reset pool (nm_reset_rows.h)
+      if constexpr (D::kind < nmrows::kKinds)       // off also drops the kind's reset pool (nm_reset_rows.h); the base wrench has none
+        if (rrows_drop(D::kind, s)) return 1;
       return rows_turn(D::kind, false);
     }
     // the rows are judged on the host before anything of the env changes
@@ -993,6 +1039,24 @@ template <class real> struct Env : nm_env {
     HIPCHK(hipSetDevice(device));
     if (rows_alloc(s) || draw<3, nm::kTorqueP>(nmrows::torque_rows(envp_dev, N), nm::kTorqueKey, lo, hi, s)) return 1;
     return rows_turn(nmrows::kTorque, true);
+  }
+  // ---- the external wrench on the base: rows (F[3], pad, tau[3], pad) through the descriptor; the schedule's rows through k_wrench
+  int set_base_wrench(const void* rows_in, hipStream_t s) override { return kind_set<nmrows::WrenchKind>("nm_set_base_wrench", rows_in, s); }
+  int get_base_wrench(void* out, hipStream_t s) override { return kind_get<nmrows::WrenchKind>(out, s); }
+  // the rows that hold once step wrench_step has begun, and the kind on; without a schedule (interval 0) zero rows, and the kind stays
+  // what it is. Synchronous, like nm_set_servo_state: the entry point has no stream
+  int install_wrench_schedule() override {
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipDeviceSynchronize());
+    if (wrench_interval == 0) {
+      if (envp_dev && kind_fill<nmrows::WrenchKind>(nmrows::wrench_rows(envp_dev, N), nullptr)) return 1;
+    } else {
+      if (rows_alloc(nullptr)) return 1;
+      if (launch_wrench(nm::wrench_window(wrench_interval, wrench_step), nm::wrench_held(wrench_interval, wrench_duration, wrench_step) == 1, nullptr)) return 1;
+      rows_turn(nmrows::kWrench, true);
+    }
+    HIPCHK(hipDeviceSynchronize());
+    return 0;
   }
   // ---- per-env actuation latency
   int set_action_latency(const int* substeps, hipStream_t s) override {
@@ -1416,6 +1480,52 @@ int nm_draw_torque_limit(nm_env* env, const double lo[3], const double hi[3], vo
     for (int k = 0; k < 3; k++)
       if (!((float)lo[k] > 0.0f)) return fail("nm_draw_torque_limit: a limit must be above 0 in float32");
   return env->draw_torque_limit(lo, hi, (hipStream_t)stream);
+}
+// The external wrench on the base stands for MuJoCo's xfrc_applied on the base body (level 7 of the step, nm_core.h stage A)
+int nm_set_base_wrench(nm_env* env, const void* rows_dev, void* stream) {      // constant rows, or NULL = off
+  NEED_ENV(env);
+  if (rows_dev && env->wrench_interval > 0) return fail("nm_set_base_wrench: a wrench schedule is on (nm_set_wrench_schedule with interval_steps = 0 switches it off)");
+  if (!rows_dev) { env->wrench_interval = 0; env->wrench_duration = 0; }      // off ends a schedule too
+  return env->set_base_wrench(rows_dev, (hipStream_t)stream);
+}
+int nm_get_base_wrench(nm_env* env, void* out_dev, void* stream) {
+  NEED_ENV(env);
+  return env->get_base_wrench(out_dev, (hipStream_t)stream);
+}
+int nm_set_wrench_schedule(nm_env* env, int64_t interval_steps, int64_t duration_steps, const double max_force[3], const double max_torque[3],
+                           uint64_t start_step) {
+  const std::string w = "nm_set_wrench_schedule: ";
+  if (interval_steps < 0) return fail(w + "interval_steps must be >= 0 (0 = no schedule)");
+  if (interval_steps >= ((int64_t)1 << 31)) return fail(w + "an interval of 2^31 steps or more is not admitted");
+  if (interval_steps > 0) {
+    if (!max_force || !max_torque) return fail(w + "max_force / max_torque is NULL");
+    for (int k = 0; k < 3; k++) {
+      if (!std::isfinite(max_force[k]) || max_force[k] < 0.0) return fail(w + "max_force must be finite and >= 0");
+      if (!std::isfinite(max_torque[k]) || max_torque[k] < 0.0) return fail(w + "max_torque must be finite and >= 0");
+    }
+    if (duration_steps < 1 || duration_steps > interval_steps) return fail(w + "duration_steps must lie in [1, interval_steps]");
+  }
+  NEED_ENV(env);
+  if (interval_steps > 0 && env->dtype == NM_DTYPE_F32)
+    for (int k = 0; k < 3; k++)
+      if (!std::isfinite((float)max_force[k]) || !std::isfinite((float)max_torque[k])) return fail(w + "the maxima must be finite in float32");
+  env->wrench_interval = (int)interval_steps; env->wrench_duration = interval_steps > 0 ? (int)duration_steps : 0; env->wrench_step = start_step;
+  for (int k = 0; k < 3; k++) {
+    env->wrench_max[k] = interval_steps > 0 ? max_force[k] : 0.0;
+    env->wrench_max[3 + k] = interval_steps > 0 ? max_torque[k] : 0.0;
+  }
+  return env->install_wrench_schedule();
+}
+int nm_get_wrench_schedule(nm_env* env, int64_t* interval_steps, int64_t* duration_steps, double max_force[3], double max_torque[3], uint64_t* step) {
+  NEED_ENV(env);
+  if (interval_steps) *interval_steps = env->wrench_interval;
+  if (duration_steps) *duration_steps = env->wrench_duration;
+  for (int k = 0; k < 3; k++) {
+    if (max_force) max_force[k] = env->wrench_max[k];
+    if (max_torque) max_torque[k] = env->wrench_max[3 + k];
+  }
+  if (step) *step = env->wrench_step;
+  return 0;
 }
 int nm_step_tape(nm_env* env, const nm_tape_args* args, void* stream) {
   if (!env) return fail("nm_step_tape: env is NULL");

@@ -26,8 +26,8 @@ namespace nmr {
 // The rollout's policy_step with three differences: the policy files the actions only (kPolicyPlay: the mean itself when deterministic),
 // its noise key starts at step0, and the env step's action and observation buffers are the same for every step (set by the host), so
 // the act of step t reads back what this wave's step t - 1 wrote into P.obs. The episode books (nm_env_loop.h) are play's: no storage rows.
-// Out of line, like policy_step: its registers are not live across the physics.
-template <class S, int ACT>
+// Out of line, like policy_step: its registers are not live across the physics. WX: the launch carries the wrench schedule (level 7 alone).
+template <class S, int ACT, bool WX>
 __device__ __noinline__ void play_step(float* xb, const PlayArgs* Ps, nm::Args<float>* As, int t, int wave, uint64_t noise0) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // state rows, observation, reward / done / time-out of the previous step: stored
   BookRegs rec;
@@ -38,6 +38,7 @@ __device__ __noinline__ void play_step(float* xb, const PlayArgs* Ps, nm::Args<f
   if (t > 0) { books_file(rec, Ps, As, t - 1, wave); step_reset_noise(Ps, As, rec.d, wave); step_reset_rows(Ps, As, rec.d, wave); }   // the reset draw of step t - 1, before the push of step t
   if (threadIdx.x == 0) step_args(As, Ps, t, noise0);
   step_push(Ps, As, t, wave);
+  if constexpr (WX) step_wrench(As, t, wave);
   step_close();
 }
 
@@ -55,7 +56,7 @@ __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_play(const nm::Mo
   const uint64_t noise0 = A.noise_step;
   const int K = P.K;
   for (int t = 0; t < K; t++) {
-    play_step<S, ACT>(xb, &Ps, &As, t, wave, noise0);     // (+ the bookkeeping of step t - 1)
+    play_step<S, ACT, (EP >= 7)>(xb, &Ps, &As, t, wave, noise0);     // (+ the bookkeeping of step t - 1)
     nm::wave_step<float, 2, EP>(sh, Ms, As, wave);        // env.step: load, decimation x mj_step, epilogue - the code of k_env_step
   }
   books_last(&Ps, &As, K - 1, wave);
@@ -63,7 +64,7 @@ __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_play(const nm::Mo
 
 template <int ACT>
 int PlayKernels<ACT>::play(const nm::Model<float>* M_dev, const nm::Args<float>& a, const PlayArgs& P, int level, hipStream_t s) {
-  nmrows::with_level6(level, [&](auto L) { hipLaunchKernelGGL((k_env_play<RefShape, ACT, decltype(L)::value>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, P); });
+  nmrows::with_level7(level, [&](auto L) { hipLaunchKernelGGL((k_env_play<RefShape, ACT, decltype(L)::value>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, P); });
   return hipGetLastError() != hipSuccess;
 }
 template struct PlayKernels<NM_PLAY_ACT>;

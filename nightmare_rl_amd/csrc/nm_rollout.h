@@ -251,6 +251,21 @@ struct PushArgs {
   int past0;
   float maxv;                   // float32(max_vel_xy)
 };
+// The external wrench on the base inside a K-step launch (nm_wrench.h; step_wrench of nm_env_loop.h): the env's wrench step index at the
+// launch's first step, s0, travels as phase = s0 % interval, q0 = s0 / interval (mod 2^32: the counter's window number) and
+// past0 = (s0 >= interval), so that the wave needs 32-bit arithmetic only. With p = phase + t and dq = p / interval, step t draws window
+// q0 + dq iff p % interval == 0 && (past0 || dq > 0), and zeroes the rows iff duration < interval && p % interval == duration &&
+// (past0 || dq > 0). phase < 2^31 and t < 4096: no overflow. The struct does NOT travel in RollArgs / PlayArgs / TapeArgs, whose copies
+// sit in the LDS of every level's kernel: the launcher writes it, stream-ordered (k_wrench_args), into the env object's device memory
+// behind the wrench rows (nm::wrench_args_of), where the level-7 kernels alone read it.
+struct WrenchArgs {
+  int interval;                 // env steps between two windows; 0 = no schedule
+  int duration;                 // env steps a window lasts, 1..interval
+  uint32_t phase, q0;
+  int past0;
+  float maxv[6];                // float32 of (max_force[3], max_torque[3])
+};
+static_assert(sizeof(WrenchArgs) == 44 && sizeof(WrenchArgs) <= 48 && alignof(WrenchArgs) == 4, "fits nm::kWrenchArgBytes behind rows of either dtype");
 // Randomised reset states inside a K-step launch (nm_reset_noise.h; step_reset_noise of nm_env_loop.h): the converted ranges, the model's
 // qpos0 row in device memory and the envs' reset counts, which the owning wave reads and advances itself.
 struct ResetNoiseArgs {

@@ -22,7 +22,8 @@ namespace nmr {
 // The record of step t - 1 (t > 0; the episode books of nm_env_loop.h) and PPO.act of step t for the wave's envs + the launch arguments
 // of the env step that follows.
 // Out of line: its registers (weight ring, accumulators) are not live across the physics, and the physics' are not live here.
-template <class S, int ACT>
+// WX: the launch carries the wrench schedule (level 7 alone), so that the step functions of the lower levels keep their code.
+template <class S, int ACT, bool WX>
 __device__ __noinline__ void policy_step(float* xb, const RollArgs* Rs, nm::Args<float>* As, int t, int wave, uint64_t noise0) {
   const int N = As->N;
   const size_t so = (size_t)t * N;
@@ -39,6 +40,7 @@ __device__ __noinline__ void policy_step(float* xb, const RollArgs* Rs, nm::Args
     step_args(As, Rs, t, noise0);
   }
   step_push(Rs, As, t, wave);
+  if constexpr (WX) step_wrench(As, t, wave);
   step_close();
 }
 // PPO.compute_returns' `last_values = actor_critic.evaluate(last_critic_obs)` for the wave's envs: the forward once more, on the observation the
@@ -65,7 +67,7 @@ __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_rollout(const nm:
   const int K = R.K;
   if (R.wave_clock && threadIdx.x == 0) R.wave_clock[2 * wave] = __builtin_amdgcn_s_memtime();
   for (int t = 0; t < K; t++) {
-    policy_step<S, ACT>(xb, &Rs, &As, t, wave, noise0);    // (+ the record of step t - 1)
+    policy_step<S, ACT, (EP >= 7)>(xb, &Rs, &As, t, wave, noise0);    // (+ the record of step t - 1)
     nm::wave_step<float, 2, EP>(sh, Ms, As, wave);        // env.step: load, decimation x mj_step, epilogue - the code of k_env_step
   }
   books_last(&Rs, &As, K - 1, wave);
@@ -89,7 +91,7 @@ int RollKernels<ACT>::act(const float* wp, const float* bp, const float* stdv, c
 }
 template <int ACT>
 int RollKernels<ACT>::rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, int level, hipStream_t s) {
-  nmrows::with_level6(level, [&](auto L) { hipLaunchKernelGGL((k_env_rollout<RefShape, ACT, decltype(L)::value>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, R); });
+  nmrows::with_level7(level, [&](auto L) { hipLaunchKernelGGL((k_env_rollout<RefShape, ACT, decltype(L)::value>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, R); });
   return hipGetLastError() != hipSuccess;
 }
 template struct RollKernels<NM_ROLLOUT_ACT>;

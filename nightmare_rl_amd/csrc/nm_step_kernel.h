@@ -79,7 +79,7 @@ constexpr int kWG = 1;
 #endif
 // EP: level of per-env physics parameters (nm_core.h env_mu): 0 none, 1 friction / gain rows (nm::Args::envp), 2 those and body rows, 3 those
 // and actuation latency, 4 those and gravity rows, 5 those and the servo target model, 6 those and the servo torque
-// limit - the host launches a level above 0 only while its rows are set
+// limit, 7 those and the external wrench on the base - the host launches a level above 0 only while its rows are set
 //
 // The launch arguments are read where they are used, by scalar loads from the kernel's own kernarg segment (nm::KernArgs): the wave's
 // first instructions are the loads of the base pointers and then the env rows' HBM reads, the epilogue fetches its pointers again from

@@ -20,7 +20,8 @@
 namespace nmr {
 
 // The bookkeeping of step t - 1 (t > 0) and the launch arguments of env step t. Out of line, like play_step: nothing of it is live across
-// the physics.
+// the physics. WX: the launch carries the wrench schedule (level 7 alone).
+template <bool WX>
 __device__ __noinline__ void tape_step(const TapeArgs* Ts, nm::Args<float>* As, int t, int wave, uint64_t noise0) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // state rows, observation, reward / done / time-out of the previous step: stored
   if (t > 0) {
@@ -37,6 +38,7 @@ __device__ __noinline__ void tape_step(const TapeArgs* Ts, nm::Args<float>* As, 
     step_args(As, Ts, t, noise0);
   }
   step_push(Ts, As, t, wave);
+  if constexpr (WX) step_wrench(As, t, wave);
   step_close();
 }
 
@@ -52,14 +54,14 @@ __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_tape(const nm::Mo
   const uint64_t noise0 = A.noise_step;
   const int K = T.K;
   for (int t = 0; t < K; t++) {
-    tape_step(&Ts, &As, t, wave, noise0);             // (+ the bookkeeping of step t - 1)
+    tape_step<(EP >= 7)>(&Ts, &As, t, wave, noise0);             // (+ the bookkeeping of step t - 1)
     nm::wave_step<float, 2, EP>(sh, Ms, As, wave);        // env.step: load, decimation x mj_step, epilogue - the code of k_env_step
   }
   books_last(&Ts, &As, K - 1, wave);
 }
 
 int tape_kernel(const nm::Model<float>* M_dev, const nm::Args<float>& a, const TapeArgs& T, int level, hipStream_t s) {
-  nmrows::with_level6(level, [&](auto L) { hipLaunchKernelGGL(k_env_tape<decltype(L)::value>, dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, T); });
+  nmrows::with_level7(level, [&](auto L) { hipLaunchKernelGGL(k_env_tape<decltype(L)::value>, dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, T); });
   return hipGetLastError() != hipSuccess;
 }
 

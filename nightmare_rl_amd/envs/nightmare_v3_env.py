@@ -36,6 +36,9 @@ Differences a caller can observe (all documented in DESIGN.md):
   * and cfg.domain_rand.resample_on_reset / resample_pool_size: every per-env kind whose randomize_* switch is on is then re-drawn at
     every reset of an env - in step(), reset_idx, policy_rollout, policy_play and step_tape alike - from a pool of rows filled from the
     same ranges (set_reset_pool), instead of being drawn once
+  * and external_wrench with wrench_interval_s / wrench_duration_s / max_wrench_force / max_wrench_torque: a random force and torque on
+    the base body, MuJoCo's xfrc_applied, held for wrench_duration_s out of every wrench_interval_s (set_wrench_schedule; a constant
+    wrench: set_base_wrench). It acts through the physics and the contact solver, unlike a push; the reference applies none
 """
 import ctypes as C
 import numpy as np
@@ -63,6 +66,48 @@ def push_config(cfg, dt):
     if steps >= 2 ** 31:
         raise ValueError("cfg.domain_rand.push_interval_s is more than 2^31 env steps")
     return int(steps), vel
+
+
+def wrench_config(cfg, dt):
+    """(interval_steps, duration_steps, max_force, max_torque) of the optional cfg.domain_rand, None when the class is missing or
+    external_wrench is false. wrench_interval_s and wrench_duration_s are converted with the env's dt by push_config's rule (whole steps,
+    rounded down; 1e-9 of a step absorbs the division's rounding); max_wrench_force (N) and max_wrench_torque (N m) are each a scalar - all
+    three axes - or three values, finite and >= 0, and at least one of the two must be given (the other is then zero). An interval or a
+    duration below one step, a duration above the interval, or a bad maximum is a ValueError."""
+    dr = getattr(cfg, "domain_rand", None)
+    if dr is None or not getattr(dr, "external_wrench", False):
+        return None
+    steps = []
+    for name in ("wrench_interval_s", "wrench_duration_s"):
+        v = getattr(dr, name, None)
+        if v is None:
+            raise ValueError(f"cfg.domain_rand.external_wrench needs {name}")
+        s = float(v) / float(dt) + 1e-9
+        if not s >= 1:
+            raise ValueError(f"cfg.domain_rand.{name} must be at least one env step (dt)")
+        if s >= 2 ** 31:
+            raise ValueError(f"cfg.domain_rand.{name} is more than 2^31 env steps")
+        steps.append(int(s))
+    if steps[1] > steps[0]:
+        raise ValueError("cfg.domain_rand.wrench_duration_s must not exceed wrench_interval_s")
+    maxima = []
+    for name in ("max_wrench_force", "max_wrench_torque"):
+        v = getattr(dr, name, None)
+        if v is None:
+            maxima.append(None)
+            continue
+        try:
+            a = np.asarray(v, np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            raise ValueError(f"cfg.domain_rand.{name} must be a number or three numbers") from None
+        if a.size not in (1, 3):
+            raise ValueError(f"cfg.domain_rand.{name} must be a number or three numbers (x, y, z)")
+        if not (np.isfinite(a).all() and (a >= 0).all()):
+            raise ValueError(f"cfg.domain_rand.{name} must be finite and >= 0")
+        maxima.append([float(x) for x in np.broadcast_to(a, (3,))])
+    if maxima[0] is None and maxima[1] is None:
+        raise ValueError("cfg.domain_rand.external_wrench needs max_wrench_force or max_wrench_torque")
+    return steps[0], steps[1], maxima[0] or [0.0] * 3, maxima[1] or [0.0] * 3
 
 
 def _range(dr, name, lowest=None, strict=False, whole=False):
@@ -429,6 +474,7 @@ class NightmareV3Env:
         servo_ranges = servo_config(cfg)
         torque_limit, torque_range = torque_config(cfg)
         resample_size = resample_config(cfg)
+        wrench_sched = wrench_config(cfg, self.dt)
         # reward table: zero scales dropped, the rest x dt (reference :123-128). Every name the reference has a _reward_ function
         # for (:399-497) is compiled; a name without one (`collision`, `feet_stumble`, config :95-96) fails like upstream's getattr.
         names = [L.nm_reward_name(i).decode() for i in range(_lib.NUM_REWARDS)]
@@ -528,6 +574,10 @@ class NightmareV3Env:
             self.set_torque_limit(torque_limit)
         for kind, values in pools.items():
             self.set_reset_pool(kind, **values)
+        # the external wrench on the base (optional cfg.domain_rand; no reference line): the schedule starts at step 0
+        self.wrench_interval = 0
+        if wrench_sched is not None:
+            self.set_wrench_schedule(*wrench_sched)
         # randomised reset states (optional cfg.domain_rand; no reference line): on before the first reset(), whose reset_idx(all) is
         # draw 0 of every env
         if reset_ranges is not None:
@@ -851,6 +901,62 @@ class NightmareV3Env:
         lo, hi = (C.c_double * 3)(*a[:, 0]), (C.c_double * 3)(*a[:, 1])
         self._ck(self._L.nm_draw_torque_limit(self._h, C.byref(lo), C.byref(hi), self._stream()))
         return self.torque_limit()
+
+    def set_base_wrench(self, force=None, torque=None):
+        """A constant external wrench on the base body (nm_set_base_wrench; include/nightmare_hip.h states the semantics: MuJoCo's
+        xfrc_applied on the base). force (N) and torque (N m) are in the world frame, the force applied at the base body's centre of mass;
+        each is None (zero), 3 values (every env) or [num_envs, 3]. Both None switches the feature off (and ends a schedule). It is
+        physics: step(), step_physics, policy_rollout, policy_play and step_tape honour it alike; no observation, reward or log field
+        changes. The rows hold until they are set again; no reset touches them. The library refuses non-finite values, and rows while
+        a schedule is on."""
+        if force is None and torque is None:
+            self._rows_keep["wrench"] = None
+            self._ck(self._L.nm_set_base_wrench(self._h, None, self._stream()))
+            self.wrench_interval = 0
+            return
+        n = self.num_envs
+        rows = torch.zeros(n, 8, dtype=self._real, device=self.device)
+        for col, v in ((0, force), (4, torque)):
+            if v is None:
+                continue
+            t = torch.as_tensor(v, dtype=self._real).detach().to(self.device)
+            if t.dim() == 1 and t.numel() == 3:
+                t = t.expand(n, 3)
+            elif tuple(t.shape) != (n, 3):
+                raise ValueError("set_base_wrench: force and torque are 3 values or [num_envs, 3]")
+            rows[:, col:col + 3] = t
+        self._ck(self._L.nm_set_base_wrench(self._h, C.c_void_p(rows.data_ptr()), self._stream()))
+        self._rows_keep["wrench"] = rows
+
+    def base_wrench(self):
+        """{"force": [num_envs, 3], "torque": [num_envs, 3]} in the env's dtype: the wrench every env's physics reads at its next step
+        (nm_get_base_wrench); zero while the feature is off."""
+        rows = torch.empty(self.num_envs, 8, dtype=self._real, device=self.device)
+        self._ck(self._L.nm_get_base_wrench(self._h, C.c_void_p(rows.data_ptr()), self._stream()))
+        return {"force": rows[:, 0:3].clone(), "torque": rows[:, 4:7].clone()}
+
+    def set_wrench_schedule(self, interval_steps, duration_steps, max_force, max_torque, start_step=0):
+        """Random wrenches on the base over time windows (nm_set_wrench_schedule): from step interval_steps on, every interval_steps env
+        steps every env draws a force uniform in [-max_force, max_force) and a torque uniform in [-max_torque, max_torque) per axis, holds
+        them for duration_steps steps (1 <= duration_steps <= interval_steps) and then zero until the next window - in step(),
+        policy_rollout, policy_play and step_tape alike. max_force (N), max_torque (N m): a scalar gives all three axes. The env's wrench
+        step index restarts at start_step, and the rows that hold there are installed: wrench_schedule()'s numbers continue a run exactly.
+        interval_steps = 0 switches the schedule off and the rows to zero. Keyed by the global env id: shards of one population draw
+        what the whole would."""
+        mf = (C.c_double * 3)(*np.broadcast_to(np.asarray(max_force, np.float64), (3,)))
+        mt = (C.c_double * 3)(*np.broadcast_to(np.asarray(max_torque, np.float64), (3,)))
+        torch.cuda.current_stream(self.device).synchronize()      # the call is synchronous on the device's null stream
+        self._ck(self._L.nm_set_wrench_schedule(self._h, int(interval_steps), int(duration_steps), C.byref(mf), C.byref(mt), int(start_step)))
+        self.wrench_interval = int(interval_steps)
+        self._rows_keep["wrench"] = None
+
+    def wrench_schedule(self):
+        """(interval_steps, duration_steps, max_force[3], max_torque[3], step) as nm_get_wrench_schedule returns them: what a checkpoint
+        needs to continue the schedule."""
+        iv, du, st = C.c_int64(0), C.c_int64(0), C.c_uint64(0)
+        mf, mt = (C.c_double * 3)(), (C.c_double * 3)()
+        self._ck(self._L.nm_get_wrench_schedule(self._h, C.byref(iv), C.byref(du), C.byref(mf), C.byref(mt), C.byref(st)))
+        return iv.value, du.value, list(mf), list(mt), st.value
 
     # ------------------------------------------------------------------ per-env rows re-drawn at reset, from pools
     @staticmethod

@@ -141,7 +141,7 @@ class OnPolicyRunner:
         self.rollout_mode = "one launch (nm_rollout)" if one_launch else "per-step launches"
         want_graph = not one_launch and bool(self.cfg.get("graph_rollout", True)) and torch.device(dev).type == "cuda" and hasattr(env, "_h") \
             and not getattr(env, "add_noise", False) and not getattr(getattr(env.cfg, "viewer", None), "record_states", False) \
-            and not getattr(env, "push_interval", 0)          # (a push is a launch the host decides per step: not in a replayed graph)
+            and not getattr(env, "push_interval", 0) and not getattr(env, "wrench_interval", 0)    # (a push, or a wrench window's start or end, is a launch the host decides per step: not in a replayed graph)
         graph = None
         ev0, ev1 = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) if on_gpu else (None, None)
         # Pipelined logging (fused update): rsl_rl's runner reads the iteration's statistics from the device after every update

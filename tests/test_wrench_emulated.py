@@ -1,0 +1,203 @@
+"""The external wrench on the base (nm_set_base_wrench, level 7 of the step) in the host emulation of the device source
+(tests/emul/nm_emul_wrench.cpp, levels 0 and 7 only): the fp64 emulation of the mixed batch (env e under set e % 5 of the fixture, set 3
+with its payload's body row) against the fp64 fixture of the patched oracle (tests/golden/make_wrench_goldens.py), teacher-forced and
+free-running, one and two envs per wave; the fp32 emulation inside the project's fp32 bounds; zero rows at level 7 against level 0 under
+==; the device's layout functions against nm_env_rows.h; N = 7 and its padded half; the mixed batch against the uniform ones bit for bit;
+the sensitivity of the comparison; a physics-only launch; and the stand-alone sanitizer build of the shim."""
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import load_golden
+from wrench_tools import POPS, mixed, mixed_payload, mixed_wrench, set_of
+
+
+@pytest.fixture(scope="module")
+def G():
+    return load_golden("wrench.npz")
+
+
+@pytest.fixture(scope="module")
+def emul():
+    from emul import emul_wrench
+    emul_wrench.build()
+    return emul_wrench
+
+
+def body_rows(g, n=8):
+    from nightmare_rl_amd.model import payload as pl
+    dm, r = mixed_payload(g, n)
+    return pl.payload_rows(dm, r)
+
+
+def load_step(env, g, pop, t, state=True):
+    """Start state of step t of the mixed batch (state False: the step's inputs only - a free-running env keeps its own state)."""
+    n = env.N
+    pick = lambda k: mixed(g, f"{pop}_{k}", t, n)
+    if state:
+        env.set("qpos", pick("qpos")); env.set("qvel", pick("qvel")); env.set("qwarm", pick("qw"))
+        env.set("dofpos", pick("dof_pos")); env.set("dofvel", pick("dof_vel")); env.set("act", pick("act")); env.set("cmd", pick("cmd"))
+        env.eplen[:] = pick("ep_len")
+    return pick("actions"), pick("cmd_u").astype(np.float64)
+
+
+def run(emul, g, pop, wrench, double, steps=None, envs_per_wave=2, forced=True, force_level=-1, physics_only=False, n=8, payload=True):
+    """Single steps of the mixed batch under `wrench` ([n,6] or None = no rows), set 3's envs with their payload's body rows; teacher-forced
+    (every step from the recorded state) or free-running from the first. Returns per-step (obs, rew, qpos, qvel, qwarm) and the errors."""
+    env = emul.EmulWrench(n, double=double, seed=5, envs_per_wave=envs_per_wave)
+    env.set_base_wrench(wrench)
+    if payload and (wrench is not None or force_level == 7):
+        env.set_body_rows(body_rows(g, n))
+    out, oerrs, serrs, flags = [], [], [], 0
+    T = g[f"{pop}_actions"].shape[1] if steps is None else steps
+    for t in range(T):
+        a, cu = load_step(env, g, pop, t, state=forced or t == 0)
+        obs, rew, done, _ = env.step(a, cmd_u=cu, force_level=force_level, physics_only=physics_only)
+        oe = np.abs(obs.astype(np.float64) - mixed(g, f"{pop}_obs", t, n)).max(axis=1)
+        re_ = np.abs(rew.astype(np.float64) - mixed(g, f"{pop}_rew", t, n))
+        serrs.append(np.maximum(np.abs(env.get("qpos") - mixed(g, f"{pop}_qpos", t + 1, n)).max(axis=1), np.abs(env.get("qvel") - mixed(g, f"{pop}_qvel", t + 1, n)).max(axis=1)))
+        flags += int((done != mixed(g, f"{pop}_done", t, n)).sum())
+        oerrs.append(np.maximum(oe, re_))
+        out.append((obs.copy(), rew.copy(), env.get("qpos"), env.get("qvel"), env.get("qwarm")))
+    return out, (np.stack(oerrs), flags), np.stack(serrs)
+
+
+def same(a, b, m=slice(None)):
+    for x, y in zip(a, b):
+        for u, v in zip(x, y):
+            np.testing.assert_array_equal(u[m], v[m])
+
+
+def test_layout_and_level(emul):
+    for n in (1, 7, 8):
+        for double in (False, True):
+            env = emul.EmulWrench(n, double=double)
+            assert env.device_layout_agrees(), n      # nm::wrench_rows_of / wrench_args_of against nm_env_rows.h
+            assert env.level() == 0 and env.level(True) == 0
+            np.testing.assert_array_equal(env.wrench_rows(), np.zeros((n, 8)))      # defaults while the kind is off
+            env.set_base_wrench([3.0, -2.0, 4.0, 0.3, -0.2, 0.25])
+            assert env.level() == 7 and env.level(True) == 7      # physics: a physics-only launch takes level 7 too
+            want = np.array([3.0, -2.0, 4.0, 0.0, 0.3, -0.2, 0.25, 0.0]).astype(np.float64 if double else np.float32)
+            np.testing.assert_array_equal(env.wrench_rows(), np.tile(want, (n, 1)))
+            env.set_base_wrench()
+            assert env.level() == 0 and (env.wrench_rows() == 0).all()
+    env = emul.EmulWrench(4)
+    for bad in ((np.nan, 0, 0, 0, 0, 0), (0, np.inf, 0, 0, 0, 0), (0, 0, 0, 0, 0, -np.inf), (0, 0, 0, np.nan, 0, 0)):
+        with pytest.raises(ValueError):
+            env.set_base_wrench(bad)
+        assert env.level() == 0 and (env.wrench_rows() == 0).all()      # refused before anything changes
+    env.set_base_wrench(np.zeros(6))
+    assert env.level() == 7
+
+
+@pytest.mark.parametrize("forced", [True, False], ids=["forced", "free"])
+@pytest.mark.parametrize("envs_per_wave", [2, 1])
+@pytest.mark.parametrize("pop", POPS)
+def test_fp64_emulation_matches_the_patched_oracle(G, emul, pop, envs_per_wave, forced):
+    """Tolerances: the project's fp64 ones (tests/test_gpu_parity.py: obs / reward < 1e-6, state < 1e-8), teacher-forced and
+    free-running alike. The oracle reaches J'[F; tau] through its own jac_point and cdof, the device source through the free joint's
+    closed form: a wrong frame of the rotational dofs, or a wrong ipos under set 3's payload, misses these bounds by orders of magnitude."""
+    _, (err, flags), serr = run(emul, G, pop, mixed_wrench(G), double=True, envs_per_wave=envs_per_wave, forced=forced)
+    assert flags == 0
+    print(f"{pop}: max obs/reward error {err.max():.2e}, max state error {serr.max():.2e}")
+    assert err.max() < 1e-6 and serr.max() < 1e-8, (err.max(), serr.max())
+
+
+@pytest.mark.parametrize("pop", POPS)
+def test_fp32_emulation_stays_inside_the_fp32_bounds(G, emul, pop):
+    """The project's fp32 bounds: median < 5e-6, p99 < 1e-4, teacher-forced."""
+    _, (err, flags), _ = run(emul, G, pop, mixed_wrench(G), double=False)
+    assert flags == 0
+    print(f"{pop}: fp32 emulation vs fixture: median {np.median(err):.2e}, p99 {np.percentile(err, 99):.2e}, max {err.max():.2e}")
+    assert np.median(err) < 5e-6 and np.percentile(err, 99) < 1e-4
+
+
+@pytest.mark.parametrize("envs_per_wave", [2, 1])
+@pytest.mark.parametrize("double", [False, True], ids=["fp32", "fp64"])
+def test_default_rows_at_level_7_equal_level_0(G, emul, double, envs_per_wave):
+    """Zero rows are no wrench at all, under == in every output (every kind at its defaults, through the level-7 code)."""
+    for pop in POPS:
+        off, _, _ = run(emul, G, pop, None, double=double, steps=3, envs_per_wave=envs_per_wave, payload=False)
+        on, _, _ = run(emul, G, pop, np.zeros((8, 6)), double=double, steps=3, envs_per_wave=envs_per_wave, payload=False)
+        same(off, on)
+
+
+@pytest.mark.parametrize("double", [False, True], ids=["fp32", "fp64"])
+def test_seven_envs_leave_the_padded_half_finite(G, emul, double):
+    """N = 7: the last wave's second slot recomputes env 6; every output is finite and envs 0..6 equal those of the batch of eight."""
+    for pop in POPS:
+        a, (err, flags), _ = run(emul, G, pop, mixed_wrench(G, 7), double=double, steps=3, n=7)
+        b, _, _ = run(emul, G, pop, mixed_wrench(G, 8), double=double, steps=3, n=8)
+        assert flags == 0 and all(np.isfinite(u).all() for x in a for u in x)
+        for x, y in zip(a, b):
+            for u, v in zip(x, y):
+                np.testing.assert_array_equal(u, v[:7])
+
+
+@pytest.mark.parametrize("double", [False, True], ids=["fp32", "fp64"])
+@pytest.mark.parametrize("pop", POPS)
+def test_mixed_batch_equals_uniform_batches_bit_for_bit(G, emul, pop, double):
+    """Every env is independent: env e of the mixed batch equals env e of the batch in which EVERY env holds e's wrench and body row."""
+    from nightmare_rl_amd.model import payload as pl
+    w = mixed_wrench(G)
+    t0 = emul.lib().emux_together_count()
+    mx, _, _ = run(emul, G, pop, w, double=double, steps=3)
+    if pop == "stand" and not double:
+        assert emul.lib().emux_together_count() > t0      # both envs of a wave in ONE constraint pass under different rows
+    dm, r = mixed_payload(G)
+    for e in range(5):      # envs 0..4 hold the five sets
+        env = emul.EmulWrench(8, double=double, seed=5)
+        env.set_base_wrench(np.tile(w[e], (8, 1)))
+        env.set_body_rows(pl.payload_rows(np.full(8, dm[e]), np.tile(r[e], (8, 1))))
+        uni = []
+        for t in range(3):
+            a, cu = load_step(env, G, pop, t)
+            obs, rew, _, _ = env.step(a, cmd_u=cu)
+            uni.append((obs.copy(), rew.copy(), env.get("qpos"), env.get("qvel"), env.get("qwarm")))
+        same(mx, uni, slice(e, e + 1))
+
+
+@pytest.mark.parametrize("pop", POPS)
+def test_cleared_rows_miss_the_fixture_exactly_where_a_wrench_is_set(G, emul, pop):
+    """Sensitivity of the comparison: with zero wrench rows (set 3 keeps its payload) the fp64 emulation misses the fixture in the envs of
+    sets 1..4 and matches it in those of set 0."""
+    _, (err, _), serr = run(emul, G, pop, None, double=True, force_level=7)
+    loaded = set_of(8) != 0
+    e, s = err.max(axis=0), serr.max(axis=0)
+    print(f"{pop}: per-env obs/reward error with cleared rows {np.array2string(e, precision=2)}, state {np.array2string(s, precision=2)}")
+    assert (e[~loaded] < 1e-6).all() and (s[~loaded] < 1e-8).all()
+    assert (s[loaded] > 1e-6).all(), s
+
+
+@pytest.mark.parametrize("pop", POPS)
+def test_physics_only_launch_honours_the_wrench(G, emul, pop):
+    """nm_step_physics is physics: from the recorded state and the command the full step forms (the emulation's physics-only launch forms
+    it from the current joint angles, which ARE the dof_pos buffer at a step's start), it lands on the oracle's qpos / qvel."""
+    env = emul.EmulWrench(8, double=True, seed=5)
+    env.set_base_wrench(mixed_wrench(G))
+    env.set_body_rows(body_rows(G))
+    a, _ = load_step(env, G, pop, 0)
+    np.testing.assert_array_equal(mixed(G, f"{pop}_dof_pos", 0), mixed(G, f"{pop}_qpos", 0)[:, 7:])
+    assert env.level(True) == 7
+    env.step(a, physics_only=True)
+    assert np.abs(env.get("qpos") - mixed(G, f"{pop}_qpos", 1)).max() < 1e-8
+    assert np.abs(env.get("qvel") - mixed(G, f"{pop}_qvel", 1)).max() < 1e-8
+
+
+def test_standalone_sanitizer_build_of_the_shim_runs_clean(G, emul, tmp_path):
+    """The shim as a program of its own (its own main, nothing loaded into Python) under AddressSanitizer and UBSan: one mixed-batch step
+    of each population over the fixture's states, fp32 and fp64; exit status 0 = no report, every value finite, the two-env pass taken."""
+    from emul.emul_wrench import rows8
+    parts = []
+    for pop in POPS:
+        for k in ("qpos", "qvel", "qw", "dof_pos", "dof_vel", "act", "cmd", "actions"):
+            parts.append(np.asarray(mixed(G, f"{pop}_{k}", 0), np.float64).ravel())
+        parts += [rows8(mixed_wrench(G), 8).ravel(), body_rows(G).ravel()]
+    states = tmp_path / "states.bin"
+    np.concatenate(parts).tofile(states)
+    exe = emul.build_program(str(tmp_path / "nm_emul_wrench_asan"), ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], opt="-O0")
+    r = subprocess.run([exe, str(states)], capture_output=True, text=True)
+    print(r.stdout, r.stderr[-2000:])
+    assert r.returncode == 0, (r.stdout, r.stderr[-2000:])
+    assert "fp32" in r.stdout and "fp64" in r.stdout

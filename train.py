@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """train.py - the reference's training entry point (reference train.py:1-54) on the MI355X backend.
 Same flags (-r resume, -v render [rejected: no viewer], -n num_threads [accepted, unused], -e envs, -p resume_path) plus
---iters / --seed / --gpus / --push-interval-s / --push-vel / --friction-range / --gain-range / --reset-dof-pos / --reset-vel. Multi-GPU: `python train.py --gpus G -e <total envs>` (starts its G ranks as child processes) or
+--iters / --seed / --gpus / --push-interval-s / --push-vel / --wrench-interval-s / --wrench-duration-s / --wrench-force / --wrench-torque / --friction-range / --gain-range / --reset-dof-pos / --reset-vel. Multi-GPU: `python train.py --gpus G -e <total envs>` (starts its G ranks as child processes) or
 `python -m torch.distributed.run --nproc-per-node G train.py -e <total envs>`."""
 import argparse
 import datetime
@@ -30,6 +30,14 @@ def main():
     ap.add_argument("--push-interval-s", type=float, default=0.0, dest="push_interval_s",
                     help="push perturbations: seconds between two pushes of every robot's base velocity (0 = off, the default)")
     ap.add_argument("--push-vel", type=float, default=1.0, dest="push_vel", help="push perturbations: max |vx|, |vy| of a push in m/s")
+    ap.add_argument("--wrench-interval-s", type=float, default=0.0, dest="wrench_interval_s",
+                    help="external wrench on the base: seconds between the starts of two windows with a random force and torque (0 = off, the default)")
+    ap.add_argument("--wrench-duration-s", type=float, default=None, dest="wrench_duration_s",
+                    help="external wrench: seconds a window lasts, at most the interval (default: the whole interval)")
+    ap.add_argument("--wrench-force", type=float, default=None, metavar="F", dest="wrench_force",
+                    help="external wrench: each component of the force drawn from U[-F, F) N per window (default: 0)")
+    ap.add_argument("--wrench-torque", type=float, default=None, metavar="T", dest="wrench_torque",
+                    help="external wrench: each component of the torque drawn from U[-T, T) N m per window (default: 0)")
     ap.add_argument("--friction-range", type=float, nargs=2, default=None, metavar=("LO", "HI"), dest="friction_range",
                     help="per-env sliding friction, drawn once from U[LO, HI) (default: 1.0 in every env)")
     ap.add_argument("--added-mass-range", type=float, nargs=2, default=None, metavar=("LO", "HI"), dest="added_mass_range",
@@ -88,10 +96,17 @@ def main():
     if args.reset_dof_pos < 0 or args.reset_vel < 0:
         ap.error("--reset-dof-pos and --reset-vel must not be negative")
     reset_noise = args.reset_dof_pos > 0 or args.reset_vel > 0
-    if (args.push_interval_s > 0 or args.friction_range or args.gain_range or args.added_mass_range or args.com_range is not None or args.latency_range
+    if args.wrench_interval_s < 0:
+        ap.error("--wrench-interval-s must not be negative")
+    if args.wrench_interval_s > 0 and args.wrench_force is None and args.wrench_torque is None:
+        ap.error("--wrench-interval-s needs --wrench-force or --wrench-torque")
+    if (args.push_interval_s > 0 or args.wrench_interval_s > 0 or args.friction_range or args.gain_range or args.added_mass_range or args.com_range is not None or args.latency_range
             or reset_noise):
         class domain_rand:      # the optional class NightmareV3Env reads
             push_robots, push_interval_s, max_push_vel_xy = args.push_interval_s > 0, args.push_interval_s, args.push_vel
+            external_wrench, wrench_interval_s = args.wrench_interval_s > 0, args.wrench_interval_s
+            wrench_duration_s = args.wrench_duration_s if args.wrench_duration_s is not None else args.wrench_interval_s
+            max_wrench_force, max_wrench_torque = args.wrench_force, args.wrench_torque
             randomize_friction, friction_range = args.friction_range is not None, args.friction_range
             randomize_gains = args.gain_range is not None
             stiffness_multiplier_range = damping_multiplier_range = args.gain_range
@@ -119,6 +134,9 @@ def main():
     env = NightmareV3Env(cfg, log_dir=log_dir, num_threads=args.num_threads, device=f"cuda:{local_rank}", seed=seed, env_id_offset=lo)
     if rank == 0:
         print(f"push perturbations: every {env.push_interval} steps, |v| < {env.max_push_vel_xy} m/s" if env.push_interval else "push perturbations: off", flush=True)
+        if env.wrench_interval:
+            iv, du, mf, mt, _ = env.wrench_schedule()
+            print(f"external wrench: every {iv} steps for {du} steps, |F| < {mf[0]} N, |tau| < {mt[0]} N m per axis", flush=True)
         if reset_noise:
             print(f"randomised reset states: joint angles +-{args.reset_dof_pos} rad, velocities +-{args.reset_vel}", flush=True)
         if args.friction_range or args.gain_range:
