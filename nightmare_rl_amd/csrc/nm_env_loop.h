@@ -9,7 +9,7 @@
 #include <type_traits>
 
 #include "nm_core.h"
-#include "nm_env_rows.h"     // with_level7: the launchers of the three K-step kernels pick the step's level through it
+#include "nm_env_rows.h"     // with_level: the launchers of the three K-step kernels pick the step's level through it
 #include "nm_push.h"
 #include "nm_reset_noise.h"
 #include "nm_reset_rows.h"

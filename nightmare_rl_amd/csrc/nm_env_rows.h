@@ -1,10 +1,11 @@
 // nm_env_rows.h - host side, plain C++17, no HIP header: the one owner of what the host decides about the per-env rows behind
-// nm::Args::envp (friction / gains, body rows, actuation latency, gravity, the servo target model, the servo torque limit, the base wrench) - layout, default rows, admission, which kinds are on and which level of
-// the step a launch takes. Used by the env object (nm_hip.hip), the K-step launchers and the host emulation (tests/emul, -DNM_EMUL).
+// nm::Args::envp - layout, default rows, admission, which kinds are on and which level of the step a launch takes. Used by the env object
+// (nm_hip.hip), the K-step launchers and the host emulation (tests/emul, -DNM_EMUL).
 //
 // The invariant every owner of a block keeps: ONCE THE BLOCK IS ALLOCATED, EVERY REGION WHOSE KIND IS OFF HOLDS THAT KIND'S DEFAULTS -
-// default friction / gain rows, default body rows, zero delays, default gravity rows, default servo rows, default torque rows, zero wrench rows - so a transition writes or refills its own region and
-// looks at no other kind's flag. The action history and the servo's limited targets are exempt: they are state, not parameters, and keep what they hold.
+// default friction / gain rows, default body rows, zero delays, default gravity, servo and torque rows, zero wrench rows - so a transition
+// writes or refills its own region and looks at no other kind's flag. The action history and the servo's limited targets are exempt: they
+// are state, not parameters, and keep what they hold.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -17,35 +18,45 @@ namespace nmrows {
 
 enum Kind { kFric = 0, kBody = 1, kLat = 2, kGrav = 3, kServo = 4, kTorque = 5, kWrench = 6 };      // kWrench lies outside the pooled range [0, kKinds)
 
-// ---- layout: one block of `real`s - N friction / gain rows, N body rows, then the latency words (4 bytes each in either dtype): N
-// delays, N action histories; then, at the next multiple of sizeof(real), N gravity rows. The device finds the last three through
-// nm::lat_delay / nm::lat_hist / nm::grav_rows_of (nm_core.h), which tests/emul checks against these.
-template <class real> constexpr size_t grav_offset(size_t N) {
-  return N * (nm::kEnvP + nm::kBodyP) + (N * nm::kLatP * 4 + sizeof(real) - 1) / sizeof(real);
-}
-template <class real> constexpr size_t block_reals(size_t N) { return grav_offset<real>(N) + N * nm::kGravP; }
-template <class real> inline real* fric_rows(real* base, int) { return base; }
-template <class real> inline real* body_rows(real* base, int N) { return base + (size_t)N * nm::kEnvP; }
-template <class real> inline int* delays(real* base, int N) { return reinterpret_cast<int*>(base + (size_t)N * (nm::kEnvP + nm::kBodyP)); }
-template <class real> inline float* histories(real* base, int N) { return reinterpret_cast<float*>(delays(base, N) + N); }
+// ---- layout: ONE block, the regions below in this order, as byte offsets from the base. The device walks it through nm::lat_delay /
+// lat_hist / grav_rows_of / servo_rows_of / servo_state_of / torque_rows_of / wrench_rows_of / wrench_args_of (nm_core.h); tests/emul
+// checks every one of them, and that the regions tile the block.
 constexpr size_t hist_words(size_t N) { return N * nm::kLatH * nm::kNU; }
-template <class real> inline real* grav_rows(real* base, int N) { return base + grav_offset<real>((size_t)N); }
-// The servo target model is appended behind the gravity rows: N rows of kServoP reals, then the state, N x kNU limited targets. block_reals
-// stays the block through the gravity rows (what a holder of levels 0..4 alone allocates); an owner that can launch level 5 allocates
-// servo_block_reals. The device's way there: nm::servo_rows_of / nm::servo_state_of.
-template <class real> constexpr size_t servo_block_reals(size_t N) { return block_reals<real>(N) + N * (nm::kServoP + nm::kNU); }
-template <class real> inline real* servo_rows(real* base, int N) { return base + block_reals<real>((size_t)N); }
-template <class real> inline real* servo_state(real* base, int N) { return servo_rows(base, N) + (size_t)N * nm::kServoP; }
-// The servo torque limit is appended behind the servo state: N rows of kTorqueP reals. servo_block_reals stays what a holder of levels
-// 0..5 alone allocates; an owner that can launch level 6 allocates torque_block_reals. The device's way there: nm::torque_rows_of.
-template <class real> constexpr size_t torque_block_reals(size_t N) { return servo_block_reals<real>(N) + N * nm::kTorqueP; }
-template <class real> inline real* torque_rows(real* base, int N) { return base + servo_block_reals<real>((size_t)N); }
-// The external wrench on the base is appended behind the torque rows: N rows of kWrenchP reals, then kWrenchArgBytes for the schedule
-// parameters of a K-step launch (zero = no schedule). torque_block_reals stays what a holder of levels 0..6 alone allocates; an owner
-// that can launch level 7 allocates wrench_block_reals. The device's way there: nm::wrench_rows_of / nm::wrench_args_of.
-template <class real> constexpr size_t wrench_block_reals(size_t N) { return torque_block_reals<real>(N) + N * nm::kWrenchP + nm::kWrenchArgBytes / sizeof(real); }
-template <class real> inline real* wrench_rows(real* base, int N) { return base + torque_block_reals<real>((size_t)N); }
-template <class real> inline void* wrench_args(real* base, int N) { return wrench_rows(base, N) + (size_t)N * nm::kWrenchP; }
+struct Layout { size_t fric, body, delays, hist, pad, grav, servo, servo_state, torque, wrench, wrench_args, total; };
+template <class real> constexpr Layout layout(size_t N) {
+  constexpr size_t R = sizeof(real);
+  static_assert(nm::kLatP == 1 + nm::kLatH * nm::kNU && nm::kWrenchArgBytes % R == 0, "the latency words and the wrench arguments as the device counts them");
+  Layout L{};                                         // fric: N friction / gain rows of kEnvP reals
+  L.body = L.fric + N * nm::kEnvP * R;                // N body rows of kBodyP reals (base payload)
+  L.delays = L.body + N * nm::kBodyP * R;             // N ints: actuation latency in substeps
+  L.hist = L.delays + N * sizeof(int);                // N x kLatH x kNU floats: the action history (state)
+  L.pad = L.hist + hist_words(N) * sizeof(float);     // up to the next multiple of sizeof(real): 4 bytes in fp64 with an odd N, else empty
+  L.grav = (L.pad + R - 1) / R * R;                   // N gravity rows of kGravP reals
+  L.servo = L.grav + N * nm::kGravP * R;              // N servo rows of kServoP reals
+  L.servo_state = L.servo + N * nm::kServoP * R;      // N x kNU reals: the servo's limited targets (state)
+  L.torque = L.servo_state + N * nm::kNU * R;         // N torque rows of kTorqueP reals
+  L.wrench = L.torque + N * nm::kTorqueP * R;         // N wrench rows of kWrenchP reals
+  L.wrench_args = L.wrench + N * nm::kWrenchP * R;    // kWrenchArgBytes: the schedule parameters of a K-step launch (zero = no schedule)
+  L.total = L.wrench_args + nm::kWrenchArgBytes;
+  return L;
+}
+// the block sizes, in reals: the whole block (wrench_block_reals, what the env object allocates) and its prefixes that end in front of
+// the servo, the torque and the wrench regions - all that an owner reads which launches no level above 4, 5 or 6
+template <class real> constexpr size_t block_reals(size_t N) { return layout<real>(N).servo / sizeof(real); }
+template <class real> constexpr size_t servo_block_reals(size_t N) { return layout<real>(N).torque / sizeof(real); }
+template <class real> constexpr size_t torque_block_reals(size_t N) { return layout<real>(N).wrench / sizeof(real); }
+template <class real> constexpr size_t wrench_block_reals(size_t N) { return layout<real>(N).total / sizeof(real); }
+template <class T, class real> inline T* region(real* base, size_t bytes) { return reinterpret_cast<T*>(reinterpret_cast<char*>(base) + bytes); }
+template <class real> inline real* fric_rows(real* base, int N) { return region<real>(base, layout<real>(N).fric); }
+template <class real> inline real* body_rows(real* base, int N) { return region<real>(base, layout<real>(N).body); }
+template <class real> inline int* delays(real* base, int N) { return region<int>(base, layout<real>(N).delays); }
+template <class real> inline float* histories(real* base, int N) { return region<float>(base, layout<real>(N).hist); }
+template <class real> inline real* grav_rows(real* base, int N) { return region<real>(base, layout<real>(N).grav); }
+template <class real> inline real* servo_rows(real* base, int N) { return region<real>(base, layout<real>(N).servo); }
+template <class real> inline real* servo_state(real* base, int N) { return region<real>(base, layout<real>(N).servo_state); }
+template <class real> inline real* torque_rows(real* base, int N) { return region<real>(base, layout<real>(N).torque); }
+template <class real> inline real* wrench_rows(real* base, int N) { return region<real>(base, layout<real>(N).wrench); }
+template <class real> inline void* wrench_args(real* base, int N) { return region<void>(base, layout<real>(N).wrench_args); }
 
 // ---- default rows: the model's own values (the fourth word of a friction / gain row is padding, zero)
 template <class real> inline void fric_default(const nm::Model<real>& M, real out[3]) {
@@ -159,10 +170,10 @@ template <class real> inline std::string fric_rows_fault(const real* rows, int N
   return std::string();
 }
 
-// ---- descriptors: the kinds that are "N rows of W reals in the env's dtype, set whole, judged on the host" - body and gravity rows - differ
-// in nothing but this. Every owner of a block (the env object, the emulation) has ONE set / get / fill for them, written over a
-// descriptor D: D::kind, D::W, D::rows(base, N), D::dflt(M, out[W]), D::fault(rows, N). A new kind of that shape supplies its descriptor
-// (and its region in the layout above), its entry points, and the device's reads.
+// ---- descriptors: the kinds that are "N rows of W reals in the env's dtype, set whole, judged on the host" - body, gravity, servo, torque
+// and wrench rows - differ in nothing but this. Every owner of a block (the env object, the emulation) has ONE set / get / fill for them,
+// written over a descriptor D: D::kind, D::W, D::rows(base, N), D::dflt(M, out[W]), D::fault(rows, N). A new kind of that shape supplies
+// its descriptor, its region in the layout above, its place in for_each_row_kind, its entry points, and the device's reads.
 template <Kind K> struct RowKind;
 template <> struct RowKind<kBody> {
   static constexpr Kind kind = kBody;
@@ -204,6 +215,8 @@ typedef RowKind<kGrav> GravKind;
 typedef RowKind<kServo> ServoKind;
 typedef RowKind<kTorque> TorqueKind;
 typedef RowKind<kWrench> WrenchKind;
+// f(D{}) for every descriptor kind in block order, until one returns true (= failed); what an owner fills a new block's defaults through
+template <class F> inline bool for_each_row_kind(F&& f) { return f(BodyKind{}) || f(GravKind{}) || f(ServoKind{}) || f(TorqueKind{}) || f(WrenchKind{}); }
 
 // the rows of a reset pool (nm_reset_rows.h) of P rows of `kind`, judged by the rule the kind's own setter applies: `rows` holds P rows of
 // the kind's width in `real` - for kLat, P ints. The pooled kinds are the first six: the base wrench (kWrench) has no pool
@@ -226,11 +239,9 @@ template <class real> inline std::string pool_rows_fault(int kind, const void* r
 // ---- state: which kinds are on, and what follows from that for a launch
 struct State {
   bool on[7] = {false, false, false, false, false, false, false};
-  // the level of the step a launch takes: the highest kind that is on; a physics-only launch ignores latency (level 2 on the rows level 3
-  // reads; at level 4, which physics-only launches take too, the kernel skips it at run time: nm::Args::physics_only; at level 5 it skips
-  // the servo row and its state the same way; the torque limit is physics: level 6 whenever it is on, physics-only launches included,
-  // and the kernel skips latency and the servo row at run time there as levels 4 and 5 do; the base wrench is physics as well: level 7
-  // whenever it is on)
+  // the level of the step a launch takes: the highest kind that is on. Latency and the servo target model are not physics: a physics-only
+  // launch with latency as the highest kind drops to level 2 (the rows level 3 reads), and at levels 4..7, which physics-only launches
+  // take too, the kernel skips the delay, the servo row and its state at run time (nm::Args::physics_only)
   int level(bool physics_only = false) const {
     return on[kWrench] ? 7 : on[kTorque] ? 6 : on[kServo] ? 5 : on[kGrav] ? 4 : (on[kLat] ? (physics_only ? 2 : 3) : (on[kBody] ? 2 : (on[kFric] ? 1 : 0)));
   }
@@ -238,34 +249,20 @@ struct State {
   template <class real> real* envp(real* base) const { return level() ? base : nullptr; }
 };
 
-// f(std::integral_constant<int, L>{}) for the level: the one place a run-time level becomes a template argument
-template <class F> inline auto with_level(int level, F&& f) {
-  switch (level) {
-    case 4: return f(std::integral_constant<int, 4>{});
-    case 3: return f(std::integral_constant<int, 3>{});
-    case 2: return f(std::integral_constant<int, 2>{});
-    case 1: return f(std::integral_constant<int, 1>{});
-    default: return f(std::integral_constant<int, 0>{});
-  }
+// ---- level dispatch: f(std::integral_constant<int, L>{}) for the level, the one place a run-time level becomes a template argument. Mask
+// holds one bit per level that the caller compiles in: f is instantiated for those alone, and a level outside the mask returns false with
+// nothing run. A level that is no level at all is taken as level 0. The product passes no mask: every level.
+constexpr int kLevels = 8;
+constexpr unsigned kAllLevels = (1u << kLevels) - 1;
+template <unsigned Mask, int L, class F> inline bool at_level(int level, F& f) {
+  if constexpr ((Mask >> L) & 1u)
+    if (level == L) { f(std::integral_constant<int, L>{}); return true; }
+  return false;
 }
-
-// the same for an owner that can launch level 5. with_level keeps the cases it had, so a holder of levels 0..4 alone (tests/emul's rows
-// shim) instantiates what it did and nothing more
-template <class F> inline auto with_level5(int level, F&& f) {
-  if (level == 5) return f(std::integral_constant<int, 5>{});
-  return with_level(level, f);
-}
-
-// and for an owner that can launch level 6; with_level and with_level5 keep their cases
-template <class F> inline auto with_level6(int level, F&& f) {
-  if (level == 6) return f(std::integral_constant<int, 6>{});
-  return with_level5(level, f);
-}
-
-// and for an owner that can launch level 7; with_level, with_level5 and with_level6 keep their cases
-template <class F> inline auto with_level7(int level, F&& f) {
-  if (level == 7) return f(std::integral_constant<int, 7>{});
-  return with_level6(level, f);
+template <unsigned Mask = kAllLevels, class F> inline bool with_level(int level, F&& f) {
+  if (level < 0 || level >= kLevels) level = 0;
+  return at_level<Mask, 7>(level, f) || at_level<Mask, 6>(level, f) || at_level<Mask, 5>(level, f) || at_level<Mask, 4>(level, f) ||
+         at_level<Mask, 3>(level, f) || at_level<Mask, 2>(level, f) || at_level<Mask, 1>(level, f) || at_level<Mask, 0>(level, f);
 }
 
 }  // namespace nmrows

@@ -410,7 +410,7 @@ template <class real> struct Env : nm_env {
       if constexpr (sizeof(real) == 4 && G == 2) HIPCHK(nm_launch_step_lean(N, s, (const nm::Model<float>*)M_dev, a));
 #endif
     } else {
-      nmrows::with_level7(rows.level(physics_only), [&](auto L) {
+      nmrows::with_level(rows.level(physics_only), [&](auto L) {
         hipLaunchKernelGGL((k_env_step<real, G, decltype(L)::value>), dim3((N + G * W - 1) / (G * W)), dim3(64 * W), 0, s, (const nm::Model<real>*)M_dev, a);
       });
       HIPCHK(hipGetLastError());
@@ -923,9 +923,7 @@ template <class real> struct Env : nm_env {
   int rows_alloc(hipStream_t s) {
     if (envp_dev) return 0;
     if (dalloc(&envp_dev, nmrows::wrench_block_reals<real>((size_t)N))) return 1;
-    return envp_write({}, s) || kind_fill<nmrows::BodyKind>(nmrows::body_rows(envp_dev, N), s) || kind_fill<nmrows::GravKind>(nmrows::grav_rows(envp_dev, N), s) ||
-           kind_fill<nmrows::ServoKind>(nmrows::servo_rows(envp_dev, N), s) || kind_fill<nmrows::TorqueKind>(nmrows::torque_rows(envp_dev, N), s) ||
-           kind_fill<nmrows::WrenchKind>(nmrows::wrench_rows(envp_dev, N), s);
+    return envp_write({}, s) || nmrows::for_each_row_kind([&](auto D) { return kind_fill<decltype(D)>(decltype(D)::rows(envp_dev, N), s) != 0; });
   }
   int rows_turn(nmrows::Kind k, bool on) {
     rows.on[k] = on;

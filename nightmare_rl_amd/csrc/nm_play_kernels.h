@@ -64,7 +64,7 @@ __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_play(const nm::Mo
 
 template <int ACT>
 int PlayKernels<ACT>::play(const nm::Model<float>* M_dev, const nm::Args<float>& a, const PlayArgs& P, int level, hipStream_t s) {
-  nmrows::with_level7(level, [&](auto L) { hipLaunchKernelGGL((k_env_play<RefShape, ACT, decltype(L)::value>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, P); });
+  nmrows::with_level(level, [&](auto L) { hipLaunchKernelGGL((k_env_play<RefShape, ACT, decltype(L)::value>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, P); });
   return hipGetLastError() != hipSuccess;
 }
 template struct PlayKernels<NM_PLAY_ACT>;

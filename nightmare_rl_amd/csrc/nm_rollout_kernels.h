@@ -91,7 +91,7 @@ int RollKernels<ACT>::act(const float* wp, const float* bp, const float* stdv, c
 }
 template <int ACT>
 int RollKernels<ACT>::rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, int level, hipStream_t s) {
-  nmrows::with_level7(level, [&](auto L) { hipLaunchKernelGGL((k_env_rollout<RefShape, ACT, decltype(L)::value>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, R); });
+  nmrows::with_level(level, [&](auto L) { hipLaunchKernelGGL((k_env_rollout<RefShape, ACT, decltype(L)::value>), dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, R); });
   return hipGetLastError() != hipSuccess;
 }
 template struct RollKernels<NM_ROLLOUT_ACT>;

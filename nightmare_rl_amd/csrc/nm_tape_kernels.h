@@ -61,7 +61,7 @@ __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_tape(const nm::Mo
 }
 
 int tape_kernel(const nm::Model<float>* M_dev, const nm::Args<float>& a, const TapeArgs& T, int level, hipStream_t s) {
-  nmrows::with_level7(level, [&](auto L) { hipLaunchKernelGGL(k_env_tape<decltype(L)::value>, dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, T); });
+  nmrows::with_level(level, [&](auto L) { hipLaunchKernelGGL(k_env_tape<decltype(L)::value>, dim3((a.N + 1) / 2), dim3(64), 0, s, M_dev, a, T); });
   return hipGetLastError() != hipSuccess;
 }
 

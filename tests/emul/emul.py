@@ -1,63 +1,98 @@
-"""ctypes binding of the host SIMT emulation of the device kernel (tests only; see nm_emul.cpp)."""
+"""ctypes binding of the host SIMT emulation of the device kernel (tests only; see nm_emul.cpp): one source, one library per set of step
+levels compiled in. Layout, defaults, admission and the level a launch takes are the host object's own (nightmare_rl_amd/csrc/nm_env_rows.h)."""
 import ctypes as C
+import functools
 import os
 import subprocess
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-LIB = os.path.join(HERE, "libnm_emul.so")
 SRC = [os.path.join(HERE, "nm_emul.cpp")] + [os.path.join(HERE, "..", "..", "nightmare_rl_amd", "csrc", f)
-                                             for f in ("nm_core.h", "simt.h", "nm_host_model.h", os.path.join("..", "model", "nm_model_data.h"))]
+                                             for f in ("nm_core.h", "simt.h", "nm_host_model.h", "nm_env_rows.h", os.path.join("..", "model", "nm_model_data.h"))]
+# the one set of flags, so every library rounds alike; NM_DEBUG_SOLVER only adds debug words
+FLAGS = ["-O1", "-std=c++17", "-ffp-contract=off", "-Wno-missing-braces", "-DNM_DEBUG_SOLVER"]
+# the level sets the suite uses: a library costs about 25 s of compile time per level. BASE also holds the lean step
+BASE, ROWS = (0,), (0, 1, 2, 3, 4)
+H = 3
+FRIC, BODY, LAT, GRAV = range(4)      # nmrows::Kind, the kinds of levels 1..4
+WIDTH = {FRIC: 3, BODY: 20, GRAV: 8}
 
 
-def build(force=False):
-    if force or not os.path.exists(LIB) or any(os.path.getmtime(s) > os.path.getmtime(LIB) for s in SRC):
-        subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-missing-braces", "-DNM_DEBUG_SOLVER",
-                               "-o", LIB, SRC[0]])
-    return LIB
+def mask(levels):
+    return sum(1 << l for l in set(levels))
 
 
-_lib = None
+def build(levels=BASE, force=False):
+    """libnm_emul_<mask>.so, built under a name of this process's own and renamed: two processes may build the same library at once."""
+    out = os.path.join(HERE, "libnm_emul_%02x.so" % mask(levels))
+    if force or not os.path.exists(out) or any(os.path.getmtime(s) > os.path.getmtime(out) for s in SRC):
+        tmp = "%s.%d.so" % (out[:-3], os.getpid())
+        subprocess.check_call(["g++"] + FLAGS + ["-fPIC", "-shared", "-DNM_EMUL_LEVELS=%du" % mask(levels), "-o", tmp, SRC[0]])
+        os.replace(tmp, out)
+    return out
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        build()
-        L = C.CDLL(LIB)
-        L.emu_create.restype = C.c_void_p
-        L.emu_create.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_int64, C.c_int]
-        L.emu_destroy.argtypes = [C.c_void_p]
-        L.emu_step.argtypes = [C.c_void_p] * 7 + [C.c_int, C.c_int] + [C.c_void_p] * 3
-        L.emu_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.emu_set.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.emu_set_noise.argtypes = [C.c_void_p] * 3
-        L.emu_record.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.emu_configure.argtypes = [C.c_void_p] * 3
-        L.emu_feet.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.emu_hull_cache.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.emu_eplen.argtypes = [C.c_void_p]
-        L.emu_eplen.restype = C.POINTER(C.c_int64)
-        L.emu_together_count.restype = C.c_long
-        _lib = L
-    return _lib
+def build_program(out, levels, extra=(), opt="-O1"):
+    """The shim as a stand-alone program (its own main; e.g. extra=["-fsanitize=address,undefined"]): never loaded into Python. It takes
+    the mode (envp, payload, latency) and the states file; `levels`: the level the mode runs. No -g, and -O0 for
+    instrumented builds: the optimiser's passes over the instrumented lockstep loops take the compiler minutes."""
+    subprocess.check_call(["g++"] + [f for f in FLAGS if f != "-O1"] + [opt, "-DNM_EMUL_MAIN", "-DNM_EMUL_LEVELS=%du" % mask(levels)] + list(extra) + ["-o", out, SRC[0]])
+    return out
+
+
+@functools.lru_cache(None)
+def _load(m):
+    L = C.CDLL(build([l for l in range(8) if m >> l & 1]))
+    vp = C.c_void_p
+    L.emu_create.restype = vp
+    L.emu_create.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_int64, C.c_int, C.c_int]
+    L.emu_step.argtypes = [vp] * 7 + [C.c_int] * 2 + [vp] * 3
+    L.emu_array.argtypes = [vp, C.c_int, C.c_int, vp]
+    for f in (L.emu_set_rows, L.emu_get_rows, L.emu_default_row, L.emu_record):
+        f.argtypes = [vp, C.c_int, vp]
+    for f in (L.emu_destroy, L.emu_layout_agrees, L.emu_refused):
+        f.argtypes = [vp]
+    L.emu_set_noise.argtypes = L.emu_configure.argtypes = [vp] * 3
+    L.emu_feet.argtypes = [vp, C.c_int, vp, vp]
+    L.emu_hull_cache.argtypes = [vp, C.c_int, vp]
+    L.emu_flags.argtypes = [vp] * 4
+    L.emu_hist.argtypes = L.emu_eplen.argtypes = [vp]
+    L.emu_hist.restype = C.POINTER(C.c_float)
+    L.emu_eplen.restype = C.POINTER(C.c_int64)
+    L.emu_together_count.restype = C.c_long
+    L.emu_levels.restype = C.c_uint
+    sizes = np.zeros(6, np.int32)
+    L.emu_sizes(_p(sizes))
+    assert L.emu_levels() == m and sizes.tolist() == [len(REW_NAMES), 256, H] + [WIDTH[k] for k in (FRIC, BODY, GRAV)]
+    return L
+
+
+def lib(levels=BASE):
+    return _load(mask(levels))
 
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-WHAT = dict(qpos=(0, 25), qvel=(1, 24), qwarm=(2, 24), dofpos=(3, 18), dofvel=(4, 18), act=(5, 18), cmd=(6, 3), epsum=(7, 16))
+WHAT = dict(qpos=(0, 25), qvel=(1, 24), qwarm=(2, 24), dofpos=(3, 18), dofvel=(4, 18), act=(5, 18), cmd=(6, 3), epsum=(7, 16),
+            feetair=(8, 6), feetflags=(9, 1), hcache=(10, 8), rngctr=(11, 1))      # the last four: what else a step carries over
+DBG_NTOG, DBG_NCON, DBG_NWARN = 156, 160, 161      # words of an env's debug row (nm_core.h env_debug)
 REW_NAMES = ["action_rate", "ang_vel_xy", "base_height", "body_contact_forces", "default_position", "dof_acc", "dof_vel", "feet_air_time",
              "feet_contact_forces", "lin_vel_z", "orientation", "stand_still", "torques", "tracking_ang_vel", "tracking_lin_vel", "termination"]
 
 
 class EmulEnv:
-    def __init__(self, N, double=False, seed=0, env_off=0, envs_per_wave=2):
-        self.L = lib()
+    """One env object of the shim, from the library of the class's `levels`. lean=True (fp32, two envs per wave, level 0 in the library):
+    wave_step on nm::CfgLean, which refuses (refused()) what the host refuses for the lean kernel."""
+    levels = BASE
+
+    def __init__(self, N, double=False, seed=0, env_off=0, envs_per_wave=2, lean=False):
+        self.L = lib(self.levels)
         self.N = N
-        self.h = self.L.emu_create(N, int(double), seed, env_off, envs_per_wave)
+        self.lean = lean
+        self.h = self.L.emu_create(N, int(double), seed, env_off, envs_per_wave, int(lean))
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -67,14 +102,82 @@ class EmulEnv:
     def get(self, name):
         w, k = WHAT[name]
         out = np.empty((self.N, k))
-        self.L.emu_get(self.h, w, _p(out))
+        self.L.emu_array(self.h, w, 0, _p(out))
         return out
 
     def set(self, name, val):
         w, k = WHAT[name]
-        v = np.ascontiguousarray(val, np.float64).reshape(self.N, k)
-        self.L.emu_set(self.h, w, _p(v))
+        self.L.emu_array(self.h, w, 1, _p(np.ascontiguousarray(val, np.float64).reshape(self.N, k)))
 
+    # ---- the per-env rows. Every setter: rows, or None = off; ValueError where the host's admission refuses them (nothing changes)
+    def _set_rows(self, kind, rows, what):
+        r = None if rows is None else np.ascontiguousarray(rows, np.int32 if kind == LAT else np.float64).reshape((self.N,) if kind == LAT else (self.N, WIDTH[kind]))
+        if self.L.emu_set_rows(self.h, kind, _p(r)):
+            raise ValueError(what + " rows refused")
+
+    def _rows(self, kind):
+        """What the region holds, whatever is on: the defaults of a kind that is off."""
+        out = np.zeros(self.N, np.int32) if kind == LAT else np.zeros((self.N, WIDTH[kind]))
+        assert self.L.emu_get_rows(self.h, kind, _p(out)) == 0
+        return out
+
+    def set_env_params(self, rows=None):
+        """[N,3] rows (mu, p_gain, kv)."""
+        self._set_rows(FRIC, rows, "friction")
+
+    def set_body_params(self, rows=None):
+        """[N,20] body rows (nightmare_rl_amd.model.payload.payload_rows)."""
+        self._set_rows(BODY, rows, "body")
+
+    def set_action_latency(self, substeps=None):
+        """[N] delays in physics substeps."""
+        self._set_rows(LAT, substeps, "latency")
+
+    def set_gravity(self, rows=None):
+        """[N,8] rows (g[3], pad, gravity_vec[3], pad)."""
+        self._set_rows(GRAV, rows, "gravity")
+
+    def default_body_row(self):
+        """The model's own body row in the env's precision: what nm_get_body_params reports while the feature is off."""
+        out = np.zeros(20)
+        assert self.L.emu_default_row(self.h, BODY, _p(out)) == 0
+        return out
+
+    default_row = default_body_row
+
+    def rows(self):
+        """([N,3] friction / gains, [N,20] body rows, [N] delays, [N,8] gravity rows)."""
+        return tuple(self._rows(k) for k in (FRIC, BODY, LAT, GRAV))
+
+    def gravity(self):
+        return self._rows(GRAV)
+
+    def _flags(self):
+        on, lv, c = np.zeros(7, np.int32), np.zeros(2, np.int32), np.zeros(1, np.int32)
+        self.L.emu_flags(self.h, _p(on), _p(lv), _p(c))
+        return on, lv, bool(c[0])
+
+    def state(self, physics_only=False):
+        """(kinds that are on as a string of F, B, L, G; the level a launch takes)."""
+        return "".join(k for i, k in enumerate("FBLG") if self._flags()[0][i]), self.level(physics_only)
+
+    def level(self, physics_only=False):
+        return int(self._flags()[1][int(physics_only)])
+
+    def carries_block(self):
+        """Whether a launch carries the block at all (nm::Args::envp non-null)."""
+        return self._flags()[2]
+
+    def layout_agrees(self):
+        """The device's accessors, the host's and the layout agree over the whole block, and the regions tile it (nm_emul.cpp)."""
+        return bool(self.L.emu_layout_agrees(self.h))
+
+    @property
+    def history(self):
+        """[N,H,18] float32 view of the env's action history, row 0 the latest."""
+        return np.ctypeslib.as_array(self.L.emu_hist(self.h), (self.N, H, 18))
+
+    # ---- configuration, feet, hull cache, noise, the state log
     def configure(self, reward_scales, tibia_contact_mode=1, tibia_max_contact_force=2.0, body_contact_mode=1, body_max_contact_force=2.0,
                   base_height_target=0.1, max_contact_force=10.0):
         sc = np.array([float(reward_scales.get(n, 0.0)) for n in REW_NAMES])
@@ -109,21 +212,31 @@ class EmulEnv:
         self.L.emu_record(self.h, env, _p(out))
         return out[:25], out[25:49], int(out[49])
 
+    def refused(self):
+        """lean only: steps that did not run because the configuration or an optional input is not the lean kernel's."""
+        return self.L.emu_refused(self.h)
+
     @property
     def eplen(self):
         return np.ctypeslib.as_array(self.L.emu_eplen(self.h), (self.N,))
 
+    def together_count(self):
+        return int(self.L.emu_together_count())
+
     def step(self, actions, cmd_u=None, nsub=2, physics_only=False, want_dbg=False):
+        """RuntimeError for a level that the library does not hold."""
         N = self.N
         a = np.ascontiguousarray(actions, np.float32).reshape(N, 18)
         cu = None if cmd_u is None else np.ascontiguousarray(cmd_u, np.float64).reshape(N, 4)
-        obs = np.zeros((N, 66), np.float32)
-        rew = np.zeros(N, np.float32)
-        done = np.zeros(N, np.int64)
-        to = np.zeros(N, np.float32)
+        obs, rew, done, to = np.zeros((N, 66), np.float32), np.zeros(N, np.float32), np.zeros(N, np.int64), np.zeros(N, np.float32)
         dbg = np.zeros((N, 256)) if want_dbg else None
-        ssum = np.zeros(16)
-        scnt = np.zeros(2, np.int32)
-        self.L.emu_step(self.h, _p(a), _p(cu), _p(obs), _p(rew), _p(done), _p(to), nsub, int(physics_only), _p(dbg), _p(ssum), _p(scnt))
+        ssum, scnt = np.zeros(16), np.zeros(2, np.int32)
+        if self.L.emu_step(self.h, _p(a), _p(cu), _p(obs), _p(rew), _p(done), _p(to), nsub, int(physics_only), _p(dbg), _p(ssum), _p(scnt)):
+            raise RuntimeError("the library holds levels of mask %#x only" % self.L.emu_levels())
         self.dbg, self.stat_sum, self.stat_cnt = dbg, ssum, scnt
         return obs, rew, done, to
+
+
+class EmulRows(EmulEnv):
+    """The same env from the library that holds levels 0..4."""
+    levels = ROWS

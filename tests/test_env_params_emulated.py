@@ -1,4 +1,4 @@
-"""Per-env friction and servo gains (nm::Args::envp) in the host emulation of the device source (tests/emul/nm_emul_rows.cpp):
+"""Per-env friction and servo gains (nm::Args::envp) in the host emulation of the device source (tests/emul/nm_emul.cpp):
 the fp64 emulation of a batch that mixes the four parameter sets over its envs against the fp64 fixture of the variant oracles
 (tests/golden/make_envparam_goldens.py), mixed batches against uniform ones bit for bit, identity values against no rows at all, and
 the stand-alone sanitizer build of the shim. The fixture's states are teacher-forced: env e of the mixed batch starts every step from the
@@ -21,9 +21,9 @@ def G():
 
 @pytest.fixture(scope="module")
 def emul():
-    from emul import emul_rows
-    emul_rows.build()
-    return emul_rows
+    from emul import emul as em
+    em.build(em.ROWS)
+    return em
 
 
 def set_of(n, shift=0):
@@ -86,13 +86,13 @@ def test_fp64_emulation_of_a_mixed_batch_matches_the_variant_oracles(G, emul, po
     """Tolerances: the project's fp64 ones (tests/test_gpu_parity.py: obs / reward < 1e-6, state < 1e-8). Two envs per wave is the fp32
     kernel's layout, one env per wave the fp64 kernel's (its own load stage)."""
     sets = set_of(16)
-    tog0 = emul.lib().emur_together_count()
+    tog0 = emul.lib(emul.ROWS).emu_together_count()
     _, (err, flags), serr, ntog, nbig = run_forced(emul, G, pop, sets, double=True, envs_per_wave=envs_per_wave)
     assert flags == 0
     print(f"{pop}: max obs/reward error {err.max():.2e}, max state error {serr:.2e}, two-env passes {ntog}, env-steps above 16 contacts {nbig}")
     assert err.max() < 1e-6 and serr < 1e-8, (err.max(), serr)
     if pop == "stand" and envs_per_wave == 2:      # both envs of a wave in ONE constraint pass, with different friction in its halves
-        assert ntog > 0 and emul.lib().emur_together_count() > tog0
+        assert ntog > 0 and emul.lib(emul.ROWS).emu_together_count() > tog0
         assert (G["sets"][sets[0::2], 0] != G["sets"][sets[1::2], 0]).all()
     if pop == "belly":      # the matrix-free layout ran
         assert nbig >= 4
@@ -162,7 +162,7 @@ def test_standalone_sanitizer_build_of_the_shim_runs_clean(G, emul, tmp_path):
             parts.append(np.asarray(G[f"{pop}_{k}"][sets, t, ev], np.float64).ravel())
     states = tmp_path / "states.bin"
     np.concatenate(parts).tofile(states)
-    exe = emul.build_program(str(tmp_path / "nm_emul_rows_asan"), ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], opt="-O0")
+    exe = emul.build_program(str(tmp_path / "nm_emul_asan"), (1,), ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], opt="-O0")
     r = subprocess.run([exe, "envp", str(states)], capture_output=True, text=True)
     print(r.stdout, r.stderr[-2000:])
     assert r.returncode == 0, (r.stdout, r.stderr[-2000:])

@@ -1,4 +1,4 @@
-"""Per-env gravity vectors (gravity rows, level 4 of the step) in the host emulation of the device source (tests/emul/nm_emul_rows.cpp):
+"""Per-env gravity vectors (gravity rows, level 4 of the step) in the host emulation of the device source (tests/emul/nm_emul.cpp):
 the fp64 emulation of a batch that mixes the four gravity sets over its envs against the fp64 fixture of the variant oracles
 (tests/golden/make_gravity_goldens.py: the unchanged oracle compiled against a header with another gravity; for the observed sets with the
 one line of its env layer that holds upstream's constant replaced), teacher-forced and free-running; the fp32 emulation inside the fp32
@@ -20,9 +20,9 @@ def G():
 
 @pytest.fixture(scope="module")
 def emul():
-    from emul import emul_rows
-    emul_rows.build()
-    return emul_rows
+    from emul import emul as em
+    em.build(em.ROWS)
+    return em
 
 
 def set_of(n, shift=0):
@@ -81,9 +81,9 @@ def test_layout_state_and_admission(G, emul):
     """The gravity region lies behind the histories where the device looks for it and ends the block; while the kind is off it holds the
     defaults; gravity on means level 4, for physics-only launches too; rows the admission refuses change nothing."""
     for double in (False, True):
-        for n in (1, 3, 8):      # n * 55 latency words: odd counts leave the fp64 block a pad word in front of the gravity rows
+        for n in (1, 2, 3, 5, 8):      # n * 55 latency words: odd counts leave the fp64 block a pad word in front of the gravity rows
             env = emul.EmulRows(n, double=double)
-            assert env.device_layout_agrees()
+            assert env.layout_agrees()
             dflt = env.gravity()
             np.testing.assert_array_equal(dflt, np.tile([0, 0, np.float32(-9.81) if not double else -9.81, 0] * 2, (n, 1)))
             assert env.state() == ("", 0)

@@ -1,5 +1,5 @@
 """Per-env actuation latency (nm_set_action_latency, level 3 of the step) in the host emulation of the device source
-(tests/emul/nm_emul_rows.cpp): the fp64 emulation of the fixture's mixed batch - delays 0..6 and 0 over eight envs - against the fp64
+(tests/emul/nm_emul.cpp): the fp64 emulation of the fixture's mixed batch - delays 0..6 and 0 over eight envs - against the fp64
 fixture of the patched oracle (tests/golden/make_latency_goldens.py), delay 0 against no delays at all and the mixed batch against the
 seven uniform ones bit for bit, and the stand-alone sanitizer build of the shim. The fixture's states are teacher-forced: every step
 starts from the recorded state AND the recorded action history."""
@@ -20,9 +20,9 @@ def G():
 
 @pytest.fixture(scope="module")
 def emul():
-    from emul import emul_rows
-    emul_rows.build()
-    return emul_rows
+    from emul import emul as em
+    em.build(em.ROWS)
+    return em
 
 
 def load_step(env, g, pop, t, n=8):
@@ -157,7 +157,7 @@ def test_standalone_sanitizer_build_of_the_shim_runs_clean(G, emul, tmp_path):
             parts.append(np.asarray(G[f"{pop}_{k}"][0], np.float64).ravel())
     states = tmp_path / "states.bin"
     np.concatenate(parts).tofile(states)
-    exe = emul.build_program(str(tmp_path / "nm_emul_rows_asan"), ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], opt="-O0")
+    exe = emul.build_program(str(tmp_path / "nm_emul_asan"), (3,), ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], opt="-O0")
     r = subprocess.run([exe, "latency", str(states)], capture_output=True, text=True)
     print(r.stdout, r.stderr[-2000:])
     assert r.returncode == 0, (r.stdout, r.stderr[-2000:])

@@ -1,5 +1,5 @@
 """The four kinds of per-env rows together - friction / gains, body rows, actuation latency, gravity vectors - in the host emulation of the
-device source (tests/emul/nm_emul_rows.cpp, the one shim with all four regions), whose layout, default rows, on / off state and level
+device source (tests/emul/nm_emul.cpp, the one shim), whose layout, default rows, on / off state and level
 are the host object's own (nightmare_rl_amd/csrc/nm_env_rows.h): the walk of tests/rows_walk.py over every single-kind transition from
 every state of the other three kinds. After every toggle the env that took the walk must be indistinguishable from a fresh env put
 directly into that state: the same rows, the same level for full and physics-only launches, and bit-identical steps. N = 3 at two envs
@@ -16,9 +16,9 @@ ARRAYS = ("qpos", "qvel", "qwarm", "dofpos", "dofvel", "act", "cmd", "epsum", "f
 
 @pytest.fixture(scope="module")
 def emul():
-    from emul import emul_rows
-    emul_rows.build()
-    return emul_rows
+    from emul import emul as em
+    em.build(em.ROWS)
+    return em
 
 
 @pytest.fixture(scope="module")
@@ -40,10 +40,10 @@ def test_the_walk_is_an_eulerian_circuit_of_the_cube():
 
 @pytest.mark.parametrize("double", [False, True], ids=["fp32", "fp64"])
 def test_device_and_host_agree_on_where_the_latency_words_lie(emul, double):
-    """nm_core.h lat_delay / lat_hist / grav_rows_of (the device's way) against nm_env_rows.h (the host's): the history ends inside the
-    block, in front of the gravity rows, and those end the block."""
-    for n in (1, 2, 3, 8, 9):
-        assert emul.EmulRows(n, double=double).device_layout_agrees(), n
+    """Every accessor of nm_core.h (the device's way) against nm_env_rows.h (the host's), over the whole block: the regions tile it in
+    order, with no gap but the pad behind the histories, and the last one ends it."""
+    for n in (1, 2, 3, 5, 8, 9):
+        assert emul.EmulRows(n, double=double).layout_agrees(), n
 
 
 def put(env, values, body_of):

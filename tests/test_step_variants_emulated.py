@@ -1,5 +1,5 @@
 """The step's lean configuration traits (nm::CfgLean: what nm_step_lean.hip compiles the step kernel with) against the generic ones
-(nm::CfgAsk), both as host SIMT emulations of the device source from one library (tests/emul/nm_emul_lean.cpp): over the goldens
+(nm::CfgAsk), both as host SIMT emulations of the device source from one library (tests/emul/nm_emul.cpp): over the goldens
 recorded with the default configuration the two must agree BIT FOR BIT in everything a step returns and leaves behind, and the lean
 one must refuse what the host refuses to launch the lean kernel for."""
 import numpy as np
@@ -13,9 +13,9 @@ KEPT = ("qpos", "qvel", "qwarm", "dofpos", "dofvel", "act", "cmd", "epsum")
 
 @pytest.fixture(scope="module")
 def lean():
-    from emul import emul_lean as el
-    el.build()
-    return el
+    from emul import emul as em
+    em.build(em.BASE)
+    return em
 
 
 @pytest.mark.parametrize("name", DEFAULT_CONFIG)
@@ -25,7 +25,7 @@ def test_lean_traits_equal_generic_traits_over_the_default_config_goldens(lean, 
     g = load_golden(name)
     from test_oracle_env_golden import golden_config
     T, N = g["actions"].shape[:2]
-    envs = [lean.Env(N, lean=True), lean.Env(N, lean=False)]
+    envs = [lean.EmulEnv(N, lean=True), lean.EmulEnv(N, lean=False)]
     for e in envs:
         e.configure(**golden_config(g))         # the golden's own record of the default configuration: the lean env refuses any other
     qpos, qvel, qw = g["init_qpos"], g["init_qvel"], g["init_qacc_warmstart"]
@@ -56,7 +56,7 @@ def test_lean_traits_equal_generic_traits_over_the_default_config_goldens(lean, 
 def test_lean_emulation_refuses_what_the_lean_kernel_is_not_launched_for(lean):
     N = 2
     a = np.zeros((N, 18), np.float32)
-    e = lean.Env(N, lean=True)
+    e = lean.EmulEnv(N, lean=True)
     e.step(a)
     assert e.refused() == 0
     e.step(a, cmd_u=np.full((N, 4), 0.5))
