@@ -89,6 +89,30 @@ int nm_invalidate_time_outs(nm_env* env, void* stream);
  * no rewards/obs/reset (BASELINE config "dynamics+contact kernel only"). */
 int nm_step_physics(nm_env* env, const float* actions_dev, void* stream);
 
+/* The privileged critic row of an asymmetric actor-critic (no reference counterpart: upstream's critic sees the actor's observation,
+ * envs/nightmare_v3_env.py:317-319): out_dev [N, NM_NUM_PRIVILEGED_OBS] float32 (device) =
+ *   cols 0..65    obs_dev [N, 66], the observation the step wrote, copied bit for bit (its noise and clipping included)
+ *   cols 66..88   NM_NUM_PRIVILEGED = 23 values of the env's own physics, read on the device from the per-env rows and the state:
+ *     66     friction           mu
+ *     67 68  gain ratios        p_gain / the config's p_gain, kv / the model's kv
+ *     69     payload mass       base mass - the model's base mass (kg)
+ *     70-72  payload com        base ipos - the model's base ipos (m, base body frame)
+ *     73     latency steps      delay in substeps / decimation
+ *     74-76  gravity            g / 9.81 (the frame of the floor)
+ *     77     servo inv rate     1 / rate limit (+inf, no limit -> 0)
+ *     78     servo d_gain
+ *     79-81  inv torque limit   1 / limit of the coxa, femur, tibia servos (+inf -> 0)
+ *     82-87  wrench             F[3] / (m g), tau[3] / (m g x 1 m), m the MODEL's total mass
+ *     88     base height        qpos[2]
+ *   An env whose rows were never set shows every kind's default: (mu, 1, 1, 0, 0 0 0, 0, 0 0 -1, 0, 0, 0 0 0, 0 x 6).
+ * One launch of one small gather kernel (k_priv_obs) on `stream`, in stream order: called behind nm_step it shows the rows and the state AS
+ * THAT STEP'S LAUNCHES LEFT THEM - the rows the NEXT step runs under: rows re-drawn at an in-step reset (nm_set_reset_rows), a wrench window
+ * that opened or closed, the height after the reset. It reads, never writes, the env: not calling it is the feature off. The K-step
+ * launches (nm_rollout, nm_play, nm_step_tape) do not produce the row. */
+#define NM_NUM_PRIVILEGED 23
+#define NM_NUM_PRIVILEGED_OBS (NM_NUM_OBS + NM_NUM_PRIVILEGED)
+int nm_privileged_obs(nm_env* env, const float* obs_dev, float* out_dev, void* stream);
+
 /* MjData state access (data[i].qpos / qvel / qacc_warmstart, envs/nightmare_v3_env.py:217-221,349-350).
  * HOST double arrays [N,25] [N,24] [N,24]; NULL entries are skipped. Synchronous. */
 int nm_get_state(nm_env* env, double* qpos, double* qvel, double* qacc_warmstart);
@@ -474,12 +498,21 @@ int nm_ppo_sample(const float* net_out_dev, const float* std_dev, const float* o
 int nm_ppo_record(const float* rew_dev, const int64_t* done_dev, const float* time_outs_dev, const float* values_dev, float gamma, int32_t N,
                   float* rewards_store_dev, unsigned char* dones_store_dev, float* cur_ret_dev, float* cur_len_dev, float* fin3_dev,
                   const float* ep_stats_dev, const int32_t* ep_idx_dev, int32_t n_ep, float* ep_acc_dev, void* stream);
+/* nm_ppo_sample for an asymmetric actor-critic: obs_dev [N, n_obs] is the CRITIC's row, whose first n_prefix columns are the actor's
+ * observation. obs_store_dev (if not NULL) receives the rows as before; prefix_store_dev (if not NULL) [N, n_prefix] receives the
+ * prefix - the storage's observations and privileged observations of one step, filled in the same launch. */
+int nm_ppo_sample_prefix(const float* net_out_dev, const float* std_dev, const float* obs_dev, int32_t N, int32_t A, int32_t n_obs, uint64_t seed,
+                         const int64_t* iter_dev, int32_t step, float* actions_dev, float* logp_dev, float* values_dev, float* mu_dev, float* sigma_dev,
+                         float* obs_store_dev, int32_t n_prefix, float* prefix_store_dev, void* stream);
 
 /* ---- PPO mini-batch update (rsl_rl v1.0.2 `algorithms/ppo.py` PPO.update: clipped surrogate + clipped value loss + entropy bonus,
  * adaptive-KL learning rate, gradient-norm clipping, Adam; caller reference train.py:54; hyper-parameters envs/nightmare_v3_config.py:111-128)
  * as two launches per mini-batch (forward/backward; then partial-gradient reduction, gradient-norm clip, KL-adaptive learning rate, Adam and
- * the repacking of the weights in one launch with one grid barrier) with no host synchronisation. actor_dims / critic_dims = {n_obs, h1, ..., n_out} (same depth, same
- * observation, critic output 1, hidden activation ELU - or any NM_ACT_* code with nm_ppo_create_act, reference envs/nightmare_v3_config.py:109).
+ * the repacking of the weights in one launch with one grid barrier) with no host synchronisation. actor_dims / critic_dims = {n_in, h1, ..., n_out} (same depth,
+ * critic output 1, hidden activation ELU - or any NM_ACT_* code with nm_ppo_create_act, reference envs/nightmare_v3_config.py:109).
+ * actor_dims[0] <= critic_dims[0]: the actor reads the FIRST actor_dims[0] columns of the row the critic reads (equal widths: the shared
+ * observation; a wider critic row: observation + privileged columns, nm_privileged_obs). Every `obs` / n_obs below is then the critic's row
+ * and its width. A wider actor is refused. Asymmetric networks run the generic kernels (nm_ppo_has_fast_path = 0).
  * The parameters live in ONE caller-owned flat device vector in the order
  * actor W0 b0 W1 b1 ..., critic W0 b0 ..., std[A] (W row-major [out, in] as torch.nn.Linear); Adam's moments in two more such vectors. */
 typedef struct nm_ppo nm_ppo;

@@ -37,7 +37,8 @@ EXPORTS = ["nm_default_config", "nm_reward_name", "nm_last_error", "nm_create", 
            "nm_set_torque_limit", "nm_get_torque_limit", "nm_draw_torque_limit",
            "nm_set_base_wrench", "nm_get_base_wrench", "nm_set_wrench_schedule", "nm_get_wrench_schedule",
            "nm_set_step_variant", "nm_get_step_variant",
-           "nm_set_reset_rows", "nm_get_reset_rows", "nm_set_reset_row_counts", "nm_get_reset_row_counts", "nm_reset_rows_pick"]
+           "nm_set_reset_rows", "nm_get_reset_rows", "nm_set_reset_row_counts", "nm_get_reset_row_counts", "nm_reset_rows_pick",
+           "nm_privileged_obs", "nm_ppo_sample_prefix"]
 
 
 class NmConfig(C.Structure):
@@ -143,6 +144,8 @@ def _bind(L, full):
     L.nm_reset.argtypes = [vp, vp, C.c_int32, vp, vp, vp]
     L.nm_step.argtypes = [vp] * 9
     L.nm_step_physics.argtypes = [vp, vp, vp]
+    if hasattr(L, "nm_privileged_obs"):
+        L.nm_privileged_obs.argtypes = [vp, vp, vp, vp]
     L.nm_get_state.argtypes = [vp] * 4
     L.nm_set_state.argtypes = [vp] * 4
     L.nm_get_buffers.argtypes = [vp] * 6
@@ -228,6 +231,7 @@ def _bind(L, full):
     L.nm_gae.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_float, vp, vp]
     L.nm_gae_advantages.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_float, vp, vp, vp, C.c_int32, vp]
     L.nm_ppo_sample.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp]
+    L.nm_ppo_sample_prefix.argtypes = [vp, vp, vp, C.c_int32, C.c_int32, C.c_int32, C.c_uint64, vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp]
     L.nm_ppo_record.argtypes = [vp, vp, vp, vp, C.c_float, C.c_int32, vp, vp, vp, vp, vp, vp, vp, C.c_int32, vp, vp]
     L.nm_ppo_create.argtypes = [vp, vp, C.c_int32, C.c_int32, C.POINTER(vp)]
     L.nm_ppo_create_act.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, C.POINTER(vp)]

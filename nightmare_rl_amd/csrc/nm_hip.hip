@@ -12,6 +12,7 @@
 #include "nm_host_model.h"
 #include "nm_env_loop.h"
 #include "nm_env_rows.h"
+#include "nm_priv_obs.h"
 #include "nm_push.h"
 #include "nm_reset_noise.h"
 #include "nm_reset_rows.h"
@@ -224,6 +225,7 @@ struct nm_env {
   virtual int get_reset_rows(int kind, uint32_t* P, void* out_dev, hipStream_t s) = 0;
   virtual int set_reset_row_counts(const uint32_t* counts_host) = 0;
   virtual int get_reset_row_counts(uint32_t* counts_host) = 0;
+  virtual int priv_obs(const float* obs, float* out, hipStream_t s) = 0;
 };
 
 // what puts a K-step launch's nmr::WrenchArgs behind the wrench rows (nm::wrench_args_of), on the launch's stream
@@ -755,6 +757,24 @@ template <class real> struct Env : nm_env {
     HIPCHK(hipGetLastError());
     return 0;
   }
+  // ---- the privileged critic row (nm_priv_obs.h): obs [N, 66] and what the block and the state hold now -> out [N, 89], on `s` behind
+  // whatever it carries; the regions are null while the block does not exist (the kernel then writes the default rows' values)
+  int priv_obs(const float* obs, float* out, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (!obs || !out) return fail("nm_privileged_obs: NULL pointer");
+    nm::PrivObsArgs<real> p{};
+    if (envp_dev) {
+      p.fric = nmrows::fric_rows(envp_dev, N); p.body = nmrows::body_rows(envp_dev, N); p.delay = nmrows::delays(envp_dev, N);
+      p.grav = nmrows::grav_rows(envp_dev, N); p.servo = nmrows::servo_rows(envp_dev, N); p.torque = nmrows::torque_rows(envp_dev, N);
+      p.wrench = nmrows::wrench_rows(envp_dev, N);
+    }
+    p.qpos = A.qpos; p.obs = obs; p.out = out; p.N = N; p.nxcd = A.nxcd; p.nsub = A.nsub;
+    p.mu = (double)M.mu; p.p_gain = (double)M.p_gain; p.kv = (double)M.kv; p.base_mass = (double)M.basec[nm::BP_MASS];
+    for (int j = 0; j < 3; j++) p.base_ipos[j] = (double)M.basec[nm::BP_IPOS + j];
+    p.grav0 = (double)M.grav; p.weight = (double)M.total_mass * (double)M.grav;
+    HIPCHK(nm_launch_priv_obs(p, s));
+    return 0;
+  }
   // the reset-rows arguments of a K-step launch
   nmr::ResetRowsArgs kstep_rrows() {
     nmr::ResetRowsArgs r{};
@@ -1193,6 +1213,7 @@ int nm_step(nm_env* env, const float* actions, int64_t* eplen, float* obs, float
             void* stream) {
   NEED(env); return env->step(actions, eplen, obs, rew, done, time_outs, ep_stats, 0, (hipStream_t)stream);
 }
+int nm_privileged_obs(nm_env* env, const float* obs_dev, float* out_dev, void* stream) { NEED(env); return env->priv_obs(obs_dev, out_dev, (hipStream_t)stream); }
 int nm_step_physics(nm_env* env, const float* actions, void* stream) {
   NEED(env); return env->step(actions, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 1, (hipStream_t)stream);
 }

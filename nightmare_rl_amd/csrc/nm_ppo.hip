@@ -1297,8 +1297,14 @@ extern "C" int nm_ppo_destroy(nm_ppo* h) {
   return 0;
 }
 
-// actor_dims / critic_dims: {n_obs, h1, ..., n_out} with the same number of layers and the same input; critic output 1.
-// Flat parameter order: actor W0 b0 W1 b1 ..., critic W0 b0 ..., std[A] (W row-major [out, in] as torch.nn.Linear).
+// actor_dims / critic_dims: {n_in, h1, ..., n_out} with the same number of layers; critic output 1; actor_dims[0] <= critic_dims[0]: the
+// actor reads the first actor_dims[0] columns of the row the critic reads (an asymmetric actor-critic: the critic's row is the observation
+// followed by privileged columns). The merged layer 0 is as wide as the critic's row; the actor's rows of it hold parameters in their first
+// actor_dims[0] columns and in the bias column only - the columns in between are in no `map` entry, so they are zero in Wm and in every
+// packing, receive no gradient that anyone reads and are never stepped: one more structurally-zero block, like the off-diagonal blocks of
+// the hidden layers.
+// Flat parameter order: actor W0 b0 W1 b1 ..., critic W0 b0 ..., std[A] (W row-major [out, in] as torch.nn.Linear; actor W0 is
+// [h1, actor_dims[0]]).
 extern "C" int nm_ppo_create(const int32_t* actor_dims, const int32_t* critic_dims, int32_t n_layers, int32_t device, nm_ppo** out) {
   return nm_ppo_create_act(actor_dims, critic_dims, n_layers, NM_ACT_ELU, device, out);
 }
@@ -1311,8 +1317,11 @@ extern "C" int nm_ppo_create_act(const int32_t* actor_dims, const int32_t* criti
     return nm_policy_set_error(("nm_ppo_create: unknown activation code " + std::to_string(activation) + " (NM_ACT_*: 0.." +
                                 std::to_string(NM_NUM_ACTIVATIONS - 1) + ")").c_str());
   if (!actor_dims || !critic_dims || n_layers < 1 || n_layers > kL) return nm_policy_set_error("nm_ppo_create: 1..4 layers");
-  if (actor_dims[0] != critic_dims[0] || critic_dims[n_layers] != 1 || actor_dims[n_layers] > kMaxA || actor_dims[n_layers] < 1)
-    return nm_policy_set_error("nm_ppo_create: actor and critic must share the observation, critic output 1, at most 32 actions");
+  if (actor_dims[0] > critic_dims[0])
+    return nm_policy_set_error(("nm_ppo_create: the actor reads a prefix of the critic's row: actor input " + std::to_string(actor_dims[0]) +
+                                " is wider than critic input " + std::to_string(critic_dims[0])).c_str());
+  if (actor_dims[0] < 1 || critic_dims[n_layers] != 1 || actor_dims[n_layers] > kMaxA || actor_dims[n_layers] < 1)
+    return nm_policy_set_error("nm_ppo_create: critic output 1, at most 32 actions");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return nm_policy_set_error("nm_ppo_create: no such HIP device");
   PPO_CHK(hipSetDevice(device));
@@ -1322,7 +1331,7 @@ extern "C" int nm_ppo_create_act(const int32_t* actor_dims, const int32_t* criti
   n.n_layers = n_layers; n.A = h->A; n.act = activation;
   int goff = 0;
   for (int l = 0; l < n_layers; l++) {
-    n.Kr[l] = l == 0 ? actor_dims[0] : actor_dims[l] + critic_dims[l];
+    n.Kr[l] = l == 0 ? critic_dims[0] : actor_dims[l] + critic_dims[l];      // layer 0: the critic's row, whose prefix the actor reads
     n.Or[l] = actor_dims[l + 1] + critic_dims[l + 1];
     n.Kp[l] = (n.Kr[l] + 1 + 15) & ~15;
     n.Op[l] = (n.Or[l] + 15) & ~15;

@@ -100,15 +100,25 @@ extern "C" int nm_gae_advantages(const float* rewards, const float* values, cons
 // step s of the rollout storage - instead of ~25 elementwise launches per step.
 // 16 lanes per env: lane j < ceil(A/2) draws the action pair (2j, 2j+1) (Box-Muller: two normals per pair of uniforms), the
 // log-probability is summed over the 16 lanes, and the block copies its 16 envs' observations as one contiguous run.
+// Asymmetric actor-critic (nm_ppo_sample_prefix): `obs` is the critic's row of n_obs words, whose first n_prefix words are the actor's
+// observation; the block also files that prefix of its rows into prefix_store ([N, n_prefix], contiguous in itself).
 constexpr int kSampleEnvs = 16;    // envs per 256-thread block
 __global__ void __launch_bounds__(256) k_ppo_sample(const float* __restrict__ net_out, const float* __restrict__ std, const float* __restrict__ obs, int N, int A, int n_obs,
                              uint64_t seed, const int64_t* __restrict__ iter_dev, int step, float* __restrict__ actions, float* __restrict__ logp,
-                             float* __restrict__ values, float* __restrict__ mu, float* __restrict__ sigma, float* __restrict__ obs_store) {
+                             float* __restrict__ values, float* __restrict__ mu, float* __restrict__ sigma, float* __restrict__ obs_store,
+                             int n_prefix, float* __restrict__ prefix_store) {
   const int e0 = blockIdx.x * kSampleEnvs;
   if (obs_store) {
     const size_t base = (size_t)e0 * n_obs;
     const int cnt = min(kSampleEnvs, N - e0) * n_obs;
     for (int i = threadIdx.x; i < cnt; i += 256) obs_store[base + i] = obs[base + i];
+  }
+  if (prefix_store) {
+    const int cnt = min(kSampleEnvs, N - e0) * n_prefix;
+    for (int i = threadIdx.x; i < cnt; i += 256) {
+      const int el = i / n_prefix, c = i - el * n_prefix;
+      prefix_store[(size_t)e0 * n_prefix + i] = obs[(size_t)(e0 + el) * n_obs + c];
+    }
   }
   const int e = e0 + (threadIdx.x >> 4), j = 2 * (threadIdx.x & 15);
   float lp = 0.0f;
@@ -131,14 +141,21 @@ __global__ void __launch_bounds__(256) k_ppo_sample(const float* __restrict__ ne
   lp += __shfl_xor(lp, 1); lp += __shfl_xor(lp, 2); lp += __shfl_xor(lp, 4); lp += __shfl_xor(lp, 8);
   if (e < N && j == 0) logp[e] = lp;
 }
+extern "C" int nm_ppo_sample_prefix(const float* net_out, const float* std, const float* obs, int32_t N, int32_t A, int32_t n_obs, uint64_t seed,
+                                    const int64_t* iter_dev, int32_t step, float* actions, float* logp, float* values, float* mu, float* sigma, float* obs_store,
+                                    int32_t n_prefix, float* prefix_store, void* stream) {
+  if (!net_out || !std || !iter_dev || !actions || !logp || !values || !mu || !sigma || N <= 0 || A <= 0 || A > 32) return nm_policy_set_error("nm_ppo_sample: bad argument (1..32 actions)");
+  if ((obs_store || prefix_store) && (!obs || n_obs <= 0)) return nm_policy_set_error("nm_ppo_sample: a store needs the rows it copies");
+  if (prefix_store && (n_prefix <= 0 || n_prefix > n_obs)) return nm_policy_set_error("nm_ppo_sample: the prefix must be 1..n_obs words of a row");
+  hipLaunchKernelGGL(k_ppo_sample, dim3((N + kSampleEnvs - 1) / kSampleEnvs), dim3(256), 0, (hipStream_t)stream, net_out, std, obs, N, A, n_obs, seed, iter_dev, step, actions,
+                     logp, values, mu, sigma, obs_store, n_prefix, prefix_store);
+  if (hipGetLastError() != hipSuccess) return nm_policy_set_error("nm_ppo_sample: launch failed");
+  return 0;
+}
 extern "C" int nm_ppo_sample(const float* net_out, const float* std, const float* obs, int32_t N, int32_t A, int32_t n_obs, uint64_t seed,
                              const int64_t* iter_dev, int32_t step, float* actions, float* logp, float* values, float* mu, float* sigma, float* obs_store,
                              void* stream) {
-  if (!net_out || !std || !iter_dev || !actions || !logp || !values || !mu || !sigma || N <= 0 || A <= 0 || A > 32) return nm_policy_set_error("nm_ppo_sample: bad argument (1..32 actions)");
-  hipLaunchKernelGGL(k_ppo_sample, dim3((N + kSampleEnvs - 1) / kSampleEnvs), dim3(256), 0, (hipStream_t)stream, net_out, std, obs, N, A, n_obs, seed, iter_dev, step, actions,
-                     logp, values, mu, sigma, obs_store);
-  if (hipGetLastError() != hipSuccess) return nm_policy_set_error("nm_ppo_sample: launch failed");
-  return 0;
+  return nm_ppo_sample_prefix(net_out, std, obs, N, A, n_obs, seed, iter_dev, step, actions, logp, values, mu, sigma, obs_store, 0, nullptr, stream);
 }
 
 // PPO.process_env_step + the runner's episode bookkeeping for one step: reward with the time-out bootstrap

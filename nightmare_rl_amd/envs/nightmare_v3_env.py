@@ -45,6 +45,7 @@ import numpy as np
 import torch
 
 from .. import _lib
+from . import privileged
 from .helpers import class_to_dict
 from .nightmare_v3_config import NightmareV3Config
 from .state_log import ROW as _LOG_ROW, StateLog
@@ -522,6 +523,14 @@ class NightmareV3Env:
         self._obs_idx = 0
         self.obs_buf = self._obs_pair[0]
         self.privileged_obs_buf = None
+        # the privileged critic row (optional cfg.env.privileged_obs; envs/privileged.py; no reference line): [N, 66 + 23], gathered on the
+        # device behind every step() and double-buffered like obs_buf. Off: the reference's surface (num_privileged_obs = num_obs, :34;
+        # no privileged observations, :317-319)
+        self.privileged_obs_has_obs_prefix = privileged.enabled(cfg)
+        if self.privileged_obs_has_obs_prefix:
+            self.num_privileged_obs = privileged.NUM_PRIVILEGED_OBS
+            self._priv_pair = torch.zeros((2, N, self.num_privileged_obs), dtype=torch.float32, device=dev)
+            self.privileged_obs_buf = self._priv_pair[0]
         self.rew_buf = torch.zeros(N, dtype=torch.float32, device=dev)
         self.reset_buf = torch.ones(N, dtype=torch.int64, device=dev)
         self.episode_length_buf = torch.zeros(N, dtype=torch.int64, device=dev)  # assignable, like the reference (:88)
@@ -1140,7 +1149,11 @@ class NightmareV3Env:
             self._record_state()
         if "episode" not in self.extras:
             self._fill_extras()
-        return self.obs_buf, None, self.rew_buf, self.reset_buf, self.extras
+        if self.privileged_obs_has_obs_prefix:
+            # behind the step's own launches: the row shows the per-env rows and the state as they left them (nm_privileged_obs)
+            self.privileged_obs_buf = self._priv_pair[self._obs_idx]
+            self._ck(self._L.nm_privileged_obs(self._h, self.obs_buf.data_ptr(), self.privileged_obs_buf.data_ptr(), self._stream()))
+        return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras
 
     # ------------------------------------------------------------------ K steps per launch with the policy in the env's wave
     def _kstep_launch_args(self, a, obs_field, params_flat, seed, iter_dev, ep):
@@ -1389,7 +1402,14 @@ class NightmareV3Env:
         return self.obs_buf
 
     def get_privileged_observations(self):
-        return None
+        """None (the reference, :317-319) unless cfg.env.privileged_obs is on: then the [num_envs, 89] row of the last step() (envs/privileged.py).
+        policy_rollout, policy_play and step_tape evaluate no critic outside their launch and do not refresh it."""
+        return self.privileged_obs_buf
+
+    def privileged_defaults(self):
+        """The model's constants the privileged row is normalised by, in the env's dtype (privileged.model_defaults)."""
+        mu, pg, kv = self._envp_default
+        return privileged.model_defaults(pg, self.cfg.control.decimation, mu, kv, np.float64 if self._real == torch.float64 else np.float32)
 
     def render(self):
         pass

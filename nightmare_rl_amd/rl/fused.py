@@ -8,6 +8,9 @@ train.py:54), writing straight into the rollout storage:
   * other qualifying networks: THREE - the fused actor+critic forward on the matrix cores (`nm_policy_forward` on one merged network:
     the two MLPs side by side, block-diagonal hidden layers), `nm_ppo_sample`, `nm_ppo_record`; the packed copy of the parameters is
     refreshed once per iteration by `refresh()`, outside any captured graph.
+An asymmetric actor-critic - the critic's row is the actor's observation followed by privileged columns (envs/privileged.py) - takes the
+three-launch path: the merged layer 0 is as wide as the critic's row, the actor's rows of it are zero beyond the observation, `act` is fed
+the wide row and files both the observation prefix and the wide row into the storage (`nm_ppo_sample_prefix`).
 
 Used by PPO when the networks qualify (`FusedCollector.supported`: any activation of `_lib.ACTIVATIONS`); otherwise PPO keeps its
 torch path (host tests, deeper or wider networks)."""
@@ -27,9 +30,9 @@ class FusedCollector:
             return False
         a = [m for m in ac.actor if isinstance(m, nn.Linear)]
         c = [m for m in ac.critic if isinstance(m, nn.Linear)]
-        if len(a) != len(c) or len(a) > 4 or a[0].in_features != c[0].in_features or c[-1].out_features != 1 or a[-1].out_features > 32:
-            return False
-        return all(x.out_features + y.out_features <= 256 for x, y in zip(a, c)) and a[0].in_features <= 256
+        if len(a) != len(c) or len(a) > 4 or a[0].in_features > c[0].in_features or c[-1].out_features != 1 or a[-1].out_features > 32:
+            return False      # (the actor reads a prefix of the critic's row: equal widths, or a wider critic)
+        return all(x.out_features + y.out_features <= 256 for x, y in zip(a, c)) and c[0].in_features <= 256
 
     def __init__(self, ac, num_envs, device, seed=0, update=None):
         self.last_values = None          # set by rollout(): the critic's value of the rollout's last observation, for PPO.compute_returns
@@ -42,7 +45,9 @@ class FusedCollector:
         self.a_lin = [m for m in ac.actor if isinstance(m, nn.Linear)]
         self.c_lin = [m for m in ac.critic if isinstance(m, nn.Linear)]
         self.A = self.a_lin[-1].out_features
-        dims = [self.a_lin[0].in_features] + [x.out_features + y.out_features for x, y in zip(self.a_lin, self.c_lin)]
+        self.n_actor_in, self.n_in = self.a_lin[0].in_features, self.c_lin[0].in_features
+        self.asymmetric = self.n_in > self.n_actor_in
+        dims = [self.n_in] + [x.out_features + y.out_features for x, y in zip(self.a_lin, self.c_lin)]
         self.net = PackedMLP(dims, self.device, self.activation)
         self.out = torch.empty(self.N, self.A + 1, device=self.device)
         self.iter_dev = torch.zeros(1, dtype=torch.int64, device=self.device)
@@ -59,18 +64,24 @@ class FusedCollector:
         if self.update is None:
             ws, bs = [], []
             for l, (x, y) in enumerate(zip(self.a_lin, self.c_lin)):
-                ws.append(torch.cat([x.weight, y.weight], 0) if l == 0 else torch.block_diag(x.weight, y.weight))
+                if l == 0:      # the actor's rows read the first n_actor_in columns of the row: zeros beyond them
+                    ws.append(torch.cat([nn.functional.pad(x.weight, (0, self.n_in - self.n_actor_in)), y.weight], 0))
+                else:
+                    ws.append(torch.block_diag(x.weight, y.weight))
                 bs.append(torch.cat([x.bias, y.bias], 0))
             self.net.load(ws, bs)
         self.std = self.ac.std.detach().contiguous()
         self.iter_dev.fill_(int(iteration))
 
     def act(self, obs, storage):
-        """One collection step: actions for `obs`, with the whole transition filed into step `storage.step` of the storage."""
+        """One collection step: actions for `obs`, with the whole transition filed into step `storage.step` of the storage. Asymmetric
+        networks: `obs` is the critic's wide row; its prefix goes to storage.observations, the row to storage.privileged_observations."""
         s = storage.step
         if s >= storage.num_transitions_per_env:
             raise AssertionError("Rollout buffer overflow")
         obs = obs if (obs.dtype == torch.float32 and obs.is_contiguous()) else obs.contiguous().float()
+        if obs.dim() != 2 or obs.shape[0] != self.N or obs.shape[1] != self.n_in:
+            raise ValueError(f"act: rows must be [{self.N}, {self.n_in}], got {tuple(obs.shape)}")
         if self.update is not None:
             stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
             if self._pending is not None:      # the previous step's bookkeeping rides at the head of this launch
@@ -86,6 +97,14 @@ class FusedCollector:
             return storage.actions[s]
         self.net.forward(obs, out=self.out)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        if self.asymmetric:
+            if storage.privileged_observations is None or storage.privileged_observations.shape[-1] != self.n_in or storage.observations.shape[-1] != self.n_actor_in:
+                raise ValueError("act: an asymmetric actor-critic needs a storage with observations and privileged observations of the networks' widths")
+            _lib.check(self._L.nm_ppo_sample_prefix(self.out.data_ptr(), self.std.data_ptr(), obs.data_ptr(), self.N, self.A, self.n_in, self.seed,
+                                                    self.iter_dev.data_ptr(), s, storage.actions[s].data_ptr(), storage.actions_log_prob[s].data_ptr(),
+                                                    storage.values[s].data_ptr(), storage.mu[s].data_ptr(), storage.sigma[s].data_ptr(),
+                                                    storage.privileged_observations[s].data_ptr(), self.n_actor_in, storage.observations[s].data_ptr(), stream))
+            return storage.actions[s]
         _lib.check(self._L.nm_ppo_sample(self.out.data_ptr(), self.std.data_ptr(), obs.data_ptr(), self.N, self.A, obs.shape[1], self.seed,
                                          self.iter_dev.data_ptr(), s, storage.actions[s].data_ptr(), storage.actions_log_prob[s].data_ptr(),
                                          storage.values[s].data_ptr(), storage.mu[s].data_ptr(), storage.sigma[s].data_ptr(),
@@ -170,7 +189,7 @@ class FusedUpdate:
             return False
         a = [m for m in ac.actor if isinstance(m, nn.Linear)]
         c = [m for m in ac.critic if isinstance(m, nn.Linear)]
-        return all(x.out_features + y.out_features + 1 <= 128 for x, y in zip(a, c)) and a[0].in_features + 1 <= 128 and a[-1].out_features <= 32
+        return all(x.out_features + y.out_features + 1 <= 128 for x, y in zip(a, c)) and c[0].in_features + 1 <= 128 and a[-1].out_features <= 32
 
     def __init__(self, ac, optimizer, device, lr):
         self.ac, self.opt, self.device = ac, optimizer, torch.device(device)
@@ -216,7 +235,7 @@ class FusedUpdate:
                     os.environ["NM_PPO_UNFUSED_STEP"] = prev
         self._h = h
         assert self._L.nm_ppo_num_params(h) == n
-        self.A, self.n_obs = a[-1].out_features, a[0].in_features
+        self.A, self.n_obs = a[-1].out_features, c[0].in_features      # the width of the rows a mini-batch is given as: the critic's
         self.has_fast_path = bool(self._L.nm_ppo_has_fast_path(h))
         self.step_count = 0
         self._bind_optimizer_state()

@@ -37,11 +37,18 @@ class PPO:
         self.value_loss_coef, self.entropy_coef = value_loss_coef, entropy_coef
         self.gamma, self.lam, self.max_grad_norm, self.use_clipped_value_loss = gamma, lam, max_grad_norm, use_clipped_value_loss
 
-    def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape):
+    def init_storage(self, num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape, critic_has_obs_prefix=False):
+        """critic_has_obs_prefix: the caller's promise that the first actor_obs_shape[0] columns of every critic row ARE the observation the
+        actor is given in the same step (this repo's env with cfg.env.privileged_obs: `privileged_obs_has_obs_prefix`). Only then do the
+        kernels take an asymmetric actor-critic - they feed the actor the prefix of the critic's row; any other env with privileged
+        observations keeps the torch path."""
         self.storage = RolloutStorage(num_envs, num_transitions_per_env, actor_obs_shape, critic_obs_shape, action_shape, self.device)
-        # collection on the hand-written kernels when the networks qualify and the critic sees the actor's observation
+        # collection on the hand-written kernels when the networks qualify and the critic sees the actor's observation - alone, or as the
+        # prefix of its own row
         self.fused = self.fused_update = None
-        if (critic_obs_shape is None or critic_obs_shape[0] is None) and FusedCollector.supported(self.actor_critic, self.device):
+        symmetric = critic_obs_shape is None or critic_obs_shape[0] is None
+        self.critic_row = not symmetric and bool(critic_has_obs_prefix)      # act() and update() hand the kernels the critic's rows
+        if (symmetric or self.critic_row) and FusedCollector.supported(self.actor_critic, self.device):
             # the update first: it re-homes the parameters in one flat vector, which the collector then reads
             if FusedUpdate.supported(self.actor_critic, self.device):
                 try:
@@ -83,8 +90,8 @@ class PPO:
         self.actor_critic.train()
 
     def act(self, obs, critic_obs):
-        if getattr(self, "fused", None) is not None and critic_obs is obs:
-            return self.fused.act(obs, self.storage)
+        if getattr(self, "fused", None) is not None and (critic_obs is obs or getattr(self, "critic_row", False)):
+            return self.fused.act(critic_obs, self.storage)      # (an asymmetric actor-critic: the wide row, whose prefix the actor reads)
         t = self.transition
         t.actions = self.actor_critic.act(obs).detach()
         t.values = self.actor_critic.evaluate(critic_obs).detach()
@@ -161,7 +168,7 @@ class PPO:
                   desired_kl=self.desired_kl if self.desired_kl is not None else 0.0,
                   adaptive=self.desired_kl is not None and self.schedule == "adaptive", max_grad_norm=self.max_grad_norm)
         fu = self.fused_update
-        if self.device_permutation and self.storage.privileged_observations is None:
+        if self.device_permutation:
             # rsl_rl's mini_batch_generator (indices = randperm; obs[batch_idx] ... per mini-batch) without the permuted copies of the rollout:
             # the permutation comes from one small kernel, and the forward / backward kernel gathers its rows through it
             st = self.storage
@@ -170,7 +177,9 @@ class PPO:
             self._update_count = getattr(self, "_update_count", 0) + 1
             rank = dist.get_rank() if _world() > 1 else 0
             self._perm = fu.permutation(self.num_mini_batches * mb, torch.initial_seed() + 104729 * rank, self._update_count, out=getattr(self, "_perm", None))
-            flat = (st.observations.flatten(0, 1), st.actions.flatten(0, 1), st.values.reshape(-1), st.advantages.reshape(-1), st.returns.reshape(-1),
+            # (with privileged observations on this path the critic's rows are the one row array: the actor reads their prefix)
+            rows_of = st.privileged_observations if st.privileged_observations is not None else st.observations
+            flat = (rows_of.flatten(0, 1), st.actions.flatten(0, 1), st.values.reshape(-1), st.advantages.reshape(-1), st.returns.reshape(-1),
                     st.actions_log_prob.reshape(-1), st.mu.flatten(0, 1), st.sigma.flatten(0, 1))
 
             def epochs():
@@ -217,9 +226,9 @@ class PPO:
             else:
                 epochs()
         else:
-            for (obs, _cobs, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma, _hid, _mask) in \
+            for (_obs, cobs, actions, target_values, advantages, returns, old_logp, old_mu, old_sigma, _hid, _mask) in \
                     self.storage.mini_batch_generator(self.num_mini_batches, self.num_learning_epochs):
-                batch = (obs, actions, target_values.reshape(-1), advantages.reshape(-1), returns.reshape(-1), old_logp.reshape(-1), old_mu, old_sigma)
+                batch = (cobs, actions, target_values.reshape(-1), advantages.reshape(-1), returns.reshape(-1), old_logp.reshape(-1), old_mu, old_sigma)
                 if _dp():
                     fu.minibatch_data_parallel(*batch, hp=hp, world=_world())
                 else:

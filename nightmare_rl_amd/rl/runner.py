@@ -43,7 +43,10 @@ class OnPolicyRunner:
         # the reference env announces num_privileged_obs = num_obs (env.py:34) but hands out no privileged observations (:317-319):
         # the critic then sees the actor's observation, and a second copy of it in the storage would only cost bandwidth
         has_priv = env.get_privileged_observations() is not None
-        self.alg.init_storage(env.num_envs, self.num_steps_per_env, [env.num_obs], [env.num_privileged_obs if has_priv else None], [env.num_actions])
+        # an env whose privileged row starts with the observation it hands the actor (this repo's, cfg.env.privileged_obs) keeps the
+        # hand-written kernels: the critic reads the row, the actor its prefix. Any other privileged layout takes the torch path.
+        self.alg.init_storage(env.num_envs, self.num_steps_per_env, [env.num_obs], [env.num_privileged_obs if has_priv else None], [env.num_actions],
+                              critic_has_obs_prefix=bool(has_priv and getattr(env, "privileged_obs_has_obs_prefix", False)))
         self.log_dir = log_dir
         self.tot_timesteps, self.tot_time, self.current_learning_iteration = 0, 0.0, 0
         self.history = []
@@ -128,11 +131,14 @@ class OnPolicyRunner:
                 alg.end_rollout()
             # The rollout starts from a buffer of its own: a captured graph reads and writes fixed addresses, and an env that
             # alternates its observation buffers ends an odd-length rollout in the buffer the next replay would NOT read first.
-            if on_gpu and priv is None:
+            if on_gpu:
                 if state.get("stage") is None:
                     state["stage"] = torch.empty_like(o)
+                    state["stage_c"] = torch.empty_like(co) if priv is not None else state["stage"]
                 state["stage"].copy_(o)
-                o = co = state["stage"]
+                if priv is not None:
+                    state["stage_c"].copy_(co)
+                o, co = state["stage"], state["stage_c"]
             state["obs"], state["critic_obs"] = o, co
 
         on_gpu = torch.device(dev).type == "cuda"

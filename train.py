@@ -61,6 +61,9 @@ def main():
                     help="every servo delivers at most F N m (MuJoCo's actuator forcerange; default: no limit)")
     ap.add_argument("--resample-on-reset", type=int, nargs="?", const=1024, default=None, metavar="P", dest="resample_on_reset",
                     help="re-draw every per-env range above at every reset of an env, from a pool of P rows per kind (default P: 1024), instead of once")
+    ap.add_argument("--privileged-obs", action="store_true", default=False, dest="privileged_obs",
+                    help="asymmetric actor-critic: the critic also sees every env's drawn physics parameters (friction, gains, payload, latency, "
+                         "gravity, servo, torque limit, wrench) and the base height; the actor keeps the 66 observations (default: off)")
     ap.add_argument("--gpus", type=int, default=None, help="ranks (one per GPU); without torch.distributed.run, train.py starts them itself")
     args = ap.parse_args()
 
@@ -90,7 +93,12 @@ def main():
 
     log_root = "logs/nightmare_v3/"
     log_dir = f"logs/nightmare_v3/{datetime.datetime.now()}/"
-    cfg, train_cfg = NightmareV3Config(), NightmareV3ConfigPPO()
+    cfg_class = NightmareV3Config
+    if args.privileged_obs:
+        class cfg_class(NightmareV3Config):      # the optional attribute NightmareV3Env reads
+            class env(NightmareV3Config.env):
+                privileged_obs = True
+    cfg, train_cfg = cfg_class(), NightmareV3ConfigPPO()
     cfg.viewer.render = args.render
     cfg.viewer.record_states = bool(args.record_states) and rank == 0        # one log: rank 0's env 0
     if args.reset_dof_pos < 0 or args.reset_vel < 0:
