@@ -40,8 +40,9 @@ template <class real> constexpr Layout layout(size_t N) {
   L.total = L.wrench_args + nm::kWrenchArgBytes;
   return L;
 }
-// the block sizes, in reals: the whole block (wrench_block_reals, what the env object allocates) and its prefixes that end in front of
-// the servo, the torque and the wrench regions - all that an owner reads which launches no level above 4, 5 or 6
+// the block sizes, in reals: the whole block (wrench_block_reals, what every owner allocates) and its prefixes that end in front of the
+// servo, the torque and the wrench regions. No owner allocates a prefix any more: the three prefix sizes are named only by the emulation
+// shims of earlier commits and by layout_agrees() (tests/emul), and are to be deleted together with that clause
 template <class real> constexpr size_t block_reals(size_t N) { return layout<real>(N).servo / sizeof(real); }
 template <class real> constexpr size_t servo_block_reals(size_t N) { return layout<real>(N).torque / sizeof(real); }
 template <class real> constexpr size_t torque_block_reals(size_t N) { return layout<real>(N).wrench / sizeof(real); }

@@ -13,10 +13,13 @@ SRC = [os.path.join(HERE, "nm_emul.cpp")] + [os.path.join(HERE, "..", "..", "nig
 # the one set of flags, so every library rounds alike; NM_DEBUG_SOLVER only adds debug words
 FLAGS = ["-O1", "-std=c++17", "-ffp-contract=off", "-Wno-missing-braces", "-DNM_DEBUG_SOLVER"]
 # the level sets the suite uses: a library costs about 25 s of compile time per level. BASE also holds the lean step
-BASE, ROWS = (0,), (0, 1, 2, 3, 4)
+BASE, ROWS, SERVO, TORQUE, WRENCH = (0,), (0, 1, 2, 3, 4), (0, 5), (0, 6), (0, 7)
 H = 3
-FRIC, BODY, LAT, GRAV = range(4)      # nmrows::Kind, the kinds of levels 1..4
-WIDTH = {FRIC: 3, BODY: 20, GRAV: 8}
+FRIC, BODY, LAT, GRAV, SRV, TRQ, WRN = range(7)      # nmrows::Kind, the kinds of levels 1..7
+# row widths and columns as nm_core.h has them: stated here so that shapes exist before a library is loaded, and tied to the header by
+# the assert on emu_sizes in _load, which every library passes before its first use
+WIDTH = {FRIC: 3, BODY: 20, GRAV: 8, SRV: 4, TRQ: 4, WRN: 8}
+EP_KV, SV_RATE, SV_DGAIN, WP_F, WP_T = 2, 0, 1, 0, 4      # columns of a friction / gain, a servo and a wrench row
 
 
 def mask(levels):
@@ -35,7 +38,7 @@ def build(levels=BASE, force=False):
 
 def build_program(out, levels, extra=(), opt="-O1"):
     """The shim as a stand-alone program (its own main; e.g. extra=["-fsanitize=address,undefined"]): never loaded into Python. It takes
-    the mode (envp, payload, latency) and the states file; `levels`: the level the mode runs. No -g, and -O0 for
+    the mode (envp, payload, latency, servo, torque, wrench) and the states file; `levels`: the level the mode runs. No -g, and -O0 for
     instrumented builds: the optimiser's passes over the instrumented lockstep loops take the compiler minutes."""
     subprocess.check_call(["g++"] + [f for f in FLAGS if f != "-O1"] + [opt, "-DNM_EMUL_MAIN", "-DNM_EMUL_LEVELS=%du" % mask(levels)] + list(extra) + ["-o", out, SRC[0]])
     return out
@@ -47,8 +50,9 @@ def _load(m):
     vp = C.c_void_p
     L.emu_create.restype = vp
     L.emu_create.argtypes = [C.c_int, C.c_int, C.c_uint64, C.c_int64, C.c_int, C.c_int]
-    L.emu_step.argtypes = [vp] * 7 + [C.c_int] * 2 + [vp] * 3
+    L.emu_step.argtypes = [vp] * 7 + [C.c_int] * 2 + [vp] * 3 + [C.c_int]
     L.emu_array.argtypes = [vp, C.c_int, C.c_int, vp]
+    L.emu_servo_state.argtypes = [vp, C.c_int, vp]
     for f in (L.emu_set_rows, L.emu_get_rows, L.emu_default_row, L.emu_record):
         f.argtypes = [vp, C.c_int, vp]
     for f in (L.emu_destroy, L.emu_layout_agrees, L.emu_refused):
@@ -62,9 +66,10 @@ def _load(m):
     L.emu_eplen.restype = C.POINTER(C.c_int64)
     L.emu_together_count.restype = C.c_long
     L.emu_levels.restype = C.c_uint
-    sizes = np.zeros(6, np.int32)
+    sizes = np.zeros(14, np.int32)
     L.emu_sizes(_p(sizes))
-    assert L.emu_levels() == m and sizes.tolist() == [len(REW_NAMES), 256, H] + [WIDTH[k] for k in (FRIC, BODY, GRAV)]
+    assert L.emu_levels() == m
+    assert sizes.tolist() == [len(REW_NAMES), 256, H] + [WIDTH[k] for k in (FRIC, BODY, GRAV, SRV, TRQ, WRN)] + [EP_KV, SV_RATE, SV_DGAIN, WP_F, WP_T]
     return L
 
 
@@ -81,6 +86,14 @@ WHAT = dict(qpos=(0, 25), qvel=(1, 24), qwarm=(2, 24), dofpos=(3, 18), dofvel=(4
 DBG_NTOG, DBG_NCON, DBG_NWARN = 156, 160, 161      # words of an env's debug row (nm_core.h env_debug)
 REW_NAMES = ["action_rate", "ang_vel_xy", "base_height", "body_contact_forces", "default_position", "dof_acc", "dof_vel", "feet_air_time",
              "feet_contact_forces", "lin_vel_z", "orientation", "stand_still", "torques", "tracking_ang_vel", "tracking_lin_vel", "termination"]
+
+
+def rows8(wrench, n):
+    """[n,8] rows (F, pad, tau, pad) of [n,6] or [6] wrenches (F, tau)."""
+    w = np.broadcast_to(np.asarray(wrench, np.float64), (n, 6))
+    r = np.zeros((n, WIDTH[WRN]))
+    r[:, WP_F:WP_F + 3], r[:, WP_T:WP_T + 3] = w[:, 0:3], w[:, 3:6]
+    return r
 
 
 class EmulEnv:
@@ -136,6 +149,56 @@ class EmulEnv:
     def set_gravity(self, rows=None):
         """[N,8] rows (g[3], pad, gravity_vec[3], pad)."""
         self._set_rows(GRAV, rows, "gravity")
+
+    set_body_rows = set_body_params
+
+    def set_kv(self, kv=None):
+        """[N] kv (a scalar: every env) in the default friction / gain rows, which turns that kind on; None: the default rows, off."""
+        self.set_env_params()
+        if kv is not None:
+            r = self._rows(FRIC)
+            r[:, EP_KV] = kv
+            self.set_env_params(r)
+
+    def set_servo(self, rate=None, d_gain=None):
+        """[N] rates and d_gains (scalars: every env; one of them None: its default, inf or 0), or both None: off."""
+        r = None if rate is None and d_gain is None else np.zeros((self.N, WIDTH[SRV]))
+        if r is not None:
+            r[:, SV_RATE], r[:, SV_DGAIN] = np.inf if rate is None else rate, 0.0 if d_gain is None else d_gain
+        self._set_rows(SRV, r, "servo")
+
+    def servo(self):
+        """([N] rate, [N] d_gain): what the region holds, the defaults (inf, 0) while the kind is off."""
+        r = self._rows(SRV)
+        return r[:, SV_RATE].copy(), r[:, SV_DGAIN].copy()
+
+    def servo_state(self):
+        """[N,18] the servo's limited targets: state, like the history."""
+        out = np.empty((self.N, 18))
+        self.L.emu_servo_state(self.h, 0, _p(out))
+        return out
+
+    def set_servo_state(self, lim):
+        self.L.emu_servo_state(self.h, 1, _p(np.ascontiguousarray(lim, np.float64).reshape(self.N, 18)))
+
+    def set_torque_limit(self, limit=None):
+        """[N,3] limits (or anything that broadcasts to it), None: off."""
+        r = None if limit is None else np.zeros((self.N, WIDTH[TRQ]))
+        if r is not None:
+            r[:, :3] = limit
+        self._set_rows(TRQ, r, "torque")
+
+    def torque_rows(self):
+        """[N,4]: what the region holds, (inf, inf, inf, 0) while the kind is off."""
+        return self._rows(TRQ)
+
+    def set_base_wrench(self, wrench=None):
+        """[N,6] (F, tau) or anything that broadcasts to it, None: off."""
+        self._set_rows(WRN, None if wrench is None else rows8(wrench, self.N), "wrench")
+
+    def wrench_rows(self):
+        """[N,8]: what the region holds, zero while the kind is off."""
+        return self._rows(WRN)
 
     def default_body_row(self):
         """The model's own body row in the env's precision: what nm_get_body_params reports while the feature is off."""
@@ -223,15 +286,16 @@ class EmulEnv:
     def together_count(self):
         return int(self.L.emu_together_count())
 
-    def step(self, actions, cmd_u=None, nsub=2, physics_only=False, want_dbg=False):
-        """RuntimeError for a level that the library does not hold."""
+    def step(self, actions, cmd_u=None, nsub=2, physics_only=False, want_dbg=False, force_level=-1):
+        """At the level the host chooses from what is on, or default rows through force_level's code. RuntimeError for a level that the
+        library does not hold."""
         N = self.N
         a = np.ascontiguousarray(actions, np.float32).reshape(N, 18)
         cu = None if cmd_u is None else np.ascontiguousarray(cmd_u, np.float64).reshape(N, 4)
         obs, rew, done, to = np.zeros((N, 66), np.float32), np.zeros(N, np.float32), np.zeros(N, np.int64), np.zeros(N, np.float32)
         dbg = np.zeros((N, 256)) if want_dbg else None
         ssum, scnt = np.zeros(16), np.zeros(2, np.int32)
-        if self.L.emu_step(self.h, _p(a), _p(cu), _p(obs), _p(rew), _p(done), _p(to), nsub, int(physics_only), _p(dbg), _p(ssum), _p(scnt)):
+        if self.L.emu_step(self.h, _p(a), _p(cu), _p(obs), _p(rew), _p(done), _p(to), nsub, int(physics_only), _p(dbg), _p(ssum), _p(scnt), force_level):
             raise RuntimeError("the library holds levels of mask %#x only" % self.L.emu_levels())
         self.dbg, self.stat_sum, self.stat_cnt = dbg, ssum, scnt
         return obs, rew, done, to
@@ -240,3 +304,15 @@ class EmulEnv:
 class EmulRows(EmulEnv):
     """The same env from the library that holds levels 0..4."""
     levels = ROWS
+
+
+class EmulServo(EmulEnv):
+    levels = SERVO
+
+
+class EmulTorque(EmulEnv):
+    levels = TORQUE
+
+
+class EmulWrench(EmulEnv):
+    levels = WRENCH

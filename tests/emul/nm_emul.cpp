@@ -10,11 +10,11 @@
 // With level 0 in the mask the fp32, two-envs-per-wave env has a second step on the lean configuration traits (nm::CfgLean, as in the
 // kernel of nm_step_lean.hip), which refuses what the host refuses for the lean kernel (nm::lean_config).
 //
-// The suite builds levels {0} and {0..4} of it; levels 5, 6 and 7 have shims of their own (nm_emul_servo.cpp, nm_emul_torque.cpp,
-// nm_emul_wrench.cpp).
+// The suite builds levels {0}, {0..4}, {0,5}, {0,6} and {0,7} of it: one small library per feature's suite. A library of all eight levels
+// is one -DNM_EMUL_LEVELS=0xffu away and would be the slowest build of the suite.
 //
 // With -DNM_EMUL_MAIN the file is a stand-alone program (for sanitizer builds, which must not be loaded into Python):
-// <program> envp|payload|latency <states file>; see the end of the file.
+// <program> envp|payload|latency|servo|torque|wrench <states file>; see the end of the file.
 #define NM_EMUL 1
 #ifndef NM_EMUL_LEVELS
 #define NM_EMUL_LEVELS 1u
@@ -45,8 +45,9 @@ template <class F> int with_kind(int kind, F&& f) {
 struct Base {
   virtual ~Base() {}
   virtual int step(const float* actions, const double* cmd_u, float* obs, float* rew, int64_t* done, float* to, int nsub, int physics_only,
-                   double* dbg, double* stat_sum, int* stat_cnt) = 0;
+                   double* dbg, double* stat_sum, int* stat_cnt, int force_level) = 0;
   virtual void array(int what, int set, double* io) = 0;
+  virtual void servo_state(int set, double* io) = 0;
   virtual int set_rows(int kind, const void* in) = 0;
   virtual int get_rows(int kind, void* out) = 0;
   virtual int default_row(int kind, double* out) = 0;
@@ -113,6 +114,9 @@ template <class real> struct Emu : Base {
     with_array(what, [&](auto& a) {
       for (size_t i = 0; i < a.size(); i++) { if (set) a[i] = (typename std::decay_t<decltype(a)>::value_type)io[i]; else io[i] = (double)a[i]; }
     });
+  }
+  void servo_state(int set, double* io) override {      // [N,kNU] limited targets: state, like the history in front of them
+    for (int i = 0; i < N * nm::kNU; i++) { if (set) lim()[i] = (real)io[i]; else io[i] = (double)lim()[i]; }
   }
   void hull_cache(int set, int* hc) override {
     for (size_t i = 0; i < hcache.size(); i++) { if (set) hcache[i] = hc[i]; else hc[i] = hcache[i]; }
@@ -220,7 +224,9 @@ template <class real> struct Emu : Base {
     return device && host && tiles && prefixes && L.total == envp.size() * R;
   }
 
-  // ---- stepping, at the level that is the host's own choice from what is on. Non-zero, with nothing run, for a level that is not compiled in.
+  // ---- stepping, at the level that is the host's own choice from what is on (force_level -1), or at force_level: whatever is on, the
+  // block holds every other kind's defaults, so a forced level runs default rows through that level's code. Non-zero, with nothing run,
+  // for a level that is not compiled in.
   template <int GG> bool waves(const nm::Args<real>& A, int level) {
     static thread_local typename nm::ShWSel<real, GG, kTop>::type sh;
     nm::ShW<real, GG>& w = nm::ShWSel<real, GG, kTop>::images(sh);
@@ -239,18 +245,18 @@ template <class real> struct Emu : Base {
     return A;
   }
   int step(const float* actions, const double* cmd_u, float* obs, float* rew, int64_t* done, float* to, int nsub, int physics_only,
-           double* dbg, double* stat_sum, int* stat_cnt) override {
+           double* dbg, double* stat_sum, int* stat_cnt, int force_level) override {
     std::vector<real> cu, dbgr(dbg ? (size_t)N * nm::kDbgN : 0, 0), ssum(nm::kNREW, 0);
     int scnt[4] = {0, 0, 0, 0};
     nm::Args<real> A = args(actions, obs, rew, done, to, nsub, physics_only, ssum.data(), scnt);
     if (lean) {
-      if (cmd_u || dbg || !nvec.empty() || rec_env >= 0 || rows.level() || !step_lean(A)) { refused++; return 0; }
+      if (cmd_u || dbg || !nvec.empty() || rec_env >= 0 || rows.level() || force_level > 0 || !step_lean(A)) { refused++; return 0; }
     } else {
-      const int level = rows.level(physics_only != 0);
+      const int level = force_level >= 0 ? force_level : rows.level(physics_only != 0);
       if (cmd_u) { cu.resize((size_t)N * 4); for (size_t i = 0; i < cu.size(); i++) cu[i] = (real)cmd_u[i]; }
       A.cmd_u = cmd_u ? cu.data() : nullptr;
       A.dbg = dbg ? dbgr.data() : nullptr;
-      A.envp = level ? envp.data() : nullptr;      // as nmrows::State::envp: level 0 never looks
+      A.envp = level ? envp.data() : nullptr;      // as nmrows::State::envp, and for a forced level too: level 0 never looks
       if (!physics_only) {
         A.noise_vec = nvec.empty() ? nullptr : nvec.data(); A.noise_u = nu.empty() ? nullptr : nu.data(); A.noise_step = nstep;
         A.rec = rec_env >= 0 ? rec.data() : nullptr; A.rec_env = rec_env;
@@ -285,10 +291,11 @@ void* emu_create(int N, int use_double, uint64_t seed, int64_t env_off, int envs
 }
 void emu_destroy(void* h) { delete (Base*)h; }
 int emu_step(void* h, const float* actions, const double* cmd_u, float* obs, float* rew, int64_t* done, float* to, int nsub, int physics_only,
-             double* dbg, double* stat_sum, int* stat_cnt) {
-  return ((Base*)h)->step(actions, cmd_u, obs, rew, done, to, nsub, physics_only, dbg, stat_sum, stat_cnt);
+             double* dbg, double* stat_sum, int* stat_cnt, int force_level) {
+  return ((Base*)h)->step(actions, cmd_u, obs, rew, done, to, nsub, physics_only, dbg, stat_sum, stat_cnt, force_level);
 }
 void emu_array(void* h, int what, int set, double* io) { ((Base*)h)->array(what, set, io); }
+void emu_servo_state(void* h, int set, double* io) { ((Base*)h)->servo_state(set, io); }
 int emu_set_rows(void* h, int kind, const void* in) { return ((Base*)h)->set_rows(kind, in); }
 int emu_get_rows(void* h, int kind, void* out) { return ((Base*)h)->get_rows(kind, out); }
 int emu_default_row(void* h, int kind, double* out) { return ((Base*)h)->default_row(kind, out); }
@@ -304,32 +311,41 @@ void emu_hull_cache(void* h, int set, int* hc) { ((Base*)h)->hull_cache(set, hc)
 int emu_refused(void* h) { return ((Base*)h)->refused_steps(); }
 long emu_together_count() { return nm::nm_emul_together(); }
 unsigned emu_levels() { return kMask; }
-// (kNREW, kDbgN, kLatH, the 3 words of kEnvP in use, kBodyP, kGravP): what the binding's shapes assume
-void emu_sizes(int* out6) {
-  const int s[6] = {nm::kNREW, nm::kDbgN, nm::kLatH, 3, nm::kBodyP, nm::kGravP};
-  std::memcpy(out6, s, sizeof s);
+// what the binding's shapes and columns assume: kNREW, kDbgN, kLatH; the widths of the friction (the 3 words of kEnvP in use), body,
+// gravity, servo, torque and wrench rows; EP_KV, SV_RATE, SV_DGAIN, WP_F, WP_T
+void emu_sizes(int* out14) {
+  const int s[14] = {nm::kNREW,   nm::kDbgN,    nm::kLatH, 3,           nm::kBodyP,   nm::kGravP, nm::kServoP,
+                     nm::kTorqueP, nm::kWrenchP, nm::EP_KV, nm::SV_RATE, nm::SV_DGAIN, nm::WP_F,   nm::WP_T};
+  std::memcpy(out14, s, sizeof s);
 }
 }
 #else
-// ---- the stand-alone program:  <program> envp|payload|latency <states file>
+// ---- the stand-alone program:  <program> envp|payload|latency|servo|torque|wrench <states file>
 // It steps one mixed batch of N = 8 envs per population of that feature's fixture, two envs per wave, fp32 and fp64, from start states it
 // reads from the file, and prints what ran. Exit status 0 = every result finite, the two-env constraint pass taken, and the mode's own
-// condition: the matrix-free layout taken (envp, payload), every history shifted (latency). The file holds raw doubles, which the
-// feature's test writes from its fixture: `head` doubles first (payload: the body rows of the four payload sets), then per population
-// the state record
+// condition: the matrix-free layout taken (envp, payload), every history shifted (latency), no limited target moved faster than its
+// env's rate (servo). The file holds raw doubles, which the feature's test writes from its fixture: `head` doubles first (payload: the
+// body rows of the four payload sets), then per population the state record
 //   qpos[N*25] qvel[N*24] qacc_warmstart[N*24] dof_pos[N*18] dof_vel[N*18] previous actions[N*18] commands[N*3] actions[N*18]
-// and behind it `tail` doubles per env: latency history[N*3*18]. Build it with the mode's level alone in NM_EMUL_LEVELS.
+// and behind it `tail` doubles per env: latency history[N*3*18]; servo history[N*3*18] limited targets[N*18]; torque limits[N*3] kv[N];
+// wrench wrench rows[N*8] body rows[N*20]. Build it with the mode's level alone in NM_EMUL_LEVELS.
 constexpr int kN = 8, kState = 25 + 24 + 24 + 18 + 18 + 18 + 3 + 18, kHist = nm::kLatH * 18;
-struct Mode { const char* name; int level, pops, head, tail; uint64_t seed; const char* also; };
-const Mode kModes[3] = {{"envp", 1, 3, 0, 0, 3, "envs in the matrix-free layout"},
+struct Mode { const char* name; int level, pops, head, tail; uint64_t seed; const char* also; };      // also: what the mode counts besides, null = nothing
+const Mode kModes[6] = {{"envp", 1, 3, 0, 0, 3, "envs in the matrix-free layout"},
                         {"payload", 2, 3, 4 * nm::kBodyP, 0, 3, "envs in the matrix-free layout"},
-                        {"latency", 3, 2, 0, kHist, 3, "histories not shifted"}};
+                        {"latency", 3, 2, 0, kHist, 3, "histories not shifted"},
+                        {"servo", 5, 2, 0, kHist + 18, 5, "limited targets that moved faster than their rate"},
+                        {"torque", 6, 2, 0, 3 + 1, 5, nullptr},
+                        {"wrench", 7, 2, 0, nm::kWrenchP + nm::kBodyP, 5, nullptr}};
 
 template <class real> int run(const char* tag, const Mode& m, const std::vector<double>& file) {
   const int N = kN;
   static const double sets[4][3] = {{1.0, 20.0, 0.8}, {0.4, 20.0, 0.5}, {1.6, 14.0, 0.8}, {0.7, 26.0, 1.1}};
+  const double inf = INFINITY;
+  const double servo[16] = {inf, 0, 0.03, 0, 0.02, 0.05, 0.08, 0.05, 0.04, 0.2, inf, 0.2, 0.02, 0, 0.08, 0.1};      // (rate, d_gain) per env
   const int delays[8] = {0, 1, 2, 3, 4, 5, 6, 0};
   std::vector<float> a((size_t)N * 18), obs((size_t)N * 66), rew(N), to(N), h0((size_t)N * kHist);
+  std::vector<real> l0((size_t)N * 18);
   std::vector<int64_t> done(N);
   std::vector<double> dbg((size_t)N * nm::kDbgN);
   int bad = 0, also = 0;
@@ -340,21 +356,37 @@ template <class real> int run(const char* tag, const Mode& m, const std::vector<
     auto take = [&](std::vector<real>& dst) { for (auto& x : dst) x = (real)*p++; };
     take(e.qpos); take(e.qvel); take(e.qwarm); take(e.dofpos); take(e.dofvel); take(e.act); take(e.cmd);
     for (auto& x : a) x = (float)*p++;
-    // the mode's rows: N rows of W doubles, zero but for what put(env, column) gives
+    // the mode's rows: N rows of W doubles, zero but for what put(env, row) gives
     int refused = 0;
     auto rows_of = [&](int kind, int W, auto put) {
       std::vector<double> r((size_t)N * W, 0);
       for (int i = 0; i < N; i++) put(i, r.data() + (size_t)i * W);
       refused |= e.set_rows(kind, r.data());
     };
+    auto file_rows = [&](int kind, int W, int w) {      // the file's next N rows of w doubles, in front of rows of W
+      rows_of(kind, W, [&](int i, double* r) { std::memcpy(r, p + (size_t)i * w, sizeof(double) * w); });
+      p += (size_t)N * w;
+    };
     if (m.level == 1) rows_of(nmrows::kFric, 3, [&](int i, double* r) { for (int k = 0; k < 3; k++) r[k] = sets[(i + i / 4) % 4][k]; });      // neighbours in a wave always hold different sets
     if (m.level == 2) rows_of(nmrows::kBody, nm::kBodyP, [&](int i, double* r) { std::memcpy(r, file.data() + ((i + i / 4) % 4) * nm::kBodyP, sizeof(double) * nm::kBodyP); });
-    if (m.level == 3) {
+    if (m.level == 3 || m.level == 5) {
       e.set_latency(delays);
       for (auto& x : h0) x = (float)*p++;
       std::memcpy(e.hist(), h0.data(), sizeof(float) * h0.size());
     }
-    if (refused || e.step(a.data(), nullptr, obs.data(), rew.data(), done.data(), to.data(), 2, 0, dbg.data(), nullptr, nullptr)) return 1;
+    if (m.level == 5) {
+      rows_of(nmrows::kServo, nm::kServoP, [&](int i, double* r) { r[nm::SV_RATE] = servo[i * 2]; r[nm::SV_DGAIN] = servo[i * 2 + 1]; });
+      take(l0);
+      std::memcpy(e.lim(), l0.data(), l0.size() * sizeof(real));
+    }
+    if (m.level == 6) {      // the limits, and the default friction / gain rows with the file's kv
+      file_rows(nmrows::kTorque, nm::kTorqueP, 3);
+      real f[3];
+      nmrows::fric_default(e.M, f);
+      rows_of(nmrows::kFric, 3, [&](int i, double* r) { for (int k = 0; k < 3; k++) r[k] = k == nm::EP_KV ? p[i] : (double)f[k]; });
+    }
+    if (m.level == 7) { file_rows(nmrows::kWrench, nm::kWrenchP, nm::kWrenchP); file_rows(nmrows::kBody, nm::kBodyP, nm::kBodyP); }
+    if (refused || e.step(a.data(), nullptr, obs.data(), rew.data(), done.data(), to.data(), 2, 0, dbg.data(), nullptr, nullptr, -1)) return 1;
     for (float x : obs) bad += !std::isfinite(x);
     for (float x : rew) bad += !std::isfinite(x);
     for (real x : e.qpos) bad += !std::isfinite((double)x);
@@ -363,11 +395,16 @@ template <class real> int run(const char* tag, const Mode& m, const std::vector<
       if (m.level <= 2) also += dbg[(size_t)i * nm::kDbgN + 160] > nm::kMaxCon;
       if (m.level == 3)      // rows 1 and 2 of the new history are rows 0 and 1 of the old one
         also += std::memcmp(e.hist() + i * kHist + 18, h0.data() + i * kHist, sizeof(float) * 36) != 0;
+      if (m.level == 5)      // a finite rate bounds the move of every limited target (1e-6: float32 roundings of a target below 1 rad)
+        for (int j = 0; j < 18; j++)
+          also += std::isfinite(servo[i * 2]) && std::fabs((double)e.lim()[i * 18 + j] - (double)l0[i * 18 + j]) > servo[i * 2] + 1e-6;
     }
   }
   const long tog = nm::nm_emul_together() - tog0;
-  std::printf("%s: non-finite values %d, two-env constraint passes %ld, %s %d\n", tag, bad, tog, m.also, also);
-  return bad != 0 || tog == 0 || (m.level <= 2 ? also == 0 : also != 0);
+  std::printf("%s: non-finite values %d, two-env constraint passes %ld", tag, bad, tog);
+  if (m.also) std::printf(", %s %d", m.also, also);
+  std::printf("\n");
+  return bad != 0 || tog == 0 || (m.also && (m.level <= 2 ? also == 0 : also != 0));
 }
 int main(int argc, char** argv) {
   const Mode* m = nullptr;
@@ -375,7 +412,7 @@ int main(int argc, char** argv) {
   FILE* f = m && argc > 2 ? std::fopen(argv[2], "rb") : nullptr;
   const size_t want = m ? m->head + (size_t)m->pops * kN * (kState + m->tail) : 0;
   std::vector<double> file(want);
-  if (!f || std::fread(file.data(), sizeof(double), want, f) != want) { std::fprintf(stderr, "usage: %s envp|payload|latency <states file>\n", argv[0]); return 2; }
+  if (!f || std::fread(file.data(), sizeof(double), want, f) != want) { std::fprintf(stderr, "usage: %s envp|payload|latency|servo|torque|wrench <states file>\n", argv[0]); return 2; }
   std::fclose(f);
   const int r32 = run<float>("fp32", *m, file), r64 = run<double>("fp64", *m, file);
   return r32 | r64;

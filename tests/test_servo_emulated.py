@@ -1,4 +1,4 @@
-"""The servo target model (nm_set_servo, level 5 of the step) in the host emulation of the device source (tests/emul/nm_emul_servo.cpp,
+"""The servo target model (nm_set_servo, level 5 of the step) in the host emulation of the device source (tests/emul/nm_emul.cpp,
 levels 0 and 5 only): the fp64 emulation of the fixture's mixed batch against the fp64 fixture of the patched oracle
 (tests/golden/make_servo_goldens.py), alone (S) and behind the delays 0..6, 0 (SL), teacher-forced and free-running, with the limited
 targets after every step; the fp32 emulation inside the project's fp32 bounds; default rows at level 5 against level 0 under ==; the mixed
@@ -21,9 +21,9 @@ def G():
 
 @pytest.fixture(scope="module")
 def emul():
-    from emul import emul_servo
-    emul_servo.build()
-    return emul_servo
+    from emul import emul as em
+    em.build(em.SERVO)
+    return em
 
 
 def delays_of(g, rec):
@@ -76,7 +76,7 @@ def test_layout_and_level(emul):
     for n in (1, 7, 8):
         for double in (False, True):
             env = emul.EmulServo(n, double=double)
-            assert env.device_layout_agrees(), n
+            assert env.layout_agrees(), n
             assert env.level() == 0 and env.level(True) == 0
             rate, d_gain = env.servo()
             assert np.isinf(rate).all() and (d_gain == 0).all()      # the region holds the defaults while the kind is off
@@ -142,10 +142,11 @@ def test_mixed_batch_equals_uniform_batches_bit_for_bit(G, emul, pop, double):
     """Every env is independent: env e of the mixed batch (the fixture's rows under the fixture's delays) equals env e of the batch in which
     EVERY env holds e's row and delay."""
     rate, d_gain, delays, steps = G["rate"], G["d_gain"], G["delays"], 3
-    t0 = emul.lib().emus_together_count()
+    env = emul.EmulServo(1)
+    t0 = env.together_count()
     mixed, _, _, _ = run(emul, G, "SL", pop, rate, d_gain, double=double, steps=steps)
     if pop == "stand" and not double:
-        assert emul.lib().emus_together_count() > t0      # both envs of a wave in ONE constraint pass under different rows
+        assert env.together_count() > t0      # both envs of a wave in ONE constraint pass under different rows
     for e in range(8):
         uni, _, _, _ = run(emul, G, "SL", pop, np.full(8, rate[e]), np.full(8, d_gain[e]), double=double, steps=steps, delays=np.full(8, delays[e], np.int32))
         same(mixed, uni, slice(e, e + 1))
@@ -188,8 +189,8 @@ def test_standalone_sanitizer_build_of_the_shim_runs_clean(G, emul, tmp_path):
             parts.append(np.asarray(G[f"SL_{pop}_{k}"][0], np.float64).ravel())
     states = tmp_path / "states.bin"
     np.concatenate(parts).tofile(states)
-    exe = emul.build_program(str(tmp_path / "nm_emul_servo_asan"), ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], opt="-O0")
-    r = subprocess.run([exe, str(states)], capture_output=True, text=True)
+    exe = emul.build_program(str(tmp_path / "nm_emul_asan"), (5,), ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], opt="-O0")
+    r = subprocess.run([exe, "servo", str(states)], capture_output=True, text=True)
     print(r.stdout, r.stderr[-2000:])
     assert r.returncode == 0, (r.stdout, r.stderr[-2000:])
     assert "fp32" in r.stdout and "fp64" in r.stdout

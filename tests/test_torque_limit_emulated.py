@@ -1,5 +1,5 @@
 """The servo torque limit (nm_set_torque_limit, level 6 of the step) in the host emulation of the device source
-(tests/emul/nm_emul_torque.cpp, levels 0 and 6 only): the fp64 emulation of the mixed batch (env e under set e % 5 of the fixture, its own
+(tests/emul/nm_emul.cpp, levels 0 and 6 only): the fp64 emulation of the mixed batch (env e under set e % 5 of the fixture, its own
 kv included) against the fp64 fixture of the patched oracle (tests/golden/make_torque_goldens.py), teacher-forced and free-running, one
 and two envs per wave; the fp32 emulation inside the project's fp32 bounds; default rows at level 6 against level 0 under ==; a limit
 that is never reached against +inf; the mixed batch against the uniform ones bit for bit; the sensitivity of the comparison; a
@@ -20,9 +20,9 @@ def G():
 
 @pytest.fixture(scope="module")
 def emul():
-    from emul import emul_torque
-    emul_torque.build()
-    return emul_torque
+    from emul import emul as em
+    em.build(em.TORQUE)
+    return em
 
 
 def load_step(env, g, pop, t, state=True):
@@ -65,7 +65,7 @@ def test_layout_and_level(emul):
     for n in (1, 7, 8):
         for double in (False, True):
             env = emul.EmulTorque(n, double=double)
-            assert env.device_layout_agrees(), n
+            assert env.layout_agrees(), n
             assert env.level() == 0 and env.level(True) == 0
             np.testing.assert_array_equal(env.torque_rows(), np.tile([np.inf, np.inf, np.inf, 0.0], (n, 1)))      # defaults while the kind is off
             env.set_torque_limit([3.2, 1.0, 2.0])
@@ -129,10 +129,11 @@ def test_a_limit_that_is_never_reached_equals_no_limit(G, emul, double):
 def test_mixed_batch_equals_uniform_batches_bit_for_bit(G, emul, pop, double):
     """Every env is independent: env e of the mixed batch equals env e of the batch in which EVERY env holds e's row and kv."""
     limits, kv = mixed_rows(G)
-    t0 = emul.lib().emut_together_count()
+    env = emul.EmulTorque(1)
+    t0 = env.together_count()
     mx, _, _ = run(emul, G, pop, limits, kv, double=double, steps=3)
     if pop == "stand" and not double:
-        assert emul.lib().emut_together_count() > t0      # both envs of a wave in ONE constraint pass under different rows
+        assert env.together_count() > t0      # both envs of a wave in ONE constraint pass under different rows
     for e in range(8):
         uni, _, _ = run(emul, G, pop, np.tile(limits[e], (8, 1)), np.full(8, kv[e]), double=double, steps=3)
         same(mx, uni, slice(e, e + 1))
@@ -180,8 +181,8 @@ def test_standalone_sanitizer_build_of_the_shim_runs_clean(G, emul, tmp_path):
         parts += [limits.ravel(), kv.ravel()]
     states = tmp_path / "states.bin"
     np.concatenate(parts).tofile(states)
-    exe = emul.build_program(str(tmp_path / "nm_emul_torque_asan"), ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], opt="-O0")
-    r = subprocess.run([exe, str(states)], capture_output=True, text=True)
+    exe = emul.build_program(str(tmp_path / "nm_emul_asan"), (6,), ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], opt="-O0")
+    r = subprocess.run([exe, "torque", str(states)], capture_output=True, text=True)
     print(r.stdout, r.stderr[-2000:])
     assert r.returncode == 0, (r.stdout, r.stderr[-2000:])
     assert "fp32" in r.stdout and "fp64" in r.stdout

@@ -1,5 +1,5 @@
 """The external wrench on the base (nm_set_base_wrench, level 7 of the step) in the host emulation of the device source
-(tests/emul/nm_emul_wrench.cpp, levels 0 and 7 only): the fp64 emulation of the mixed batch (env e under set e % 5 of the fixture, set 3
+(tests/emul/nm_emul.cpp, levels 0 and 7 only): the fp64 emulation of the mixed batch (env e under set e % 5 of the fixture, set 3
 with its payload's body row) against the fp64 fixture of the patched oracle (tests/golden/make_wrench_goldens.py), teacher-forced and
 free-running, one and two envs per wave; the fp32 emulation inside the project's fp32 bounds; zero rows at level 7 against level 0 under
 ==; the device's layout functions against nm_env_rows.h; N = 7 and its padded half; the mixed batch against the uniform ones bit for bit;
@@ -20,9 +20,9 @@ def G():
 
 @pytest.fixture(scope="module")
 def emul():
-    from emul import emul_wrench
-    emul_wrench.build()
-    return emul_wrench
+    from emul import emul as em
+    em.build(em.WRENCH)
+    return em
 
 
 def body_rows(g, n=8):
@@ -73,7 +73,7 @@ def test_layout_and_level(emul):
     for n in (1, 7, 8):
         for double in (False, True):
             env = emul.EmulWrench(n, double=double)
-            assert env.device_layout_agrees(), n      # nm::wrench_rows_of / wrench_args_of against nm_env_rows.h
+            assert env.layout_agrees(), n      # nm::wrench_rows_of / wrench_args_of against nm_env_rows.h
             assert env.level() == 0 and env.level(True) == 0
             np.testing.assert_array_equal(env.wrench_rows(), np.zeros((n, 8)))      # defaults while the kind is off
             env.set_base_wrench([3.0, -2.0, 4.0, 0.3, -0.2, 0.25])
@@ -141,10 +141,11 @@ def test_mixed_batch_equals_uniform_batches_bit_for_bit(G, emul, pop, double):
     """Every env is independent: env e of the mixed batch equals env e of the batch in which EVERY env holds e's wrench and body row."""
     from nightmare_rl_amd.model import payload as pl
     w = mixed_wrench(G)
-    t0 = emul.lib().emux_together_count()
+    env = emul.EmulWrench(1)
+    t0 = env.together_count()
     mx, _, _ = run(emul, G, pop, w, double=double, steps=3)
     if pop == "stand" and not double:
-        assert emul.lib().emux_together_count() > t0      # both envs of a wave in ONE constraint pass under different rows
+        assert env.together_count() > t0      # both envs of a wave in ONE constraint pass under different rows
     dm, r = mixed_payload(G)
     for e in range(5):      # envs 0..4 hold the five sets
         env = emul.EmulWrench(8, double=double, seed=5)
@@ -188,16 +189,15 @@ def test_physics_only_launch_honours_the_wrench(G, emul, pop):
 def test_standalone_sanitizer_build_of_the_shim_runs_clean(G, emul, tmp_path):
     """The shim as a program of its own (its own main, nothing loaded into Python) under AddressSanitizer and UBSan: one mixed-batch step
     of each population over the fixture's states, fp32 and fp64; exit status 0 = no report, every value finite, the two-env pass taken."""
-    from emul.emul_wrench import rows8
     parts = []
     for pop in POPS:
         for k in ("qpos", "qvel", "qw", "dof_pos", "dof_vel", "act", "cmd", "actions"):
             parts.append(np.asarray(mixed(G, f"{pop}_{k}", 0), np.float64).ravel())
-        parts += [rows8(mixed_wrench(G), 8).ravel(), body_rows(G).ravel()]
+        parts += [emul.rows8(mixed_wrench(G), 8).ravel(), body_rows(G).ravel()]
     states = tmp_path / "states.bin"
     np.concatenate(parts).tofile(states)
-    exe = emul.build_program(str(tmp_path / "nm_emul_wrench_asan"), ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], opt="-O0")
-    r = subprocess.run([exe, str(states)], capture_output=True, text=True)
+    exe = emul.build_program(str(tmp_path / "nm_emul_asan"), (7,), ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"], opt="-O0")
+    r = subprocess.run([exe, "wrench", str(states)], capture_output=True, text=True)
     print(r.stdout, r.stderr[-2000:])
     assert r.returncode == 0, (r.stdout, r.stderr[-2000:])
     assert "fp32" in r.stdout and "fp64" in r.stdout
