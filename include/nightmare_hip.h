@@ -442,6 +442,13 @@ int nm_profile(nm_env* env, int32_t enable, double* sum_ms, int64_t* count);
  * entry points) is generic. */
 int nm_set_step_variant(nm_env* env, int32_t mode);
 int nm_get_step_variant(nm_env* env);
+/* Self-test of the lean kernel's cross-lane helpers (no env needed): each helper that the lean kernel takes in another form than the
+ * generic kernels (csrc/simt.h: the half-wave row broadcast as two DPP moves, the lane-mask select as a compiler-visible instruction)
+ * runs in both forms on the caller's values, one wave per 64 of them, a last partial wave included. Device x / a / g [n] floats, HOST
+ * masks_host[4] lane masks; device out [2][36][n]: out[0] the generic forms, out[1] the lean forms; slot I < 32 is g + a * (x of lane I
+ * of the lane's half-wave), slot 32 + k is a under masks_host[k] and g elsewhere. The two halves must agree bit for bit. Stream-ordered. */
+#define NM_LANE_SELFTEST_SLOTS 36
+int nm_lane_selftest(const float* x_dev, const float* a_dev, const float* g_dev, const uint64_t* masks_host, int32_t n, float* out_dev, void* stream);
 /* Stage-skipping measurement switches are NOT part of this ABI: they exist only in the -DNM_MEASURE build
  * (libnightmare_hip_measure.so, include/nightmare_hip_measure.h). */
 

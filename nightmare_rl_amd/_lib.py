@@ -36,7 +36,7 @@ EXPORTS = ["nm_default_config", "nm_reward_name", "nm_last_error", "nm_create", 
            "nm_set_servo", "nm_get_servo", "nm_draw_servo", "nm_get_servo_state", "nm_set_servo_state",
            "nm_set_torque_limit", "nm_get_torque_limit", "nm_draw_torque_limit",
            "nm_set_base_wrench", "nm_get_base_wrench", "nm_set_wrench_schedule", "nm_get_wrench_schedule",
-           "nm_set_step_variant", "nm_get_step_variant",
+           "nm_set_step_variant", "nm_get_step_variant", "nm_lane_selftest",
            "nm_set_reset_rows", "nm_get_reset_rows", "nm_set_reset_row_counts", "nm_get_reset_row_counts", "nm_reset_rows_pick",
            "nm_privileged_obs", "nm_ppo_sample_prefix"]
 
@@ -210,6 +210,8 @@ def _bind(L, full):
     if hasattr(L, "nm_set_step_variant"):
         L.nm_set_step_variant.argtypes = [vp, C.c_int32]
         L.nm_get_step_variant.argtypes = [vp]
+    if hasattr(L, "nm_lane_selftest"):
+        L.nm_lane_selftest.argtypes = [vp, vp, vp, C.POINTER(C.c_uint64 * 4), C.c_int32, vp, vp]
     if hasattr(L, "nm_set_torque_limit"):
         L.nm_set_torque_limit.argtypes = [vp, vp, vp]
         L.nm_get_torque_limit.argtypes = [vp, vp, vp]

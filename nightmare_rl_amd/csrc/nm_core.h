@@ -304,6 +304,15 @@ template <class Cfg, class T> NM_FN T* cfg_opt(T* p) {
 template <class Cfg> NM_FN int cfg_flag(int f) {
   if constexpr (Cfg::kLean) return 0; else return f;
 }
+// Cross-lane helpers whose lean form moves the same bits in fewer issue slots (simt.h says how); CfgAsk keeps the form it had.
+// g + a * (x of lane I of this lane's half-wave): the row broadcast of the two-env constraint pass
+template <class Cfg, int I, class X, class B> NM_FN X half_lane_fma(const X& a, const X& x, const X& g, const B& h1) {
+  if constexpr (Cfg::kLean) return fma_half_lane_dpp<I>(a, x, g, h1); else return fma_half_lane<I>(a, x, g, h1);
+}
+// a in the lanes of the wave-uniform lane mask m, b elsewhere: the sweeps' kept values
+template <class Cfg, class X> NM_FN X lane_mask_sel(uint64_t m, const X& a, const X& b) {
+  if constexpr (Cfg::kLean) return sel_mask_open(m, a, b); else return sel_mask(m, a, b);
+}
 // what CfgLean assumes, for the host's choice of kernel (per launch: `A` as the launch will see it)
 template <class real> inline bool lean_config(const Model<real>& M, const Args<real>& A) {
   for (int k = 0; k < 3; k++)
@@ -2462,7 +2471,7 @@ template <int EP, class real, class Cfg = CfgAsk> NM_FN void stage_constraint2(S
   vr g = bb;
   for_contacts<0, kMaxCon2>(nmax, [&](auto ccT) {
     constexpr int cc = decltype(ccT)::value;
-    sfor4([&](auto rT) { constexpr int i = 4 * cc + decltype(rT)::value; g = fma_half_lane<i>(A[i], f, g, h1); });
+    sfor4([&](auto rT) { constexpr int i = 4 * cc + decltype(rT)::value; g = half_lane_fma<Cfg, i>(A[i], f, g, h1); });
   });
   {
     const vr cost = hsum32(sel(act, f * (bb + real(0.5) * (g - bb + Rr * f)), vr(real(0))));
@@ -2485,10 +2494,10 @@ template <int EP, class real, class Cfg = CfgAsk> NM_FN void stage_constraint2(S
         constexpr int cc = decltype(ccT)::value;
         sfor4([&](auto rT) {
           constexpr int i = 4 * cc + decltype(rT)::value;
-          gcap = sel_mask(rowm, g, gcap);        // the residual this row sees at its own step
+          gcap = lane_mask_sel<Cfg>(rowm, g, gcap);        // the residual this row sees at its own step
           rowm = mask_shl(rowm, 1);
           const vr dl = pgs_row_delta(g, k0, k1, nf);
-          g = fma_half_lane<i>(A[i], dl, g, h1);
+          g = half_lane_fma<Cfg, i>(A[i], dl, g, h1);
         });
       });
       const vr dcap = pgs_row_delta(gcap, k0, k1, nf);
@@ -2541,9 +2550,9 @@ template <int EP, class real, class Cfg = CfgAsk> NM_FN void stage_constraint2(S
           const vr dg = g - shfl_xor1(g);
           vr d = noslip_pair_delta(dg, invK1, lo, hi);
           if constexpr (decltype(checkT)::value) d = sel(noslip_pair_bad<real>(noslip_pair_cost(d, hK1, dg)), vr(real(0)), d);
-          g = fma_half_lane<2 * p>(A[2 * p], d, g, h1);
-          dcap = sel_mask(pairm, d, dcap);
-          dgcap = sel_mask(pairm, dg, dgcap);
+          g = half_lane_fma<Cfg, 2 * p>(A[2 * p], d, g, h1);
+          dcap = lane_mask_sel<Cfg>(pairm, d, dcap);
+          dgcap = lane_mask_sel<Cfg>(pairm, dg, dgcap);
           pairm = mask_shl(pairm, 2);
         });
       };

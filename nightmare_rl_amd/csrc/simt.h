@@ -107,6 +107,9 @@ NM_FN double sel_mask(uint64_t m, double a, double b) {
       : "v"(__double2loint(b)), "v"(__double2loint(a)), "v"(__double2hiint(b)), "v"(__double2hiint(a)), "s"(m));
   return __hiloint2double(rh, rl);
 }
+// The same select as an instruction the compiler sees (the lean step kernel): its hazard pass counts an inline-asm statement as no wait
+// state at all, so a sel_mask that stands between a VALU result and the DPP or v_readlane that reads it still got an s_nop beside it.
+NM_FN float sel_mask_open(uint64_t m, float a, float b) { return __builtin_amdgcn_inverse_ballot_w64(m) ? a : b; }
 // m << k as a value the optimiser cannot fold (the rows are unrolled, so it would otherwise turn the walking mask into one 64-bit literal
 // per row and keep them all in scalar registers: 334 SGPR spills)
 NM_FN uint64_t mask_shl(uint64_t m, int k) { m <<= k; asm("" : "+s"(m)); return m; }
@@ -132,6 +135,22 @@ template <int I> NM_FN float fma_half_lane(float a, float x, float g, bool h1) {
 template <int I> NM_FN double fma_half_lane(double a, double x, double g, bool h1) {
   const double s0 = rdlane(x, I), s1 = rdlane(x, 32 + I);
   return vfma(a, h1 ? s1 : s0, g);
+}
+// The same value by two DPP moves instead of two v_readlane, two moves and a select (the lean step kernel, nm::CfgLean): row_newbcast:I
+// gives every row of 16 lanes the value of ITS lane I - right in rows 0 and 2 (lanes I and 32 + I) - and row_bcast:15 under row mask
+// 0xA hands lane 15 of rows 0 and 2 on to rows 1 and 3. Pure data movement: the multiply-add sees the same operand bits in every lane.
+// Rows I >= 16 live in rows 1 and 3, from where no DPP control reaches the row in front: they keep the v_readlane form. Needs all 64
+// lanes executing, which the sweeps' wave-uniform control flow guarantees.
+#define NM_DPP_ROW_NEWBCAST0 0x150  /* + I: lane I of each row of 16 to the whole row (gfx90a and later) */
+#define NM_DPP_ROW_BCAST15 0x142    /* lane 15 of each row to every lane of the next row */
+template <int I> NM_FN float fma_half_lane_dpp(float a, float x, float g, bool h1) {
+  if constexpr (I < 16) {
+    int t = __builtin_amdgcn_update_dpp(0, __float_as_int(x), NM_DPP_ROW_NEWBCAST0 + I, 0xF, 0xF, true);
+    t = __builtin_amdgcn_update_dpp(t, t, NM_DPP_ROW_BCAST15, 0xA, 0xF, false);
+    return vfma(a, __int_as_float(t), g);
+  } else {
+    return fma_half_lane<I>(a, x, g, h1);
+  }
 }
 // x with lane l (wave-uniform) replaced by the wave-uniform value v. The lane id goes through an empty asm so
 // the `lane == l` mask is recomputed here (v_cmp + v_cndmask) instead of being hoisted out of the solver's
@@ -360,10 +379,19 @@ template <class T> NM_FN V<T> sel_mask(uint64_t m, const V<T>& a, const V<T>& b)
   for (int i = 0; i < NM_WAVE; i++) r.v[i] = ((m >> i) & 1ull) ? a.v[i] : b.v[i];
   return r;
 }
+template <class T> NM_FN V<T> sel_mask_open(uint64_t m, const V<T>& a, const V<T>& b) { return sel_mask(m, a, b); }
 NM_FN uint64_t mask_shl(uint64_t m, int k) { return m << k; }
 template <int I, class T> NM_FN V<T> fma_half_lane(const V<T>& a, const V<T>& x, const V<T>& g, const VB&) {
   V<T> r;
   for (int i = 0; i < NM_WAVE; i++) r.v[i] = a.v[i] * x.v[(i & 32) + I] + g.v[i];
+  return r;
+}
+// (the device's two-DPP form of the same broadcast, said lane by lane: row_newbcast:I inside each row of 16, then row_bcast:15 into rows 1 and 3)
+template <int I, class T> NM_FN V<T> fma_half_lane_dpp(const V<T>& a, const V<T>& x, const V<T>& g, const VB& h1) {
+  if (I >= 16) return fma_half_lane<I>(a, x, g, h1);
+  V<T> t, r;
+  for (int i = 0; i < NM_WAVE; i++) t.v[i] = x.v[(i & ~15) + (I & 15)];
+  for (int i = 0; i < NM_WAVE; i++) r.v[i] = a.v[i] * ((i & 16) ? t.v[(i & ~15) - 1] : t.v[i]) + g.v[i];
   return r;
 }
 template <class T> NM_FN T rdlane(const V<T>& x, int l) { return x.v[l]; }
