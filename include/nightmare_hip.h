@@ -634,6 +634,28 @@ int nm_rollout_act_ex(nm_env* env, const float* params_flat_dev, const float* ob
                       float* actions_dev, float* logp_dev, float* values_dev, float* mu_dev, float* sigma_dev, float* obs_store_dev, int32_t activation,
                       void* stream);
 
+/* ---- The same collection loop for the asymmetric actor-critic (no upstream line for the rows: the reference's critic reads the actor's
+ * observation, envs/nightmare_v3_config.py:105-109; the loop is train.py:54's `alg.act(obs, critic_obs)` with critic_obs = the privileged
+ * row of nm_privileged_obs). Actor {66,54,42,30,18} on columns 0..65 of the row, critic {89,54,42,30,1} on all NM_NUM_PRIVILEGED_OBS of it.
+ * The wave that owns the env gathers the privileged columns itself between two steps, with the arithmetic of nm_privileged_obs (the same
+ * bits), where the per-step path calls it: behind the step's reset draws, in front of the next step's push and wrench. */
+typedef struct {
+  const float* priv0_dev;              /* [N,89] the row the first act sees (the env's current privileged row); nm_rollout_args.obs0_dev is not read */
+  float* priv_final_dev;               /* [N,89] receives the row after the last step (a buffer of its own, as the env double-buffers it); last_values_dev is evaluated on it */
+  float* s_priv;                       /* [K,N,89] storage: row t = what act t saw; s_obs row t = its first 66 columns */
+} nm_rollout_priv_args;
+/* 1 exactly for actor_dims {66,54,42,30,18}, critic_dims {89,54,42,30,1}, n_layers 4 and a known activation code (reference hidden layers and
+ * activation: envs/nightmare_v3_config.py:107-109). Host only. */
+int nm_rollout_supported_priv(const int32_t* actor_dims, const int32_t* critic_dims, int32_t n_layers, int32_t activation);
+/* nm_rollout_ex with the privileged rows (collection loop: reference train.py:54). params_flat_dev is the flat vector of the 66 / 89 networks
+ * (actor W0 [54,66] ..., critic W0 [54,89] ..., std[18]). Refuses an fp64 env, steps beyond the episode length and NULL privileged pointers. */
+int nm_rollout_priv(nm_env* env, const nm_rollout_args* args, const nm_rollout_priv_args* priv, int32_t activation, void* stream);
+/* nm_rollout_act_ex reading an [N,89] row (PPO.act caller: reference train.py:54): the step-by-step reference of nm_rollout_priv.
+ * obs_store_dev [N,66] receives the row's first 66 columns, row_store_dev [N,89] the row; either may be NULL. Refuses an fp64 env. */
+int nm_rollout_act_priv(nm_env* env, const float* params_flat_dev, const float* rows_dev, uint64_t seed, const int64_t* iter_dev, int32_t step,
+                        float* actions_dev, float* logp_dev, float* values_dev, float* mu_dev, float* sigma_dev, float* obs_store_dev,
+                        float* row_store_dev, int32_t activation, void* stream);
+
 /* ---- Playing a policy (the loop of reference play.py:118-132: `actions = nn.act(obs)`, scale / clip, servo command, mj_step x decimation)
  * as ONE launch of `steps` steps with nothing collected for PPO: every wavefront keeps its two envs, evaluates the actor on the observation
  * its previous step left and steps the env. fp32 env, networks nm_play_supported accepts. Per step the results are those of nm_rollout_act_ex

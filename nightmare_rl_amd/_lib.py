@@ -38,7 +38,8 @@ EXPORTS = ["nm_default_config", "nm_reward_name", "nm_last_error", "nm_create", 
            "nm_set_base_wrench", "nm_get_base_wrench", "nm_set_wrench_schedule", "nm_get_wrench_schedule",
            "nm_set_step_variant", "nm_get_step_variant", "nm_lane_selftest",
            "nm_set_reset_rows", "nm_get_reset_rows", "nm_set_reset_row_counts", "nm_get_reset_row_counts", "nm_reset_rows_pick",
-           "nm_privileged_obs", "nm_ppo_sample_prefix"]
+           "nm_privileged_obs", "nm_ppo_sample_prefix",
+           "nm_rollout_supported_priv", "nm_rollout_priv", "nm_rollout_act_priv"]
 
 
 class NmConfig(C.Structure):
@@ -59,6 +60,10 @@ class NmRolloutArgs(C.Structure):     # nm_rollout_args of include/nightmare_hip
                 ("s_sigma", C.c_void_p), ("s_rewards", C.c_void_p), ("s_dones", C.c_void_p), ("gamma", C.c_float),
                 ("cur_ret", C.c_void_p), ("cur_len", C.c_void_p), ("fin3", C.c_void_p),
                 ("ep_idx_dev", C.c_void_p), ("n_ep", C.c_int32), ("ep_acc_dev", C.c_void_p), ("last_values_dev", C.c_void_p)]
+
+
+class NmRolloutPrivArgs(C.Structure):  # nm_rollout_priv_args of include/nightmare_hip.h
+    _fields_ = [("priv0_dev", C.c_void_p), ("priv_final_dev", C.c_void_p), ("s_priv", C.c_void_p)]
 
 
 class NmPlayArgs(C.Structure):        # nm_play_args of include/nightmare_hip.h
@@ -164,6 +169,10 @@ def _bind(L, full):
         L.nm_rollout_supported_act.argtypes = [vp, vp, C.c_int32, C.c_int32]
         L.nm_rollout_ex.argtypes = [vp, C.POINTER(NmRolloutArgs), C.c_int32, vp]
         L.nm_rollout_act_ex.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_int32, vp, vp, vp, vp, vp, vp, C.c_int32, vp]
+    if hasattr(L, "nm_rollout_priv"):
+        L.nm_rollout_supported_priv.argtypes = [vp, vp, C.c_int32, C.c_int32]
+        L.nm_rollout_priv.argtypes = [vp, C.POINTER(NmRolloutArgs), C.POINTER(NmRolloutPrivArgs), C.c_int32, vp]
+        L.nm_rollout_act_priv.argtypes = [vp, vp, vp, C.c_uint64, vp, C.c_int32, vp, vp, vp, vp, vp, vp, vp, C.c_int32, vp]
     L.nm_profile.argtypes = [vp, C.c_int32, vp, vp]
     L.nm_set_observation_noise.argtypes = [vp, vp]
     L.nm_set_noise_uniforms.argtypes = [vp, vp]

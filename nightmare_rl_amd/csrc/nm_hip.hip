@@ -226,11 +226,19 @@ struct nm_env {
   virtual int set_reset_row_counts(const uint32_t* counts_host) = 0;
   virtual int get_reset_row_counts(uint32_t* counts_host) = 0;
   virtual int priv_obs(const float* obs, float* out, hipStream_t s) = 0;
+  virtual int rollout_priv(const nm_rollout_args* r, const nm_rollout_priv_args* pv, int act, hipStream_t s) = 0;
+  virtual int rollout_act_priv(const float* flat, const float* rows, uint64_t seed, const int64_t* iter_dev, int step, int act, float* actions, float* logp,
+                               float* values, float* mu, float* sigma, float* obs_store, float* row_store, hipStream_t s) = 0;
 };
 
 // what puts a K-step launch's nmr::WrenchArgs behind the wrench rows (nm::wrench_args_of), on the launch's stream
 __global__ void k_wrench_args(nmr::WrenchArgs* dst, nmr::WrenchArgs w) {
   if (threadIdx.x == 0 && blockIdx.x == 0) *dst = w;
+}
+
+// the same for the nm::PrivObsArgs an asymmetric K-step launch gathers its privileged rows with (device memory of the env object)
+__global__ void k_priv_args(nm::PrivObsArgs<float>* dst, nm::PrivObsArgs<float> p) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) *dst = p;
 }
 
 template <class real> struct Env : nm_env {
@@ -762,18 +770,24 @@ template <class real> struct Env : nm_env {
   int priv_obs(const float* obs, float* out, hipStream_t s) override {
     HIPCHK(hipSetDevice(device));
     if (!obs || !out) return fail("nm_privileged_obs: NULL pointer");
+    nm::PrivObsArgs<real> p = priv_args();
+    p.obs = obs; p.out = out;
+    HIPCHK(nm_launch_priv_obs(p, s));
+    return 0;
+  }
+  // the regions and model constants of the privileged row, as they are now
+  nm::PrivObsArgs<real> priv_args() {
     nm::PrivObsArgs<real> p{};
     if (envp_dev) {
       p.fric = nmrows::fric_rows(envp_dev, N); p.body = nmrows::body_rows(envp_dev, N); p.delay = nmrows::delays(envp_dev, N);
       p.grav = nmrows::grav_rows(envp_dev, N); p.servo = nmrows::servo_rows(envp_dev, N); p.torque = nmrows::torque_rows(envp_dev, N);
       p.wrench = nmrows::wrench_rows(envp_dev, N);
     }
-    p.qpos = A.qpos; p.obs = obs; p.out = out; p.N = N; p.nxcd = A.nxcd; p.nsub = A.nsub;
+    p.qpos = A.qpos; p.N = N; p.nxcd = A.nxcd; p.nsub = A.nsub;
     p.mu = (double)M.mu; p.p_gain = (double)M.p_gain; p.kv = (double)M.kv; p.base_mass = (double)M.basec[nm::BP_MASS];
     for (int j = 0; j < 3; j++) p.base_ipos[j] = (double)M.basec[nm::BP_IPOS + j];
     p.grav0 = (double)M.grav; p.weight = (double)M.total_mass * (double)M.grav;
-    HIPCHK(nm_launch_priv_obs(p, s));
-    return 0;
+    return p;
   }
   // the reset-rows arguments of a K-step launch
   nmr::ResetRowsArgs kstep_rrows() {
@@ -837,24 +851,62 @@ template <class real> struct Env : nm_env {
     p.push = kstep_push(K); p.rnoise = kstep_rnoise(); p.rrows = kstep_rrows();
     rec_done_valid = log != nullptr;
   }
-  int rollout(const nm_rollout_args* r, int act, hipStream_t s) override {
+  int rollout(const nm_rollout_args* r, int act, hipStream_t s) override { return rollout_any("nm_rollout", r, nullptr, act, s); }
+  int rollout_priv(const nm_rollout_args* r, const nm_rollout_priv_args* pv, int act, hipStream_t s) override {
+    if (!pv) return fail("nm_rollout_priv: priv args is NULL");
+    return rollout_any("nm_rollout_priv", r, pv, act, s);
+  }
+  // ---- the asymmetric rollout (nm_rollout_priv, nm_rollout_act_priv): the packed PrivShape networks and the gather's descriptor
+  typedef nmr::PrivShape PS;
+  float *rollp_wp = nullptr, *rollp_bp = nullptr;
+  nm::PrivObsArgs<float>* priv_desc_dev = nullptr;
+  int roll_pack_priv(const float* flat, hipStream_t s) {
+    if (!rollp_wp && (dalloc(&rollp_wp, (size_t)PS::nfrag() * 256) || dalloc(&rollp_bp, (size_t)PS::nbias()))) return 1;
+    if (nmr::launch_pack_priv(flat, rollp_wp, rollp_bp, s)) return fail("nm_rollout_priv: packing the policy failed to launch");
+    return 0;
+  }
+  int rollout_act_priv(const float* flat, const float* rows, uint64_t seed, const int64_t* iter_dev, int step, int act, float* actions, float* logp, float* values,
+                       float* mu, float* sigma, float* obs_store, float* row_store, hipStream_t s) override {
     HIPCHK(hipSetDevice(device));
+    if constexpr (sizeof(real) == 8) return fail("nm_rollout_act_priv: the privileged rollout runs on the fp32 env only");
+    if (!flat || !rows || !iter_dev || !actions || !logp || !values || !mu || !sigma) return fail("nm_rollout_act_priv: NULL pointer");
+    if (roll_pack_priv(flat, s)) return 1;
+    nmr::ActOut o{actions, logp, values, mu, sigma, row_store};
+    if (nmr::launch_act_priv(rollp_wp, rollp_bp, flat + PS::stdoff(), rows, N, seed, iter_dev, step, o, obs_store, act, s)) return fail("nm_rollout_act_priv: launch failed");
+    return 0;
+  }
+  // nm_rollout (pv = null) and nm_rollout_priv: the same arguments, books and closing launches; `who` names the entry point in messages
+  int rollout_any(const char* who_, const nm_rollout_args* r, const nm_rollout_priv_args* pv, int act, hipStream_t s) {
+    HIPCHK(hipSetDevice(device));
+    const std::string who(who_);
     if constexpr (sizeof(real) == 8 || NM_ENVS_PER_WAVE != 2) {
-      return fail("nm_rollout: the fused rollout runs on the fp32 kernel (two envs per wave) only");
+      return fail(who + ": the fused rollout runs on the fp32 kernel (two envs per wave) only");
     } else {
-      if (!r) return fail("nm_rollout: args is NULL");
+      if (!r) return fail(who + ": args is NULL");
       const int K = r->steps;
-      if (kstep_check("nm_rollout", K, "", r->n_ep, r->ep_idx_dev, r->ep_acc_dev, r->ep_stats_dev)) return 1;
-      if ((double)K > (double)M.max_ep_len) return fail("nm_rollout: more steps than an episode has (an env may time out once per rollout)");
-      if (!r->params_flat_dev || !r->iter_dev || !r->obs0_dev || !r->obs_final_dev || !r->episode_length_dev || !r->rew_dev || !r->done_dev || !r->s_obs ||
+      if (kstep_check(who_, K, "", r->n_ep, r->ep_idx_dev, r->ep_acc_dev, r->ep_stats_dev)) return 1;
+      if ((double)K > (double)M.max_ep_len) return fail(who + ": more steps than an episode has (an env may time out once per rollout)");
+      if (pv && (!pv->priv0_dev || !pv->priv_final_dev || !pv->s_priv)) return fail(who + ": NULL privileged pointer");
+      if (!r->params_flat_dev || !r->iter_dev || (!pv && !r->obs0_dev) || !r->obs_final_dev || !r->episode_length_dev || !r->rew_dev || !r->done_dev || !r->s_obs ||
           !r->s_actions || !r->s_logp || !r->s_values || !r->s_mu || !r->s_sigma || !r->s_rewards || !r->s_dones || !r->cur_ret || !r->cur_len || !r->fin3)
-        return fail("nm_rollout: NULL pointer");
+        return fail(who + ": NULL pointer");
       real* log = nullptr;
       if (roll_reserve(K) || log_rows(K, &log)) return 1;
-      if (roll_pack(r->params_flat_dev, s)) return 1;
+      if (pv ? roll_pack_priv(r->params_flat_dev, s) : roll_pack(r->params_flat_dev, s)) return 1;
+      if (pv) {      // the gather's descriptor: the regions and constants as they are now, written in front of the launch on its stream
+        if (!priv_desc_dev && dalloc(&priv_desc_dev, 1)) return 1;
+        hipLaunchKernelGGL(k_priv_args, dim3(1), dim3(64), 0, s, priv_desc_dev, priv_args());
+        HIPCHK(hipGetLastError());
+      }
       const nm::Args<real> a = kstep_args(K, nullptr, r->episode_length_dev, r->obs_final_dev, r->rew_dev, r->done_dev, log);
-      nmr::RollArgs R;
-      R.K = K; R.wp = (const nmr::f32x4*)roll_wp; R.bp = roll_bp; R.stdv = r->params_flat_dev + RS::stdoff();
+      nmr::RollPrivArgs R;
+      if (pv) {
+        R.K = K; R.wp = (const nmr::f32x4*)rollp_wp; R.bp = rollp_bp; R.stdv = r->params_flat_dev + PS::stdoff();
+        R.desc = priv_desc_dev; R.priv0 = pv->priv0_dev; R.priv_final = pv->priv_final_dev; R.s_priv = pv->s_priv;
+      } else {
+        R.K = K; R.wp = (const nmr::f32x4*)roll_wp; R.bp = roll_bp; R.stdv = r->params_flat_dev + RS::stdoff();
+        R.desc = nullptr; R.priv0 = nullptr; R.priv_final = nullptr; R.s_priv = nullptr;
+      }
       R.seed = r->seed; R.iter_dev = r->iter_dev; R.obs0 = r->obs0_dev; R.obs_final = r->obs_final_dev;
       R.s_obs = r->s_obs; R.s_actions = r->s_actions; R.s_logp = r->s_logp; R.s_values = r->s_values; R.s_mu = r->s_mu; R.s_sigma = r->s_sigma;
       R.s_rewards = r->s_rewards; R.s_dones = r->s_dones; R.cur_ret = r->cur_ret; R.cur_len = r->cur_len; R.fin3 = r->fin3;
@@ -865,7 +917,8 @@ template <class real> struct Env : nm_env {
       R.wave_clock = A.dbg ? reinterpret_cast<unsigned long long*>(A.dbg) : nullptr;   // measurement: the debug buffer ([N,256] reals) takes the waves' clocks instead
       const nmr::TailArgs ta = kstep_tail(r, K, r->bootstrap_time_outs ? r->gamma : -1.0f, r->s_values, r->s_rewards);
       if (kstep_wrench(K, s)) return 1;
-      if (nmr::launch_rollout(M_dev, a, R, ta, act, rows.level(), s)) return fail("nm_rollout: launch failed");
+      if (pv ? nmr::launch_rollout_priv(M_dev, a, R, ta, act, rows.level(), s) : nmr::launch_rollout(M_dev, a, R, ta, act, rows.level(), s))
+        return fail(who + ": launch failed");
       return 0;
     }
   }
@@ -1260,6 +1313,26 @@ int nm_rollout_act_ex(nm_env* env, const float* flat, const float* obs, uint64_t
   NEED(env);
   if (!nmact::valid(activation)) return bad_activation("nm_rollout_act", activation);
   return env->rollout_act(flat, obs, seed, iter_dev, step, activation, actions, logp, values, mu, sigma, obs_store, (hipStream_t)stream);
+}
+int nm_rollout_supported_priv(const int32_t* actor_dims, const int32_t* critic_dims, int32_t n_layers, int32_t activation) {
+  typedef nmr::PrivShape PS;
+  if (!nmact::valid(activation)) return 0;
+  if (!actor_dims || !critic_dims || n_layers != PS::NL) return 0;
+  if (actor_dims[0] != PS::IA || critic_dims[0] != PS::I) return 0;
+  for (int l = 0; l < PS::NL; l++)
+    if (actor_dims[l + 1] != PS::aout(l) || critic_dims[l + 1] != PS::cout(l)) return 0;
+  return 1;
+}
+int nm_rollout_priv(nm_env* env, const nm_rollout_args* args, const nm_rollout_priv_args* priv, int32_t activation, void* stream) {
+  NEED(env);
+  if (!nmact::valid(activation)) return bad_activation("nm_rollout_priv", activation);
+  return env->rollout_priv(args, priv, activation, (hipStream_t)stream);
+}
+int nm_rollout_act_priv(nm_env* env, const float* flat, const float* rows, uint64_t seed, const int64_t* iter_dev, int32_t step, float* actions, float* logp,
+                        float* values, float* mu, float* sigma, float* obs_store, float* row_store, int32_t activation, void* stream) {
+  NEED(env);
+  if (!nmact::valid(activation)) return bad_activation("nm_rollout_act_priv", activation);
+  return env->rollout_act_priv(flat, rows, seed, iter_dev, step, activation, actions, logp, values, mu, sigma, obs_store, row_store, (hipStream_t)stream);
 }
 #ifdef NM_MEASURE   // include/nightmare_hip_measure.h: not part of the shipped ABI
 int nm_set_ablation(nm_env* env, int32_t mask) { NEED(env); env->set_ablate(mask); return 0; }

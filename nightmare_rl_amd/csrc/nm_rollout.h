@@ -28,6 +28,7 @@
 #include "nm_sample.h"
 #include "nm_sfor.h"
 
+namespace nm { template <class real> struct PrivObsArgs; }     // nm_priv_obs.h
 namespace nmr {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -37,12 +38,16 @@ typedef float f32x2u __attribute__((ext_vector_type(2), aligned(4)));
 // Network shape, compile time: observation I, three hidden layers of the actor (A1..A3) and of the critic (C1..C3), AO actions, value 1.
 // Layer l of the merged network: inputs ka(l) | kc(l) (layer 0: both read the observation), outputs padded to whole 4-neuron blocks:
 // oa4(l) actor neurons first, then oc4(l) critic neurons.
-template <int I_, int A1, int A2, int A3, int AO_, int C1, int C2, int C3>
-struct Shape {
-  static constexpr int NL = 4, I = I_, AO = AO_;
+// ShapeT is the general form: the actor reads the first IA_ floats of a row of IC_ (IA_ <= IC_: the asymmetric actor-critic, whose critic row
+// is the actor's observation + privileged columns, nm_priv_obs.h). Layer 0 then runs over kq(0) = up4(IC_) / 4 k quads, and the actor's
+// neurons get packed zeros for k >= IA_ (widx below) - an exact + 0 per FMA, so the actor computes what it computes on its own row.
+// Shape<I_, ...> is the symmetric case ShapeT<I_, I_, ...> under the name the kernels have always been instantiated with.
+template <int IA_, int IC_, int A1, int A2, int A3, int AO_, int C1, int C2, int C3>
+struct ShapeT {
+  static constexpr int NL = 4, I = IC_, IA = IA_, AO = AO_;      // I: floats of the row the wave loads
   static constexpr __host__ __device__ int up4(int x) { return (x + 3) & ~3; }
-  static constexpr __host__ __device__ int ka(int l) { return l == 0 ? I_ : l == 1 ? A1 : l == 2 ? A2 : A3; }
-  static constexpr __host__ __device__ int kc(int l) { return l == 0 ? I_ : l == 1 ? C1 : l == 2 ? C2 : C3; }
+  static constexpr __host__ __device__ int ka(int l) { return l == 0 ? IA_ : l == 1 ? A1 : l == 2 ? A2 : A3; }
+  static constexpr __host__ __device__ int kc(int l) { return l == 0 ? IC_ : l == 1 ? C1 : l == 2 ? C2 : C3; }
   static constexpr __host__ __device__ int aout(int l) { return l == 0 ? A1 : l == 1 ? A2 : l == 2 ? A3 : AO_; }
   static constexpr __host__ __device__ int cout(int l) { return l == 0 ? C1 : l == 1 ? C2 : l == 2 ? C3 : 1; }
   static constexpr __host__ __device__ int oa4(int l) { return up4(aout(l)); }
@@ -72,10 +77,14 @@ struct Shape {
     const int oc = o - oa4(l);
     return oc < cout(l) ? cb(l) + oc : -1;
   }
-  static_assert(A1 <= 64 && A2 <= 64 && A3 <= 64 && C1 <= 64 && C2 <= 64 && C3 <= 64 && I_ <= 124 && AO_ <= 32 && AO_ % 2 == 0, "shape limits of the LDS activation rows");
+  static_assert(A1 <= 64 && A2 <= 64 && A3 <= 64 && C1 <= 64 && C2 <= 64 && C3 <= 64 && IA_ <= IC_ && IC_ <= 124 && AO_ <= 32 && AO_ % 2 == 0, "shape limits of the LDS activation rows");
 };
+template <int I_, int A1, int A2, int A3, int AO_, int C1, int C2, int C3>
+struct Shape : ShapeT<I_, I_, A1, A2, A3, AO_, C1, C2, C3> {};
 // the reference's networks (envs/nightmare_v3_config.py:107-109): 66 -> 54 -> 42 -> 30 -> 18 | 1
 typedef Shape<66, 54, 42, 30, 18, 54, 42, 30> RefShape;
+// the same hidden layers around the privileged critic row (nm_priv_obs.h: 66 + 23): actor 66 -> ... -> 18, critic 89 -> ... -> 1
+typedef ShapeT<66, 89, 54, 42, 30, 18, 54, 42, 30> PrivShape;
 
 constexpr int kXW = 128;                 // floats per env in an activation row: actor part at 0, critic part at 64 (layer 0: the observation at 0)
 constexpr int kXFloats = 2 * 2 * kXW;    // two rows (ping-pong) x two envs
@@ -120,8 +129,10 @@ struct ActOut {
 // MODE kPolicyValueOnly: the same forward, but nothing is sampled or filed except the critic's value into o.values[env] (the last observation of a rollout).
 // MODE kPolicyPlay (k_env_play, reference play.py:118-132): the same forward and the same draw, but only o.actions is filed - the mean itself when
 // `deterministic` (act_inference), mean + std * z otherwise (nn.act); no log-probability, value, mu or sigma.
+// LOAD = false (the asymmetric rollout, nm_rollout_kernels.h): the caller has put the rows into row 0 of xb itself, zero padding included;
+// `obs` and o.obs_store are not read.
 constexpr int kPolicyFull = 0, kPolicyValueOnly = 1, kPolicyPlay = 2;
-template <class S, int ACT, int MODE = kPolicyFull>
+template <class S, int ACT, int MODE = kPolicyFull, bool LOAD = true>
 __device__ __forceinline__ void policy_wave(float* xb, const f32x4* __restrict__ wp, const float* __restrict__ bp, const float* __restrict__ stdv,
                                             const float* obs, int N, int wave, uint64_t seed, uint64_t ctr, const ActOut& o, bool deterministic = false) {
   constexpr bool VALUE_ONLY = MODE == kPolicyValueOnly;
@@ -142,7 +153,7 @@ __device__ __forceinline__ void policy_wave(float* xb, const f32x4* __restrict__
   f32x4 ring[kRing];
   sfor<kRing>([&](auto i) { ring[i] = wg[(size_t)(i < NF ? (int)i : 0) * 64 + lane]; __builtin_amdgcn_sched_barrier(0); });
   // ---- observation rows -> LDS (row 0), zero padded to the next k quad
-  {
+  if constexpr (LOAD) {
     const int e0 = min(wave * 2, N - 1), e1 = min(wave * 2 + 1, N - 1);
 #pragma unroll
     for (int i = 0; i < (2 * I + 63) / 64; i++) {
@@ -306,6 +317,17 @@ struct RollArgs {
   // rollout's storage rows), kStepRecord = optional [K,N] reward / done rows
   static constexpr bool kPlayBooks = false, kStepRecord = false;
 };
+// The rollout with the privileged critic row (k_env_rollout over PrivShape, nm_rollout_kernels.h): what the LDS copy of the launch
+// arguments holds on top of RollArgs - four pointers. The model constants and region pointers the gather needs (nm::PrivObsArgs, 176 B)
+// do not fit beside them at level 7; the launcher writes them, stream-ordered, into device memory of the env object (`desc`), as it does
+// with ResetRowsDesc and WrenchArgs. RollArgs::obs0 is not read: the first act sees `priv0`, whose first kNOBS columns are that row.
+struct RollPrivArgs : RollArgs {
+  const nm::PrivObsArgs<float>* desc;
+  const float* priv0;           // [N,kPrivRow]: the env's current privileged row
+  float* priv_final;            // [N,kPrivRow]: the row after the last step
+  float* s_priv;                // [K,N,kPrivRow]: storage, row t = what act t saw
+};
+static_assert(sizeof(RollPrivArgs) == sizeof(RollArgs) + 32, "a few pointers only: the symmetric level-7 kernel leaves 584 B of the 20,480 B a workgroup may use at two waves per SIMD");
 constexpr int kRecRow = 50;            // qpos 25 | qvel 24 | bad-state resets of the step (what wave_step files through Args::rec)
 // k_env_play (nm_play_kernels.h): K x [policy on the observation the previous step left, env.step], nothing collected - reference play.py:118-132
 struct PlayArgs {
@@ -365,6 +387,13 @@ template <int ACT> struct RollKernels {
                  const ActOut& o, hipStream_t s);
   static int rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, int level, hipStream_t s);
 };
+// the same for the asymmetric network (PrivShape): defined in nm_rollout_kernels.h under NM_ROLLOUT_PRIV, instantiated once per code by
+// nm_rollout_priv_<activation>.hip. act: `rows` [N,89]; o.obs_store takes the [N,89] row, prefix_store the [N,66] prefix (either may be null)
+template <int ACT> struct RollPrivKernels {
+  static int act(const float* wp, const float* bp, const float* stdv, const float* rows, int N, uint64_t seed, const int64_t* iter_dev, int step,
+                 const ActOut& o, float* prefix_store, hipStream_t s);
+  static int rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollPrivArgs& R, int level, hipStream_t s);
+};
 // the launch of k_env_play for one hidden activation: defined in nm_play_kernels.h, instantiated once per code by nm_play_<activation>.hip
 template <int ACT> struct PlayKernels {
   static int play(const nm::Model<float>* M_dev, const nm::Args<float>& a, const PlayArgs& P, int level, hipStream_t s);
@@ -381,11 +410,22 @@ extern template struct RollKernels<NM_ACT_RELU>;
 extern template struct RollKernels<NM_ACT_LRELU>;
 extern template struct RollKernels<NM_ACT_TANH>;
 extern template struct RollKernels<NM_ACT_SIGMOID>;
+extern template struct RollPrivKernels<NM_ACT_ELU>;
+extern template struct RollPrivKernels<NM_ACT_SELU>;
+extern template struct RollPrivKernels<NM_ACT_RELU>;
+extern template struct RollPrivKernels<NM_ACT_LRELU>;
+extern template struct RollPrivKernels<NM_ACT_TANH>;
+extern template struct RollPrivKernels<NM_ACT_SIGMOID>;
 // act: the hidden activation (NM_ACT_*); a code this build has no instantiation for (the measurement build: ELU only) fails the launch.
 // level: which instantiation of the step the K-step kernel carries - nmrows::State::level() of the env object (nm_env_rows.h)
 int launch_act(const float* wp, const float* bp, const float* stdv, const float* obs, int N, uint64_t seed, const int64_t* iter_dev, int step, const ActOut& o,
                int act, hipStream_t s);
 int launch_rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, const TailArgs& t, int act, int level, hipStream_t s);
+// the asymmetric counterparts (PrivShape; flat = the 66 / 89 networks' vector)
+int launch_pack_priv(const float* flat, float* wp, float* bp, hipStream_t s);
+int launch_act_priv(const float* wp, const float* bp, const float* stdv, const float* rows, int N, uint64_t seed, const int64_t* iter_dev, int step, const ActOut& o,
+                    float* prefix_store, int act, hipStream_t s);
+int launch_rollout_priv(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollPrivArgs& R, const TailArgs& t, int act, int level, hipStream_t s);
 // k_env_play + the rollout's closing launches (k_rollout_tail without the time-out bootstrap, k_rollout_clear)
 int launch_play(const nm::Model<float>* M_dev, const nm::Args<float>& a, const PlayArgs& P, const TailArgs& t, int act, int level, hipStream_t s);
 // the launch of k_env_tape (nm_tape.hip), and launch_tape = that + the same closing launches as launch_play

@@ -87,6 +87,12 @@ int launch_pack(const float* flat, float* wp, float* bp, hipStream_t s) {
   return hipGetLastError() != hipSuccess;
 }
 
+int launch_pack_priv(const float* flat, float* wp, float* bp, hipStream_t s) {
+  const int n = PrivShape::nfrag() * 256;
+  hipLaunchKernelGGL(k_roll_pack<PrivShape>, dim3((n + 255) / 256), dim3(256), 0, s, flat, wp, bp);
+  return hipGetLastError() != hipSuccess;
+}
+
 // The per-activation instantiations (nm_rollout_<activation>.hip; each k_env_rollout carries its own copy of the physics: ~19 s of device
 // compile apiece). The measurement build (-DNM_MEASURE: stage-skipping switches, used with the ELU networks of scripts/) links ELU only.
 template <class F> static int with_act(int act, F&& fn) {
@@ -110,6 +116,14 @@ static int launch_tail(const TailArgs& t, hipStream_t s) {
 }
 int launch_rollout(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollArgs& R, const TailArgs& t, int act, int level, hipStream_t s) {
   if (with_act(act, [&](auto ACT) { return RollKernels<decltype(ACT)::value>::rollout(M_dev, a, R, level, s); })) return 1;
+  return launch_tail(t, s);
+}
+int launch_act_priv(const float* wp, const float* bp, const float* stdv, const float* rows, int N, uint64_t seed, const int64_t* iter_dev, int step, const ActOut& o,
+                    float* prefix_store, int act, hipStream_t s) {
+  return with_act(act, [&](auto ACT) { return RollPrivKernels<decltype(ACT)::value>::act(wp, bp, stdv, rows, N, seed, iter_dev, step, o, prefix_store, s); });
+}
+int launch_rollout_priv(const nm::Model<float>* M_dev, const nm::Args<float>& a, const RollPrivArgs& R, const TailArgs& t, int act, int level, hipStream_t s) {
+  if (with_act(act, [&](auto ACT) { return RollPrivKernels<decltype(ACT)::value>::rollout(M_dev, a, R, level, s); })) return 1;
   return launch_tail(t, s);
 }
 // nm_play: the same closing launches. Without the bootstrap (t.gamma < 0) k_rollout_tail needs each env's LATEST time-out step only: the

@@ -1184,9 +1184,14 @@ class NightmareV3Env:
         params_flat: the flat parameter vector of FusedUpdate (actor W0 b0 ..., critic ..., std). last_values ([N] float32 on the device,
         optional) receives the critic's value of the last observation - what PPO.compute_returns evaluates next. activation: the networks'
         hidden activation (a name of _lib.ACTIVATIONS, as ActorCritic takes it). With cfg.viewer.record_states the launch keeps the state log's
-        K rows on the device and they are read - one host synchronisation - after it has been enqueued."""
+        K rows on the device and they are read - one host synchronisation - after it has been enqueued.
+        A storage with privileged rows of this env's width (89, observations 66) on an env with cfg.env.privileged_obs takes the asymmetric
+        launch (nm_rollout_priv): params_flat is then the 66 / 89 networks' vector, the first act reads the env's current privileged row,
+        every act's row is filed in storage.privileged_observations, and get_privileged_observations() is afterwards the row of the last
+        step, double-buffered as step() does it."""
         T = int(steps)
-        if storage.num_transitions_per_env < T or storage.num_envs != self.num_envs or storage.privileged_observations is not None:
+        priv = self._storage_takes_priv_rows(storage)
+        if storage.num_transitions_per_env < T or storage.num_envs != self.num_envs or (storage.privileged_observations is not None and not priv):
             raise ValueError("policy_rollout: storage must hold `steps` rows of this env's transitions (no privileged observations)")
         a = _lib.NmRolloutArgs()
         a.steps = T
@@ -1198,7 +1203,14 @@ class NightmareV3Env:
         a.gamma = float(gamma)
         a.cur_ret, a.cur_len, a.fin3 = cur_ret.data_ptr(), cur_len.data_ptr(), fin.data_ptr()
         a.last_values_dev = last_values.data_ptr() if last_values is not None else None
-        self._ck(self._L.nm_rollout_ex(self._h, C.byref(a), _lib.activation_code(activation), self._stream()))
+        if priv:
+            pa = _lib.NmRolloutPrivArgs()
+            pa.priv0_dev = self.privileged_obs_buf.data_ptr()
+            self.privileged_obs_buf = self._priv_pair[self._obs_idx]      # (the index _kstep_launch_args has just swapped)
+            pa.priv_final_dev, pa.s_priv = self.privileged_obs_buf.data_ptr(), storage.privileged_observations.data_ptr()
+            self._ck(self._L.nm_rollout_priv(self._h, C.byref(a), C.byref(pa), _lib.activation_code(activation), self._stream()))
+        else:
+            self._ck(self._L.nm_rollout_ex(self._h, C.byref(a), _lib.activation_code(activation), self._stream()))
         self._keep_rollout = (params_flat, iter_dev, storage, cur_ret, cur_len, fin, ep_idx, ep_acc, last_values)
         self.common_step_counter += T
         storage.step = T
@@ -1358,9 +1370,26 @@ class NightmareV3Env:
         self.set_buffers(commands=np.tile(np.array([vx * keep, 0.0, yaw]), (self.num_envs, 1)))
         self._fixed_cmd = (vx, yaw)
 
+    def _storage_takes_priv_rows(self, storage):
+        """Does `storage` ask for the asymmetric wave policy - privileged rows of this env's width next to observation rows, on an env that
+        hands such rows out?"""
+        p = storage.privileged_observations
+        return bool(p is not None and self.privileged_obs_has_obs_prefix and p.shape[-1] == self.num_privileged_obs
+                    and storage.observations.shape[-1] == self.num_obs)
+
     def policy_act(self, params_flat, obs, seed, iter_dev, step, storage, activation="elu"):
-        """PPO.act as one launch of the rollout's wave code (nm_rollout_act_ex): the per-step counterpart of policy_rollout."""
+        """PPO.act as one launch of the rollout's wave code (nm_rollout_act_ex): the per-step counterpart of policy_rollout. A storage with
+        privileged rows (policy_rollout says which) takes nm_rollout_act_priv: `obs` is then the [N, 89] row; the row goes to
+        storage.privileged_observations[step], its first 66 columns to storage.observations[step]."""
         s = int(step)
+        if storage.privileged_observations is not None:
+            if not self._storage_takes_priv_rows(storage) or obs.shape[-1] != self.num_privileged_obs:
+                raise ValueError("policy_act: privileged rows need cfg.env.privileged_obs, a storage of this env's widths and the wide row as `obs`")
+            self._ck(self._L.nm_rollout_act_priv(self._h, params_flat.data_ptr(), obs.data_ptr(), int(seed), iter_dev.data_ptr(), s, storage.actions[s].data_ptr(),
+                                                 storage.actions_log_prob[s].data_ptr(), storage.values[s].data_ptr(), storage.mu[s].data_ptr(),
+                                                 storage.sigma[s].data_ptr(), storage.observations[s].data_ptr(), storage.privileged_observations[s].data_ptr(),
+                                                 _lib.activation_code(activation), self._stream()))
+            return storage.actions[s]
         self._ck(self._L.nm_rollout_act_ex(self._h, params_flat.data_ptr(), obs.data_ptr(), int(seed), iter_dev.data_ptr(), s, storage.actions[s].data_ptr(),
                                            storage.actions_log_prob[s].data_ptr(), storage.values[s].data_ptr(), storage.mu[s].data_ptr(),
                                            storage.sigma[s].data_ptr(), storage.observations[s].data_ptr(), _lib.activation_code(activation), self._stream()))
@@ -1403,7 +1432,8 @@ class NightmareV3Env:
 
     def get_privileged_observations(self):
         """None (the reference, :317-319) unless cfg.env.privileged_obs is on: then the [num_envs, 89] row of the last step() (envs/privileged.py).
-        policy_rollout, policy_play and step_tape evaluate no critic outside their launch and do not refresh it."""
+        policy_rollout into a storage with privileged rows leaves the row of its last step; policy_play, step_tape and the symmetric
+        policy_rollout evaluate no critic outside their launch and do not refresh it."""
         return self.privileged_obs_buf
 
     def privileged_defaults(self):

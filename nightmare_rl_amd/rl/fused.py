@@ -10,7 +10,9 @@ train.py:54), writing straight into the rollout storage:
     refreshed once per iteration by `refresh()`, outside any captured graph.
 An asymmetric actor-critic - the critic's row is the actor's observation followed by privileged columns (envs/privileged.py) - takes the
 three-launch path: the merged layer 0 is as wide as the critic's row, the actor's rows of it are zero beyond the observation, `act` is fed
-the wide row and files both the observation prefix and the wide row into the storage (`nm_ppo_sample_prefix`).
+the wide row and files both the observation prefix and the wide row into the storage (`nm_ppo_sample_prefix`). On this repo's env with
+`cfg.env.privileged_obs` its whole rollout can be ONE launch as well (`can_rollout_privileged`, `nm_rollout_priv`: the env's wave gathers
+the privileged columns itself; the runner's opt-in `privileged_rollout`).
 
 Used by PPO when the networks qualify (`FusedCollector.supported`: any activation of `_lib.ACTIVATIONS`); otherwise PPO keeps its
 torch path (host tests, deeper or wider networks)."""
@@ -42,6 +44,7 @@ class FusedCollector:
         self.activation = ac.activation_name
         self.act_code = _lib.activation_code(self.activation)
         self.update = update if (update is not None and update.has_fast_path) else None
+        self._flat_update = update       # any FusedUpdate: the privileged one-launch rollout reads its flat vector, fast path or not
         self.a_lin = [m for m in ac.actor if isinstance(m, nn.Linear)]
         self.c_lin = [m for m in ac.critic if isinstance(m, nn.Linear)]
         self.A = self.a_lin[-1].out_features
@@ -151,14 +154,29 @@ class FusedCollector:
         c = (C.c_int32 * (len(self.c_lin) + 1))(self.c_lin[0].in_features, *[m.out_features for m in self.c_lin])
         return bool(self._L.nm_rollout_supported_act(a, c, len(self.a_lin), self.act_code))
 
+    def can_rollout_privileged(self, env):
+        """The same question for the asymmetric actor-critic (nm_rollout_priv): this repo's fp32 env on the same device with
+        cfg.env.privileged_obs, the 66 / 89 networks of the compiled shape, and a FusedUpdate of them - the generic one: the kernel reads
+        its flat parameter vector, not the fast path's packed weights."""
+        if self._flat_update is None or not self.asymmetric or not hasattr(env, "policy_rollout") or getattr(env, "_dtype", None) != _lib.DTYPE_F32:
+            return False
+        if env.num_envs != self.N or torch.device(env.device) != self.device or not getattr(env, "privileged_obs_has_obs_prefix", False):
+            return False
+        if env.get_privileged_observations() is None or env.num_privileged_obs != self.n_in or env.num_obs != self.n_actor_in:
+            return False
+        a = (C.c_int32 * (len(self.a_lin) + 1))(self.a_lin[0].in_features, *[m.out_features for m in self.a_lin])
+        c = (C.c_int32 * (len(self.c_lin) + 1))(self.c_lin[0].in_features, *[m.out_features for m in self.c_lin])
+        return bool(self._L.nm_rollout_supported_priv(a, c, len(self.a_lin), self.act_code))
+
     def rollout(self, env, storage, steps, gamma, cur_ret, cur_len, fin, ep=None):
         """`steps` x (PPO.act, env.step, PPO.process_env_step + the runner's bookkeeping) as one launch; returns the last observation.
-        Same noise keys as act(): (seed, iteration set by refresh(), step, env, action pair)."""
+        Same noise keys as act(): (seed, iteration set by refresh(), step, env, action pair). A storage with privileged rows makes it the
+        asymmetric launch (can_rollout_privileged): the last critic row is then env.get_privileged_observations()."""
         self.drop_pending()
         storage.clear()
         if getattr(self, "_last_values", None) is None or self._last_values.numel() != env.num_envs:
             self._last_values = torch.zeros(env.num_envs, device=self.device)
-        o = env.policy_rollout(steps, self.update.flat, self.seed, self.iter_dev, storage, gamma, cur_ret, cur_len, fin, ep=ep, last_values=self._last_values,
+        o = env.policy_rollout(steps, self._flat_update.flat, self.seed, self.iter_dev, storage, gamma, cur_ret, cur_len, fin, ep=ep, last_values=self._last_values,
                                activation=self.activation)
         self.last_values = self._last_values      # the value of the observation after the last step: PPO.compute_returns takes it (once)
         return o

@@ -27,6 +27,11 @@ def _world():
     return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
 
 
+# cfg["runner"]["privileged_rollout"]: with privileged critic observations, collect the rollout as ONE launch (nm_rollout_priv) instead of
+# per-step launches. Opt-in; the key is not part of the reference's config tree.
+PRIVILEGED_ROLLOUT_DEFAULT = False
+
+
 class OnPolicyRunner:
     def __init__(self, env, train_cfg, log_dir=None, device="cpu"):
         self.cfg, self.alg_cfg, self.policy_cfg = train_cfg["runner"], train_cfg["algorithm"], train_cfg["policy"]
@@ -92,7 +97,8 @@ class OnPolicyRunner:
                 if ep_acc is None:
                     ep_acc = torch.zeros(len(state["ep_keys"]), device=dev)
                 o = alg.fused.rollout(env, alg.storage, T, alg.gamma, cur_ret, cur_len, fin, ep=(state["ep_idx"], ep_acc))
-                state["obs"] = state["critic_obs"] = o
+                state["obs"] = o
+                state["critic_obs"] = env.get_privileged_observations() if one_launch_priv else o      # (compute_returns takes the in-kernel last values)
                 return
             for _ in range(T):
                 actions = alg.act(o, co)
@@ -144,7 +150,11 @@ class OnPolicyRunner:
         on_gpu = torch.device(dev).type == "cuda"
         one_launch = bool(self.cfg.get("fused_rollout", True)) and getattr(alg, "fused", None) is not None and priv is None \
             and alg.fused.can_rollout(env) and T <= int(env.max_episode_length)
-        self.rollout_mode = "one launch (nm_rollout)" if one_launch else "per-step launches"
+        one_launch_priv = bool(self.cfg.get("privileged_rollout", PRIVILEGED_ROLLOUT_DEFAULT)) and bool(self.cfg.get("fused_rollout", True)) \
+            and getattr(alg, "fused", None) is not None and priv is not None and alg.storage.privileged_observations is not None \
+            and alg.fused.can_rollout_privileged(env) and T <= int(env.max_episode_length)
+        one_launch = one_launch or one_launch_priv
+        self.rollout_mode = "one launch (nm_rollout, privileged)" if one_launch_priv else "one launch (nm_rollout)" if one_launch else "per-step launches"
         want_graph = not one_launch and bool(self.cfg.get("graph_rollout", True)) and torch.device(dev).type == "cuda" and hasattr(env, "_h") \
             and not getattr(env, "add_noise", False) and not getattr(getattr(env.cfg, "viewer", None), "record_states", False) \
             and not getattr(env, "push_interval", 0) and not getattr(env, "wrench_interval", 0)    # (a push, or a wrench window's start or end, is a launch the host decides per step: not in a replayed graph)

@@ -64,6 +64,9 @@ def main():
     ap.add_argument("--privileged-obs", action="store_true", default=False, dest="privileged_obs",
                     help="asymmetric actor-critic: the critic also sees every env's drawn physics parameters (friction, gains, payload, latency, "
                          "gravity, servo, torque limit, wrench) and the base height; the actor keeps the 66 observations (default: off)")
+    ap.add_argument("--privileged-rollout", action="store_true", default=False, dest="privileged_rollout",
+                    help="with privileged critic observations, collect the rollout as one launch with the policy in the env's wave instead of "
+                         "per-step launches; implies --privileged-obs (default: off)")
     ap.add_argument("--gpus", type=int, default=None, help="ranks (one per GPU); without torch.distributed.run, train.py starts them itself")
     args = ap.parse_args()
 
@@ -94,7 +97,7 @@ def main():
     log_root = "logs/nightmare_v3/"
     log_dir = f"logs/nightmare_v3/{datetime.datetime.now()}/"
     cfg_class = NightmareV3Config
-    if args.privileged_obs:
+    if args.privileged_obs or args.privileged_rollout:
         class cfg_class(NightmareV3Config):      # the optional attribute NightmareV3Env reads
             class env(NightmareV3Config.env):
                 privileged_obs = True
@@ -137,6 +140,8 @@ def main():
     lo, hi = shard_range(args.num_envs, rank, world)
     cfg.env.num_envs = hi - lo
     train_cfg.runner.resume = args.resume
+    if args.privileged_rollout:
+        train_cfg.runner.privileged_rollout = True
     seed = train_cfg.seed if args.seed is None else args.seed
     torch.manual_seed(seed + rank)
     env = NightmareV3Env(cfg, log_dir=log_dir, num_threads=args.num_threads, device=f"cuda:{local_rank}", seed=seed, env_id_offset=lo)
