@@ -384,6 +384,51 @@ int nm_get_base_wrench(nm_env* env, void* out_dev, void* stream);
 int nm_set_wrench_schedule(nm_env* env, int64_t interval_steps, int64_t duration_steps, const double max_force[3], const double max_torque[3],
                            uint64_t start_step);
 int nm_get_wrench_schedule(nm_env* env, int64_t* interval_steps, int64_t* duration_steps, double max_force[3], double max_torque[3], uint64_t* step);
+/* Per-env sensor model: observation latency and bias. There is no reference line: upstream's policy reads the exact state of the current
+ * step (envs/nightmare_v3_env.py:274-305) plus optional white noise; a real robot's IMU / state estimator and servo feedback arrive one
+ * to three control periods late and carry offsets that stay constant over an episode. The model is a pure function of the observation
+ * rows the step already files and sits between the step and whoever reads the observation; the physics and the rewards do not see it.
+ * Columns 0..8 (base lin vel, base ang vel, projected gravity) form the group `imu`, columns 12..47 (dof_pos, dof_vel) the group `joint`;
+ * columns 9..11 (commands) and 48..65 (previous actions) are passed through bit for bit, never delayed or biased.
+ * Each env carries two delays d_imu, d_joint in 0..3 whole env steps, a float32 bias row b[66] in observation units (already multiplied
+ * by the obs scale; zero in the pass-through columns), a history of its last 4 true observations and a count n of the observations pushed
+ * since the history was last cleared.
+ * Semantics: y_s is the observation the step produces at step s, after its own noise and its own clip - the "true" observation. After
+ * every full step, for every env: (1) push y_s, n <- n + 1; (2) a column c of group g reads
+ *   sensed[c] = clamp(y_{s - min(d_g, n - 1)}[c] + b[c], -clip_obs, +clip_obs)   (one float32 add, the step's float32 clip_obs)
+ * and a pass-through column sensed[c] = y_s[c]; (3) if the step's done flag is set, n <- 0 - after the read: the done step's own reading
+ * is delayed like any other, and the next step sees only itself. nm_reset clears n for the ids it resets; nm_create, nm_set_sensor and
+ * nm_draw_sensor clear it for all envs: a reading never reaches behind a clear. The model is float32 whatever the env's dtype.
+ * While the model is on, the sensed row is what nm_step, nm_rollout, nm_rollout_priv, nm_play and nm_step_tape file wherever they filed
+ * the observation before (the caller's buffer, the rollout storage, the observation record, the first 66 columns of the privileged row
+ * the asymmetric launch gathers - call nm_privileged_obs on the sensed row); the policy inside the K-step launches reads it; the true row
+ * of the last step stays in the env (nm_get_true_obs). Physics-only launches do not touch the model. Off is the default, and delays 0
+ * with bias 0 equal off under == in every output.
+ * nm_set_sensor: delays_dev is a DEVICE array [N,2] int32 (d_imu, d_joint) or NULL (= zeros), bias_dev a DEVICE array [N,66] float32 or
+ *   NULL (= zeros), copied on `stream`; both NULL switch the model off (nothing is freed). It clears the history. Refused, named by
+ *   nm_last_error with the env and the column, before anything of the env changes (the arrays are read back and judged on the host, which
+ *   waits for `stream`): a delay outside 0..3, a non-finite bias, a non-zero bias in a pass-through column.
+ * nm_get_sensor: *on, and the delays / the bias into DEVICE arrays [N,2] int32 / [N,66] float32 on `stream` (any pointer may be NULL);
+ *   zeros while the model is off.
+ * nm_draw_sensor: delay[e][g] uniform on the integers [lo[g], hi[g]], lo + ((bits (hi - lo + 1)) >> 24); bias[e][c] = (2 u - 1)
+ *   float32(bias_max[k]) for a column of kind k (0 lin_vel, 1 ang_vel, 2 gravity, 3 dof_pos, 4 dof_vel; maxima in observation units),
+ *   u = bits 2^-24 in float32, zero in the pass-through columns; bits from the counter RNG keyed by (seed + "SENSO", global env id, word),
+ *   word = the column for a bias and 66 + g for a delay: sharding changes nothing. It switches the model on and clears the history.
+ *   Refused before the handle is looked at: lo < 0, lo > hi, hi > 3, a negative or non-finite maximum.
+ * nm_sensor_draw_values: the draw of the env with global id `global_env`, computed on the host by the function the kernel calls; no env,
+ *   no device.
+ * nm_get_sensor_state / nm_set_sensor_state: the history as HOST arrays, ring [N,4,66] float32 (slot n mod 4 takes the push of an env
+ *   whose count is n) and count [N] uint32, in the style of nm_get_servo_state (synchronous; zeros before the first use of the model).
+ * nm_get_true_obs: the true observation of the last step into a DEVICE array [N,66] float32 on `stream`; refused while the model is off
+ *   (the observation the step returned is then the true one). */
+int nm_set_sensor(nm_env* env, const int32_t* delays_dev, const float* bias_dev, void* stream);
+int nm_get_sensor(nm_env* env, int32_t* on, int32_t* delays_out_dev, float* bias_out_dev, void* stream);
+int nm_draw_sensor(nm_env* env, const int32_t lo[2], const int32_t hi[2], const double bias_max[5], void* stream);
+int nm_sensor_draw_values(uint64_t seed, int64_t global_env, const int32_t lo[2], const int32_t hi[2], const double bias_max[5], int32_t out_delays[2],
+                          float out_bias[NM_NUM_OBS]);
+int nm_get_sensor_state(nm_env* env, float* ring, uint32_t* count);
+int nm_set_sensor_state(nm_env* env, const float* ring, const uint32_t* count);
+int nm_get_true_obs(nm_env* env, float* out_dev, void* stream);
 /* Per-env rows re-drawn at every reset, from pools - the `mode="reset"` events of Isaac Lab, legged_gym's per-reset payload; it replaces
  * nothing upstream (the reference has one robot, one floor and ideal servos, and its reset_idx touches no model constant).
  * kind: 0 friction / gains [4] (mu, p_gain, kv, pad), 1 body rows [20], 2 actuation latency [1] (a 4-byte int in either dtype), 3 gravity

@@ -39,7 +39,9 @@ EXPORTS = ["nm_default_config", "nm_reward_name", "nm_last_error", "nm_create", 
            "nm_set_step_variant", "nm_get_step_variant", "nm_lane_selftest",
            "nm_set_reset_rows", "nm_get_reset_rows", "nm_set_reset_row_counts", "nm_get_reset_row_counts", "nm_reset_rows_pick",
            "nm_privileged_obs", "nm_ppo_sample_prefix",
-           "nm_rollout_supported_priv", "nm_rollout_priv", "nm_rollout_act_priv"]
+           "nm_rollout_supported_priv", "nm_rollout_priv", "nm_rollout_act_priv",
+           "nm_set_sensor", "nm_get_sensor", "nm_draw_sensor", "nm_sensor_draw_values", "nm_get_sensor_state", "nm_set_sensor_state",
+           "nm_get_true_obs"]
 
 
 class NmConfig(C.Structure):
@@ -237,6 +239,15 @@ def _bind(L, full):
         L.nm_set_wrench_schedule.argtypes = [vp, C.c_int64, C.c_int64, C.POINTER(C.c_double * 3), C.POINTER(C.c_double * 3), C.c_uint64]
         L.nm_get_wrench_schedule.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_double * 3), C.POINTER(C.c_double * 3),
                                              C.POINTER(C.c_uint64)]
+    if hasattr(L, "nm_set_sensor"):
+        i2, d5 = C.POINTER(C.c_int32 * 2), C.POINTER(C.c_double * 5)
+        L.nm_set_sensor.argtypes = [vp, vp, vp, vp]
+        L.nm_get_sensor.argtypes = [vp, C.POINTER(C.c_int32), vp, vp, vp]
+        L.nm_draw_sensor.argtypes = [vp, i2, i2, d5, vp]
+        L.nm_sensor_draw_values.argtypes = [C.c_uint64, C.c_int64, i2, i2, d5, i2, C.POINTER(C.c_float * NUM_OBS)]
+        L.nm_get_sensor_state.argtypes = [vp, vp, vp]
+        L.nm_set_sensor_state.argtypes = [vp, vp, vp]
+        L.nm_get_true_obs.argtypes = [vp, vp, vp]
     if not full:        # the measurement build holds the env entry points only
         return L
     L.nm_gae.argtypes = [vp, vp, vp, vp, C.c_int32, C.c_int32, C.c_float, C.c_float, vp, vp]

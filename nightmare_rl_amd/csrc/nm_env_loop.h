@@ -1,6 +1,6 @@
 // nm_env_loop.h - what the K-step launches k_env_rollout (nm_rollout_kernels.h), k_env_play (nm_play_kernels.h) and k_env_tape
 // (nm_tape_kernels.h) share: the wave index, the launch prologue, the episode books of the wave's two envs, the per-step update of the
-// env step's launch arguments, the push perturbation of a step (nm_push.h), the wrench schedule of a step (nm_wrench.h), the reset draw of a step (nm_reset_noise.h) and the re-draw of its per-env rows (nm_reset_rows.h). X below is the launch's own argument struct, RollArgs, PlayArgs or TapeArgs (nm_rollout.h): the helpers read
+// env step's launch arguments, the push perturbation of a step (nm_push.h), the wrench schedule of a step (nm_wrench.h), the reset draw of a step (nm_reset_noise.h), the re-draw of its per-env rows (nm_reset_rows.h) and the sensor model of a step (nm_sensor.h). X below is the launch's own argument struct, RollArgs, PlayArgs or TapeArgs (nm_rollout.h): the helpers read
 // the fields all carry (cur_ret, cur_len, fin3, to_step, st_sum, st_cnt, rec_log) and `if constexpr` on the struct's traits (kPlayBooks,
 // kStepRecord) decides what only some of them file.
 #pragma once
@@ -14,6 +14,7 @@
 #include "nm_reset_noise.h"
 #include "nm_reset_rows.h"
 #include "nm_rollout.h"
+#include "nm_sensor.h"
 #include "nm_wrench.h"
 
 namespace nmr {
@@ -158,6 +159,48 @@ __device__ __forceinline__ void step_reset_rows(const X* Xs, const nm::Args<floa
   if (__builtin_amdgcn_readfirstlane(Xs->rrows.on) == 0) return;
   const int mask = (int)(__builtin_amdgcn_ballot_w64(d > 0) & 3ull);
   if (mask) reset_rows_store(Xs, As, mask, wave);
+}
+// The sensor model of the step that just ended (nm_sensor.h; X::sensor), for the wave's two envs: the true row the step filed in the env's
+// true-obs buffer (where Args::obs points for the whole launch while the model is on) -> ring, count and the sensed row in `dst` [N,66]
+// (null: the descriptor's `out`, the env's own buffer). `d` is the done word of that step in lanes 0 / 1 (env 2 wave + lane), as
+// books_load leaves it. The 2 x 66 columns are split over the lanes in three rounds; an env past N on an odd last wave files nothing.
+// Called behind the wait at the head of the step function (or behind books_last, which waits): the step's observation and done stores,
+// issued by other lanes of this wave, have landed. Both counts are loaded before any round runs, and the store of a new count needs the
+// loaded value, so every lane has read the count by then; a delayed read takes another ring slot than the one the round pushes into.
+// The body ends with a wait of its own: the policy's (or priv_gather's) loads of the sensed row, by other lanes of this wave through
+// the same L1, come behind the stores, and so does the next step's push into the ring. Within a launch only the wave that owns the env
+// touches its ring and count; across launches, and against k_sensor, stream order covers it. The test is wave-uniform; the body is out
+// of line, like reset_noise_store: while the model is off the step pays one scalar compare, and the body's registers are nobody else's.
+template <class X>
+__device__ __noinline__ void sensor_store(const X* Xs, const nm::Args<float>* As, float* dst, int mask, int wave) {
+  const int lane = threadIdx.x, N = As->N;
+  mask = __builtin_amdgcn_readfirstlane(mask);
+  const nm::SensorDesc* dp = Xs->sensor.desc;
+  nm::SensorDesc D;
+  D.delay = simt::gld1(&dp->delay, 0); D.bias = simt::gld1(&dp->bias, 0); D.ring = simt::gld1(&dp->ring, 0); D.count = simt::gld1(&dp->count, 0);
+  D.true_obs = simt::gld1(&dp->true_obs, 0); D.out = simt::gld1(&dp->out, 0); D.clip_obs = simt::gld1(&dp->clip_obs, 0); D.pad = 0;
+  if (!dst) dst = D.out;
+  // (lanes 0 / 1 load the two counts, as books_load loads the done words: a per-lane address is a vector load, whose L1 sees this wave's stores)
+  const int nl = (int)simt::gld1((const uint32_t*)D.count, (size_t)min(wave * 2 + (lane & 1), N - 1));
+  const uint32_t n0 = (uint32_t)__builtin_amdgcn_readlane(nl, 0), n1 = (uint32_t)__builtin_amdgcn_readlane(nl, 1);
+#pragma unroll 1
+  for (int i = 0; i < (2 * nm::kNOBS + 63) / 64; i++) {
+    const int idx = lane + 64 * i, e = idx >= nm::kNOBS ? 1 : 0, c = idx - e * nm::kNOBS, env = wave * 2 + e;
+    if (idx < 2 * nm::kNOBS && env < N) nm::sensor_apply(D, (size_t)env, c, e ? n1 : n0, ((mask >> e) & 1) != 0, dst);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+template <class X>
+__device__ __forceinline__ void step_sensor(const X* Xs, const nm::Args<float>* As, float* dst, long long d, int wave) {
+  if (__builtin_amdgcn_readfirstlane(Xs->sensor.on) == 0) return;
+  sensor_store(Xs, As, dst, (int)(__builtin_amdgcn_ballot_w64(d > 0) & 3ull), wave);
+}
+// the same behind books_last, which keeps the done word to itself: lanes 0 / 1 load it again
+template <class X>
+__device__ __forceinline__ void step_sensor_last(const X* Xs, const nm::Args<float>* As, float* dst, int wave) {
+  if (__builtin_amdgcn_readfirstlane(Xs->sensor.on) == 0) return;
+  const long long d = simt::gld1(As->done, (size_t)min(wave * 2 + ((int)threadIdx.x & 1), As->N - 1));
+  sensor_store(Xs, As, dst, (int)(__builtin_amdgcn_ballot_w64(d > 0) & 3ull), wave);
 }
 // the books of the launch's last step (no policy step follows it)
 template <class X>

@@ -17,6 +17,7 @@
 #include "nm_reset_noise.h"
 #include "nm_reset_rows.h"
 #include "nm_rollout.h"
+#include "nm_sensor.h"
 #include "nm_wrench.h"
 
 static thread_local std::string g_err;
@@ -226,6 +227,14 @@ struct nm_env {
   virtual int set_reset_row_counts(const uint32_t* counts_host) = 0;
   virtual int get_reset_row_counts(uint32_t* counts_host) = 0;
   virtual int priv_obs(const float* obs, float* out, hipStream_t s) = 0;
+  // the sensor model (nm_sensor.h): on or off; its delays, bias, ring, counts and true-obs buffer are device memory of the env object
+  bool sensor_on = false;
+  virtual int set_sensor(const int32_t* delays, const float* bias, hipStream_t s) = 0;
+  virtual int get_sensor(int32_t* on, int32_t* delays_out, float* bias_out, hipStream_t s) = 0;
+  virtual int draw_sensor(const int32_t* lo, const int32_t* hi, const double* bias_max, hipStream_t s) = 0;
+  virtual int get_sensor_state(float* ring, uint32_t* count) = 0;
+  virtual int set_sensor_state(const float* ring, const uint32_t* count) = 0;
+  virtual int get_true_obs(float* out, hipStream_t s) = 0;
   virtual int rollout_priv(const nm_rollout_args* r, const nm_rollout_priv_args* pv, int act, hipStream_t s) = 0;
   virtual int rollout_act_priv(const float* flat, const float* rows, uint64_t seed, const int64_t* iter_dev, int step, int act, float* actions, float* logp,
                                float* values, float* mu, float* sigma, float* obs_store, float* row_store, hipStream_t s) = 0;
@@ -367,6 +376,7 @@ template <class real> struct Env : nm_env {
     HIPCHK(hipGetLastError());
     if (rnoise_on && launch_reset_noise(nullptr, idp, n, s)) return 1;     // the same envs' reset draw (nm_reset_noise.h)
     if (rrows_any() && launch_reset_rows(nullptr, idp, n, s)) return 1;    // and the re-draw of their per-env rows (nm_reset_rows.h)
+    if (sensor.count) HIPCHK(nm_launch_sensor_clear(sensor.count, idp, n, s));      // a reading never reaches behind a reset (nm_sensor.h)
     return finalize(ep_stats, nullptr, s);
   }
   int step(const float* actions, int64_t* eplen, float* obs, float* rew, int64_t* done, float* time_outs, float* ep_stats, int physics_only,
@@ -379,6 +389,7 @@ template <class real> struct Env : nm_env {
     a.cmd_u = cmd_u_on ? cmd_u_dev : nullptr;
     a.physics_only = physics_only;
     a.ep_stats = ep_stats; a.time_outs = time_outs; a.counters = counters_dev;
+    if (!physics_only && sensor_on) a.obs = sensor.true_obs;      // the sensor model (nm_sensor.h): the step files the true row, k_sensor below the caller's
     if (!physics_only) {
       a.noise_vec = noise_on ? noise_vec_dev : nullptr;
       a.noise_u = noise_on && noise_u_on ? noise_u_dev : nullptr;
@@ -430,6 +441,8 @@ template <class real> struct Env : nm_env {
     if (!physics_only && rnoise_on && launch_reset_noise(done, nullptr, N, s)) return 1;
     // per-env rows re-drawn at reset: the same decision on the device, for the kinds that have a pool (nm_reset_rows.h)
     if (!physics_only && rrows_any() && launch_reset_rows(done, nullptr, N, s)) return 1;
+    // the sensor model: the true row -> ring, count and the sensed row in the caller's buffer (nm_sensor.h)
+    if (!physics_only && sensor_on) HIPCHK(nm_launch_sensor(sensor, done, obs, N, s));
     return 0;
   }
   int d2h(const real* dev, double* host, size_t n) {
@@ -765,6 +778,118 @@ template <class real> struct Env : nm_env {
     HIPCHK(hipGetLastError());
     return 0;
   }
+  // ---- the sensor model (nm_sensor.h): delays, bias, ring, counts and the true-obs buffer, allocated (zeroed) at first use; `sensor` is the
+  // descriptor as the host holds it (k_sensor takes it by value), sensor_desc_dev the copy the K-step kernels read, rewritten
+  // stream-ordered in front of a launch whenever the host's differs from what was last published (only `out` ever does)
+  nm::SensorDesc sensor = {};
+  nm::SensorDesc* sensor_desc_dev = nullptr;
+  float* sensor_out_published = nullptr;
+  bool sensor_published = false;
+  int sensor_reserve() {
+    if (sensor.count) return 0;
+    const size_t n_ = (size_t)N;
+    int32_t* dl = nullptr; float* bs = nullptr;
+    if (dalloc(&dl, n_ * nm::kSensorGroups) || dalloc(&bs, n_ * nm::kNOBS) || dalloc(&sensor.ring, n_ * nm::kSensorSlots * nm::kNOBS) ||
+        dalloc(&sensor.true_obs, n_ * nm::kNOBS) || dalloc(&sensor_desc_dev, 1) || dalloc(&sensor.count, n_))
+      return 1;
+    sensor.delay = dl; sensor.bias = bs;
+    sensor.clip_obs = (float)M.clip_obs;
+    HIPCHK(hipMemset(dl, 0, n_ * nm::kSensorGroups * sizeof(int32_t)));
+    HIPCHK(hipMemset(bs, 0, n_ * nm::kNOBS * sizeof(float)));
+    HIPCHK(hipMemset(sensor.ring, 0, n_ * nm::kSensorSlots * nm::kNOBS * sizeof(float)));
+    HIPCHK(hipMemset(sensor.true_obs, 0, n_ * nm::kNOBS * sizeof(float)));
+    HIPCHK(hipMemset(sensor.count, 0, n_ * sizeof(uint32_t)));
+    HIPCHK(hipDeviceSynchronize());
+    return 0;
+  }
+  // the sensor arguments of a K-step launch; out: the env's observation buffer of this launch
+  int kstep_sensor(nmr::SensorArgs& a, float* out, hipStream_t s) {
+    a = nmr::SensorArgs{};
+    if (!sensor_on) return 0;
+    sensor.out = out;
+    if (!sensor_published || sensor_out_published != out) {
+      HIPCHK(nm_launch_sensor_desc(sensor_desc_dev, sensor, s));
+      sensor_published = true; sensor_out_published = out;
+    }
+    a.desc = sensor_desc_dev; a.on = 1;
+    return 0;
+  }
+  int set_sensor(const int32_t* delays, const float* bias, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (!delays && !bias) { sensor_on = false; return 0; }      // off; nothing is freed, the model and its history keep what they hold
+    // the model is judged on the host before anything of the env changes
+    const size_t n_ = (size_t)N;
+    std::vector<int32_t> hd(delays ? n_ * nm::kSensorGroups : 0);
+    std::vector<float> hb(bias ? n_ * nm::kNOBS : 0);
+    HIPCHK(hipStreamSynchronize(s));
+    if (delays) HIPCHK(hipMemcpy(hd.data(), delays, hd.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (bias) HIPCHK(hipMemcpy(hb.data(), bias, hb.size() * sizeof(float), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < hd.size(); i++)
+      if (hd[i] < 0 || hd[i] > nm::kSensorMaxDelay)
+        return fail("nm_set_sensor: env " + std::to_string(i / nm::kSensorGroups) + " column " + std::to_string(i % nm::kSensorGroups) + " (" +
+                    (i % nm::kSensorGroups ? "joint" : "imu") + " delay): " + std::to_string(hd[i]) + " outside 0.." + std::to_string(nm::kSensorMaxDelay) + " env steps");
+    for (size_t i = 0; i < hb.size(); i++) {
+      const int c = (int)(i % nm::kNOBS);
+      if (!std::isfinite(hb[i])) return fail("nm_set_sensor: env " + std::to_string(i / nm::kNOBS) + " column " + std::to_string(c) + ": the bias is not finite");
+      if (nm::sensor_col_group(c) < 0 && hb[i] != 0.0f)
+        return fail("nm_set_sensor: env " + std::to_string(i / nm::kNOBS) + " column " + std::to_string(c) + ": a bias in a pass-through column (commands 9..11, actions 48..65)");
+    }
+    if (sensor_reserve()) return 1;
+    if (delays) HIPCHK(hipMemcpyAsync((void*)sensor.delay, delays, hd.size() * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    else HIPCHK(hipMemsetAsync((void*)sensor.delay, 0, n_ * nm::kSensorGroups * sizeof(int32_t), s));
+    if (bias) HIPCHK(hipMemcpyAsync((void*)sensor.bias, bias, hb.size() * sizeof(float), hipMemcpyDeviceToDevice, s));
+    else HIPCHK(hipMemsetAsync((void*)sensor.bias, 0, n_ * nm::kNOBS * sizeof(float), s));
+    HIPCHK(hipMemsetAsync(sensor.count, 0, n_ * sizeof(uint32_t), s));      // the history is cleared
+    sensor_on = true;
+    return 0;
+  }
+  int get_sensor(int32_t* on, int32_t* delays_out, float* bias_out, hipStream_t s) override {
+    if (on) *on = sensor_on ? 1 : 0;
+    const bool have = sensor_on && sensor.count;
+    return words_out(delays_out, have ? sensor.delay : nullptr, (size_t)N * nm::kSensorGroups, s) ||
+           words_out(bias_out, have ? sensor.bias : nullptr, (size_t)N * nm::kNOBS, s);
+  }
+  int draw_sensor(const int32_t* lo, const int32_t* hi, const double* bias_max, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (sensor_reserve()) return 1;
+    nm_sensor_draw_args a;
+    for (int g = 0; g < nm::kSensorGroups; g++) { a.lo[g] = lo[g]; a.hi[g] = hi[g]; }
+    for (int k = 0; k < nm::kSensorKinds; k++) a.bmax[k] = (float)bias_max[k];
+    HIPCHK(nm_launch_sensor_draw((int32_t*)sensor.delay, (float*)sensor.bias, N, A.seed, A.env_offset, a, s));
+    HIPCHK(hipMemsetAsync(sensor.count, 0, (size_t)N * sizeof(uint32_t), s));
+    sensor_on = true;
+    return 0;
+  }
+  int get_sensor_state(float* ring, uint32_t* count) override {
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipDeviceSynchronize());
+    const size_t n_ = (size_t)N, rw = n_ * nm::kSensorSlots * nm::kNOBS;
+    if (!sensor.count) {      // never allocated: zero, as at construction
+      if (ring) memset(ring, 0, rw * sizeof(float));
+      if (count) memset(count, 0, n_ * sizeof(uint32_t));
+      return 0;
+    }
+    if (ring) HIPCHK(hipMemcpy(ring, sensor.ring, rw * sizeof(float), hipMemcpyDeviceToHost));
+    if (count) HIPCHK(hipMemcpy(count, sensor.count, n_ * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return 0;
+  }
+  int set_sensor_state(const float* ring, const uint32_t* count) override {
+    HIPCHK(hipSetDevice(device));
+    HIPCHK(hipDeviceSynchronize());
+    if (!ring || !count) return fail("nm_set_sensor_state: the state is NULL");
+    if (sensor_reserve()) return 1;
+    const size_t n_ = (size_t)N;
+    HIPCHK(hipMemcpy(sensor.ring, ring, n_ * nm::kSensorSlots * nm::kNOBS * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(sensor.count, count, n_ * sizeof(uint32_t), hipMemcpyHostToDevice));
+    return 0;
+  }
+  int get_true_obs(float* out, hipStream_t s) override {
+    HIPCHK(hipSetDevice(device));
+    if (!out) return fail("nm_get_true_obs: out_dev is NULL");
+    if (!sensor_on) return fail("nm_get_true_obs: the sensor model is off (the observation the step returned is the true one)");
+    HIPCHK(hipMemcpyAsync(out, sensor.true_obs, (size_t)N * nm::kNOBS * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
+  }
   // ---- the privileged critic row (nm_priv_obs.h): obs [N, 66] and what the block and the state hold now -> out [N, 89], on `s` behind
   // whatever it carries; the regions are null while the block does not exist (the kernel then writes the default rows' values)
   int priv_obs(const float* obs, float* out, hipStream_t s) override {
@@ -849,6 +974,7 @@ template <class real> struct Env : nm_env {
     p.st_sum = roll_sum; p.st_cnt = roll_cnt; p.to_step = roll_to;
     p.rec_log = log; p.rec_done = log ? rec_done : nullptr; p.rec_env = rec_env;
     p.push = kstep_push(K); p.rnoise = kstep_rnoise(); p.rrows = kstep_rrows();
+    p.sensor = nmr::SensorArgs{};      // (the entry point fills it: kstep_sensor needs the launch's stream)
     rec_done_valid = log != nullptr;
   }
   int rollout(const nm_rollout_args* r, int act, hipStream_t s) override { return rollout_any("nm_rollout", r, nullptr, act, s); }
@@ -898,7 +1024,7 @@ template <class real> struct Env : nm_env {
         hipLaunchKernelGGL(k_priv_args, dim3(1), dim3(64), 0, s, priv_desc_dev, priv_args());
         HIPCHK(hipGetLastError());
       }
-      const nm::Args<real> a = kstep_args(K, nullptr, r->episode_length_dev, r->obs_final_dev, r->rew_dev, r->done_dev, log);
+      const nm::Args<real> a = kstep_args(K, nullptr, r->episode_length_dev, sensor_on ? sensor.true_obs : r->obs_final_dev, r->rew_dev, r->done_dev, log);
       nmr::RollPrivArgs R;
       if (pv) {
         R.K = K; R.wp = (const nmr::f32x4*)rollp_wp; R.bp = rollp_bp; R.stdv = r->params_flat_dev + PS::stdoff();
@@ -914,6 +1040,7 @@ template <class real> struct Env : nm_env {
       R.last_values = r->last_values_dev;
       R.rec_log = log;
       R.push = kstep_push(K); R.rnoise = kstep_rnoise(); R.rrows = kstep_rrows();
+      if (kstep_sensor(R.sensor, r->obs_final_dev, s)) return 1;
       R.wave_clock = A.dbg ? reinterpret_cast<unsigned long long*>(A.dbg) : nullptr;   // measurement: the debug buffer ([N,256] reals) takes the waves' clocks instead
       const nmr::TailArgs ta = kstep_tail(r, K, r->bootstrap_time_outs ? r->gamma : -1.0f, r->s_values, r->s_rewards);
       if (kstep_wrench(K, s)) return 1;
@@ -939,14 +1066,14 @@ template <class real> struct Env : nm_env {
       if (roll_reserve(K) || log_rows(K, &log)) return 1;
       if (!play_scratch && dalloc(&play_scratch, (size_t)N * 4 + 4)) return 1;
       if (roll_pack(r->params_flat_dev, s)) return 1;
-      const nm::Args<real> a = kstep_args(K, r->actions_dev, r->episode_length_dev, r->obs_dev, r->rew_dev, r->done_dev, log);
+      const nm::Args<real> a = kstep_args(K, r->actions_dev, r->episode_length_dev, sensor_on ? sensor.true_obs : r->obs_dev, r->rew_dev, r->done_dev, log);
       nmr::PlayArgs P;
       P.K = K; P.deterministic = r->deterministic != 0;
       P.wp = (const nmr::f32x4*)roll_wp; P.bp = roll_bp; P.stdv = r->params_flat_dev + RS::stdoff();
       P.seed = r->seed; P.iter_dev = r->iter_dev; P.step0 = r->step0;
       P.obs0 = r->obs0_dev; P.obs = r->obs_dev; P.actions = r->actions_dev;
       kstep_books(P, r, K, log);
-      if (kstep_wrench(K, s)) return 1;
+      if (kstep_sensor(P.sensor, r->obs_dev, s) || kstep_wrench(K, s)) return 1;
       if (nmr::launch_play(M_dev, a, P, kstep_tail(r, K), act, rows.level(), s)) return fail("nm_play: launch failed");
       return 0;
     }
@@ -966,12 +1093,12 @@ template <class real> struct Env : nm_env {
       real* log = nullptr;
       if (roll_reserve(K) || log_rows(K, &log)) return 1;
       if (!play_scratch && dalloc(&play_scratch, (size_t)N * 4 + 4)) return 1;
-      const nm::Args<real> a = kstep_args(K, r->actions_dev, r->episode_length_dev, r->obs_dev, r->rew_dev, r->done_dev, log);
+      const nm::Args<real> a = kstep_args(K, r->actions_dev, r->episode_length_dev, sensor_on ? sensor.true_obs : r->obs_dev, r->rew_dev, r->done_dev, log);
       nmr::TapeArgs T;
       T.K = K; T.tape = r->actions_dev;
       T.rec_obs = r->rec_obs_dev; T.rec_rew = r->rec_rew_dev; T.rec_dones = r->rec_done_dev;
       kstep_books(T, r, K, log);
-      if (kstep_wrench(K, s)) return 1;
+      if (kstep_sensor(T.sensor, r->obs_dev, s) || kstep_wrench(K, s)) return 1;
       if (nmr::launch_tape(M_dev, a, T, kstep_tail(r, K), rows.level(), s)) return fail("nm_step_tape: launch failed");
       // with an observation record every step filed its observation in its row: the env's own buffer receives the last one
       const size_t n_ = (size_t)N;
@@ -1553,6 +1680,56 @@ int nm_get_servo_state(nm_env* env, double* limited) {
 int nm_set_servo_state(nm_env* env, const double* limited) {
   NEED_ENV(env);
   return env->set_servo_state(limited);
+}
+// ---- the sensor model (nm_sensor.h): observation latency and bias between the step and whoever reads the observation
+static int sensor_draw_bad(const char* who, const int32_t* lo, const int32_t* hi, const double* bias_max) {
+  static const char* kGroup[nm::kSensorGroups] = {"imu", "joint"};
+  static const char* kKind[nm::kSensorKinds] = {"lin_vel", "ang_vel", "gravity", "dof_pos", "dof_vel"};
+  if (!lo || !hi || !bias_max) return fail(std::string(who) + ": NULL bounds");
+  for (int g = 0; g < nm::kSensorGroups; g++) {
+    if (lo[g] < 0) return fail(std::string(who) + ": lo < 0 for the " + kGroup[g] + " delay");
+    if (lo[g] > hi[g]) return fail(std::string(who) + ": lo > hi for the " + kGroup[g] + " delay");
+    if (hi[g] > nm::kSensorMaxDelay) return fail(std::string(who) + ": hi above " + std::to_string(nm::kSensorMaxDelay) + " env steps for the " + kGroup[g] + " delay");
+  }
+  for (int k = 0; k < nm::kSensorKinds; k++)
+    if (!(bias_max[k] >= 0.0) || !std::isfinite((float)bias_max[k])) return fail(std::string(who) + ": the maximum of " + kKind[k] + " must be finite and >= 0");
+  return 0;
+}
+int nm_set_sensor(nm_env* env, const int32_t* delays_dev, const float* bias_dev, void* stream) {
+  NEED_ENV(env);
+  return env->set_sensor(delays_dev, bias_dev, (hipStream_t)stream);
+}
+int nm_get_sensor(nm_env* env, int32_t* on, int32_t* delays_out_dev, float* bias_out_dev, void* stream) {
+  NEED_ENV(env);
+  return env->get_sensor(on, delays_out_dev, bias_out_dev, (hipStream_t)stream);
+}
+int nm_draw_sensor(nm_env* env, const int32_t lo[2], const int32_t hi[2], const double bias_max[5], void* stream) {
+  // the bounds are judged first, so a bad range is named whatever the handle is
+  if (sensor_draw_bad("nm_draw_sensor", lo, hi, bias_max)) return 1;
+  NEED_ENV(env);
+  return env->draw_sensor(lo, hi, bias_max, (hipStream_t)stream);
+}
+int nm_sensor_draw_values(uint64_t seed, int64_t global_env, const int32_t lo[2], const int32_t hi[2], const double bias_max[5], int32_t out_delays[2],
+                          float out_bias[NM_NUM_OBS]) {
+  if (sensor_draw_bad("nm_sensor_draw_values", lo, hi, bias_max)) return 1;
+  if (!out_delays || !out_bias) return fail("nm_sensor_draw_values: NULL output");
+  float bmax[nm::kSensorKinds];
+  for (int k = 0; k < nm::kSensorKinds; k++) bmax[k] = (float)bias_max[k];
+  for (int w = 0; w < nm::kSensorDrawWords; w++)
+    nm::sensor_draw(seed, (uint64_t)global_env, lo, hi, bmax, w, out_delays + (w < nm::kNOBS ? 0 : w - nm::kNOBS), out_bias + (w < nm::kNOBS ? w : 0));
+  return 0;
+}
+int nm_get_sensor_state(nm_env* env, float* ring, uint32_t* count) {
+  NEED_ENV(env);
+  return env->get_sensor_state(ring, count);
+}
+int nm_set_sensor_state(nm_env* env, const float* ring, const uint32_t* count) {
+  NEED_ENV(env);
+  return env->set_sensor_state(ring, count);
+}
+int nm_get_true_obs(nm_env* env, float* out_dev, void* stream) {
+  NEED_ENV(env);
+  return env->get_true_obs(out_dev, (hipStream_t)stream);
 }
 // The servo torque limit stands for MuJoCo's actuator forcerange: the clamp of mj_fwdActuation and, in mj_implicit (implicitfast), the
 // velocity derivative mjd_actuator_vel leaves out for an actuator whose force sits on its bound (level 6 of the step, nm_core.h stage A)

@@ -32,6 +32,7 @@ __device__ __noinline__ void play_step(float* xb, const PlayArgs* Ps, nm::Args<f
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // state rows, observation, reward / done / time-out of the previous step: stored
   BookRegs rec;
   if (t > 0) books_load(rec, Ps, As, wave);
+  if (t > 0) step_sensor(Ps, As, Ps->obs, rec.d, wave);      // the sensor model of step t - 1 (the step filed the true row where the launcher pointed it): the sensed row act t reads
   ActOut o{Ps->actions, nullptr, nullptr, nullptr, nullptr, nullptr};
   policy_wave<S, ACT, kPolicyPlay>(xb, Ps->wp, Ps->bp, Ps->stdv, t == 0 ? Ps->obs0 : (const float*)Ps->obs, As->N, wave, Ps->seed,
                                    (uint64_t)simt::gld1(Ps->iter_dev, 0) * 4096ull + Ps->step0 + (uint64_t)t, o, Ps->deterministic != 0);
@@ -60,6 +61,7 @@ __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_play(const nm::Mo
     nm::wave_step<float, 2, EP>(sh, Ms, As, wave);        // env.step: load, decimation x mj_step, epilogue - the code of k_env_step
   }
   books_last(&Ps, &As, K - 1, wave);
+  step_sensor_last(&Ps, &As, Ps.obs, wave);     // the last step's sensed row
 }
 
 template <int ACT>

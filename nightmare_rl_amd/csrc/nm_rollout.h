@@ -29,6 +29,7 @@
 #include "nm_sfor.h"
 
 namespace nm { template <class real> struct PrivObsArgs; }     // nm_priv_obs.h
+namespace nm { struct SensorDesc; }                            // nm_sensor.h
 namespace nmr {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -295,6 +296,15 @@ struct ResetRowsArgs {
   int pad;
 };
 static_assert(sizeof(ResetRowsArgs) == 24, "one small member of the K-step argument structs");
+// The sensor model inside a K-step launch (nm_sensor.h; step_sensor of nm_env_loop.h): delays, bias, ring, counts and the true-obs buffer
+// live behind a descriptor in device memory of the env object, for the same reason. While `on`, the launcher points Args::obs at the
+// true-obs buffer for every step of the launch, and the kernels leave it there.
+struct SensorArgs {
+  const nm::SensorDesc* desc;
+  int on;                       // 0 = the model is off: desc is not read
+  int pad;
+};
+static_assert(sizeof(SensorArgs) == 16, "one small member of the K-step argument structs");
 // ---- the K-step launch (kernels in nm_rollout.hip - a translation unit of its own, so that the code generation of k_env_step in
 // nm_hip.hip is not touched by a second kernel around the same physics; host launchers below)
 struct RollArgs {
@@ -313,6 +323,7 @@ struct RollArgs {
   PushArgs push;
   ResetNoiseArgs rnoise;
   ResetRowsArgs rrows;
+  SensorArgs sensor;
   // what the episode books of nm_env_loop.h file for this launch: kPlayBooks = per-env return sums + the logged env's reset flag (else the
   // rollout's storage rows), kStepRecord = optional [K,N] reward / done rows
   static constexpr bool kPlayBooks = false, kStepRecord = false;
@@ -327,7 +338,7 @@ struct RollPrivArgs : RollArgs {
   float* priv_final;            // [N,kPrivRow]: the row after the last step
   float* s_priv;                // [K,N,kPrivRow]: storage, row t = what act t saw
 };
-static_assert(sizeof(RollPrivArgs) == sizeof(RollArgs) + 32, "a few pointers only: the symmetric level-7 kernel leaves 584 B of the 20,480 B a workgroup may use at two waves per SIMD");
+static_assert(sizeof(RollPrivArgs) == sizeof(RollArgs) + 32, "a few pointers only: the symmetric level-7 kernel leaves 568 B of the 20,480 B a workgroup may use at two waves per SIMD");
 constexpr int kRecRow = 50;            // qpos 25 | qvel 24 | bad-state resets of the step (what wave_step files through Args::rec)
 // k_env_play (nm_play_kernels.h): K x [policy on the observation the previous step left, env.step], nothing collected - reference play.py:118-132
 struct PlayArgs {
@@ -345,6 +356,7 @@ struct PlayArgs {
   PushArgs push;
   ResetNoiseArgs rnoise;
   ResetRowsArgs rrows;
+  SensorArgs sensor;
   static constexpr bool kPlayBooks = true, kStepRecord = false;
 };
 // k_env_tape (nm_tape_kernels.h): K x env.step with the actions of step t read from row t of a [K,N,18] tape - no policy, no sampling
@@ -363,6 +375,7 @@ struct TapeArgs {
   PushArgs push;
   ResetNoiseArgs rnoise;
   ResetRowsArgs rrows;
+  SensorArgs sensor;
   static constexpr bool kPlayBooks = true, kStepRecord = true;
 };
 struct TailArgs {

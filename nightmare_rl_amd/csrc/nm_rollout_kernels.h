@@ -34,13 +34,15 @@ __device__ __noinline__ void policy_step(float* xb, const RollArgs* Rs, nm::Args
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // state rows, observation, reward / done / time-out of the previous step: stored
   BookRegs rec;
   if (t > 0) books_load(rec, Rs, As, wave);          // issued before the observation loads below: they return together
+  if (t > 0) step_sensor(Rs, As, Rs->s_obs + so * nm::kNOBS, rec.d, wave);      // the sensor model of step t - 1: the sensed row into the storage row act t reads
   ActOut o{Rs->s_actions + so * nm::kNU, Rs->s_logp + so, Rs->s_values + so, Rs->s_mu + so * nm::kNU, Rs->s_sigma + so * nm::kNU, t == 0 ? Rs->s_obs : nullptr};
   // the observation is the one this wave's previous step wrote into the storage row of step t
   policy_wave<S, ACT>(xb, Rs->wp, Rs->bp, Rs->stdv, t == 0 ? Rs->obs0 : Rs->s_obs + so * nm::kNOBS, N, wave, Rs->seed, (uint64_t)simt::gld1(Rs->iter_dev, 0) * 4096ull + (uint64_t)t, o);
   if (t > 0) { books_file(rec, Rs, As, t - 1, wave); step_reset_noise(Rs, As, rec.d, wave); step_reset_rows(Rs, As, rec.d, wave); }   // the reset draw of step t - 1, before the push of step t
   if (threadIdx.x == 0) {
     As->actions = o.actions;
-    As->obs = t + 1 < Rs->K ? Rs->s_obs + (so + N) * nm::kNOBS : Rs->obs_final;     // the step files its observation where the next act reads it
+    // the step files its observation where the next act reads it - or, while the sensor model is on, where the launcher pointed it: the true-obs buffer
+    if (Rs->sensor.on == 0) As->obs = t + 1 < Rs->K ? Rs->s_obs + (so + N) * nm::kNOBS : Rs->obs_final;
     step_args(As, Rs, t, noise0);
   }
   step_push(Rs, As, t, wave);
@@ -75,6 +77,7 @@ __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_rollout(const nm:
     nm::wave_step<float, 2, EP>(sh, Ms, As, wave);        // env.step: load, decimation x mj_step, epilogue - the code of k_env_step
   }
   books_last(&Rs, &As, K - 1, wave);
+  step_sensor_last(&Rs, &As, Rs.obs_final, wave);     // the last step's sensed row, in front of the value of it
   if (Rs.last_values) value_last<S, ACT>(xb, &Rs, &As, wave);
   if (Rs.wave_clock && threadIdx.x == 0) Rs.wave_clock[2 * wave + 1] = __builtin_amdgcn_s_memtime();
 }
@@ -166,6 +169,7 @@ __device__ __noinline__ void policy_step(float* xb, const RollPrivArgs* Rs, nm::
     BookRegs rec;
     books_load(rec, Rs, As, wave);
     books_file(rec, Rs, As, t - 1, wave); step_reset_noise(Rs, As, rec.d, wave); step_reset_rows(Rs, As, rec.d, wave);
+    step_sensor(Rs, As, Rs->s_obs + so * nm::kNOBS, rec.d, wave);      // the sensor model of step t - 1: the gather below reads the sensed row
     priv_gather(xb, Rs->desc, Rs->s_obs + so * nm::kNOBS, Rs->s_priv + so * nm::kPrivRow, N, wave);
   } else {
     priv_first(xb, Rs->priv0, Rs->s_priv, Rs->s_obs, N, wave);
@@ -174,7 +178,7 @@ __device__ __noinline__ void policy_step(float* xb, const RollPrivArgs* Rs, nm::
   policy_wave<S, ACT, kPolicyFull, false>(xb, Rs->wp, Rs->bp, Rs->stdv, nullptr, N, wave, Rs->seed, (uint64_t)simt::gld1(Rs->iter_dev, 0) * 4096ull + (uint64_t)t, o);
   if (threadIdx.x == 0) {
     As->actions = o.actions;
-    As->obs = t + 1 < Rs->K ? Rs->s_obs + (so + N) * nm::kNOBS : Rs->obs_final;
+    if (Rs->sensor.on == 0) As->obs = t + 1 < Rs->K ? Rs->s_obs + (so + N) * nm::kNOBS : Rs->obs_final;      // (on: the true-obs buffer, set by the launcher)
     step_args(As, Rs, t, noise0);
   }
   step_push(Rs, As, t, wave);
@@ -210,6 +214,7 @@ __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_rollout(const nm:
     nm::wave_step<float, 2, EP>(sh, Ms, As, wave);
   }
   books_last(&Rs, &As, K - 1, wave);
+  step_sensor_last(&Rs, &As, Rs.obs_final, wave);     // the last step's sensed row, in front of the final gather
   value_last<S, ACT>(xb, &Rs, &As, wave);
   if (Rs.wave_clock && threadIdx.x == 0) Rs.wave_clock[2 * wave + 1] = __builtin_amdgcn_s_memtime();
 }

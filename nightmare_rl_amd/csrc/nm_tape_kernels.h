@@ -30,11 +30,13 @@ __device__ __noinline__ void tape_step(const TapeArgs* Ts, nm::Args<float>* As, 
     books_file(rec, Ts, As, t - 1, wave);
     step_reset_noise(Ts, As, rec.d, wave);           // the reset draw of step t - 1, before the push of step t
     step_reset_rows(Ts, As, rec.d, wave);            // and the re-draw of its per-env rows
+    // the sensor model of step t - 1: the sensed row into its record row, or (null) into the env's own buffer
+    step_sensor(Ts, As, Ts->rec_obs ? Ts->rec_obs + (size_t)(t - 1) * As->N * nm::kNOBS : nullptr, rec.d, wave);
   }
   if (threadIdx.x == 0) {
     const size_t so = (size_t)t * As->N;
     As->actions = Ts->tape + so * nm::kNU;
-    if (Ts->rec_obs) As->obs = Ts->rec_obs + so * nm::kNOBS;
+    if (Ts->rec_obs && Ts->sensor.on == 0) As->obs = Ts->rec_obs + so * nm::kNOBS;      // (sensor model on: the true-obs buffer, set by the launcher)
     step_args(As, Ts, t, noise0);
   }
   step_push(Ts, As, t, wave);
@@ -58,6 +60,7 @@ __global__ void __launch_bounds__(64, NM_WAVES_PER_SIMD) k_env_tape(const nm::Mo
     nm::wave_step<float, 2, EP>(sh, Ms, As, wave);        // env.step: load, decimation x mj_step, epilogue - the code of k_env_step
   }
   books_last(&Ts, &As, K - 1, wave);
+  step_sensor_last(&Ts, &As, Ts.rec_obs ? Ts.rec_obs + (size_t)(K - 1) * As.N * nm::kNOBS : nullptr, wave);     // the last step's sensed row
 }
 
 int tape_kernel(const nm::Model<float>* M_dev, const nm::Args<float>& a, const TapeArgs& T, int level, hipStream_t s) {

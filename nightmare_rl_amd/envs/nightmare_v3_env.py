@@ -39,6 +39,10 @@ Differences a caller can observe (all documented in DESIGN.md):
   * and external_wrench with wrench_interval_s / wrench_duration_s / max_wrench_force / max_wrench_torque: a random force and torque on
     the base body, MuJoCo's xfrc_applied, held for wrench_duration_s out of every wrench_interval_s (set_wrench_schedule; a constant
     wrench: set_base_wrench). It acts through the physics and the contact solver, unlike a push; the reference applies none
+  * and randomize_obs_latency with imu_latency_range / joint_latency_range (whole env steps, at most 3), randomize_sensor_bias with
+    sensor_bias (maxima per kind, physical units): the per-env sensor model - the IMU and joint columns of the observation arrive late
+    and carry a constant offset, in step(), policy_rollout, policy_play and step_tape alike (set_sensor_model, draw_sensor_model),
+    drawn once at construction; the commands and the previous actions are never touched, and true_observations() is the step's own row
 """
 import ctypes as C
 import numpy as np
@@ -167,6 +171,47 @@ def latency_config(cfg):
     randomize_action_latency needs action_latency_range; a range that is not two integers 0 <= lo <= hi is a ValueError (the upper limit,
     three env steps, is the library's to judge: it depends on the decimation)."""
     return _switched(getattr(cfg, "domain_rand", None), "randomize_action_latency", "action_latency_range", lowest=0, whole=True)
+
+
+def sensor_config(cfg):
+    """(imu_latency_range, joint_latency_range, bias_max) of the sensor model from the optional cfg.domain_rand: what draw_sensor_model
+    takes. Each range is a (lo, hi) pair of whole env steps or None, bias_max a dict {kind: maximum absolute offset in OBSERVATION units}
+    or None. randomize_obs_latency needs imu_latency_range and/or joint_latency_range (integers 0 <= lo <= hi; the upper limit, three env
+    steps, is the library's to judge); randomize_sensor_bias needs sensor_bias, a class or dict of any of lin_vel, ang_vel, gravity,
+    dof_pos, dof_vel as finite maxima >= 0 in physical units, which are multiplied here by cfg.normalization.obs_scales (gravity, a unit
+    vector's components, has no scale). Anything else is a ValueError."""
+    dr = getattr(cfg, "domain_rand", None)
+    imu = joint = bias = None
+    if getattr(dr, "randomize_obs_latency", False):
+        imu = _range(dr, "imu_latency_range", lowest=0, whole=True)
+        joint = _range(dr, "joint_latency_range", lowest=0, whole=True)
+        if imu is None and joint is None:
+            raise ValueError("cfg.domain_rand.randomize_obs_latency needs imu_latency_range or joint_latency_range")
+    if getattr(dr, "randomize_sensor_bias", False):
+        sb = getattr(dr, "sensor_bias", None)
+        if sb is None:
+            raise ValueError("cfg.domain_rand.randomize_sensor_bias needs sensor_bias")
+        items = dict(sb) if isinstance(sb, dict) else {k: getattr(sb, k) for k in dir(sb) if not k.startswith("_")}
+        unknown = sorted(set(items) - set(SENSOR_BIAS_KINDS))
+        if unknown:
+            raise ValueError(f"cfg.domain_rand.sensor_bias: unknown kinds {unknown} (known: {list(SENSOR_BIAS_KINDS)})")
+        if not items:
+            raise ValueError("cfg.domain_rand.sensor_bias must name at least one of " + ", ".join(SENSOR_BIAS_KINDS))
+        scales = getattr(getattr(cfg, "normalization", None), "obs_scales", None)
+        bias = {}
+        for k, v in items.items():
+            try:
+                v = float(v)
+            except (TypeError, ValueError):
+                raise ValueError(f"cfg.domain_rand.sensor_bias.{k} must be a number") from None
+            if not (np.isfinite(v) and v >= 0):
+                raise ValueError(f"cfg.domain_rand.sensor_bias.{k} must be finite and >= 0")
+            bias[k] = v * (1.0 if k == "gravity" else float(getattr(scales, k)))
+    return imu, joint, bias
+
+
+SENSOR_BIAS_KINDS = ("lin_vel", "ang_vel", "gravity", "dof_pos", "dof_vel")      # nm_sensor.h sensor_col_kind: columns 0..2, 3..5, 6..8, 12..29, 30..47
+SENSOR_MAX_DELAY, SENSOR_SLOTS = 3, 4                                            # nm_sensor.h kSensorMaxDelay, kSensorSlots
 
 
 def servo_config(cfg):
@@ -476,6 +521,7 @@ class NightmareV3Env:
         torque_limit, torque_range = torque_config(cfg)
         resample_size = resample_config(cfg)
         wrench_sched = wrench_config(cfg, self.dt)
+        sensor_ranges = sensor_config(cfg)
         # reward table: zero scales dropped, the rest x dt (reference :123-128). Every name the reference has a _reward_ function
         # for (:399-497) is compiled; a name without one (`collision`, `feet_stumble`, config :95-96) fails like upstream's getattr.
         names = [L.nm_reward_name(i).decode() for i in range(_lib.NUM_REWARDS)]
@@ -587,6 +633,9 @@ class NightmareV3Env:
         self.wrench_interval = 0
         if wrench_sched is not None:
             self.set_wrench_schedule(*wrench_sched)
+        # the sensor model - observation latency and bias (optional cfg.domain_rand; no reference line): drawn once, here
+        if any(r is not None for r in sensor_ranges):
+            self.draw_sensor_model(*sensor_ranges)
         # randomised reset states (optional cfg.domain_rand; no reference line): on before the first reset(), whose reset_idx(all) is
         # draw 0 of every env
         if reset_ranges is not None:
@@ -1081,6 +1130,90 @@ class NightmareV3Env:
         if a.shape != (self.num_envs, 18):
             raise ValueError("set_servo_state: [num_envs, 18]")
         self._ck(self._L.nm_set_servo_state(self._h, a.ctypes.data))
+
+    # ------------------------------------------------------------------ the sensor model (nm_sensor.h; no reference line)
+    def set_sensor_model(self, imu_delay=None, joint_delay=None, bias=None):
+        """Per-env observation latency and bias (nm_set_sensor; include/nightmare_hip.h states the semantics): columns 0..8 of the
+        observation (base velocities, projected gravity) arrive imu_delay[e] whole env steps late, columns 12..47 (dof_pos, dof_vel)
+        joint_delay[e] steps late, 0 <= d <= 3, and both carry the constant offset bias[e] ([66] float32, observation units, zero in the
+        command and action columns, which are never delayed or biased). What step(), get_observations(), policy_rollout, policy_play and
+        step_tape hand out, what the policy inside the launches reads and what the storage keeps is then the sensed row;
+        true_observations() is the step's own. imu_delay / joint_delay: num_envs integers, one integer for every env, or None = 0;
+        bias: [num_envs, 66], one row [66] for every env, or None = 0. All three None: off. Setting the model clears its history."""
+        N, dev = self.num_envs, self.device
+        if imu_delay is None and joint_delay is None and bias is None:
+            self._rows_keep["sensor"] = None
+            self._ck(self._L.nm_set_sensor(self._h, None, None, self._stream()))
+            return
+        cols = []
+        for name, d in (("imu_delay", imu_delay), ("joint_delay", joint_delay)):
+            a = np.asarray(0 if d is None else (d.detach().cpu().numpy() if torch.is_tensor(d) else d))
+            if a.size not in (1, N) or not np.array_equal(a, np.round(a)):
+                raise ValueError(f"set_sensor_model: {name} must be one whole number or num_envs of them")
+            cols.append(np.broadcast_to(a.reshape(-1), (N,)).astype(np.int32))
+        dl = torch.from_numpy(np.ascontiguousarray(np.stack(cols, axis=1))).to(dev)
+        bt = None
+        if bias is not None:
+            b = torch.as_tensor(bias, dtype=torch.float32)
+            if tuple(b.shape) not in ((self.num_obs,), (N, self.num_obs)):
+                raise ValueError(f"set_sensor_model: bias must be [{self.num_obs}] or [{N}, {self.num_obs}]")
+            bt = b.expand(N, self.num_obs).to(dev).contiguous()
+        self._ck(self._L.nm_set_sensor(self._h, C.c_void_p(dl.data_ptr()), None if bt is None else C.c_void_p(bt.data_ptr()), self._stream()))
+        self._rows_keep["sensor"] = (dl, bt)
+
+    def sensor_model(self):
+        """{'on': bool, 'imu_delay': int32 [num_envs], 'joint_delay': int32 [num_envs], 'bias': float32 [num_envs, 66]} on the env's device
+        (nm_get_sensor); zeros while the model is off."""
+        on = C.c_int32(0)
+        dl = torch.empty((self.num_envs, 2), dtype=torch.int32, device=self.device)
+        b = torch.empty((self.num_envs, self.num_obs), dtype=torch.float32, device=self.device)
+        self._ck(self._L.nm_get_sensor(self._h, C.byref(on), C.c_void_p(dl.data_ptr()), C.c_void_p(b.data_ptr()), self._stream()))
+        return {"on": bool(on.value), "imu_delay": dl[:, 0].contiguous(), "joint_delay": dl[:, 1].contiguous(), "bias": b}
+
+    def draw_sensor_model(self, imu_latency_range=None, joint_latency_range=None, bias_max=None):
+        """Draw every env's delays and bias on the device (nm_draw_sensor) and switch the model on: each delay uniform on the integers of
+        its (lo, hi) range (None: 0), each bias column uniform in +-bias_max[kind] (a dict of any of lin_vel, ang_vel, gravity, dof_pos,
+        dof_vel, in observation units; a missing kind or None: 0). Keyed by the global env id: shards of one population draw what the whole
+        would. Returns what sensor_model() then reports."""
+        lo, hi = (C.c_int32 * 2)(), (C.c_int32 * 2)()
+        for g, (name, r) in enumerate((("imu_latency_range", imu_latency_range), ("joint_latency_range", joint_latency_range))):
+            a, b = (0, 0) if r is None else r
+            if int(a) != a or int(b) != b:
+                raise ValueError(f"draw_sensor_model: {name}: whole env steps")
+            lo[g], hi[g] = int(a), int(b)
+        bm = dict(bias_max or {})
+        unknown = sorted(set(bm) - set(SENSOR_BIAS_KINDS))
+        if unknown:
+            raise ValueError(f"draw_sensor_model: unknown bias kinds {unknown} (known: {list(SENSOR_BIAS_KINDS)})")
+        mx = (C.c_double * 5)(*[float(bm.get(k, 0.0)) for k in SENSOR_BIAS_KINDS])
+        self._ck(self._L.nm_draw_sensor(self._h, C.byref(lo), C.byref(hi), C.byref(mx), self._stream()))
+        return self.sensor_model()
+
+    def sensor_state(self):
+        """(ring float32 [num_envs, 4, 66], count uint32 [num_envs]) numpy: every env's last true observations - slot n % 4 takes the push
+        of an env whose count is n - and the number pushed since the history was last cleared (nm_get_sensor_state). A checkpoint's content."""
+        ring = np.zeros((self.num_envs, SENSOR_SLOTS, self.num_obs), np.float32)
+        count = np.zeros(self.num_envs, np.uint32)
+        self._ck(self._L.nm_get_sensor_state(self._h, ring.ctypes.data_as(C.c_void_p), count.ctypes.data_as(C.c_void_p)))
+        return ring, count
+
+    def set_sensor_state(self, ring, count=None):
+        """Overwrite the history (what sensor_state() returns, as two arguments or as its tuple): checkpoints and tests."""
+        if count is None:
+            ring, count = ring
+        r, k = np.ascontiguousarray(ring, np.float32), np.ascontiguousarray(count, np.uint32).reshape(-1)
+        if r.shape != (self.num_envs, SENSOR_SLOTS, self.num_obs) or k.size != self.num_envs:
+            raise ValueError(f"set_sensor_state: ring [{self.num_envs}, {SENSOR_SLOTS}, {self.num_obs}] and count [{self.num_envs}]")
+        self._ck(self._L.nm_set_sensor_state(self._h, r.ctypes.data_as(C.c_void_p), k.ctypes.data_as(C.c_void_p)))
+
+    def true_observations(self):
+        """float32 [num_envs, 66], a fresh tensor: the observation the last step itself produced, before the sensor model
+        (nm_get_true_obs); while the model is off, a copy of get_observations()."""
+        if not self.sensor_model()["on"]:
+            return self.obs_buf.clone()
+        out = torch.empty((self.num_envs, self.num_obs), dtype=torch.float32, device=self.device)
+        self._ck(self._L.nm_get_true_obs(self._h, C.c_void_p(out.data_ptr()), self._stream()))
+        return out
 
     def _record_state(self):
         # reference :261-272: when env 0 resets, dump what was logged so far, then log (time, qpos, qvel, act) of env 0

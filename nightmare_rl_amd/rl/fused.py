@@ -145,7 +145,8 @@ class FusedCollector:
     def can_rollout(self, env):
         """Can the whole rollout run as ONE launch inside the env's own waves (nm_rollout)? Needs this repo's fp32 env on the same device,
         networks of the compiled shape next to a FusedUpdate (its flat parameter vector is what the kernel reads), no privileged observations.
-        The env's state log (cfg.viewer.record_states) is kept inside the launch and is no reason to leave it."""
+        The env's state log (cfg.viewer.record_states) is kept inside the launch and is no reason to leave it; nor is the env's sensor model
+        (set_sensor_model): the wave applies it between two steps."""
         if self.update is None or not hasattr(env, "policy_rollout") or getattr(env, "_dtype", None) != _lib.DTYPE_F32:
             return False
         if env.num_envs != self.N or torch.device(env.device) != self.device or env.get_privileged_observations() is not None:

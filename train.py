@@ -46,6 +46,12 @@ def main():
                     help="where the added mass sits: each coordinate in the base body frame drawn once from U[-R, R) m (default: the base origin)")
     ap.add_argument("--latency-range", type=int, nargs=2, default=None, metavar=("LO", "HI"), dest="latency_range",
                     help="per-env actuation latency in physics substeps, drawn once from the integers LO..HI, at most 3 x decimation (default: none)")
+    ap.add_argument("--obs-latency-range", type=int, nargs=2, default=None, metavar=("LO", "HI"), dest="obs_latency_range",
+                    help="sensor model: per-env observation latency of the IMU and of the joint feedback in whole env steps, each drawn once from "
+                         "the integers LO..HI, at most 3 (default: none)")
+    ap.add_argument("--sensor-bias", type=str, nargs="+", default=None, metavar="KIND=MAX", dest="sensor_bias",
+                    help="sensor model: per-env constant observation offsets, each column of KIND (lin_vel, ang_vel, gravity, dof_pos, dof_vel) drawn "
+                         "once from U[-MAX, MAX) in physical units (default: none)")
     ap.add_argument("--reset-dof-pos", type=float, default=0.0, metavar="R", dest="reset_dof_pos",
                     help="randomised reset states: every reset draws each joint angle from U[-R, R) rad around the default pose (0 = off, the default)")
     ap.add_argument("--reset-vel", type=float, default=0.0, metavar="V", dest="reset_vel",
@@ -111,8 +117,17 @@ def main():
         ap.error("--wrench-interval-s must not be negative")
     if args.wrench_interval_s > 0 and args.wrench_force is None and args.wrench_torque is None:
         ap.error("--wrench-interval-s needs --wrench-force or --wrench-torque")
+    sensor_bias = {}
+    for item in args.sensor_bias or []:
+        kind, sep, val = item.partition("=")
+        try:
+            sensor_bias[kind] = float(val)
+        except ValueError:
+            sep = ""
+        if not sep or kind not in ("lin_vel", "ang_vel", "gravity", "dof_pos", "dof_vel"):
+            ap.error(f"--sensor-bias takes KIND=MAX with KIND one of lin_vel, ang_vel, gravity, dof_pos, dof_vel, got {item!r}")
     if (args.push_interval_s > 0 or args.wrench_interval_s > 0 or args.friction_range or args.gain_range or args.added_mass_range or args.com_range is not None or args.latency_range
-            or reset_noise):
+            or reset_noise or args.obs_latency_range or sensor_bias):
         class domain_rand:      # the optional class NightmareV3Env reads
             push_robots, push_interval_s, max_push_vel_xy = args.push_interval_s > 0, args.push_interval_s, args.push_vel
             external_wrench, wrench_interval_s = args.wrench_interval_s > 0, args.wrench_interval_s
@@ -125,11 +140,15 @@ def main():
             randomize_com_displacement = args.com_range is not None
             com_displacement_range = None if args.com_range is None else (-args.com_range, args.com_range)
             randomize_action_latency, action_latency_range = args.latency_range is not None, args.latency_range
+            randomize_obs_latency = args.obs_latency_range is not None
+            imu_latency_range = joint_latency_range = args.obs_latency_range
+            randomize_sensor_bias = bool(sensor_bias)
             randomize_reset_state = reset_noise
             reset_dof_pos_range = (-args.reset_dof_pos, args.reset_dof_pos)
             reset_base_lin_vel_range = reset_base_ang_vel_range = reset_dof_vel_range = (-args.reset_vel, args.reset_vel)
             resample_on_reset = args.resample_on_reset is not None
             resample_pool_size = args.resample_on_reset if args.resample_on_reset is not None else 1024
+        domain_rand.sensor_bias = sensor_bias
         cfg.domain_rand = domain_rand
     if args.action_rate_limit is not None:      # upstream's own names (reference envs/nightmare_v3_config.py:37-38)
         cfg.control.action_rate_limit = args.action_rate_limit
@@ -150,6 +169,8 @@ def main():
         if env.wrench_interval:
             iv, du, mf, mt, _ = env.wrench_schedule()
             print(f"external wrench: every {iv} steps for {du} steps, |F| < {mf[0]} N, |tau| < {mt[0]} N m per axis", flush=True)
+        if env.sensor_model()["on"]:
+            print(f"sensor model: observation latency {args.obs_latency_range or 'off'} env steps, bias maxima {sensor_bias or 'off'}", flush=True)
         if reset_noise:
             print(f"randomised reset states: joint angles +-{args.reset_dof_pos} rad, velocities +-{args.reset_vel}", flush=True)
         if args.friction_range or args.gain_range:
