@@ -10,6 +10,20 @@
  * build_custom_mujoco.sh:8-10), which is a third-party dependency absent from /root/reference and
  * not installable here: the physics part is "PARITY UNPINNED" against MuJoCo itself and is pinned
  * only by the known-answer tests in tests/test_oracle_physics.py.
+ *
+ * PER-ENV ROWS (nmo_rows): of the device step's seven kinds of rows every env carries six, and what they mean is stated here once:
+ *   gravity          physics gravity (the RNE's cacc[0]) and, apart from it, the gravity_vec the env layer projects and observes
+ *   env params       mu (contact friction), kv (servo gain and bias, the implicit factor's h kv), p_gain (the env layer's ctrl)
+ *   action latency   a delay in substeps behind a history of the last NMO_NHIST scaled and clipped float32 actions
+ *   servo            (rate, d_gain) and the limited targets lim[18]: a slew-rate limiter behind the delay line, d_gain on dof_vel
+ *   torque limit     fmax by joint type: the clamp of mj_fwdActuation and the factor mask of mj_implicit (MuJoCo's forcerange)
+ *   base wrench      xfrc_applied on the base body, through mj_jac at xipos[1]
+ * The seventh, a base payload, is no row: it changes the model tables, so it is a library compiled against another nm_model_data.h (oracle.build).
+ * PARITY STATUS of the rows: p_gain, gravity_vec, the delay line and the servo model belong to the env layer but have no upstream
+ * counterpart in the reference class (its config holds one constant each, and it has neither a delay nor a limiter): they are this
+ * project's definitions, pinned by tests/golden/{env_params,gravity,latency,servo,allrand,allkinds}.npz through
+ * tests/test_oracle_rows.py. gravity, mu, kv, the torque limit and the wrench restate MuJoCo's opt.gravity, geom friction, actuator
+ * gainprm / biasprm, forcerange and xfrc_applied, and are PARITY UNPINNED against MuJoCo like the rest of the physics.
  */
 #ifndef NM_ORACLE_H
 #define NM_ORACLE_H
@@ -26,6 +40,20 @@ extern "C" {
 #define NMO_NSENS 13
 #define NMO_MAXCON 48
 #define NMO_MAXEFC (4 * NMO_MAXCON)
+
+#define NMO_NHIST 3
+/* per-env rows and the state that goes with them. nmo_rows_default() fills the values under which a step is what it was without rows. */
+typedef struct {
+  double gravity[3], gravity_vec[3];   /* physics; env layer (projected_gravity, the termination angle) */
+  double mu, kv, p_gain;
+  double rate, d_gain, lim[NMO_NU];    /* servo row and the limited targets */
+  double fmax[3], margin;              /* torque limit coxa / femur / tibia; smallest | |f| - fmax | over finite limits since the last read */
+  double wrench[6];                    /* F, tau on the base, world frame */
+  double late[NMO_NU];                 /* scratch of a step: the command behind the switch substep */
+  float hist[NMO_NHIST][NMO_NU];       /* hist[j] = a_{t-1-j} */
+  int32_t delay, factor_mask;          /* substeps; 0 = the clamp alone, every dof stays in the implicit factor */
+} nmo_rows;
+void nmo_rows_default(nmo_rows* r);
 
 /* per-env MjData equivalent: persistent state + the outputs the env reads after mj_step */
 typedef struct {
@@ -50,6 +78,7 @@ typedef struct {
   double efc_force[NMO_MAXEFC];
   double sensordata[NMO_NSENS];
   int32_t solver_niter, noslip_niter, nwarning, pad;
+  nmo_rows* rows; /* NULL = the defaults; survives nmo_reset_data */
 } nmo_data;
 
 /* per-thread scratch for the constraint rows */
@@ -83,7 +112,8 @@ void nmo_env_reset_idx(nmo_env* e, const int32_t* ids, int n, const double* cmd_
 void nmo_env_step(nmo_env* e, const float* actions, const double* cmd_u, float* obs, float* rew, int64_t* done,
                   float* time_outs, double* obs64, double* rew64);
 /* dynamics + contact only (BASELINE config 2; reference simple_test.py:25-45): servo command from the live joint angles, then
- * mj_step(model, data[i], decimation) over the threads. No epilogue; env-level buffers untouched. */
+ * mj_step(model, data[i], decimation) over the threads. No epilogue; env-level buffers untouched. Of the rows it takes p_gain and
+ * those of the physics; the delay line and the servo model belong to nmo_env_step alone. */
 void nmo_env_step_physics(nmo_env* e, const float* actions);
 /* non-default reward table / contact modes (config.py:17-21, 77-100). reward_scales[NMO_NREW] are the RAW config scales (x dt is
  * applied here, env.py:123-128; 0 drops the term); NULL keeps the current ones */
@@ -107,6 +137,21 @@ void nmo_env_set_buffers(nmo_env* e, const double* dof_pos, const double* dof_ve
 /* extras['episode'] of the last step in which >=1 env reset: mean episode sum / 20 per reward; returns #resets of last step */
 int nmo_env_episode_stats(nmo_env* e, double* out /* [NMO_NREW] */);
 nmo_data* nmo_env_data(nmo_env* e, int i);
+/* ---- per-env rows: arrays are [N, ...], NULL restores the default, getters' outputs may be NULL */
+void nmo_env_set_gravity(nmo_env* e, const double* g3, const double* gravity_vec3);
+void nmo_env_get_gravity(nmo_env* e, double* g3, double* gravity_vec3);
+void nmo_env_set_env_params(nmo_env* e, const double* mu_pgain_kv3);
+void nmo_env_get_env_params(nmo_env* e, double* mu_pgain_kv3);
+/* delay [N] substeps, 0 .. NMO_NHIST * decimation (clamped); hist [N,NMO_NHIST,18] f32, NULL = zero. Also puts
+ * every limited target where a servo without a limit holds it, the target of the last late action */
+void nmo_env_set_action_latency(nmo_env* e, const int32_t* delay, const float* hist);
+void nmo_env_get_action_history(nmo_env* e, int32_t* delay, float* hist);
+void nmo_env_set_servo(nmo_env* e, const double* rate_dgain2, const double* lim18); /* lim18 NULL = the target of the last late action */
+void nmo_env_get_servo(nmo_env* e, double* rate_dgain2, double* lim18);
+void nmo_env_set_torque_limit(nmo_env* e, const double* fmax3, int factor_mask);
+void nmo_env_get_torque_limit(nmo_env* e, double* fmax3, double* margin /* [N]; read and put back to INFINITY */);
+void nmo_env_set_base_wrench(nmo_env* e, const double* wrench6);
+void nmo_env_get_base_wrench(nmo_env* e, double* wrench6);
 /* intermediate per-env buffers of the last step, for golden comparison (each may be NULL):
  * base_lin_vel[N,3] base_ang_vel[N,3] projected_gravity[N,3] tibia[N,6] feet[N,6] body[N] rew_terms[NMO_NREW,N] */
 void nmo_env_get_debug(nmo_env* e, double* blv, double* bav, double* pg, double* tibia, double* feet, double* body,

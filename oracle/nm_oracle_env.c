@@ -12,11 +12,10 @@
 
 #include "nm_oracle.h"
 
-#include "../nightmare_rl_amd/model/nm_model_data.h"
+#include "nm_model_data.h" /* -I$(MODEL): the committed tables, or a header emitted for other ones */
 
 /* config constants: reference envs/nightmare_v3_config.py */
 #define DECIMATION 2            /* :45 */
-#define P_GAIN 20.0             /* :36 */
 #define ACTION_SCALE_F 0.2f     /* :46 (float32 product, see step()) */
 #define CLIP_ACTIONS_F 1.0f     /* :74 */
 #define CLIP_OBS 100.0          /* :73 */
@@ -52,6 +51,7 @@ struct nmo_env {
   uint8_t *last_contacts, *last_contacts_filt;
   double* base_height; /* xipos[1][2] of the last forward pass (env.py:223) */
   nmo_data* data;
+  nmo_rows* rows; /* per env; data[i].rows points here */
   nmo_scratch* scratch; /* per thread */
   double *dof_pos, *dof_vel, *commands, *episode_sums;
   float *actions, *prev_actions;
@@ -97,7 +97,9 @@ nmo_env* nmo_env_create(int N, uint64_t seed, int64_t env_off, int nthreads) {
   e->base_height_target = 0.1; e->max_contact_force = 10.0;                                 /* config.py:99-100 */
   e->data = (nmo_data*)calloc(N, sizeof(nmo_data));
   e->scratch = (nmo_scratch*)calloc(e->nthreads, sizeof(nmo_scratch));
-  for (int i = 0; i < N; i++) nmo_reset_data(&e->data[i]);
+  e->rows = (nmo_rows*)calloc(N, sizeof(nmo_rows));
+  for (int i = 0; i < N; i++) { nmo_reset_data(&e->data[i]); nmo_rows_default(&e->rows[i]); e->data[i].rows = &e->rows[i]; }
+  nmo_env_set_action_latency(e, NULL, NULL); /* the limited targets of a zero history */
 #define AL(p, T, n) e->p = (T*)calloc((size_t)(n), sizeof(T))
   AL(dof_pos, double, N * 18); AL(dof_vel, double, N * 18); AL(commands, double, N * 3);
   AL(episode_sums, double, NMO_NREW * N); AL(actions, float, N * 18); AL(prev_actions, float, N * 18);
@@ -111,7 +113,7 @@ nmo_env* nmo_env_create(int N, uint64_t seed, int64_t env_off, int nthreads) {
 }
 void nmo_env_destroy(nmo_env* e) {
   if (!e) return;
-  free(e->data); free(e->scratch); free(e->dof_pos); free(e->dof_vel); free(e->commands); free(e->episode_sums);
+  free(e->data); free(e->rows); free(e->scratch); free(e->dof_pos); free(e->dof_vel); free(e->commands); free(e->episode_sums);
   free(e->actions); free(e->prev_actions); free(e->ep_len); free(e->rng_ctr); free(e->blv); free(e->bav); free(e->pg);
   free(e->tibia); free(e->feet); free(e->body); free(e->rew_terms); free(e->reset_buf); free(e->time_out); free(e->noise_u);
   free(e->feet_air_time); free(e->last_contacts); free(e->last_contacts_filt); free(e->base_height);
@@ -193,7 +195,7 @@ void nmo_env_step_physics(nmo_env* e, const float* actions) {
     for (int j = 0; j < 18; j++) {
       float a = actions[i * 18 + j] * ACTION_SCALE_F;
       a = a < -CLIP_ACTIONS_F ? -CLIP_ACTIONS_F : (a > CLIP_ACTIONS_F ? CLIP_ACTIONS_F : a);
-      e->data[i].ctrl[j] = (((double)a - default_pos[j % 3]) - e->data[i].qpos[7 + j]) * P_GAIN;
+      e->data[i].ctrl[j] = (((double)a - default_pos[j % 3]) - e->data[i].qpos[7 + j]) * e->rows[i].p_gain;
     }
 #pragma omp parallel for num_threads(e->nthreads) schedule(static)
   for (int i = 0; i < N; i++) {
@@ -218,9 +220,23 @@ void nmo_env_step(nmo_env* e, const float* actions, const double* cmd_u, float* 
   }
   double* prev_dof_vel = (double*)malloc(sizeof(double) * N * 18);
   memcpy(prev_dof_vel, e->dof_vel, sizeof(double) * N * 18);
-  for (int i = 0; i < N; i++)
-    for (int j = 0; j < 18; j++)
-      e->data[i].ctrl[j] = (((double)e->actions[i * 18 + j] - default_pos[j % 3]) - e->dof_pos[i * 18 + j]) * P_GAIN;
+  /* the servo command behind the delay line and the limiter. With k = delay / DECIMATION, sw = delay % DECIMATION the step runs sw
+   * substeps under the target the servo held, then the rest under the target of the late action a_{t-k} (a_t itself where k = 0),
+   * slew-limited: d = T - L; L' = |d| <= rate ? T : L + copysign(rate, d). d_gain acts on the step-start dof_vel snapshot. */
+  for (int i = 0; i < N; i++) {
+    nmo_rows* r = &e->rows[i];
+    const int k = r->delay / DECIMATION, sw = r->delay % DECIMATION;
+    for (int j = 0; j < 18; j++) {
+      const float al = k == 0 ? e->actions[i * 18 + j] : r->hist[k - 1][j];
+      const double t = (double)al - default_pos[j % 3], l = r->lim[j], dd = t - l;
+      const double ln = fabs(dd) > r->rate ? l + copysign(r->rate, dd) : t;
+      double early = ((sw > 0 ? l : ln) - e->dof_pos[i * 18 + j]) * r->p_gain, late = (ln - e->dof_pos[i * 18 + j]) * r->p_gain;
+      if (r->d_gain != 0) { early -= r->d_gain * e->dof_vel[i * 18 + j]; late -= r->d_gain * e->dof_vel[i * 18 + j]; }
+      e->data[i].ctrl[j] = early;
+      r->late[j] = late;
+      r->lim[j] = ln;
+    }
+  }
     /* E2 (env.py:195-210): mj_step(model, data[i], decimation) fanned out over threads */
 #pragma omp parallel for num_threads(e->nthreads) schedule(static)
   for (int i = 0; i < N; i++) {
@@ -229,10 +245,17 @@ void nmo_env_step(nmo_env* e, const float* actions, const double* cmd_u, float* 
 #else
     nmo_scratch* s = &e->scratch[0];
 #endif
-    nmo_step(&e->data[i], s, DECIMATION);
+    nmo_rows* r = &e->rows[i];
+    const int sw = r->delay % DECIMATION;
+    if (sw > 0) {
+      nmo_step(&e->data[i], s, sw);
+      memcpy(e->data[i].ctrl, r->late, sizeof r->late);
+      nmo_step(&e->data[i], s, DECIMATION - sw);
+    } else nmo_step(&e->data[i], s, DECIMATION);
+    memmove(r->hist[1], r->hist[0], sizeof r->hist[0] * (NMO_NHIST - 1));
+    memcpy(r->hist[0], e->actions + i * 18, sizeof r->hist[0]);
   }
   /* E3 (env.py:212-232) */
-  const double grav[3] = {0, 0, -9.81}; /* env.py:46 */
   for (int i = 0; i < N; i++) {
     nmo_data* d = &e->data[i];
     e->ep_len[i] += 1;
@@ -240,7 +263,7 @@ void nmo_env_step(nmo_env* e, const float* actions, const double* cmd_u, float* 
     neg_quat(bq, d->qpos + 3);
     rot_vec_quat(e->blv + 3 * i, d->cvel[1] + 3, bq);
     rot_vec_quat(e->bav + 3 * i, d->cvel[1], bq);
-    rot_vec_quat(e->pg + 3 * i, grav, bq);
+    rot_vec_quat(e->pg + 3 * i, e->rows[i].gravity_vec, bq); /* env.py:46: upstream's is the constant (0, 0, -9.81) */
     for (int j = 0; j < 18; j++) { e->dof_pos[i * 18 + j] = d->qpos[7 + j]; e->dof_vel[i * 18 + j] = d->qvel[6 + j]; }
     for (int j = 0; j < 6; j++) { e->tibia[i * 6 + j] = d->sensordata[j]; e->feet[i * 6 + j] = d->sensordata[6 + j]; }
     e->body[i] = d->sensordata[12];
@@ -411,6 +434,72 @@ void nmo_env_set_noise(nmo_env* e, const double* noise_scale_vec66, const double
     memcpy(e->noise_u, u, sizeof(double) * e->N * 66);
   }
 }
+
+/* ---- per-env rows: [N, ...] arrays, NULL = the default (setters) or not wanted (getters) */
+#define FOR_ROWS for (nmo_rows* r = e->rows; r < e->rows + e->N; r++)
+static nmo_rows defaults(void) { nmo_rows r; nmo_rows_default(&r); return r; }
+static void put(double* dst, const double* src, int n) { if (dst) memcpy(dst, src, sizeof(double) * n); }
+static const double* at(const double* a, const nmo_env* e, const nmo_rows* r, int n) { return a ? a + n * (r - e->rows) : NULL; }
+static const double* or_(const double* a, const double* dflt) { return a ? a : dflt; }
+
+void nmo_env_set_gravity(nmo_env* e, const double* g, const double* vec) {
+  const nmo_rows d = defaults();
+  FOR_ROWS { put(r->gravity, or_(at(g, e, r, 3), d.gravity), 3); put(r->gravity_vec, or_(at(vec, e, r, 3), d.gravity_vec), 3); }
+}
+void nmo_env_get_gravity(nmo_env* e, double* g, double* vec) {
+  FOR_ROWS { put((double*)at(g, e, r, 3), r->gravity, 3); put((double*)at(vec, e, r, 3), r->gravity_vec, 3); }
+}
+void nmo_env_set_env_params(nmo_env* e, const double* p) {
+  const nmo_rows d = defaults();
+  const double dp[3] = {d.mu, d.p_gain, d.kv};
+  FOR_ROWS { const double* v = or_(at(p, e, r, 3), dp); r->mu = v[0]; r->p_gain = v[1]; r->kv = v[2]; }
+}
+void nmo_env_get_env_params(nmo_env* e, double* p) {
+  FOR_ROWS { const double v[3] = {r->mu, r->p_gain, r->kv}; put((double*)at(p, e, r, 3), v, 3); }
+}
+/* a fresh delay line. The limited targets go where a servo without a limit holds them, the target of the last late action a_{t-1-k}
+ * (of the oldest action kept where the history is too short to hold it: k = NMO_NHIST, whose step does not read the old target) */
+void nmo_env_set_action_latency(nmo_env* e, const int32_t* delay, const float* hist) {
+  const double default_pos[3] = {0.0, kPi / 5, 0.0};
+  FOR_ROWS {
+    const int i = (int)(r - e->rows), dl = delay ? delay[i] : 0, top = NMO_NHIST * DECIMATION;
+    r->delay = dl < 0 ? 0 : (dl > top ? top : dl);
+    if (hist) memcpy(r->hist, hist + i * NMO_NHIST * 18, sizeof r->hist); else memset(r->hist, 0, sizeof r->hist);
+    const int k = r->delay / DECIMATION < NMO_NHIST ? r->delay / DECIMATION : NMO_NHIST - 1;
+    for (int j = 0; j < 18; j++) r->lim[j] = (double)r->hist[k][j] - default_pos[j % 3];
+  }
+}
+void nmo_env_get_action_history(nmo_env* e, int32_t* delay, float* hist) {
+  FOR_ROWS {
+    const int i = (int)(r - e->rows);
+    if (delay) delay[i] = r->delay;
+    if (hist) memcpy(hist + i * NMO_NHIST * 18, r->hist, sizeof r->hist);
+  }
+}
+/* lim NULL leaves the limited targets alone: under the default row they follow the late action's target */
+void nmo_env_set_servo(nmo_env* e, const double* rows, const double* lim) {
+  const nmo_rows d = defaults();
+  const double dr[2] = {d.rate, d.d_gain};
+  FOR_ROWS { const double* v = or_(at(rows, e, r, 2), dr); r->rate = v[0]; r->d_gain = v[1]; if (lim) put(r->lim, at(lim, e, r, 18), 18); }
+}
+void nmo_env_get_servo(nmo_env* e, double* rows, double* lim) {
+  FOR_ROWS { const double v[2] = {r->rate, r->d_gain}; put((double*)at(rows, e, r, 2), v, 2); put((double*)at(lim, e, r, 18), r->lim, 18); }
+}
+void nmo_env_set_torque_limit(nmo_env* e, const double* fmax, int factor_mask) {
+  const nmo_rows d = defaults();
+  FOR_ROWS { put(r->fmax, or_(at(fmax, e, r, 3), d.fmax), 3); r->factor_mask = factor_mask; r->margin = INFINITY; }
+}
+void nmo_env_get_torque_limit(nmo_env* e, double* fmax, double* margin) {
+  FOR_ROWS {
+    put((double*)at(fmax, e, r, 3), r->fmax, 3);
+    if (margin) { margin[r - e->rows] = r->margin; r->margin = INFINITY; }
+  }
+}
+void nmo_env_set_base_wrench(nmo_env* e, const double* w) {
+  const nmo_rows d = defaults();
+  FOR_ROWS put(r->wrench, or_(at(w, e, r, 6), d.wrench), 6);
+}
+void nmo_env_get_base_wrench(nmo_env* e, double* w) { FOR_ROWS put((double*)at(w, e, r, 6), r->wrench, 6); }
 
 void nmo_env_get_state(nmo_env* e, double* qpos, double* qvel, double* qw) {
   for (int i = 0; i < e->N; i++) {

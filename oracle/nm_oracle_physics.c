@@ -12,7 +12,7 @@
 #include <math.h>
 #include <string.h>
 
-#include "../nightmare_rl_amd/model/nm_model_data.h"
+#include "nm_model_data.h" /* -I$(MODEL): the committed tables, or a header emitted for other ones */
 
 #define NB NMO_NBODY
 #define NV NMO_NV
@@ -25,6 +25,13 @@ static int g_collide_self = 1;
 void nmo_set_collide_self(int on) { g_collide_self = on; }
 int nmo_sizeof_data(void) { return (int)sizeof(nmo_data); }
 int nmo_sizeof_scratch(void) { return (int)sizeof(nmo_scratch); }
+void nmo_rows_default(nmo_rows* r) {
+  memset(r, 0, sizeof *r);
+  for (int k = 0; k < 3; k++) { r->gravity[k] = r->gravity_vec[k] = nm_gravity[k]; r->fmax[k] = INFINITY; }
+  r->mu = NM_FRICTION; r->kv = NM_KV; r->p_gain = 20.0; /* reference envs/nightmare_v3_config.py:36 */
+  r->rate = r->margin = INFINITY;
+  r->factor_mask = 1;
+}
 
 /* ------------------------------------------------------------------ small math (engine_util_blas / _spatial) */
 static double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
@@ -106,8 +113,10 @@ static int dof_body(int i) { return i < 6 ? 1 : 2 + (i - 6); }
 /* ------------------------------------------------------------------ mj_resetData */
 void nmo_reset_data(nmo_data* d) {
   int nw = d->nwarning;
+  nmo_rows* rows = d->rows;
   memset(d, 0, sizeof *d);
   d->nwarning = nw;
+  d->rows = rows;
   for (int i = 0; i < NMO_NQ; i++) d->qpos[i] = nm_qpos0[i];
 }
 
@@ -577,7 +586,7 @@ static double impedance(double pos) { /* getimpedance with margin 0 */
 }
 static void make_constraint(nmo_data* d, nmo_scratch* s) {
   int n = 0;
-  const double mu = NM_FRICTION;
+  const double mu = d->rows->mu;
   for (int c = 0; c < d->ncon; c++) {
     double jp[3][NV], jf[3][NV];
     jac_point(d, jp, d->con_body[c], d->con_pos[c]);
@@ -652,7 +661,7 @@ static void comVel(nmo_data* d) {
 static void rne(nmo_data* d) { /* mj_rne(flg_acc = 0) -> qfrc_bias */
   double cacc[NB][6], cfrc[NB][6];
   memset(cacc, 0, sizeof cacc);
-  for (int k = 0; k < 3; k++) cacc[0][3 + k] = -nm_gravity[k];
+  for (int k = 0; k < 3; k++) cacc[0][3 + k] = -d->rows->gravity[k];
   memset(cfrc[0], 0, sizeof cfrc[0]);
   for (int b = 1; b < NB; b++) {
     int p = nm_body_parent[b];
@@ -683,11 +692,23 @@ static void fwd_actuation(nmo_data* d) {
     double c = d->ctrl[j];
     if (c > NM_CTRL_MAX) c = NM_CTRL_MAX;
     if (c < -NM_CTRL_MAX) c = -NM_CTRL_MAX;
-    d->qfrc_actuator[6 + j] = NM_KV * c - NM_KV * d->qvel[6 + j]; /* gain*ctrl + biasprm[2]*velocity */
+    const double kv = d->rows->kv, f = kv * c - kv * d->qvel[6 + j], fm = d->rows->fmax[j % 3]; /* gain*ctrl + biasprm[2]*velocity */
+    if (isfinite(fm) && fabs(fabs(f) - fm) < d->rows->margin) d->rows->margin = fabs(fabs(f) - fm);
+    d->qfrc_actuator[6 + j] = f > fm ? fm : (f < -fm ? -fm : f); /* forcerange */
   }
 }
 static void fwd_acceleration(nmo_data* d) {
-  for (int i = 0; i < NV; i++) d->qfrc_smooth[i] = -d->qfrc_bias[i] + d->qfrc_actuator[i]; /* passive, applied = 0 */
+  for (int i = 0; i < NV; i++) d->qfrc_smooth[i] = -d->qfrc_bias[i] + d->qfrc_actuator[i]; /* passive = 0 */
+  const double* w = d->rows->wrench;
+  if (w[0] != 0 || w[1] != 0 || w[2] != 0 || w[3] != 0 || w[4] != 0 || w[5] != 0) { /* xfrc_applied on the base: J'[F; tau], F at xipos */
+    double jp[3][NV];
+    jac_point(d, jp, 1, d->xipos[1]);
+    for (int i = 0; i < 6; i++) {
+      double s = 0;
+      for (int k = 0; k < 3; k++) s += jp[k][i] * w[k] + d->cdof[i][k] * w[3 + k];
+      d->qfrc_smooth[i] += s;
+    }
+  }
   memcpy(d->qacc_smooth, d->qfrc_smooth, sizeof d->qacc_smooth);
   solveLD(d->qLD, d->qLDiagInv, d->qacc_smooth);
 }
@@ -827,6 +848,9 @@ static void sensor_touch(nmo_data* d) {
 
 /* ------------------------------------------------------------------ mj_forward */
 void nmo_forward(nmo_data* d, nmo_scratch* s) {
+  nmo_rows dflt;
+  const int bare = d->rows == NULL; /* a data block without rows runs under the defaults */
+  if (bare) { nmo_rows_default(&dflt); d->rows = &dflt; }
   kinematics(d);
   comPos(d);
   crb(d);
@@ -840,16 +864,19 @@ void nmo_forward(nmo_data* d, nmo_scratch* s) {
   fwd_acceleration(d);
   fwd_constraint(d, s);
   sensor_touch(d);
+  if (bare) d->rows = NULL;
 }
 
 /* ------------------------------------------------------------------ P9: mj_implicit (implicitfast) + mj_advance */
 static int is_bad(double x) { return isnan(x) || x > MJ_MAXVAL || x < -MJ_MAXVAL; }
 static void integrate(nmo_data* d) {
   const double h = NM_TIMESTEP;
-  /* (M - h dF/dv) qacc = qfrc_smooth + qfrc_constraint ; dF/dv = -kv on the 18 actuated dofs (mjd_smooth_vel) */
+  /* (M - h dF/dv) qacc = qfrc_smooth + qfrc_constraint ; dF/dv = -kv on the actuated dofs whose force is off its bound (mjd_smooth_vel) */
+  const nmo_rows* r = d->rows;
   double H[NV][NV], Hinv[NV], qacc[NV];
   memcpy(H, d->qM, sizeof H);
-  for (int j = 0; j < NU; j++) H[6 + j][6 + j] += h * NM_KV;
+  for (int j = 0; j < NU; j++)
+    if (!r->factor_mask || fabs(d->qfrc_actuator[6 + j]) < r->fmax[j % 3]) H[6 + j][6 + j] += h * r->kv;
   factorLD(H, Hinv);
   for (int i = 0; i < NV; i++) qacc[i] = d->qfrc_smooth[i] + d->qfrc_constraint[i];
   solveLD((const double(*)[NV])H, Hinv, qacc);
@@ -869,6 +896,9 @@ static void integrate(nmo_data* d) {
 }
 
 void nmo_step(nmo_data* d, nmo_scratch* s, int nstep) {
+  nmo_rows dflt;
+  const int bare = d->rows == NULL;
+  if (bare) { nmo_rows_default(&dflt); d->rows = &dflt; }
   for (int it = 0; it < nstep; it++) {
     int bad = 0; /* mj_checkPos / mj_checkVel */
     for (int i = 0; i < NMO_NQ; i++) bad |= is_bad(d->qpos[i]);
@@ -880,4 +910,5 @@ void nmo_step(nmo_data* d, nmo_scratch* s, int nstep) {
     if (bad) { d->nwarning++; nmo_reset_data(d); nmo_forward(d, s); }
     integrate(d);
   }
+  if (bare) d->rows = NULL;
 }

@@ -44,6 +44,7 @@ class NmoData(C.Structure):
         ("efc_force", d_ * MAXEFC),
         ("sensordata", d_ * NSENS),
         ("solver_niter", C.c_int32), ("noslip_niter", C.c_int32), ("nwarning", C.c_int32), ("pad", C.c_int32),
+        ("rows", C.c_void_p),      # per-env rows (nmo_rows*); NULL = the defaults
     ]
 
     def np(self, name):
@@ -63,21 +64,29 @@ class NmoScratch(C.Structure):
         return np.ctypeslib.as_array(getattr(self, name))
 
 
-def build(force=False):
-    """Compile the oracle with gcc (recipe: oracle/Makefile)."""
-    if force or not os.path.exists(LIB_PATH):
-        subprocess.check_call(["make", "-C", HERE, "-s"] + (["-B"] if force else []))
-    return LIB_PATH
+def build(force=False, header=None, out=None):
+    """Compile the oracle with gcc (recipe and flags: oracle/Makefile). header: another nm_model_data.h to compile against (a base payload
+    is a recompiled model: compile_model.emit_header of payload.modified_tables), out: where that library goes."""
+    out = out or LIB_PATH
+    if force or not os.path.exists(out):
+        cmd = ["make", "-C", HERE, "-s", "OUT=" + os.path.abspath(out)] + (["-B"] if force else [])
+        if header is not None:
+            assert os.path.basename(header) == "nm_model_data.h", header
+            cmd.append("MODEL=" + os.path.dirname(os.path.abspath(header)))
+        subprocess.check_call(cmd)
+    return out
 
 
-_lib = None
+_libs = {}
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        build()
-        L = C.CDLL(LIB_PATH)
+def lib(path=None):
+    """The bound library: oracle/libnm_oracle.so (built on demand), or another one that build(header=..., out=path) made."""
+    path = os.path.abspath(path or LIB_PATH)
+    if path not in _libs:
+        if path == os.path.abspath(LIB_PATH):
+            build()
+        L = C.CDLL(path)
         assert L.nmo_sizeof_data() == C.sizeof(NmoData), (L.nmo_sizeof_data(), C.sizeof(NmoData))
         assert L.nmo_sizeof_scratch() == C.sizeof(NmoScratch)
         P = C.POINTER
@@ -104,10 +113,15 @@ def lib():
         L.nmo_env_data.argtypes = [C.c_void_p, C.c_int]
         L.nmo_env_data.restype = P(NmoData)
         L.nmo_env_get_debug.argtypes = [C.c_void_p] * 8
+        for kind, nargs in (("gravity", 2), ("env_params", 1), ("servo", 2), ("base_wrench", 1)):
+            getattr(L, "nmo_env_set_" + kind).argtypes = getattr(L, "nmo_env_get_" + kind).argtypes = [C.c_void_p] * (1 + nargs)
+        L.nmo_env_set_action_latency.argtypes = L.nmo_env_get_action_history.argtypes = [C.c_void_p] * 3
+        L.nmo_env_set_torque_limit.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.nmo_env_get_torque_limit.argtypes = [C.c_void_p] * 3
         L.nmo_rand_u24.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32]
         L.nmo_rand_u24.restype = C.c_double
-        _lib = L
-    return _lib
+        _libs[path] = L
+    return _libs[path]
 
 
 def _ptr(a):
@@ -150,8 +164,9 @@ class Physics:
 class OracleEnv:
     """NightmareV3Env restated on the CPU (reference envs/nightmare_v3_env.py), numpy in / numpy out."""
 
-    def __init__(self, num_envs, seed=0, env_id_offset=0, num_threads=1):
-        self.L = lib()
+    def __init__(self, num_envs, seed=0, env_id_offset=0, num_threads=1, lib_path=None):
+        """lib_path: a library of build(header=..., out=...) to bind instead of oracle/libnm_oracle.so; one process can hold several."""
+        self.L = lib(lib_path)
         self.N = num_envs
         self.h = self.L.nmo_env_create(num_envs, seed, env_id_offset, num_threads)
 
@@ -209,6 +224,61 @@ class OracleEnv:
         f = lambda a: None if a is None else np.ascontiguousarray(a, np.float64)
         vec, u = f(noise_scale_vec), f(u)
         self.L.nmo_env_set_noise(self.h, _ptr(vec), _ptr(u))
+
+    # ---- per-env rows (nm_oracle.h): arrays are [N, ...], None restores the default
+    def _rows(self, a, shape, dtype=np.float64):
+        return None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype), (self.N,) + shape))
+
+    def _get(self, fn, *shapes):
+        out = [np.empty((self.N,) + s) for s in shapes]
+        fn(self.h, *[_ptr(a) for a in out])
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def set_gravity(self, g=None, gravity_vec=None):
+        """g [N,3] acts in the physics; gravity_vec [N,3] is what the env layer projects and observes (upstream: a constant)."""
+        self.L.nmo_env_set_gravity(self.h, _ptr(self._rows(g, (3,))), _ptr(self._rows(gravity_vec, (3,))))
+
+    def gravity(self):
+        return self._get(self.L.nmo_env_get_gravity, (3,), (3,))
+
+    def set_env_params(self, rows=None):
+        """rows [N,3]: mu, p_gain, kv."""
+        self.L.nmo_env_set_env_params(self.h, _ptr(self._rows(rows, (3,))))
+
+    def env_params(self):
+        return self._get(self.L.nmo_env_get_env_params, (3,))
+
+    def set_action_latency(self, delay=None, history=None):
+        """delay [N] substeps; history [N,3,18] float32, history[:, j] = a_{t-1-j} (None: zero). Starts a fresh delay line."""
+        self.L.nmo_env_set_action_latency(self.h, _ptr(self._rows(delay, (), np.int32)), _ptr(self._rows(history, (3, 18), np.float32)))
+
+    def action_history(self):
+        """(history [N,3,18] float32, delay [N])."""
+        delay, hist = np.empty(self.N, np.int32), np.empty((self.N, 3, 18), np.float32)
+        self.L.nmo_env_get_action_history(self.h, _ptr(delay), _ptr(hist))
+        return hist, delay
+
+    def set_servo(self, rows=None, lim=None):
+        """rows [N,2]: rate, d_gain; lim [N,18]: the limited targets (None: left as they are)."""
+        self.L.nmo_env_set_servo(self.h, _ptr(self._rows(rows, (2,))), _ptr(self._rows(lim, (18,))))
+
+    def servo_state(self):
+        return self._get(self.L.nmo_env_get_servo, (2,), (18,))
+
+    def set_torque_limit(self, fmax=None, factor_mask=True):
+        """fmax [N,3] by joint type (coxa, femur, tibia); factor_mask False keeps the clamp but leaves every dof in the implicit factor."""
+        self.L.nmo_env_set_torque_limit(self.h, _ptr(self._rows(fmax, (3,))), int(factor_mask))
+
+    def torque_limit(self):
+        """(fmax [N,3], margin [N]): the smallest | |f| - fmax | over finite limits since the last call."""
+        return self._get(self.L.nmo_env_get_torque_limit, (3,), ())
+
+    def set_base_wrench(self, wrench=None):
+        """wrench [N,6]: F, tau on the base body, world frame."""
+        self.L.nmo_env_set_base_wrench(self.h, _ptr(self._rows(wrench, (6,))))
+
+    def base_wrench(self):
+        return self._get(self.L.nmo_env_get_base_wrench, (6,))
 
     def reset(self):
         self.reset_idx()

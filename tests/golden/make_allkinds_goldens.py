@@ -3,20 +3,15 @@ friction / servo gains, base payloads, actuation latency, the servo target model
 external wrench on the base - which is what cfg.domain_rand plus cfg.control gives a user (level 7 of the step, every region of the row
 block non-default).
 
-No oracle machinery of its own: the seven existing generators composed, three levels above make_allrand_goldens.py. Each combined set is
-ONE library built in a temporary copy of oracle/ (oracle/ itself is not touched):
-    the header, T["gravity"], NM_FRICTION, NM_KV, P_GAIN, the gravity_vec line             as in make_allrand_goldens.py
-    the delay line with the servo target model behind it (STATE, CTRL_NEW, STEP_NEW)       (make_latency_goldens.py, make_servo_goldens.py)
-    fwd_actuation's clamp and the factor mask (GLOBALS, FORCE_NEW, FACTOR_NEW)             (make_torque_goldens.py)
-    xfrc_applied on the base behind qfrc_smooth (HEAD_NEW, LINE_NEW)                       (make_wrench_goldens.py)
-Every patch site - three of the env layer, five of the physics - is asserted to be found exactly once. Value sets and patch strings are
-IMPORTED from those generators, not retyped. Combined set k takes
+No oracle machinery of its own: the seven existing generators composed, three levels above make_allrand_goldens.py. Six kinds are
+per-env rows of the oracle (oracle/nm_oracle.h); the payload is a recompiled model, so each of the four payload sets is ONE library
+(make_payload_goldens.payload_lib), and a combined set is that library under its rows. Value sets are IMPORTED from those generators, not
+retyped. Combined set k takes
     gravity set k, friction / gain set (k + 1) % 4, payload set (k + 2) % 4      (make_allrand_goldens.SETS)
     torque set (3, 0, 2, 4)[k] of make_torque_goldens.SETS                       (its KV is not used: kv is the friction set's)
     wrench set (1, 2, 4, 3)[k] of make_wrench_goldens.SETS                       (never the zero wrench)
 so each of the four pooled kinds has its default in exactly one set and no set two defaults; env e of the 8 has the delay
-make_latency_goldens.DELAYS[e] and the servo row make_servo_goldens.ROWS[e]. Limits and wrench are process-wide in the patched physics:
-one child process per library, one OpenMP thread.
+make_latency_goldens.DELAYS[e] and the servo row make_servo_goldens.ROWS[e].
 
 Populations are allrand's (same seed, pre-rolls and action streams; 8 envs x T = 10 steps each, per set, free-running): drop, stand,
 belly. Kinds 5..7 - the servo model, the torque limit and the wrench - are switched on TOGETHER where the recorded window starts, the
@@ -41,7 +36,7 @@ because this script asserts them derivable (tests/allkinds_tools.py load() puts 
 qvel) and act (row 0 of the step-start history, widened). The end-of-step qfrc_actuator is used for the conditions and left out.
 
 Conditions asserted on the reference alone, before the file is written (all printed; the figures are those of the committed file):
-  a  the combined build with every kind at its default equals the unpatched sources against the same header bit for bit;
+  a  every kind's default rows set equal no rows set at all, on the same library (payload 0's), bit for bit;
   b  with kinds 5..7 at their defaults (servo rows (inf, 0), limits inf, zero wrench) the four combined sets reproduce
      tests/golden/allrand.npz bit for bit in every key the two files share (39 trajectory keys and the six row keys);
   c  ABLATION, eight kinds (the servo row split into rate and d_gain): per set and kind, the variant with that ONE kind at its default,
@@ -65,13 +60,10 @@ Conditions asserted on the reference alone, before the file is written (all prin
      tolerance: largest 15.2 (drop), 9.8 (stand), 12.0 (belly).
 The file is under 1 MiB (923182 bytes) and byte-stable (make_allrand_goldens.save_stable); nothing but the .npz is written into the tree.
 
-    python tests/golden/make_allkinds_goldens.py            (CPU only; 18 library builds and 46 oracle runs, 8 at a time: 14 s measured)
+    python tests/golden/make_allkinds_goldens.py            (CPU only; 4 library builds and 46 oracle runs, 8 at a time)
 """
-import ctypes as C
 import os
-import re
 import shutil
-import subprocess
 import sys
 import tempfile
 import time
@@ -83,7 +75,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 OUT = os.path.join(HERE, "allkinds.npz")
 sys.path.insert(0, HERE)
-import make_allrand_goldens as ma      # noqa: E402  (patch_once, save_stable, the arrangement of the first four kinds)
+import make_allrand_goldens as ma      # noqa: E402  (save_stable, the arrangement of the first four kinds)
 import make_envparam_goldens as me      # noqa: E402
 import make_gravity_goldens as mg      # noqa: E402
 import make_latency_goldens as ml      # noqa: E402
@@ -91,6 +83,7 @@ import make_payload_goldens as mp      # noqa: E402
 import make_servo_goldens as ms      # noqa: E402
 import make_torque_goldens as mt      # noqa: E402
 import make_wrench_goldens as mw      # noqa: E402
+from oracle import oracle as orc      # noqa: E402  (make_envparam_goldens puts the repository root on sys.path)
 
 POPS = ma.POPS
 N, T, H, SEED = ma.N, ma.T, ma.H, ma.SEED
@@ -104,97 +97,39 @@ ABLATIONS = ("gravity", "friction", "payload", "latency", "rate", "d_gain", "tor
 SEPARATION = 1e-5
 INF = float("inf")
 KEYS = ma.KEYS + ("lim", "qfrc", "margin")
-ENV_PATCHES = (("\nvoid nmo_env_step(nmo_env* e,", ms.STATE), (ml.CTRL_OLD, ms.CTRL_NEW), (ml.STEP_OLD, ml.STEP_NEW))
-PHYS_PATCHES = (("static void fwd_actuation(nmo_data* d) {", mt.GLOBALS), (mt.FORCE_OLD, mt.FORCE_NEW), (mt.FACTOR_OLD, mt.FACTOR_NEW),
-                (mw.HEAD_OLD, mw.HEAD_NEW), (mw.LINE_OLD, mw.LINE_NEW))
 
 
-def build_variant(tmp, name, grav, envp, pay):
-    """One library: gravity set `grav`, friction / gain set `envp`, payload set `pay` (rows of the generators' SETS) and every patch of
-    kinds 4..7. grav = envp = None: the UNPATCHED oracle sources against the header of payload set `pay` with nothing in it replaced."""
-    d = os.path.join(tmp, name)
-    os.makedirs(os.path.join(d, "oracle"))
-    os.makedirs(os.path.join(d, "nightmare_rl_amd", "model"))
-    for f in os.listdir(os.path.join(ROOT, "oracle")):
-        if f.endswith(".c") or f == "nm_oracle.h":
-            shutil.copy(os.path.join(ROOT, "oracle", f), os.path.join(d, "oracle", f))
-    hdr = os.path.join(d, "nightmare_rl_amd", "model", "nm_model_data.h")
-    env_c, phys_c = os.path.join(d, "oracle", "nm_oracle_env.c"), os.path.join(d, "oracle", "nm_oracle_physics.c")
-    sys.path.insert(0, ROOT)
-    from nightmare_rl_amd.model import compile_model as cm, payload as pl
-    Tv = pl.modified_tables(float(pay[0]), pay[1:])
-    row = pl.row_of_tables(Tv)
-    if grav is None:
-        cm.emit_header(Tv, hdr)
-    else:
-        np.testing.assert_array_equal(Tv["gravity"], [0.0, 0.0, -mg.G0])
-        g = mg.g_of(grav)
-        Tv["gravity"] = g
-        cm.emit_header(Tv, hdr)
-        mu, p_gain, kv = (float(x) for x in envp)
-        ma.patch_once(hdr, r"^#define NM_FRICTION .*$", f"#define NM_FRICTION {mu!r}", regex=True)
-        ma.patch_once(hdr, r"^#define NM_KV .*$", f"#define NM_KV {kv!r}", regex=True)
-        ma.patch_once(env_c, r"^#define P_GAIN \S+", f"#define P_GAIN {p_gain!r}", regex=True)
-        if grav[5]:      # the env layer sees the gravity there is
-            ma.patch_once(env_c, mg.ENV_LINE, "const double grav[3] = {%r, %r, %r};" % tuple(float(x) for x in g))
-        else:
-            assert open(env_c).read().count(mg.ENV_LINE) == 1
-        for old, new in ENV_PATCHES:
-            ma.patch_once(env_c, old, new)
-        for old, new in PHYS_PATCHES:
-            ma.patch_once(phys_c, old, new)
-    mk = open(os.path.join(ROOT, "oracle", "Makefile")).read()
-    cflags = re.search(r"^CFLAGS \?= (.*)$", mk, flags=re.M).group(1).split()
-    lib = os.path.join(d, "libnm_oracle.so")
-    subprocess.check_call(["gcc"] + cflags + ["-shared", "-o", lib, "nm_oracle_physics.c", "nm_oracle_env.c", "-lm"], cwd=os.path.join(d, "oracle"))
-    return lib, row
-
-
-def child(lib, out, spec, start):
-    """Runs in a process of its own: the oracle module bound to ONE library. spec: "plain" (a library without the patches) or an .npz of
-    delays [8], servo [8,2], fmax [3], wrench [6]. start: "-" = the populations from their own beginnings; otherwise the .npz of a
-    combined run - `drop` and `stand` replayed from ITS recorded start states, histories, limited targets, actions and command uniforms."""
-    sys.path.insert(0, ROOT)
-    from oracle import oracle as orc
-    orc.LIB_PATH = lib
-    L = orc.lib()
-    plain = spec == "plain"
-    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
-    if not plain:
-        sp = np.load(spec)
-        delays, rows = np.ascontiguousarray(sp["delays"], np.int32), np.ascontiguousarray(sp["servo"], np.float64)
-        fmax, wrench = np.ascontiguousarray(sp["fmax"], np.float64), np.ascontiguousarray(sp["wrench"], np.float64)
-        L.nmo_lat_set.argtypes = [C.c_int, C.c_void_p]
-        L.nmo_lat_hist.restype = C.POINTER(C.c_float)
-        L.nmo_servo_set.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
-        L.nmo_servo_lim.restype = C.POINTER(C.c_double)
-        L.nmo_torque_set.argtypes = [C.c_void_p, C.c_int]
-        L.nmo_torque_margin.restype = C.c_double
-        L.nmo_wrench_set.argtypes = [C.c_void_p]
+def run(lib, grav=None, envp=None, sp=None, src=None):
+    """One recording on the library `lib` under a gravity set and a friction / gain set (rows of the generators' SETS; None = never
+    set) and sp = dict(delays [8], servo [8,2], fmax [3], wrench [6]), None = none of them ever set ("plain"). src: None = the
+    populations from their own beginnings; otherwise a combined run - `drop` and `stand` replayed from ITS recorded start states,
+    histories, limited targets, actions and command uniforms."""
+    plain = sp is None
     rng = np.random.default_rng(SEED)
-    src = None if start == "-" else np.load(start)
     many = np.load(os.path.join(HERE, "env_manycontacts.npz"))["init_qpos"][:N]
     default = np.tile([0, np.pi / 5, 0], 6)
-    hist = (lambda: np.zeros((N, H, 18), np.float32)) if plain else (lambda: np.ctypeslib.as_array(L.nmo_lat_hist(), (N, H, 18)))
-    lim = lambda: np.ctypeslib.as_array(L.nmo_servo_lim(), (N, 18)) if not plain and L.nmo_servo_lim() else np.zeros((N, 18))      # zero while the model is off
     res = {}
 
     def begin():
-        o = orc.OracleEnv(N, seed=SEED)
+        o = orc.OracleEnv(N, seed=SEED, lib_path=lib)
+        if grav is not None:
+            row = mg.row_of(grav)
+            o.set_gravity(row[0:3], row[4:7])
+        if envp is not None:
+            o.set_env_params(envp)
         if not plain:
-            L.nmo_servo_set(N, None, None)
-            L.nmo_lat_set(N, ptr(delays))        # a fresh, zero history
-            L.nmo_torque_set(ptr(np.ascontiguousarray(mt.SETS[0])), 1)
-            L.nmo_wrench_set(ptr(np.ascontiguousarray(mw.SETS[0])))
+            o.set_action_latency(sp["delays"])        # a fresh, zero history; kinds 5..7 stay at their defaults
         o.reset_idx()
         return o
 
-    def servo_on(l0):
+    def servo_on(o, l0, hist=None):
         """Where the recorded window starts: kinds 5..7 come on together."""
         if not plain:
-            L.nmo_servo_set(N, ptr(rows), ptr(np.ascontiguousarray(l0, np.float64)))
-            L.nmo_torque_set(ptr(fmax), 1)
-            L.nmo_wrench_set(ptr(wrench))
+            if hist is not None:
+                o.set_action_latency(sp["delays"], hist)
+            o.set_servo(sp["servo"], l0)
+            o.set_torque_limit(sp["fmax"])
+            o.set_base_wrench(sp["wrench"])
 
     def record(o, total, actions):
         """`total` recorded steps; actions(t) gives the step's (action, command uniforms)."""
@@ -204,19 +139,18 @@ def child(lib, out, spec, start):
             q, v, w = o.get_state()
             b = o.get_buffers()
             r["qpos"].append(q); r["qvel"].append(v); r["qw"].append(w); r["dof_pos"].append(b["dof_pos"]); r["dof_vel"].append(b["dof_vel"])
-            r["act"].append(b["actions"]); r["cmd"].append(b["commands"]); r["ep_len"].append(b["ep_len"]); r["hist"].append(hist().copy())
-            r["lim"].append(lim().copy())
+            r["act"].append(b["actions"]); r["cmd"].append(b["commands"]); r["ep_len"].append(b["ep_len"]); r["hist"].append(o.action_history()[0])
+            r["lim"].append(o.servo_state()[1])
 
         state()
-        if not plain:
-            L.nmo_torque_margin()
+        o.torque_limit()      # the margins start here
         for t in range(total):
             a, cu = actions(t)
             obs, rew, done, _ = o.step(a, cmd_u=cu)
             r["actions"].append(a); r["cmd_u"].append(cu.astype(np.float32)); r["obs"].append(obs.copy()); r["rew"].append(o.rew64.copy())
             r["done"].append(done.astype(np.uint8)); r["ncon"].append(np.array([o.data(i).ncon for i in range(N)], np.uint8))
             r["qfrc"].append(np.stack([o.data(i).np("qfrc_actuator")[6:].copy() for i in range(N)]))
-            r["margin"].append(np.float64(INF if plain else L.nmo_torque_margin()))
+            r["margin"].append(np.float64(o.torque_limit()[1].min()))
             state()
         return r
 
@@ -227,9 +161,7 @@ def child(lib, out, spec, start):
             pick = lambda k: src[f"{pop}_{k}"]
             o.set_state(pick("qpos")[0], pick("qvel")[0], pick("qw")[0])
             o.set_buffers(dof_pos=pick("dof_pos")[0], dof_vel=pick("dof_vel")[0], actions=pick("act")[0], commands=pick("cmd")[0], ep_len=pick("ep_len")[0])
-            if not plain:
-                hist()[:] = pick("hist")[0]
-            servo_on(pick("lim")[0])
+            servo_on(o, pick("lim")[0], pick("hist")[0])
             r = record(o, T, lambda t: (src[f"{pop}_actions"][t], src[f"{pop}_cmd_u"][t].astype(np.float64)))
         elif pop != "belly":
             pre, amp = (7, 1.0) if pop == "drop" else (150, 0.12)
@@ -239,8 +171,8 @@ def child(lib, out, spec, start):
                 o.step(act())
                 past.append(o.get_buffers()["actions"].copy())
             if not plain:      # the servo model comes on here, holding the target of the last late action a_{t-1-k}
-                k = delays // ms.DECIMATION
-                servo_on(np.stack([past[-1 - k[e]][e] - ms.DEFAULT_POS for e in range(N)]))
+                k = sp["delays"] // ms.DECIMATION
+                servo_on(o, np.stack([past[-1 - k[e]][e] - ms.DEFAULT_POS for e in range(N)]))
             r = record(o, T, lambda t: (act(), draw_cu()))
         else:
             hold = lambda t: (np.clip((o.get_buffers()["dof_pos"] + default) / 0.2, -5, 5).astype(np.float32), draw_cu())
@@ -258,8 +190,8 @@ def child(lib, out, spec, start):
                     o.step(a, cmd_u=cu)
                     past.append(o.get_buffers()["actions"].copy())
                 if not plain:
-                    k = delays // ms.DECIMATION
-                    servo_on(np.stack([past[-1 - k[e]][e] - ms.DEFAULT_POS for e in range(N)]))
+                    k = sp["delays"] // ms.DECIMATION
+                    servo_on(o, np.stack([past[-1 - k[e]][e] - ms.DEFAULT_POS for e in range(N)]))
                 cand = record(o, 80 if plain else T, hold)
                 big = (np.stack(cand["ncon"]) > 16).sum(axis=1)
                 if plain:      # no servo model to switch on: allrand's single pass
@@ -270,14 +202,13 @@ def child(lib, out, spec, start):
                 r, best = cand, int(big.sum())
         for k_ in KEYS:
             res[f"{pop}_{k_}"] = np.stack(r[k_])
-    np.savez(out, **res)
+    return res
 
 
 def main():
     t_start = time.time()
     tmp = tempfile.mkdtemp(prefix="nm_allkinds_")
     tree_before = sorted(os.listdir(HERE))
-    env = dict(os.environ, OMP_NUM_THREADS="1")
     try:
         G, F, P = mg.SETS, me.SETS, mp.SETS
         np.testing.assert_array_equal(G[0], [0, 0, 0, 0, 0, 1]); np.testing.assert_array_equal(F[0], [1.0, 20.0, 0.8]); np.testing.assert_array_equal(P[0], 0.0)
@@ -285,39 +216,32 @@ def main():
         defaults = [int(SETS[k, 0] == 0) + int(SETS[k, 1] == 0) + int(SETS[k, 2] == 0) + int(np.isinf(TORQUE[k]).all()) for k in range(4)]
         assert defaults == [1, 1, 1, 1] and WRENCH.any(axis=1).all(), "each pooled kind has its default in exactly one set, no set two"
         pool = ThreadPoolExecutor(8)
-        # ---- the libraries: plain, all-default, the four combined sets, and per set the three variants with one compiled-in kind at its default
-        specs = {"plain": (None, None, P[0]), "default": (G[0], F[0], P[0])}
-        for k, (g, f, p) in enumerate(SETS):
-            specs[f"set{k}"] = (G[g], F[f], P[p])
-            specs[f"set{k}_gravity"] = (G[0], F[f], P[p])
-            specs[f"set{k}_friction"] = (G[g], F[0], P[p])
-            specs[f"set{k}_payload"] = (G[g], F[f], P[0])
-        libs = dict(zip(specs, pool.map(lambda kv: build_variant(tmp, kv[0], *kv[1]), specs.items())))
-        print(f"{len(libs)} libraries built; every one of the {len(ENV_PATCHES)} env-layer and {len(PHYS_PATCHES)} physics patch sites found exactly once")
+        libs = list(pool.map(lambda pay: mp.payload_lib(tmp, pay[0], pay[1:]), P))      # (library, body row) per payload set
+        print(f"{len(libs)} libraries built")
         nruns = [0]
+        DEFAULTS = dict(delays=np.zeros(N, np.int32), servo=ms.DEFAULT_ROWS, fmax=mt.SETS[0], wrench=mw.SETS[0])
 
-        def run(name, tag, start="-", plain=False, **over):
-            """One child under the rows of combined set `over["k"]` (None: every kind at its default), single kinds overridden."""
-            k = over.pop("k", None)
-            sp = dict(delays=np.zeros(N, np.int32), servo=ms.DEFAULT_ROWS, fmax=mt.SETS[0], wrench=mw.SETS[0])
-            if k is not None:
-                sp = dict(delays=DELAYS, servo=ROWS, fmax=TORQUE[k], wrench=WRENCH[k])
+        def combined(k, src=None, without=None, **over):
+            """Combined set k under its rows, the kind `without` (one of ABLATIONS) at its default, single kinds overridden."""
+            g, f, p = SETS[k]
+            sp = dict(delays=DELAYS, servo=ROWS, fmax=TORQUE[k], wrench=WRENCH[k])
+            sp.update({"latency": dict(delays=DEFAULTS["delays"]), "rate": dict(servo=no_rate), "d_gain": dict(servo=no_dgain),
+                       "torque": dict(fmax=DEFAULTS["fmax"]), "wrench": dict(wrench=DEFAULTS["wrench"])}.get(without, {}))
             sp.update(over)
-            spec, out = os.path.join(tmp, f"{name}{tag}_spec.npz"), os.path.join(tmp, f"{name}{tag}.npz")
-            np.savez(spec, **sp)
-            subprocess.check_call([sys.executable, os.path.abspath(__file__), "--child", libs[name][0], out, "plain" if plain else spec, start], env=env)
             nruns[0] += 1
-            return dict(np.load(out))
+            return run(libs[0 if without == "payload" else p][0], G[0 if without == "gravity" else g], F[0 if without == "friction" else f], sp, src)
 
+        no_rate, no_dgain = ROWS.copy(), ROWS.copy()
+        no_rate[:, 0], no_dgain[:, 1] = INF, 0.0
         # ---- a
-        plain, zero = pool.map(lambda a: run(a[0], "", plain=a[1]), [("plain", True), ("default", False)])
+        plain, zero = pool.map(lambda a: run(libs[0][0], *a), [(), (G[0], F[0], DEFAULTS)])
+        nruns[0] += 2
         for key in plain:
-            if not key.endswith(("_hist", "_lim", "_margin")):
-                np.testing.assert_array_equal(plain[key], zero[key], err_msg=key)
-        print("a: the combined build with every kind at its default equals the unpatched oracle against the same header bit for bit")
+            np.testing.assert_array_equal(plain[key], zero[key], err_msg=key)
+        print("a: every kind's default rows set equal no rows set, on the library of payload 0, bit for bit")
         # ---- b
         allrand = np.load(os.path.join(HERE, "allrand.npz"))
-        lower = list(pool.map(lambda k: run(f"set{k}", "_lower", k=k, servo=ms.DEFAULT_ROWS, fmax=mt.SETS[0], wrench=mw.SETS[0]), range(4)))
+        lower = list(pool.map(lambda k: combined(k, servo=DEFAULTS["servo"], fmax=DEFAULTS["fmax"], wrench=DEFAULTS["wrench"]), range(4)))
         shared = 0
         for key in allrand.files:
             if key.split("_")[0] in POPS:
@@ -326,9 +250,9 @@ def main():
         print(f"b: with kinds 5..7 at their defaults the four combined sets equal allrand.npz bit for bit in its {shared} trajectory keys")
 
         # ---- the combined runs
-        parts = list(pool.map(lambda k: run(f"set{k}", "", k=k), range(4)))
+        parts = list(pool.map(combined, range(4)))
         g = {"sets": SETS, "grav_rows": np.stack([mg.row_of(G[s[0]]) for s in SETS]), "envp_rows": np.stack([F[s[1]] for s in SETS]),
-             "payloads": np.stack([P[s[2]] for s in SETS]), "body_rows": np.stack([libs[f"set{k}"][1] for k in range(4)]), "delays": DELAYS,
+             "payloads": np.stack([P[s[2]] for s in SETS]), "body_rows": np.stack([libs[s[2]][1] for s in SETS]), "delays": DELAYS,
              "servo_rows": ROWS, "torque_rows": TORQUE, "wrench_rows": WRENCH}
         for key in ("sets", "grav_rows", "envp_rows", "payloads", "body_rows", "delays"):
             np.testing.assert_array_equal(g[key], allrand[key], err_msg=key)
@@ -372,29 +296,15 @@ def main():
         assert min(n1, n2, n3) >= 10, "e"
 
         # ---- c: one kind back at its default, from the combined run's own start state
-        for k in range(4):      # the children read dof_pos, dof_vel, act, lim from the recording
-            np.savez(os.path.join(tmp, f"set{k}.npz"), **parts[k])
-        start = lambda k: os.path.join(tmp, f"set{k}.npz")
-        replays = list(pool.map(lambda k: run(f"set{k}", "_replay", start(k), k=k), range(4)))
+        replays = list(pool.map(lambda k: combined(k, parts[k]), range(4)))
         for k in range(4):      # the replay from a recorded start state is the recording itself: what was recorded is the whole state
             for pop in POPS[:2]:
                 for key in KEYS:
                     np.testing.assert_array_equal(replays[k][f"{pop}_{key}"], g[f"{pop}_{key}"][k], err_msg=f"replay of set {k} {pop} {key}")
         jobs = [(k, kind) for k in range(4) for kind in ABLATIONS]
-        no_rate, no_dgain = ROWS.copy(), ROWS.copy()
-        no_rate[:, 0], no_dgain[:, 1] = INF, 0.0
-        over = dict(latency=dict(delays=np.zeros(N, np.int32)), rate=dict(servo=no_rate), d_gain=dict(servo=no_dgain), torque=dict(fmax=mt.SETS[0]),
-                    wrench=dict(wrench=mw.SETS[0]))
-
-        def ablate(job):
-            k, kind = job
-            if kind in over:
-                return run(f"set{k}", f"_{kind}", start(k), k=k, **over[kind])
-            return run(f"set{k}_{kind}", "_abl", start(k), k=k)
-
         sensitive = np.zeros((len(ABLATIONS), 4, 2, N), np.uint8)
         smallest = np.full((len(ABLATIONS), 2), INF)
-        for (k, kind), abl in zip(jobs, pool.map(ablate, jobs)):
+        for (k, kind), abl in zip(jobs, pool.map(lambda job: combined(job[0], parts[job[0]], job[1]), jobs)):
             a = ABLATIONS.index(kind)
             dflt = {"latency": DELAYS == 0, "rate": np.isinf(ROWS[:, 0]), "d_gain": ROWS[:, 1] == 0, "torque": np.full(N, np.isinf(TORQUE[k]).all()),
                     "wrench": np.full(N, not WRENCH[k].any())}.get(kind)
@@ -442,7 +352,4 @@ def main():
 
 
 if __name__ == "__main__":
-    if len(sys.argv) == 6 and sys.argv[1] == "--child":
-        child(*sys.argv[2:6])
-    else:
-        main()
+    main()

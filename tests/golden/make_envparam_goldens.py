@@ -1,13 +1,9 @@
 """Generator of tests/golden/env_params.npz: fp64 reference trajectories for per-env friction and servo gains (mu, p_gain, kv).
 
-The oracle takes these three values at compile time: NM_FRICTION and NM_KV of nightmare_rl_amd/model/nm_model_data.h, and the P_GAIN line
-of oracle/nm_oracle_env.c. A UNIFORM variant of the oracle is therefore the unchanged oracle source compiled against those three
-definitions changed. For each parameter set this script copies oracle/*.c and oracle/nm_oracle.h into a temporary directory that mirrors
-the relative include path, writes the patched header (and the one patched P_GAIN line) there, builds a library with the flags of
-oracle/Makefile and drives it through oracle/oracle.py in a child process (one library per process). Nothing but the .npz is written
-into the tree; oracle/ itself is not touched.
+The oracle carries the three values as per-env rows (oracle/nm_oracle.h: OracleEnv.set_env_params): for each parameter set this script
+gives all eight envs of an env object that row and records. Nothing but the .npz is written into the tree.
 
-    python tests/golden/make_envparam_goldens.py            (CPU only, about a minute)
+    python tests/golden/make_envparam_goldens.py            (CPU only, a few seconds)
 
 Populations (8 envs x T steps each, per set, free-running; every step's start state is the previous step's end state):
     drop   random actions while the robot falls from the initial pose and lands
@@ -16,11 +12,7 @@ Populations (8 envs x T steps each, per set, free-running; every step's start st
            consecutive ones with the most env-steps above 16 contacts (the matrix-free constraint layout)
 """
 import os
-import re
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
@@ -32,46 +24,24 @@ SETS = np.array([[1.0, 20.0, 0.8], [0.4, 20.0, 0.5], [1.6, 14.0, 0.8], [0.7, 26.
 POPS = ("drop", "stand", "belly")
 N, T = 8, 10
 SEED = 5
+KEYS = ("qpos", "qvel", "qw", "dof_pos", "dof_vel", "act", "cmd", "ep_len", "actions", "cmd_u", "obs", "rew", "done", "ncon")
+sys.path.insert(0, ROOT)
+from oracle import oracle as orc      # noqa: E402
 
 
-def build_variant(tmp, k, mu, p_gain, kv):
-    d = os.path.join(tmp, f"set{k}")
-    os.makedirs(os.path.join(d, "oracle"))
-    os.makedirs(os.path.join(d, "nightmare_rl_amd", "model"))
-    for f in os.listdir(os.path.join(ROOT, "oracle")):
-        if f.endswith(".c") or f == "nm_oracle.h":
-            shutil.copy(os.path.join(ROOT, "oracle", f), os.path.join(d, "oracle", f))
-
-    def patch(path, pattern, line):
-        s = open(path).read()
-        s, n = re.subn(pattern, line, s, flags=re.M)
-        assert n == 1, (path, pattern, n)
-        open(path, "w").write(s)
-
-    hdr = os.path.join(d, "nightmare_rl_amd", "model", "nm_model_data.h")
-    shutil.copy(os.path.join(ROOT, "nightmare_rl_amd", "model", "nm_model_data.h"), hdr)
-    patch(hdr, r"^#define NM_FRICTION .*$", f"#define NM_FRICTION {mu!r}")
-    patch(hdr, r"^#define NM_KV .*$", f"#define NM_KV {kv!r}")
-    patch(os.path.join(d, "oracle", "nm_oracle_env.c"), r"^#define P_GAIN \S+", f"#define P_GAIN {p_gain!r}")
-    mk = open(os.path.join(ROOT, "oracle", "Makefile")).read()
-    cflags = re.search(r"^CFLAGS \?= (.*)$", mk, flags=re.M).group(1).split()
-    lib = os.path.join(d, "libnm_oracle.so")
-    subprocess.check_call(["gcc"] + cflags + ["-shared", "-o", lib, "nm_oracle_physics.c", "nm_oracle_env.c", "-lm"], cwd=os.path.join(d, "oracle"))
-    return lib
-
-
-def child(lib, out):
-    """Runs in a process of its own: the oracle module bound to ONE variant library."""
-    sys.path.insert(0, ROOT)
-    from oracle import oracle as orc
-    orc.LIB_PATH = lib
+def record(setup=None, pops=POPS, lib_path=None, extra=None):
+    """One free-running recording of the populations `pops`, in this order under one action stream. setup(o) gives a fresh env object
+    its rows; lib_path binds another library (a base payload is a recompiled model); extra(o) returns more per-step keys and is first
+    called, its result dropped, where a recorded window starts. Shared by the generators of payload, gravity, torque and wrench."""
     rng = np.random.default_rng(SEED)
     res = {}
     many = np.load(os.path.join(HERE, "env_manycontacts.npz"))["init_qpos"][:N]
     default = np.tile([0, np.pi / 5, 0], 6)
-    for pop in POPS:
-        o = orc.OracleEnv(N, seed=SEED)
+    for pop in pops:
+        o = orc.OracleEnv(N, seed=SEED, lib_path=lib_path)
         o.reset_idx()
+        if setup:
+            setup(o)
         if pop == "drop":
             pre, act = 7, lambda: rng.uniform(-1, 1, (N, 18)).astype(np.float32)
         elif pop == "stand":
@@ -83,7 +53,8 @@ def child(lib, out):
         total = T if pop != "belly" else 80       # belly: the T consecutive steps with the most env-steps above 16 contacts are kept
         for _ in range(pre):
             o.step(act())
-        keys = ("qpos", "qvel", "qw", "dof_pos", "dof_vel", "act", "cmd", "ep_len", "actions", "cmd_u", "obs", "rew", "done", "ncon")
+        more = extra(o) if extra else {}
+        keys = KEYS + tuple(more)
         r = {k: [] for k in keys}
 
         def state():
@@ -99,40 +70,33 @@ def child(lib, out):
             obs, rew, done, _ = o.step(a, cmd_u=cu)
             r["actions"].append(a); r["cmd_u"].append(cu.astype(np.float32)); r["obs"].append(obs.copy()); r["rew"].append(o.rew64.copy())
             r["done"].append(done.astype(np.uint8)); r["ncon"].append(np.array([o.data(i).ncon for i in range(N)], np.uint8))
+            for k, v in (extra(o) if extra else {}).items():
+                r[k].append(v)
             state()
         big = (np.stack(r["ncon"]) > 16).sum(axis=1)
         t0 = int(np.argmax([big[i:i + T].sum() for i in range(total - T + 1)]))
         for k in keys:
             res[f"{pop}_{k}"] = np.stack(r[k][t0:t0 + T + (len(r[k]) > total)])
-    np.savez(out, **res)
+    return res
+
+
+def stacked(parts):
+    """[set, step (T or T + 1), env, ...] per key."""
+    return {key: np.stack([p[key] for p in parts]) for key in parts[0]}
 
 
 def main():
-    tmp = tempfile.mkdtemp(prefix="nm_envparam_")
-    try:
-        parts = []
-        for k, (mu, pg, kv) in enumerate(SETS):
-            lib = build_variant(tmp, k, float(mu), float(pg), float(kv))
-            out = os.path.join(tmp, f"set{k}.npz")
-            subprocess.check_call([sys.executable, os.path.abspath(__file__), "--child", lib, out])
-            parts.append(np.load(out))
-        g = {"sets": SETS}
-        for key in parts[0].files:
-            g[key] = np.stack([p[key] for p in parts])          # [set, step (T or T + 1), env, ...]
-        for pop in POPS:
-            big = (g[f"{pop}_ncon"] > 16).sum(axis=(1, 2))
-            con = (g[f"{pop}_ncon"] > 0).sum(axis=(1, 2))
-            print(f"{pop}: env-steps with contacts per set {con.tolist()}, with more than 16 contacts {big.tolist()}, resets {g[f'{pop}_done'].sum(axis=(1, 2)).tolist()}")
-        assert ((g["belly_ncon"] > 16).sum(axis=(1, 2)) >= 4).all(), "every set must exercise the matrix-free layout on several env-steps"
-        np.savez_compressed(OUT, **g)
-        print(f"wrote {OUT}: {os.path.getsize(OUT)} bytes")
-        assert os.path.getsize(OUT) < (1 << 20)
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
+    parts = [record(lambda o, row=row: o.set_env_params(row)) for row in SETS]
+    g = {"sets": SETS, **stacked(parts)}
+    for pop in POPS:
+        big = (g[f"{pop}_ncon"] > 16).sum(axis=(1, 2))
+        con = (g[f"{pop}_ncon"] > 0).sum(axis=(1, 2))
+        print(f"{pop}: env-steps with contacts per set {con.tolist()}, with more than 16 contacts {big.tolist()}, resets {g[f'{pop}_done'].sum(axis=(1, 2)).tolist()}")
+    assert ((g["belly_ncon"] > 16).sum(axis=(1, 2)) >= 4).all(), "every set must exercise the matrix-free layout on several env-steps"
+    np.savez_compressed(OUT, **g)
+    print(f"wrote {OUT}: {os.path.getsize(OUT)} bytes")
+    assert os.path.getsize(OUT) < (1 << 20)
 
 
 if __name__ == "__main__":
-    if len(sys.argv) == 4 and sys.argv[1] == "--child":
-        child(sys.argv[2], sys.argv[3])
-    else:
-        main()
+    main()

@@ -1,22 +1,21 @@
 """Generator of tests/golden/torque.npz: fp64 reference trajectories for the servo torque limit (nm_set_torque_limit), MuJoCo's actuator
 forcerange.
 
-The oracle's servo force is unbounded: qfrc_actuator = NM_KV clip(ctrl) - NM_KV qvel, and every actuated dof enters the implicit factor
-M + h NM_KV I. The variant recorded here is the oracle source with those two places of nm_oracle_physics.c patched in a temporary copy
-(the recipe of make_envparam_goldens.py; oracle/ itself is not touched), each patch asserted to apply exactly once:
-  * fwd_actuation: f = NM_KV c - NM_KV qvel becomes f > fmax ? fmax : (f < -fmax ? -fmax : f), fmax = limit[j % 3]       (mj_fwdActuation)
-  * integrate: H[6+j][6+j] += h NM_KV only where |qfrc_actuator[6+j]| < limit[j % 3]                  (mjd_actuator_vel in mj_implicit)
-The limits are process-wide (one uniform set per child process, one OpenMP thread), as is a flag that switches the second patch off
-(the "force only" variant of condition e) and the smallest | |f| - fmax | seen over finite limits, which the child reads after every step.
+Without a limit the oracle's servo force is unbounded: qfrc_actuator = kv clip(ctrl) - kv qvel, and every actuated dof enters the
+implicit factor M + h kv I. Per env the oracle carries limits by joint type (oracle/nm_oracle.h: OracleEnv.set_torque_limit):
+  * fwd_actuation: f = kv c - kv qvel becomes f > fmax ? fmax : (f < -fmax ? -fmax : f), fmax = limit[j % 3]            (mj_fwdActuation)
+  * integrate: H[6+j][6+j] += h kv only where |qfrc_actuator[6+j]| < limit[j % 3]                    (mjd_actuator_vel in mj_implicit)
+with a switch that turns the second off (the "force only" variant of condition e) and, per env, the smallest | |f| - fmax | seen over
+finite limits, which this script reads after every step.
 
 Sets (limits coxa / femur / tibia; kv) under SETS / KV; a mixed device batch gives env e set e % 5. Populations, seed, pre-rolls and action
-streams are make_envparam_goldens.py's `drop` and `stand`; the pre-rolls run in the variant itself (in `stand` the robot settles under
+streams are make_envparam_goldens.py's `drop` and `stand`; the pre-rolls run under the limits (in `stand` the robot settles under
 its own limits). Per step: start state, inputs, obs, rew, done, ncon and the end-of-step qfrc_actuator.
 Set 3 is (6.4, 0.3, 3.0): with a tibia limit of 2.4 (and 2.0 .. 2.8) some env of `drop` keeps its femur on the 0.3 bound for all 60
 joint-steps, which condition b does not admit; at 3.0 every env leaves it at least once.
 
 The script asserts, on the reference alone (the figures it prints are quoted in DESIGN 6.17):
-  a  set 0 equals the unpatched oracle bit for bit: env_params.npz set 0, drop and stand;
+  a  set 0 (infinite limits set) equals no limits set bit for bit: env_params.npz set 0, drop and stand;
   b  in drop every env of sets 1..4 has saturated and unsaturated joint-steps of every finitely limited joint type at the end of step
      (set 3's coxa limit of 6.4 is nearly unreachable and exempt);
   c  in stand, set 3 has all 60 femur joint-steps saturated in every env and no other joint saturated;
@@ -25,120 +24,35 @@ The script asserts, on the reference alone (the figures it prints are quoted in 
   f  the smallest saturation margin over the recorded window is above 1e-5 N m in every set and population;
   g  no done in any window.
 
-    python tests/golden/make_torque_goldens.py            (CPU only, about a minute)
+    python tests/golden/make_torque_goldens.py            (CPU only, a few seconds)
 """
-import ctypes as C
 import os
-import re
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(HERE))
+sys.path.insert(0, HERE)
+import make_envparam_goldens as me      # noqa: E402  (the populations, seed, pre-rolls, action streams and the recorder)
+
 OUT = os.path.join(HERE, "torque.npz")
 INF = float("inf")
 SETS = np.array([[INF, INF, INF], [3.2, 3.2, 3.2], [INF, 1.6, INF], [6.4, 0.3, 3.0], [2.0, 2.0, 2.0]])
 KV = np.array([0.8, 0.8, 0.8, 0.8, 0.5])
 POPS = ("drop", "stand")
-N, T = 8, 10
-SEED = 5
-
-GLOBALS = """/* ---- servo torque limit (tests/golden/make_torque_goldens.py) */
-static double g_tq_fmax[3] = {INFINITY, INFINITY, INFINITY};
-static int g_tq_mask = 1;            /* 0: the clamp alone, every dof stays in the implicit factor */
-static double g_tq_margin = INFINITY; /* smallest | |f| - fmax | over finite limits since the last read */
-void nmo_torque_set(const double* fmax, int mask) { for (int k = 0; k < 3; k++) g_tq_fmax[k] = fmax[k]; g_tq_mask = mask; }
-double nmo_torque_margin(void) { const double m = g_tq_margin; g_tq_margin = INFINITY; return m; }
-static void fwd_actuation(nmo_data* d) {"""
-FORCE_OLD = "    d->qfrc_actuator[6 + j] = NM_KV * c - NM_KV * d->qvel[6 + j];"
-FORCE_NEW = """    {
-      const double f_ = NM_KV * c - NM_KV * d->qvel[6 + j], fm_ = g_tq_fmax[j % 3];
-      if (isfinite(fm_) && fabs(fabs(f_) - fm_) < g_tq_margin) g_tq_margin = fabs(fabs(f_) - fm_);
-      d->qfrc_actuator[6 + j] = f_ > fm_ ? fm_ : (f_ < -fm_ ? -fm_ : f_);
-    }"""
-FACTOR_OLD = "  for (int j = 0; j < NU; j++) H[6 + j][6 + j] += h * NM_KV;"
-FACTOR_NEW = "  for (int j = 0; j < NU; j++) if (!g_tq_mask || fabs(d->qfrc_actuator[6 + j]) < g_tq_fmax[j % 3]) H[6 + j][6 + j] += h * NM_KV;"
+N, T = me.N, me.T
 
 
-def build_variant(tmp, k, kv, patched=True):
-    d = os.path.join(tmp, f"set{k}")
-    os.makedirs(os.path.join(d, "oracle"))
-    os.makedirs(os.path.join(d, "nightmare_rl_amd", "model"))
-    for f in os.listdir(os.path.join(ROOT, "oracle")):
-        if f.endswith(".c") or f == "nm_oracle.h":
-            shutil.copy(os.path.join(ROOT, "oracle", f), os.path.join(d, "oracle", f))
-    hdr = os.path.join(d, "nightmare_rl_amd", "model", "nm_model_data.h")
-    shutil.copy(os.path.join(ROOT, "nightmare_rl_amd", "model", "nm_model_data.h"), hdr)
-    s = open(hdr).read()
-    s, n = re.subn(r"^#define NM_KV .*$", f"#define NM_KV {kv!r}", s, flags=re.M)
-    assert n == 1
-    open(hdr, "w").write(s)
-    if patched:
-        phys = os.path.join(d, "oracle", "nm_oracle_physics.c")
-        s = open(phys).read()
-        for old, new in (("static void fwd_actuation(nmo_data* d) {", GLOBALS), (FORCE_OLD, FORCE_NEW), (FACTOR_OLD, FACTOR_NEW)):
-            assert s.count(old) == 1, old
-            s = s.replace(old, new)
-        open(phys, "w").write(s)
-    mk = open(os.path.join(ROOT, "oracle", "Makefile")).read()
-    cflags = re.search(r"^CFLAGS \?= (.*)$", mk, flags=re.M).group(1).split()
-    lib = os.path.join(d, "libnm_oracle.so")
-    subprocess.check_call(["gcc"] + cflags + ["-shared", "-o", lib, "nm_oracle_physics.c", "nm_oracle_env.c", "-lm"], cwd=os.path.join(d, "oracle"))
-    return lib
+def record(k, factor_mask):
+    """All eight envs under set k."""
+    def setup(o):
+        o.set_torque_limit(SETS[k], factor_mask)
+        o.set_env_params([me.SETS[0, 0], me.SETS[0, 1], KV[k]])
 
+    def extra(o):
+        return dict(qfrc=np.stack([o.data(i).np("qfrc_actuator")[6:].copy() for i in range(N)]), margin=np.float64(o.torque_limit()[1].min()))
 
-def child(lib, out, k, mask):
-    """Runs in a process of its own: the oracle module bound to ONE variant library, under set k."""
-    sys.path.insert(0, ROOT)
-    from oracle import oracle as orc
-    orc.LIB_PATH = lib
-    L = orc.lib()
-    L.nmo_torque_set.argtypes = [C.c_void_p, C.c_int]
-    L.nmo_torque_margin.restype = C.c_double
-    fmax = np.ascontiguousarray(SETS[k])
-
-    def limit(on):
-        L.nmo_torque_set(fmax.ctypes.data_as(C.c_void_p), mask)
-
-    rng = np.random.default_rng(SEED)
-    res = {}
-    for pop in POPS:
-        o = orc.OracleEnv(N, seed=SEED)
-        o.reset_idx()
-        limit(True)
-        if pop == "drop":
-            pre, act = 7, lambda: rng.uniform(-1, 1, (N, 18)).astype(np.float32)
-        else:
-            pre, act = 150, lambda: np.zeros((N, 18), np.float32)
-        for _ in range(pre):
-            o.step(act())
-        L.nmo_torque_margin()
-        keys = ("qpos", "qvel", "qw", "dof_pos", "dof_vel", "act", "cmd", "ep_len", "actions", "cmd_u", "obs", "rew", "done", "ncon", "qfrc", "margin")
-        r = {k_: [] for k_ in keys}
-
-        def state():
-            q, v, w = o.get_state()
-            b = o.get_buffers()
-            r["qpos"].append(q); r["qvel"].append(v); r["qw"].append(w); r["dof_pos"].append(b["dof_pos"]); r["dof_vel"].append(b["dof_vel"])
-            r["act"].append(b["actions"]); r["cmd"].append(b["commands"]); r["ep_len"].append(b["ep_len"])
-
-        state()
-        for t in range(T):
-            a = act()
-            cu = rng.uniform(0, 1, (N, 4)).astype(np.float32).astype(np.float64)
-            obs, rew, done, _ = o.step(a, cmd_u=cu)
-            r["actions"].append(a); r["cmd_u"].append(cu.astype(np.float32)); r["obs"].append(obs.copy()); r["rew"].append(o.rew64.copy())
-            r["done"].append(done.astype(np.uint8)); r["ncon"].append(np.array([o.data(i).ncon for i in range(N)], np.uint8))
-            r["qfrc"].append(np.stack([o.data(i).np("qfrc_actuator")[6:].copy() for i in range(N)]))
-            r["margin"].append(np.float64(L.nmo_torque_margin()))
-            state()
-        for k_ in keys:
-            res[f"{pop}_{k_}"] = np.stack(r[k_])
-    np.savez(out, **res)
+    return me.record(setup, POPS, extra=extra)
 
 
 def saturated(qfrc, limits):
@@ -147,56 +61,40 @@ def saturated(qfrc, limits):
 
 
 def main():
-    tmp = tempfile.mkdtemp(prefix="nm_torque_")
-    env = dict(os.environ, OMP_NUM_THREADS="1")
-    try:
-        full, force_only = [], []
+    full, force_only = [record(k, True) for k in range(len(SETS))], [record(k, False) for k in range(len(SETS))]
+    g = {"sets": SETS, "kv": KV, **me.stacked(full)}
+    ref = np.load(os.path.join(HERE, "env_params.npz"))
+    for pop in POPS:
+        for key in ("qpos", "qvel", "qw", "dof_pos", "dof_vel", "act", "cmd", "ep_len", "actions", "cmd_u", "obs", "rew", "done", "ncon"):      # a
+            np.testing.assert_array_equal(g[f"{pop}_{key}"][0], ref[f"{pop}_{key}"][0], err_msg=f"{pop}_{key}")
+    print("a: set 0 equals env_params.npz set 0 (no limits set) bit for bit, drop and stand")
+    for pop in POPS:
+        sat = np.stack([saturated(g[f"{pop}_qfrc"][k], SETS[k]) for k in range(len(SETS))])      # [set, T, N, 18]
+        per_env = sat.sum(axis=(1, 3))
+        moved = np.abs(g[f"{pop}_qpos"] - g[f"{pop}_qpos"][0]).max(axis=(1, 3))
+        gap = np.stack([np.abs(full[k][f"{pop}_qpos"] - force_only[k][f"{pop}_qpos"]).max(axis=(0, 2)) for k in range(len(SETS))])
+        margin = g[f"{pop}_margin"].min(axis=1)
         for k in range(len(SETS)):
-            lib = build_variant(tmp, k, float(KV[k]))
-            for mask, parts in ((1, full), (0, force_only)):
-                out = os.path.join(tmp, f"set{k}_{mask}.npz")
-                subprocess.check_call([sys.executable, os.path.abspath(__file__), "--child", lib, out, str(k), str(mask)], env=env)
-                parts.append(dict(np.load(out)))
-        g = {"sets": SETS, "kv": KV}
-        for key in full[0]:
-            g[key] = np.stack([p[key] for p in full])          # [set, step (T or T + 1), env, ...]
-        ref = np.load(os.path.join(HERE, "env_params.npz"))
-        for pop in POPS:
-            for key in ("qpos", "qvel", "qw", "dof_pos", "dof_vel", "act", "cmd", "ep_len", "actions", "cmd_u", "obs", "rew", "done", "ncon"):      # a
-                np.testing.assert_array_equal(g[f"{pop}_{key}"][0], ref[f"{pop}_{key}"][0], err_msg=f"{pop}_{key}")
-        print("a: set 0 equals env_params.npz set 0 (the unpatched oracle) bit for bit, drop and stand")
-        for pop in POPS:
-            sat = np.stack([saturated(g[f"{pop}_qfrc"][k], SETS[k]) for k in range(len(SETS))])      # [set, T, N, 18]
-            per_env = sat.sum(axis=(1, 3))
-            moved = np.abs(g[f"{pop}_qpos"] - g[f"{pop}_qpos"][0]).max(axis=(1, 3))
-            gap = np.stack([np.abs(full[k][f"{pop}_qpos"] - force_only[k][f"{pop}_qpos"]).max(axis=(0, 2)) for k in range(len(SETS))])
-            margin = g[f"{pop}_margin"].min(axis=1)
-            for k in range(len(SETS)):
-                print(f"{pop} set {k}: saturated joint-steps of {T * 18} per env {per_env[k].tolist()}, max |qpos - set 0| per env "
-                      f"{np.array2string(moved[k], precision=3)}, max |qpos - force-only variant| per env {np.array2string(gap[k], precision=3)}, "
-                      f"smallest margin {margin[k]:.3g}, base z at the end {np.array2string(g[f'{pop}_qpos'][k, -1, :, 2], precision=3)}")
-            assert per_env[0].sum() == 0
-            if pop == "drop":      # b
-                for k in range(1, len(SETS)):
-                    for jt in range(3):
-                        if np.isfinite(SETS[k, jt]) and not (k == 3 and jt == 0):
-                            n = sat[k][:, :, jt::3].sum(axis=(0, 2))
-                            assert (n > 0).all() and (n < T * 6).all(), ("b", k, jt, n)
-            else:      # c
-                assert (sat[3][:, :, 1::3].sum(axis=(0, 2)) == T * 6).all() and sat[3][:, :, 0::3].sum() == 0 and sat[3][:, :, 2::3].sum() == 0, "c"
-            assert (moved[1:4] > 1e-5).all(), "d"
-            assert (gap[1:] > 1e-4).all(), "e"
-            assert (margin[1:] > 1e-5).all(), ("f", margin)
-            assert g[f"{pop}_done"].sum() == 0, "g"
-        np.savez_compressed(OUT, **g)
-        print(f"wrote {OUT}: {os.path.getsize(OUT)} bytes")
-        assert os.path.getsize(OUT) < (1 << 20)
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
+            print(f"{pop} set {k}: saturated joint-steps of {T * 18} per env {per_env[k].tolist()}, max |qpos - set 0| per env "
+                  f"{np.array2string(moved[k], precision=3)}, max |qpos - force-only variant| per env {np.array2string(gap[k], precision=3)}, "
+                  f"smallest margin {margin[k]:.3g}, base z at the end {np.array2string(g[f'{pop}_qpos'][k, -1, :, 2], precision=3)}")
+        assert per_env[0].sum() == 0
+        if pop == "drop":      # b
+            for k in range(1, len(SETS)):
+                for jt in range(3):
+                    if np.isfinite(SETS[k, jt]) and not (k == 3 and jt == 0):
+                        n = sat[k][:, :, jt::3].sum(axis=(0, 2))
+                        assert (n > 0).all() and (n < T * 6).all(), ("b", k, jt, n)
+        else:      # c
+            assert (sat[3][:, :, 1::3].sum(axis=(0, 2)) == T * 6).all() and sat[3][:, :, 0::3].sum() == 0 and sat[3][:, :, 2::3].sum() == 0, "c"
+        assert (moved[1:4] > 1e-5).all(), "d"
+        assert (gap[1:] > 1e-4).all(), "e"
+        assert (margin[1:] > 1e-5).all(), ("f", margin)
+        assert g[f"{pop}_done"].sum() == 0, "g"
+    np.savez_compressed(OUT, **g)
+    print(f"wrote {OUT}: {os.path.getsize(OUT)} bytes")
+    assert os.path.getsize(OUT) < (1 << 20)
 
 
 if __name__ == "__main__":
-    if len(sys.argv) == 6 and sys.argv[1] == "--child":
-        child(sys.argv[2], sys.argv[3], int(sys.argv[4]), int(sys.argv[5]))
-    else:
-        main()
+    main()

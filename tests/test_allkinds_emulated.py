@@ -1,8 +1,8 @@
 """All seven kinds of per-env rows on at once - gravity vectors, friction / servo gains, base payloads, actuation latency, the servo
 target model, the servo torque limit, the external wrench on the base: what cfg.domain_rand plus cfg.control switches on, level 7 of the
 step with every region of the row block non-default - in the host emulation of the device source (tests/emul/nm_emul.cpp), against the
-fp64 fixture of the COMBINED variant oracles (tests/golden/make_allkinds_goldens.py: one library per set with every generator's patch
-applied). Each kind has such a comparison of its own; this is the one in which the places where the kinds MEET would show: a servo force
+fp64 fixture of the oracle with every kind COMBINED (tests/golden/make_allkinds_goldens.py: per set the library of its payload under
+the oracle's rows of the six other kinds). Each kind has such a comparison of its own; this is the one in which the places where the kinds MEET would show: a servo force
 formed from a delayed, slew-limited target under the env's own p_gain, with d_gain dof_vel inside the control clip, multiplied by the
 env's own kv and only then clamped by the env's torque limit; an implicit factor that leaves out exactly the joints this force saturates
 and uses the env's kv; a wrench torque ipos x Rb' F with ipos from the payload's body row under a tilted gravity; and a level-7 launch

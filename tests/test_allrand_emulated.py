@@ -1,7 +1,7 @@
 """All four kinds of per-env rows on at once - gravity vectors, friction / servo gains, base payloads, actuation latency: what
 cfg.domain_rand switches on, level 4 of the step with every region of the row block non-default - in the host emulation of the device
-source (tests/emul/nm_emul.cpp), against the fp64 fixture of the COMBINED variant oracles (tests/golden/make_allrand_goldens.py: one
-library per set with every generator's patch applied). Each kind has such a comparison of its own; this is the one in which a step that
+source (tests/emul/nm_emul.cpp), against the fp64 fixture of the oracle with every kind COMBINED (tests/golden/make_allrand_goldens.py: per
+set the library of its payload under the oracle's rows of every other kind). Each kind has such a comparison of its own; this is the one in which a step that
 read a neighbouring region's words, applied the late command with the default gain or built the base block from the default inertial
 position would show: the kinds meet in the subtree centre of mass (body mass and total mass under the env's gravity), the base bias, the
 servo stage (the env's gain on a delayed action) and the epilogue (the env's own gravity_vec).

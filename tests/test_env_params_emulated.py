@@ -1,5 +1,5 @@
 """Per-env friction and servo gains (nm::Args::envp) in the host emulation of the device source (tests/emul/nm_emul.cpp):
-the fp64 emulation of a batch that mixes the four parameter sets over its envs against the fp64 fixture of the variant oracles
+the fp64 emulation of a batch that mixes the four parameter sets over its envs against the fp64 fixture of the oracle's rows
 (tests/golden/make_envparam_goldens.py), mixed batches against uniform ones bit for bit, identity values against no rows at all, and
 the stand-alone sanitizer build of the shim. The fixture's states are teacher-forced: env e of the mixed batch starts every step from the
 recorded state of env e of ITS set's trajectory."""

@@ -1,7 +1,7 @@
 """All seven kinds of per-env rows on at once on the device - gravity vectors, friction / servo gains, base payloads, actuation latency,
 the servo target model, the servo torque limit, the external wrench on the base: what cfg.domain_rand plus cfg.control switches on,
-level 7 of the step with every region of the row block non-default. Reference: the fp64 fixture of the COMBINED variant oracles
-(tests/golden/allkinds.npz, make_allkinds_goldens.py: one library per set with every generator's patch applied), which no kernel has a
+level 7 of the step with every region of the row block non-default. Reference: the fp64 fixture of the oracle with every kind COMBINED
+(tests/golden/allkinds.npz, make_allkinds_goldens.py: per set the library of its payload under the oracle's rows), which no kernel has a
 hand in; uniform batches for what a mixed batch must give (bit for bit: every env is independent). Everything goes through the C ABI's
 per-env setters. The fp64 and fp32 emulations of these very states hold the same tolerances on the CPU (tests/test_allkinds_emulated.py)."""
 import numpy as np

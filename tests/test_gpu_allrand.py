@@ -1,6 +1,6 @@
 """All four kinds of per-env rows on at once on the device - gravity vectors, friction / servo gains, base payloads, actuation latency:
 what cfg.domain_rand switches on, level 4 of the step with every region of the row block non-default. Reference: the fp64 fixture of the
-COMBINED variant oracles (tests/golden/allrand.npz, make_allrand_goldens.py: one library per set with every generator's patch applied),
+oracle with every kind COMBINED (tests/golden/allrand.npz, make_allrand_goldens.py: per set the library of its payload under the oracle's rows),
 which no kernel has a hand in; uniform batches for what a mixed batch must give (bit for bit: every env is independent). The fp64 and
 fp32 emulations of these very states hold the same tolerances on the CPU (tests/test_allrand_emulated.py)."""
 import numpy as np

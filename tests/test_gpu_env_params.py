@@ -1,5 +1,5 @@
 """Per-env friction and servo gains (nm_set_env_params / nm_get_env_params / nm_draw_env_params) on the device, in every stepping path.
-References: the fp64 fixture of the variant oracles (tests/golden/env_params.npz, make_envparam_goldens.py) for what the values mean;
+References: the fp64 fixture of the oracle's rows (tests/golden/env_params.npz, make_envparam_goldens.py) for what the values mean;
 uniform batches for what a mixed batch must give (bit for bit: every env is independent); the per-step path for the K-step launches
 (bit for bit); a numpy restatement over oracle.rand_u24 for the draw."""
 import math

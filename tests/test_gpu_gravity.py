@@ -1,6 +1,6 @@
 """Per-env gravity vectors (nm_set_gravity / nm_get_gravity / nm_draw_gravity) on the device, in every stepping path.
-References: the fp64 fixture of the variant oracles (tests/golden/gravity.npz, make_gravity_goldens.py: the unchanged oracle compiled with
-another gravity; for the observed sets with the one line of its env layer that holds upstream's constant replaced) for what the rows mean;
+References: the fp64 fixture of the oracle's gravity rows (tests/golden/gravity.npz, make_gravity_goldens.py: the physics gravity per env;
+for the observed sets the env layer's gravity_vec as well, for the other one upstream's constant) for what the rows mean;
 uniform batches for what a mixed batch must give (bit for bit: every env is independent); the per-step path for the K-step launches (bit
 for bit); a numpy restatement over oracle.rand_u24 for the draw; closed-form free flight and a numpy rotation for two known answers that
 do not go through the oracle. The file mirrors tests/test_gpu_payload.py group for group."""

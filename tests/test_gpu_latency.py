@@ -1,5 +1,5 @@
 """Per-env actuation latency (nm_set_action_latency and friends) on the device, in every stepping path. References: the fp64 fixture of
-the patched oracle (tests/golden/latency.npz, make_latency_goldens.py) for what a delay means; uniform batches for what a mixed batch must
+the oracle's rows (tests/golden/latency.npz, make_latency_goldens.py) for what a delay means; uniform batches for what a mixed batch must
 give (bit for bit: every env is independent); an undelayed env fed the shifted action sequence for whole-step delays (bit for bit, no
 oracle involved); the per-step path for the K-step launches (bit for bit); a numpy restatement over oracle.rand_u24 for the draw.
 N = 8 throughout (four two-env waves; the fixture's delays 0..6, 0 put two different switch substeps into a wave), N = 7 where a
@@ -85,7 +85,7 @@ def free(env, g, pop, steps):
     return np.stack(errs), serr, flags, out
 
 
-# ------------------------------------------------------------------------------------------------ 1. fp64 kernel vs the patched oracle
+# ------------------------------------------------------------------------------------------------ 1. fp64 kernel vs the oracle's rows
 def test_fp64_kernel_matches_the_patched_oracle(G):
     """The fixture's batch, delays 0..6 and 0. Teacher-forced single steps and the free-running trajectories of both populations:
     obs / reward < 1e-6, state < 1e-8 (the project's fp64 tolerances, tests/test_gpu_parity.py), no done flag differing; the history

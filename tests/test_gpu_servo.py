@@ -1,5 +1,5 @@
 """The servo target model (nm_set_servo and friends, level 5 of the step) on the device, in every stepping path. References: the fp64
-fixture of the patched oracle (tests/golden/servo.npz, make_servo_goldens.py) for what the rows mean, alone (S) and behind the delays of
+fixture of the oracle's rows (tests/golden/servo.npz, make_servo_goldens.py) for what the rows mean, alone (S) and behind the delays of
 latency.npz (SL); the numpy recursion of the limiter for servo_state() (bit for bit, no oracle involved); uniform batches for what a
 mixed batch must give and the per-step path for the K-step launches (bit for bit); a numpy restatement over oracle.rand_u24 for the draw.
 N = 8 throughout (four two-env waves; the rows of the two envs of a wave always differ), N = 7 where a half-empty last wave matters; at
@@ -94,7 +94,7 @@ def free(env, g, rec, pop, steps):
     return np.stack(errs), serr, lerr, flags, out
 
 
-# ------------------------------------------------------------------------------------------------ 1. the kernels vs the patched oracle
+# ------------------------------------------------------------------------------------------------ 1. the kernels vs the oracle's rows
 @pytest.mark.parametrize("rec", RECS)
 def test_fp64_kernel_matches_the_patched_oracle(G, rec):
     """The fixture's batch under the fixture's rows, alone (S) and behind the delays 0..6, 0 (SL). Teacher-forced single steps and the

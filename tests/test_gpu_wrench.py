@@ -1,5 +1,5 @@
 """The external wrench on the base (nm_set_base_wrench, nm_set_wrench_schedule and friends, level 7 of the step) on the device, in every
-stepping path. References: the fp64 fixture of the patched oracle (tests/golden/wrench.npz, make_wrench_goldens.py) for what the rows mean
+stepping path. References: the fp64 fixture of the oracle's rows (tests/golden/wrench.npz, make_wrench_goldens.py) for what the rows mean
 - the mixed batch gives env e set e % 5, set 3 with its payload, so the two envs of a wave always differ; uniform batches for what a mixed
 batch must give and the per-step path for the K-step launches (bit for bit); numpy restatements over oracle.rand_u24 for the schedule and
 the draw (tests/wrench_tools.py). N = 8 (four two-env waves) and N = 7 (a half-empty last wave) against the fixture; N = 63 and 1 where
@@ -104,7 +104,7 @@ def free(env, g, pop, steps, compare=True):
     return (np.stack(errs), np.stack(serrs), flags, out) if compare else out
 
 
-# ------------------------------------------------------------------------------------------------ 1. the kernels vs the patched oracle
+# ------------------------------------------------------------------------------------------------ 1. the kernels vs the oracle's rows
 @pytest.mark.parametrize("N", [8, 7])
 def test_fp64_kernel_matches_the_patched_oracle(G, N):
     """Teacher-forced single steps and the free-running trajectories of both populations: obs / reward < 1e-6, state < 1e-8 (the

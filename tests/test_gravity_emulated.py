@@ -1,7 +1,7 @@
 """Per-env gravity vectors (gravity rows, level 4 of the step) in the host emulation of the device source (tests/emul/nm_emul.cpp):
-the fp64 emulation of a batch that mixes the four gravity sets over its envs against the fp64 fixture of the variant oracles
-(tests/golden/make_gravity_goldens.py: the unchanged oracle compiled against a header with another gravity; for the observed sets with the
-one line of its env layer that holds upstream's constant replaced), teacher-forced and free-running; the fp32 emulation inside the fp32
+the fp64 emulation of a batch that mixes the four gravity sets over its envs against the fp64 fixture of the oracle's gravity rows
+(tests/golden/make_gravity_goldens.py: the physics gravity per env; for the observed sets the env layer's gravity_vec as well, for the
+other one upstream's constant), teacher-forced and free-running; the fp32 emulation inside the fp32
 bounds; default rows at level 4 against level 0 and level 3; mixed batches against uniform ones bit for bit; the bad-state paths under a
 tilted gravity; and the free-flight known answer that does not go through the oracle."""
 import numpy as np

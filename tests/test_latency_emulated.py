@@ -1,6 +1,6 @@
 """Per-env actuation latency (nm_set_action_latency, level 3 of the step) in the host emulation of the device source
 (tests/emul/nm_emul.cpp): the fp64 emulation of the fixture's mixed batch - delays 0..6 and 0 over eight envs - against the fp64
-fixture of the patched oracle (tests/golden/make_latency_goldens.py), delay 0 against no delays at all and the mixed batch against the
+fixture of the oracle's rows (tests/golden/make_latency_goldens.py), delay 0 against no delays at all and the mixed batch against the
 seven uniform ones bit for bit, and the stand-alone sanitizer build of the shim. The fixture's states are teacher-forced: every step
 starts from the recorded state AND the recorded action history."""
 import subprocess

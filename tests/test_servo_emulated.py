@@ -1,5 +1,5 @@
 """The servo target model (nm_set_servo, level 5 of the step) in the host emulation of the device source (tests/emul/nm_emul.cpp,
-levels 0 and 5 only): the fp64 emulation of the fixture's mixed batch against the fp64 fixture of the patched oracle
+levels 0 and 5 only): the fp64 emulation of the fixture's mixed batch against the fp64 fixture of the oracle's rows
 (tests/golden/make_servo_goldens.py), alone (S) and behind the delays 0..6, 0 (SL), teacher-forced and free-running, with the limited
 targets after every step; the fp32 emulation inside the project's fp32 bounds; default rows at level 5 against level 0 under ==; the mixed
 batch against the uniform ones bit for bit; a physics-only launch; and the stand-alone sanitizer build of the shim."""

@@ -1,6 +1,6 @@
 """The servo torque limit (nm_set_torque_limit, level 6 of the step) in the host emulation of the device source
 (tests/emul/nm_emul.cpp, levels 0 and 6 only): the fp64 emulation of the mixed batch (env e under set e % 5 of the fixture, its own
-kv included) against the fp64 fixture of the patched oracle (tests/golden/make_torque_goldens.py), teacher-forced and free-running, one
+kv included) against the fp64 fixture of the oracle's rows (tests/golden/make_torque_goldens.py), teacher-forced and free-running, one
 and two envs per wave; the fp32 emulation inside the project's fp32 bounds; default rows at level 6 against level 0 under ==; a limit
 that is never reached against +inf; the mixed batch against the uniform ones bit for bit; the sensitivity of the comparison; a
 physics-only launch; and the stand-alone sanitizer build of the shim."""

@@ -1,6 +1,6 @@
 """The external wrench on the base (nm_set_base_wrench, level 7 of the step) in the host emulation of the device source
 (tests/emul/nm_emul.cpp, levels 0 and 7 only): the fp64 emulation of the mixed batch (env e under set e % 5 of the fixture, set 3
-with its payload's body row) against the fp64 fixture of the patched oracle (tests/golden/make_wrench_goldens.py), teacher-forced and
+with its payload's body row) against the fp64 fixture of the oracle's rows (tests/golden/make_wrench_goldens.py), teacher-forced and
 free-running, one and two envs per wave; the fp32 emulation inside the project's fp32 bounds; zero rows at level 7 against level 0 under
 ==; the device's layout functions against nm_env_rows.h; N = 7 and its padded half; the mixed batch against the uniform ones bit for bit;
 the sensitivity of the comparison; a physics-only launch; and the stand-alone sanitizer build of the shim."""
